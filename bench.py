@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the BASELINE.json metric on MI355X: rendered rays/s at 64x64 rays x 24 samples.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts the N ranks itself (one process per GPU through torch.distributed.run, rendezvous on
 127.0.0.1) when it was not already launched by torchrun, and fails loudly if fewer than N GPUs are visible; when the driver
@@ -60,6 +60,7 @@ TRAFFIC_FILE = os.path.join(REPO, "profiles", "traffic_pmc.json")          # wri
 PEAK_HBM_GBPS = 8000.0                                                     # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s copy ceiling)
 C3_IMAGES = 2824                                                           # project/utils/setup/train_setup.py:332
 ENCODER_GRAD_BYTES = 1.03e9                                                # fp32 gradient volume of the encoder per step
+DUMP_BYTES = 64 * 2 ** 20 - 2 ** 16                                        # --dump-outputs: 64 MB in all, .npy headers included
 
 
 SHORT_NOTES = {      # the prose lives in DESIGN.md section 5 ("fields of the bench line"); the line carries <= 120 characters per note
@@ -154,6 +155,22 @@ def kernel_source_digest():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(out, path):
+    """--dump-outputs: every array the headline's caller receives from its last timed step, as path/<name>.npy in float32.
+    When they come to more than DUMP_BYTES, each array is cut to its share of that budget by a sample of its flattened elements
+    at indices drawn from a fixed seed (the same indices on every run with the same arguments)."""
+    import numpy as np
+    import torch
+    arrs = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in out.items() if isinstance(v, torch.Tensor)}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    for k, a in sorted(arrs.items()):
+        if total > DUMP_BYTES:
+            keep = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a.size, keep))]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def pin_rank(local_rank, world):
     """One contiguous core set per rank (8 Python launchers on a 256-core host would otherwise share cores and oversubscribe the
     BLAS / OpenMP pools); returns (cores, threads)."""
@@ -194,6 +211,8 @@ def parse_args():
                          "during the seconds of host-side setup and needs ~50-100 ms of load to come back")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only (gloo, no GPU work): prints the number of ranks that joined")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last one as DIR/<name>.npy (float32, <= 64 MB in all)")
     return ap.parse_args()
 
 
@@ -227,6 +246,8 @@ def main():
         args.no_modes = args.no_sustained = True
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
 
@@ -397,6 +418,8 @@ def main():
             renderer.render_with_film(renderer.siren.film_params(wr), focal, poses, near, far)
         elapsed, kern_ms, out = timed_block(args.steps, True)
     assert torch.isfinite(out['gen_thumb_imgs']).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     per_rank_ms = [1e3 * x / args.steps for x in all_ranks(timed_block.own_s)]
     value = rays_per_step * args.steps / elapsed
     result = {

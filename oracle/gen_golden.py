@@ -21,7 +21,7 @@ GOLD = os.path.join(REPO, "tests", "golden")
 
 import e3dge_amd  # noqa: E402  (import shim)
 from e3dge_amd import synthetic as syn  # noqa: E402
-from oracle import camera_ref, decoder_ref, ops_ref, ref_harness, renderer_ref  # noqa: E402
+from oracle import camera_ref, decoder_ref, golden_store, ops_ref, ref_harness, renderer_ref  # noqa: E402
 
 torch.manual_seed(0)
 torch.set_num_threads(8)
@@ -32,9 +32,8 @@ def npf(t):
 
 
 def save(name, **arrays):
-    path = os.path.join(GOLD, name + ".npz")
-    np.savez_compressed(path, **arrays)
-    print(f"  wrote {name}.npz  ({os.path.getsize(path) / 1e3:.1f} kB)")
+    path = golden_store.save(GOLD, name, arrays)
+    print(f"  wrote {os.path.basename(path)}  ({os.path.getsize(path) / 1e3:.1f} kB)")
 
 
 def maxdiff(a, b):

@@ -12,6 +12,8 @@ import os
 import sys
 import types
 
+from oracle import cpu_numerics  # noqa: F401  (fixtures are recorded with the CPU arithmetic the tests check them with)
+
 REF_ROOT = os.environ.get("E3DGE_REFERENCE", "/root/reference")
 
 

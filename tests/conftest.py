@@ -9,6 +9,8 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 GOLDEN = os.path.join(REPO, "tests", "golden")
 
+import oracle.cpu_numerics  # noqa: E402,F401  (the CPU arithmetic the golden fixtures were recorded with, before any is done)
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
@@ -27,7 +29,8 @@ def pytest_collection_modifyitems(config, items):
 
 
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
+    from oracle import golden_store
+    return golden_store.load(GOLDEN, name)
 
 
 @pytest.fixture(scope="session")
