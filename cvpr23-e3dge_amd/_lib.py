@@ -9,7 +9,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E3DGE_LIB_PATH") or os.path.join(_HERE, "lib", "libe3dge_hip.so")   # override: kernel A/B variants
-ABI_VERSION = 14
+ABI_VERSION = 15
 PREC_F32, PREC_F16X3, PREC_F16X3_V1, PREC_F16X3_G2 = 0, 1, 2, 3
 AMAX_FLOATS = 64 * 32           # E3DGE_AMAX_FLOATS: one amax buffer (include/e3dge_hip.h)
 
@@ -82,7 +82,7 @@ class Dec2Plan(ctypes.Structure):
                 ("n_mod", _i32), ("mod_rows", _i32), ("mod_co", _i32), ("n_latent", _i32), ("style_dim", _i32), ("reserved0", _i32),
                 ("conv1", Dec2Conv), ("rgb1", Dec2Rgb),
                 ("up", Dec2Conv * DEC2_MAX_UP), ("conv", Dec2Conv * DEC2_MAX_UP), ("rgb", Dec2Rgb * DEC2_MAX_UP),
-                ("act", _vp * (2 * DEC2_MAX_UP + 2)), ("tbuf", _vp * DEC2_MAX_UP), ("amax", _vp), ("meta", _vp),
+                ("act", _vp * (2 * DEC2_MAX_UP + 2)), ("amax", _vp), ("meta", _vp),
                 ("fir_blur", _vp), ("fir_up", _vp), ("negative_slope", _f32), ("act_scale", _f32),
                 ("kernel_ms", ctypes.POINTER(ctypes.c_float)), ("n_kernel_ms", _i32), ("reserved1", _i32),
                 ("fir_blur_1d", _f32 * 4), ("fir_blur_separable", _i32), ("save_for_backward", _i32)]
@@ -151,7 +151,6 @@ SIGNATURES = {
     "e3dge_amax_rows": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp]),
     "e3dge_modconv3x3": (_i32, [ctypes.POINTER(ModconvArgs), _vp]),
     "e3dge_dec2_act_words": (_i64, [_i32, _i32, _i32]),
-    "e3dge_dec2_tbuf_floats": (_i64, [_i32, _i32, _i32]),
     "e3dge_dec2_prepack_weights": (_i32, [_vp, _vp, _f32, _i32, _i32, _vp]),
     "e3dge_dec2_num_launches": (_i32, [_i32]),
     "e3dge_dec2_forward": (_i32, [ctypes.POINTER(Dec2Plan), _vp]),

@@ -216,7 +216,7 @@ struct PkConvK {
     const float* in_amax;          // measured max |input| (amax buffer)
     const float* noise; const float* noise_w; const float* noise_amax; const float* bias;
     unsigned char* y;              // stride-1: packed output (B, Co/8, 2, H+2, W+2)
-    float* t;                      // up-sampling: fp32 (B, Co, 2H+3, 2W+4), T(y, x) at [y + 1][x + 2]
+    float* t;                      // unused (as are cw .. tpl below): kept so that the kernels' argument layout stays as it was
     int* out_meta;
     float* out_amax;
     // fused ToRGB of the last convolution (RGB variants): (B, 3, Co) table, (3) bias, skip (B, 3, H/2, W/2) or null, 4x4 FIR, out (B, 3, H, W)
@@ -226,8 +226,7 @@ struct PkConvK {
     int B, Ci, Co, H, W;
     int n_chunks, noise_batch;
     int tiles_x, tiles_y, co_blocks, n_tiles;
-    // up-sampling: positions (i, j) in [0, H] x [0, W] are processed per column block [j0, j0 + cwb), flattened q = i cwb + (j - j0)
-    int cw, cwl, nblk, tpf, tpl;   // block width (all but the last / the last), blocks, WG tiles per full / last block
+    int cw, cwl, nblk, tpf, tpl;
     // data-gradient launches (BWD, round 5; decoder2_bwd.h): the "input" x is a packed GRADIENT, the weight images are the transposed ones
     const unsigned char* mask_act; // packed FORWARD activation of the output's shape: the sign of its hi half selects lrelu' (1 or slope)
     const float* rgbt_d;           // (B, 3, H, W) gradient of this level's ToRGB output or null; its (scale W) s table is rgb_wm
@@ -811,407 +810,22 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
     PK_T_DONE(NW);
 }
 
-// ---- stride-2 transposed 3x3 (conv_transpose2d, padding 0) by output phase ---------------------------------------------
-// Position (i, j) in [0, H] x [0, W] produces out(2i + ey, 2j + ex); tap (ky, kx) feeds phase (ky & 1, kx & 1) from
-// x[i - (ky == 2)][j - (kx == 2)]: 4 + 2 + 2 + 1 taps, four distinct input shifts.  Positions are FLATTENED inside column
-// blocks of <= 129 columns (q = i cwb + jj), a workgroup tile is Q consecutive q: no tile is wasted on the +1 position per
-// row/column (the planar kernel spent 1.55x / 1.27x the useful MFMA work at 64^2 / 128^2).  The patch is the rows
-// [i_lo, i_hi + 1] x columns [j0, j0 + cwb] of the padded input.
-template <int NCT, int NPT, int WCO, int WQ, int NPIXMAX>
-__global__ void __launch_bounds__(64 * WCO * WQ) pkconv_up_kernel(const PkConvK a) {
-    constexpr int NW = WCO * WQ, Q = 32 * NPT * WQ;
-    constexpr int NCTB = NCT * WCO, XPLANE = NPIXMAX * 16, XST = 4 * XPLANE, WST = NCTB * kPkSlab, STAGE = XST + WST;
-    constexpr int NWP = NCTB * 18;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_pk[];
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, col = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wq = wave % WQ, wco = wave / WQ;
-    const int my_tiles = (a.n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int nsteps = my_tiles * a.n_chunks;
-    if (nsteps <= 0) return;
-    const int HP = a.H + 2, WP = a.W + 2, G = a.Ci >> 3;
-    const int64_t plane_b = (int64_t)HP * WP * 16;
-    const int TR = 2 * a.H + 3, TP = 2 * a.W + 4;
-    const float oscale = pow2_bits((unsigned)a.in_meta[0] - 21u);
-    const int tiles_per_img = (a.nblk - 1) * a.tpf + a.tpl;
-
-    struct Pos { int k, c, b, cb, j0, cwb, q0, i_lo, npix; };
-    auto tile_of = [&](Pos& p) {
-        if (p.k >= my_tiles) return;
-        int L = xcd_logical((int)blockIdx.x + p.k * (int)gridDim.x, a.n_tiles);
-        p.cb = L % a.co_blocks; L /= a.co_blocks;
-        const int idx = L % tiles_per_img; p.b = L / tiles_per_img;
-        int blk, qt;
-        if (idx < (a.nblk - 1) * a.tpf) { blk = idx / a.tpf; qt = idx - blk * a.tpf; p.cwb = a.cw; }
-        else { blk = a.nblk - 1; qt = idx - blk * a.tpf; p.cwb = a.cwl; }
-        p.j0 = blk * a.cw;
-        p.q0 = qt * Q;
-        const int qlast = min(p.q0 + Q, (a.H + 1) * p.cwb) - 1;
-        p.i_lo = p.q0 / p.cwb;
-        p.npix = (qlast / p.cwb - p.i_lo + 2) * (p.cwb + 1);
-    };
-    auto advance = [&](Pos& p) { if (++p.c == a.n_chunks) { p.c = 0; ++p.k; tile_of(p); } };
-
-    constexpr int NPW = (NWP + 4 * ((NPIXMAX + 63) / 64) + NW - 1) / NW, PPT = (NPW + 5) / 6;   // piece slots per wave (upper bound), per tap
-    auto issue = [&](const Pos& ps, int stage, int j_lo, int j_hi) {
-        const uint32_t xl = lds_u32(smem_pk + stage * STAGE), wl = xl + XST;
-        const unsigned char* wsrc = a.wimg + (int64_t)ps.b * a.wimg_bytes + ((int64_t)(ps.cb * NCTB) * a.n_chunks + ps.c) * kPkSlab;
-        const unsigned char* xsrc = a.x + ((int64_t)(ps.b * G + 2 * ps.c) * 2) * plane_b + ((int64_t)ps.i_lo * WP + ps.j0) * 16;
-        const int pwr = ps.cwb + 1, npp = (ps.npix + 63) >> 6;
-        const float rcp = 1.0f / (float)pwr;
-        const int npiece = NWP + 4 * npp;
-        for (int j = j_lo; j < j_hi; ++j) {
-            const int i = wave + j * NW;
-            if (i >= npiece) break;
-            if (i < NWP) {
-                const int ct = i / 18, pc = i - ct * 18;
-                dma_piece(wsrc + (int64_t)ct * a.n_chunks * kPkSlab + pc * 1024, (uint32_t)lane * 16u, wl + ct * kPkSlab + pc * 1024);
-            } else {
-                const int p = i - NWP, pl = p / npp, pp = p - pl * npp;
-                const int e = pp * 64 + lane;
-                if (e < ps.npix) {
-                    const int prow = div_small(e, pwr, rcp), pcol = e - prow * pwr;
-                    dma_piece(xsrc + pl * plane_b, (uint32_t)(prow * WP + pcol) * 16u, xl + pl * XPLANE + pp * 1024);
-                }
-            }
-        }
-    };
-
-    Pos p_cur{0, 0, 0, 0, 0, 1, 0, 0, 0};
-    tile_of(p_cur);
-    Pos p_nx1 = p_cur; advance(p_nx1);
-    issue(p_cur, 0, 0, NPW);
-
-    f32x16 acc[4][NCT][NPT];
-    float amax_l = 0.0f;
-    int pixb[NPT], pi[NPT], pj[NPT];        // patch index of the position's (a = 0, b = 0) entry; its (i, j); j < 0: no position
-    int pwr_cur = 1;
-    PK_T_INIT;
-
-    for (int step = 0; step < nsteps; ++step) {
-        const int cur = step & 1;
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        PK_T(0);
-        const bool has_next = step + 1 < nsteps;
-        if (p_cur.c == 0) {
-#pragma unroll
-            for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                    for (int pt = 0; pt < NPT; ++pt) acc[ph][ct][pt] = zero16();
-            const int cwb = p_cur.cwb, qn = (a.H + 1) * cwb;
-            const float rcp = 1.0f / (float)cwb;
-            pwr_cur = cwb + 1;
-#pragma unroll
-            for (int pt = 0; pt < NPT; ++pt) {
-                const int q = p_cur.q0 + (wq * NPT + pt) * 32 + col;
-                const int qc = min(q, qn - 1);
-                const int i = div_small(qc, cwb, rcp), jj = qc - i * cwb;
-                pixb[pt] = (i - p_cur.i_lo) * pwr_cur + jj;
-                pi[pt] = i;
-                pj[pt] = q < qn ? p_cur.j0 + jj : -1;
-            }
-        }
-        {
-            const unsigned char* xb = smem_pk + cur * STAGE + (size_t)(half * 2) * XPLANE;
-            const unsigned char* wb = smem_pk + cur * STAGE + XST + (size_t)(wco * NCT) * kPkSlab + lane * 16;
-            u32x4 bh[NPT][4], bl[NPT][4];       // shift s = 2 a + b: rows i - 1 + a, columns j - 1 + b of the input
-#pragma unroll
-            for (int pt = 0; pt < NPT; ++pt)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const int pix = pixb[pt] + (s >> 1) * pwr_cur + (s & 1);
-                    bh[pt][s] = *reinterpret_cast<const u32x4*>(xb + pix * 16);
-                    bl[pt][s] = *reinterpret_cast<const u32x4*>(xb + XPLANE + pix * 16);
-                }
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int ky = tap / 3, kx = tap % 3;
-                const int s = (ky == 2 ? 0 : 2) + (kx == 2 ? 0 : 1), ph = (ky & 1) * 2 + (kx & 1);
-                u32x4 ah[NCT], al[NCT];
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    ah[ct] = *reinterpret_cast<const u32x4*>(wb + ct * kPkSlab + (tap * 2 + 0) * 1024);
-                    al[ct] = *reinterpret_cast<const u32x4*>(wb + ct * kPkSlab + (tap * 2 + 1) * 1024);
-                }
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                    for (int pt = 0; pt < NPT; ++pt) {
-                        f32x16& d = acc[ph][ct][pt];
-                        d = mfma16(ah[ct], bh[pt][s], d);
-                        d = mfma16(al[ct], bh[pt][s], d);
-                        d = mfma16(ah[ct], bl[pt][s], d);
-                    }
-                if (has_next && tap * PPT < NPW) issue(p_nx1, cur ^ 1, tap * PPT, min((tap + 1) * PPT, NPW));
-                if (tap % 3 == 2) __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        PK_T(2);
-        if (p_cur.c == a.n_chunks - 1) {                    // ---- epilogue: the four phases of a position as two float2 rows ----
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                const int cot = p_cur.cb * NCTB + wco * NCT + ct;
-#pragma unroll
-                for (int pt = 0; pt < NPT; ++pt) {
-                    if (pj[pt] >= 0) {
-                        float* tp = a.t + (((int64_t)p_cur.b * a.Co + cot * 32 + 4 * half) * TR + 2 * pi[pt] + 1) * TP + 2 * pj[pt] + 2;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            float* tr = tp + (int64_t)((r & 3) + 8 * (r >> 2)) * TR * TP;
-#pragma unroll
-                            for (int ey = 0; ey < 2; ++ey) {
-                                const float v0 = acc[2 * ey][ct][pt][r] * oscale, v1 = acc[2 * ey + 1][ct][pt][r] * oscale;
-                                amax_l = fmaxf(amax_l, fmaxf(fabsf(v0), fabsf(v1)));
-                                *reinterpret_cast<float2*>(tr + ey * TP) = make_float2(v0, v1);
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        PK_T(3);
-        p_cur = p_nx1;
-        advance(p_nx1);
-    }
-    if (a.out_amax) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) amax_l = fmaxf(amax_l, __shfl_xor(amax_l, off, kWave));
-        if (lane == 0) atomic_max_nonneg(a.out_amax + (((int)blockIdx.x * NW + wave) & (kAmaxSlots - 1)) * kAmaxStride, amax_l);
-    }
-    PK_T_DONE(NW);
-}
-
 // ---- up-sampling StyledConv in ONE kernel: transposed conv by output phase + blur + noise + bias + lrelu -> packed ------
-// At the two highest resolutions the intermediate T = conv_transpose(x) (fp32, (2H+1)^2) is the dominant HBM traffic of the
-// decoder (written by the conv, read by the blur: 268 MB of 615 MB at 1024^2).  Here it never leaves the CU: a workgroup owns a
-// block of 16 x 32 POSITIONS (i0 - 1 .. i0 + 14) x (j0 - 1 .. j0 + 30) -- one position row per MFMA column tile, two rows per
-// wave -- accumulates the four output phases over all input channels, then, eight output channels at a time, writes the
-// 32 x 64 patch of T into LDS (zeros for positions outside the image = the blur's padding), blurs it (4x4 FIR, same tap order as
-// e3dge_upfirdn2d), applies StyledConv's tail and stores 28 x 60 pixels of packed entries.  Recomputed halo: 512 / 420 positions.
-// The operand scale of the output cannot come from max|T| (T is produced here): |T| <= amax_in sqrt(4 ci) (at most four taps
-// of a unit-norm demodulated filter reach one output phase).
-// NPT = position rows per wave: 2 -> 16 x 32 positions, 28 x 60 pixels per tile; 1 -> 8 x 32 positions, 12 x 60 pixels (more,
-// smaller tiles for the deep low-resolution levels, whose 16-row tiling leaves half of the CUs without a tile).
-constexpr int kUbTW = 30, kUbPC = kUbTW + 3;
-
-template <int NPT>
-__global__ void __launch_bounds__(512) pkconv_upblur_kernel(const PkConvK a, const float* __restrict__ fir) {
-    constexpr int kUbTH = 8 * NPT - 2, kUbPR = kUbTH + 3, kUbNpix = kUbPR * kUbPC, kUbTlBytes = 8 * (16 * NPT) * 64 * 4;
-    constexpr int TLR = 16 * NPT, ORows = 2 * kUbTH;                         // rows of the T patch / output rows of a tile
-    constexpr int NW = 8, XPLANE = kUbNpix * 16, XST = 4 * XPLANE, WST = kPkSlab, STAGE = XST + WST;
-    constexpr int NWP = 18, NPP = (kUbNpix + 63) / 64, NPIECE = NWP + 4 * NPP, NPW = (NPIECE + NW - 1) / NW, PPT = (NPW + 5) / 6;
-    static_assert(kUbTlBytes <= 2 * STAGE, "the T patch aliases the staging buffers");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_pk[];
-    float* const tl = reinterpret_cast<float*>(smem_pk);                     // [8 ch][TLR rows][64 cols], aliases the stages
-    float* const bias_s = reinterpret_cast<float*>(smem_pk + 2 * STAGE);
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, col = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int my_tiles = (a.n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    if (my_tiles <= 0) return;
-    const int HP = a.H + 2, WP = a.W + 2, G = a.Ci >> 3, GO = a.Co >> 3, R = 2 * a.H;
-    const int64_t plane_b = (int64_t)HP * WP * 16, oplane = (int64_t)(R + 2) * (R + 2);
-    const float oscale = pow2_bits((unsigned)a.in_meta[0] - 21u);
-    const float nw = a.noise ? a.noise_w[0] : 0.0f;
-    const float nza = a.noise ? fabsf(nw) * amax_read(a.noise_amax, lane) : 0.0f;
-    const float bound = a.act_scale * (amax_read(a.in_amax, lane) * a.knorm * 1.002f + nza + a.bias_amax) * 1.001f;   // knorm = sqrt(4 ci)
-    const unsigned eb_out = scale_exponent(bound);
-    const float kmul = a.act_scale * pow2_bits(268u - eb_out), kinv = 1.0f / pow2_bits(268u - eb_out);
-    if (blockIdx.x == 0 && tid == 0) a.out_meta[0] = (int)eb_out;
-    for (int i = tid; i < a.Co; i += 512) bias_s[i] = a.bias[i];
-    float kf[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) kf[p][q] = fir[(3 - p) * 4 + (3 - q)];
-
-    // blur-phase role of this thread: output row ry (0 .. ORows - 1), pixels 4 gx .. 4 gx + 3 (gx 0..14).  Sixteen lanes per row
-    // (gx = 15 idles): with fifteen, the 16-lane groups of a ds_read_b128 straddled two rows of the 256-byte-pitch patch and a
-    // quarter of the LDS cycles were bank conflicts (SQ_LDS_BANK_CONFLICT 2.2e6 of 8.5e6, profiles/r3_decoder_pmc.txt).
-    const int ry = tid >> 4, gx = tid & 15;
-    const bool blur_thread = ry < ORows && gx < 15;
-    float amax_l = 0.0f;
-    PK_T_INIT;
-    const int nsteps = my_tiles;
-
-    for (int k = 0; k < my_tiles; ++k) {
-        int L = xcd_logical((int)blockIdx.x + k * (int)gridDim.x, a.n_tiles);
-        const int cb = L % a.co_blocks; L /= a.co_blocks;
-        const int txi = L % a.tiles_x; L /= a.tiles_x;
-        const int tyi = L % a.tiles_y, b = L / a.tiles_y;
-        const int i0 = tyi * kUbTH, j0 = txi * kUbTW;                    // first position whose outputs this tile stores
-        auto issue = [&](int c, int stage, int j_lo, int j_hi) {
-            const uint32_t xl = lds_u32(smem_pk + stage * STAGE), wl = xl + XST;
-            const unsigned char* wsrc = a.wimg + (int64_t)b * a.wimg_bytes + ((int64_t)cb * a.n_chunks + c) * kPkSlab;
-            const unsigned char* xsrc = a.x + ((int64_t)(b * G + 2 * c) * 2) * plane_b;
-            for (int j = j_lo; j < j_hi; ++j) {
-                const int i = wave + j * NW;
-                if (i >= NPIECE) break;
-                if (i < NWP) {
-                    dma_piece(wsrc + i * 1024, (uint32_t)lane * 16u, wl + i * 1024);
-                } else {
-                    const int p = i - NWP, pl = p / NPP, pp = p - pl * NPP;
-                    const int e = pp * 64 + lane;
-                    if (e < kUbNpix) {
-                        const int prow = e / kUbPC, pcol = e - prow * kUbPC;
-                        // padded input rows i0 - 1 + prow, clamped into the buffer: positions outside the image are zeroed below
-                        const int gy = min(max(i0 - 1 + prow, 0), HP - 1), gx_ = min(max(j0 - 1 + pcol, 0), WP - 1);
-                        dma_piece(xsrc + pl * plane_b, (uint32_t)(gy * WP + gx_) * 16u, xl + pl * XPLANE + pp * 1024);
-                    }
-                }
-            }
-        };
-        __syncthreads();                                  // the previous tile's last blur round has finished reading tl
-        issue(0, 0, 0, NPW);
-        // the blur threads' noise (the same for every channel), requested while the tile's first weights are on their way
-        float nzv[4] = {0.f, 0.f, 0.f, 0.f};
-        const int oy = 2 * i0 + ry, ox0 = 2 * j0 + 4 * gx;
-        if (blur_thread && a.noise) {
-            const int oyc = min(oy, R - 1);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                nzv[j] = a.noise[(int64_t)(a.noise_batch > 1 ? b : 0) * R * R + (int64_t)oyc * R + min(ox0 + j, R - 1)];
-        }
-
-        f32x16 acc[4][NPT];
-#pragma unroll
-        for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-            for (int pt = 0; pt < NPT; ++pt) acc[ph][pt] = zero16();
-        for (int c = 0; c < a.n_chunks; ++c) {
-            const int cur = c & 1;
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-            PK_T(0);
-            const bool has_next = c + 1 < a.n_chunks;
-            const unsigned char* xb = smem_pk + cur * STAGE + (size_t)(half * 2) * XPLANE;
-            const unsigned char* wb = smem_pk + cur * STAGE + XST + lane * 16;
-            u32x4 bh[NPT][4], bl[NPT][4];       // shift s = 2 a + b: input rows i - 1 + a, columns j - 1 + b
-#pragma unroll
-            for (int pt = 0; pt < NPT; ++pt)
-#pragma unroll
-                for (int sft = 0; sft < 4; ++sft) {
-                    const int pix = (wave * NPT + pt + (sft >> 1)) * kUbPC + col + (sft & 1);
-                    bh[pt][sft] = *reinterpret_cast<const u32x4*>(xb + pix * 16);
-                    bl[pt][sft] = *reinterpret_cast<const u32x4*>(xb + XPLANE + pix * 16);
-                }
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int ky = tap / 3, kx = tap % 3;
-                const int sft = (ky == 2 ? 0 : 2) + (kx == 2 ? 0 : 1), ph = (ky & 1) * 2 + (kx & 1);
-                const u32x4 ah = *reinterpret_cast<const u32x4*>(wb + (tap * 2 + 0) * 1024);
-                const u32x4 al = *reinterpret_cast<const u32x4*>(wb + (tap * 2 + 1) * 1024);
-#pragma unroll
-                for (int pt = 0; pt < NPT; ++pt) {
-                    f32x16& d = acc[ph][pt];
-                    d = mfma16(ah, bh[pt][sft], d);
-                    d = mfma16(al, bh[pt][sft], d);
-                    d = mfma16(ah, bl[pt][sft], d);
-                }
-                if (has_next && tap * PPT < NPW) issue(c + 1, cur ^ 1, tap * PPT, min((tap + 1) * PPT, NPW));
-                if (tap % 3 == 2) __builtin_amdgcn_sched_barrier(0);
-            }
-            PK_T(1);
-        }
-        // ---- epilogue: eight output channels per round through the LDS patch of T ----
-        // The patch is stored with CHANNEL PAIRS interleaved -- tl[pair][row][col][2] -- so that the FIR and the tail run on
-        // v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 (two channels per instruction; the even-aligned register pairs come straight out
-        // of the ds_read_b128): 256 instead of 512 FMA instructions per thread and round.  (Packed fp32 next to MFMAs is an
-        // anti-lever, MI355X_MICROARCH; this phase has no MFMAs.)
-        bool pos_ok[NPT];
-#pragma unroll
-        for (int pt = 0; pt < NPT; ++pt) {
-            const int pi = i0 - 1 + wave * NPT + pt, pj = j0 - 1 + col;
-            pos_ok[pt] = pi >= 0 && pi <= a.H && pj >= 0 && pj <= a.W;
-        }
-        f32x2 nz2[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const float t_ = a.noise ? __fmul_rn(nw, nzv[j]) : 0.0f; nz2[j] = f32x2{t_, t_}; }
-        bool px_ok[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) px_ok[j] = oy < R && ox0 + j < R;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            __syncthreads();                              // staging buffers (first round) / the previous round's readers are done
-#pragma unroll
-            for (int pt = 0; pt < NPT; ++pt) {
-                const int prow = wave * NPT + pt;
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {             // channel pair 2 half + q of the group: channels 4 half + 2 q, + 1
-                    float* trow = tl + (((size_t)(2 * half + q) * TLR + 2 * prow) * 64 + 2 * col) * 2;
-#pragma unroll
-                    for (int ey = 0; ey < 2; ++ey) {
-                        f32x4 v4;                           // (column 2 col: channels e = 0, 1), (column 2 col + 1: e = 0, 1)
-                        v4[0] = pos_ok[pt] ? acc[2 * ey][pt][4 * g4 + 2 * q] * oscale : 0.0f;
-                        v4[1] = pos_ok[pt] ? acc[2 * ey][pt][4 * g4 + 2 * q + 1] * oscale : 0.0f;
-                        v4[2] = pos_ok[pt] ? acc[2 * ey + 1][pt][4 * g4 + 2 * q] * oscale : 0.0f;
-                        v4[3] = pos_ok[pt] ? acc[2 * ey + 1][pt][4 * g4 + 2 * q + 1] * oscale : 0.0f;
-                        *reinterpret_cast<f32x4*>(trow + ey * 128) = v4;
-                    }
-                }
-            }
-            __syncthreads();
-            PK_T(2);
-            if (blur_thread) {
-                const int gout = cb * 4 + g4;
-                u32x4 hi[4], lo[4];
-                float m = 0.0f;
-#pragma unroll
-                for (int cp = 0; cp < 4; ++cp) {
-                    f32x2 ac[4] = {f32x2{0.f, 0.f}, f32x2{0.f, 0.f}, f32x2{0.f, 0.f}, f32x2{0.f, 0.f}};
-#pragma unroll
-                    for (int ky = 0; ky < 4; ++ky) {
-                        const float* row = tl + (((size_t)cp * TLR + ry + 1 + ky) * 64 + 4 * gx) * 2;     // tl row <-> y = 2 i0 - 2 + row
-                        f32x2 in[8];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const f32x4 q4 = *reinterpret_cast<const f32x4*>(row + 4 * i);
-                            in[2 * i] = f32x2{q4[0], q4[1]};
-                            in[2 * i + 1] = f32x2{q4[2], q4[3]};
-                        }
-#pragma unroll
-                        for (int kx = 0; kx < 4; ++kx) {
-                            const f32x2 kk = f32x2{kf[ky][kx], kf[ky][kx]};
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) ac[j] = __builtin_elementwise_fma(in[j + kx + 1], kk, ac[j]);   // tl column <-> x = 2 j0 - 2 + column
-                        }
-                    }
-                    const f32x2 bv = *reinterpret_cast<const f32x2*>(bias_s + gout * 8 + 2 * cp);
-                    const f32x2 sl = f32x2{a.slope, a.slope}, km = f32x2{kmul, kmul};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        f32x2 tv = (ac[j] + nz2[j]) + bv;                    // (conv + noise) + bias, as the unfused kernels round it
-                        const f32x2 ls = tv * sl;
-                        tv = f32x2{fmaxf(tv[0], ls[0]), fmaxf(tv[1], ls[1])} * km;     // lrelu (0 <= slope <= 1) * act_scale * 2^k
-                        if (px_ok[j]) m = fmaxf(m, fmaxf(fabsf(tv[0]), fabsf(tv[1])));
-                        SPLIT2_TO(tv[0], tv[1], hi[j][cp], lo[j][cp]);
-                    }
-                }
-                amax_l = fmaxf(amax_l, m);
-                if (oy < R) {
-                    u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(a.y) + ((int64_t)(b * GO + gout) * 2) * oplane + (int64_t)(oy + 1) * (R + 2) + ox0 + 1;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (px_ok[j]) { dst[j] = hi[j]; dst[oplane + j] = lo[j]; }
-                }
-            }
-            PK_T(3);
-        }
-    }
-    if (a.out_amax) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) amax_l = fmaxf(amax_l, __shfl_xor(amax_l, off, kWave));
-        if (lane == 0) atomic_max_nonneg(a.out_amax + (((int)blockIdx.x * NW + wave) & (kAmaxSlots - 1)) * kAmaxStride, amax_l * kinv);
-    }
-    PK_T_DONE(NW);
-}
-
-// ---- the same layer, second generation (round 4): separable FIR, horizontal pass in registers, prefetch under the epilogue ----
-// What round 3's counters said about pkconv_upblur_kernel (profiles/r3_decoder_pmc.txt): 7 VALU per MFMA (the 4x4 FIR: ~1,100
-// VALU per thread and round of eight channels), 36 % of the LDS cycles bank conflicts, 20 % matrix-pipe busy, and the first
-// chunk of every tile waited for in the open (the T patch aliased BOTH staging buffers).  Here:
+// The transposed 3x3 (conv_transpose2d, stride 2, padding 0) by output phase: position (i, j) in [0, H] x [0, W] produces
+// T(2i + ey, 2j + ex); tap (ky, kx) feeds phase (ky & 1, kx & 1) from x[i - (ky == 2)][j - (kx == 2)]: 4 + 2 + 2 + 1 taps, four
+// distinct input shifts.  At the two highest resolutions T = conv_transpose(x) (fp32, (2H+1)^2) written by one kernel and read
+// by a separate blur was the dominant HBM traffic of the decoder (268 MB of 615 MB at 1024^2).  Here it never leaves the CU: a
+// workgroup accumulates the four output phases of a block of positions over all input channels, blurs them (zeros for
+// positions outside the image = the blur's padding), applies StyledConv's tail and stores packed entries; halo positions are
+// recomputed.  The operand scale of the output cannot come from max|T| (T is produced here): |T| <= amax_in sqrt(4 ci) (at most
+// four taps of a unit-norm demodulated filter reach one output phase).
+// Second generation (round 4): separable FIR, horizontal pass in registers, prefetch under the epilogue.  A blur kernel without a
+// symmetric rank-one factor takes the planar path (stylesdf_model.py, Decoder._dec2_ok).
+// What round 3's counters said about the first generation (4x4 FIR on a T patch in LDS; profiles/r3_decoder_pmc.txt): 7 VALU
+// per MFMA (the 4x4 FIR: ~1,100 VALU per thread and round of eight channels), 36 % of the LDS cycles bank conflicts, 20 %
+// matrix-pipe busy, and the first chunk of every tile waited for in the open (the T patch aliased BOTH staging buffers).  Here:
 //  * the FIR is applied as its two 1-D factors (Blur's kernel is make_kernel([1,3,3,1]): rank one; the host checks and passes
-//    the factor, anything else takes the first-generation kernel).  The HORIZONTAL pass runs on the accumulators themselves:
+//    the factor, anything else takes the planar path).  The HORIZONTAL pass runs on the accumulators themselves:
 //    a lane holds position column j of its row, its neighbours j-1 / j+1 are the adjacent lanes (v_mov_dpp wave_shr / wave_shl;
 //    the lanes at the ends of a 32-column tile are the halo columns whose results are never stored), 8 FMAs + 3 DPP moves per
 //    (row, channel) for the two output columns 2j, 2j+1 -- no LDS traffic, no 7-column windows;
@@ -1512,288 +1126,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) pkconv_upblur2_kerne
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Blur of an up-sampling layer + StyledConv's tail, T (fp32, zero-bordered) -> packed:  u = lrelu(upfirdn2d(T, k, pad (1, 1))
-// + noise_w noise + bias) * act_scale  (stylesdf_model.py:346, :459-466, :500-507).  Workgroup = 8 channels (one packed entry
-// group) x 16 rows x 64 columns; a thread finishes 4 adjacent pixels of all 8 channels and stores their hi / lo entries.
-// Tap order per output (ky, then kx; one fma chain) is the one of e3dge_upfirdn2d.
-// ---------------------------------------------------------------------------------------------------------------------
-struct PkBlurK {
-    const float* t; unsigned char* y; const float* fir; const float* noise; const float* noise_w; const float* noise_amax;
-    const float* bias; const float* t_amax; int* out_meta; float* out_amax;
-    float bias_amax, slope, act_scale;
-    int B, C, R, noise_batch, tiles_x, tiles_y;
-};
-constexpr int kPbRows = 16, kPbCols = 64, kPbU = kPbRows + 3, kPbPitch = 68;
-
-__global__ void __launch_bounds__(256) pk_blur_kernel(const PkBlurK a) {
-    __shared__ __attribute__((aligned(16))) float u[8 * kPbU * kPbPitch];
-    const int tid = threadIdx.x, lane = tid & 63;
-    int bid = blockIdx.x;
-    const int tx_i = bid % a.tiles_x; bid /= a.tiles_x;
-    const int ty_i = bid % a.tiles_y; bid /= a.tiles_y;
-    const int G = a.C >> 3, g = bid % G, b = bid / G;
-    const int R = a.R, TR = R + 3, TP = R + 4;
-    const int oy0 = ty_i * kPbRows, ox0 = tx_i * kPbCols;
-
-    const float nw = a.noise ? a.noise_w[0] : 0.0f;
-    const float nza = a.noise ? fabsf(nw) * amax_read(a.noise_amax, lane) : 0.0f;
-    const float bound = a.act_scale * (amax_read(a.t_amax, lane) * 1.001f + nza + a.bias_amax) * 1.001f;
-    const unsigned eb = scale_exponent(bound);
-    const float sc = pow2_bits(268u - eb);
-    if (blockIdx.x == 0 && tid == 0) a.out_meta[0] = (int)eb;
-
-    // stage 8 planes of 19 rows x 17 groups of four columns: T rows oy0 - 1 .., columns ox0 - 2 .. (one column more than the taps
-    // need: with T(y, x) stored at [y + 1][x + 2] every group is one aligned 16-byte load; the T buffer carries its own zero border)
-    constexpr int NGR = kPbPitch / 4, NE = 8 * kPbU * NGR, NIT = (NE + 255) / 256;
-    const float* __restrict__ tb = a.t + ((int64_t)b * a.C + 8 * g) * TR * TP;
-    f32x4 sv[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int idx = min(tid + it * 256, NE - 1);
-        const int ch = idx / (kPbU * NGR), rem = idx - ch * (kPbU * NGR);
-        const int r = rem / NGR, cg = rem - r * NGR;
-        const int row = min(oy0 + r, TR - 1), cc = min(ox0 + 4 * cg, TP - 4);
-        sv[it] = *reinterpret_cast<const f32x4*>(tb + ((int64_t)ch * TR + row) * TP + cc);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int idx = tid + it * 256;
-        if (idx < NE) *reinterpret_cast<f32x4*>(u + 4 * idx) = sv[it];       // u[ch][r][4 cg ..]: the same linear order
-    }
-    float kf[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) kf[p][q] = a.fir[(3 - p) * 4 + (3 - q)];
-    __syncthreads();
-
-    const int tx = tid & 15, ty = tid >> 4;
-    const int oy = oy0 + ty, ox = ox0 + 4 * tx;
-    const bool row_ok = oy < R;
-    float nz[4] = {0.f, 0.f, 0.f, 0.f};
-    if (a.noise && row_ok) {
-        const float* np_ = a.noise + (int64_t)(a.noise_batch > 1 ? b : 0) * R * R + (int64_t)oy * R + ox;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (ox + j < R) nz[j] = __fmul_rn(nw, np_[j]);
-    }
-    float amax_l = 0.0f;
-    u32x4 hi[4], lo[4];                      // per pixel j: four words = eight channels
-#pragma unroll
-    for (int cp = 0; cp < 4; ++cp) {         // channel pairs (2 cp, 2 cp + 1) -> word cp of every pixel
-        float v[2][4];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int ch = 2 * cp + e;
-            float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ky = 0; ky < 4; ++ky) {
-                const float* row = u + (ch * kPbU + ty + ky) * kPbPitch + 4 * tx;
-                const f32x4 q0 = *reinterpret_cast<const f32x4*>(row), q1 = *reinterpret_cast<const f32x4*>(row + 4);
-                const float in[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
-#pragma unroll
-                for (int kx = 0; kx < 4; ++kx)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = fmaf(in[j + kx + 1], kf[ky][kx], acc[j]);     // u column c <-> x = ox0 - 2 + c
-            }
-            const float bv = a.bias ? a.bias[8 * g + ch] : 0.0f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float t = acc[j];
-                if (a.noise) t = __fadd_rn(t, nz[j]);
-                t = t + bv;
-                t = (t > 0.0f ? t : t * a.slope) * a.act_scale;
-                if (row_ok && ox + j < R) amax_l = fmaxf(amax_l, fabsf(t));
-                v[e][j] = t * sc;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) SPLIT2_TO(v[0][j], v[1][j], hi[j][cp], lo[j][cp]);
-    }
-    // Store through LDS: a thread holds four ADJACENT pixels, so its 16-byte stores would leave 48-byte gaps between lanes (every
-    // store instruction touching 32 lines for 1 KiB).  The staging buffer is free now: entries go to LDS as [plane][row][pixel]
-    // and come back in linear order -- each store instruction then writes 64 consecutive entries of one output row.
-    __syncthreads();
-    u32x4* const eb_lds = reinterpret_cast<u32x4*>(u);              // 2 planes x 16 rows x 64 pixels x 16 B = 32 KiB
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        eb_lds[(0 * kPbRows + ty) * kPbCols + 4 * tx + j] = hi[j];
-        eb_lds[(1 * kPbRows + ty) * kPbCols + 4 * tx + j] = lo[j];
-    }
-    __syncthreads();
-    {
-        const int64_t plane = (int64_t)(R + 2) * (R + 2);
-        u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(a.y) + ((int64_t)(b * G + g) * 2) * plane;
-#pragma unroll
-        for (int it = 0; it < 2 * kPbRows * kPbCols / 256; ++it) {
-            const int e = tid + it * 256;
-            const int hl = e / (kPbRows * kPbCols), rem = e - hl * (kPbRows * kPbCols);
-            const int r = rem / kPbCols, c = rem - r * kPbCols;
-            if (oy0 + r < R && ox0 + c < R) dst[hl * plane + (int64_t)(oy0 + r + 1) * (R + 2) + ox0 + c + 1] = eb_lds[e];
-        }
-    }
-    if (a.out_amax) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) amax_l = fmaxf(amax_l, __shfl_xor(amax_l, off, kWave));
-        if (lane == 0) atomic_max_nonneg(a.out_amax + (((int)blockIdx.x * 4 + (tid >> 6)) & (kAmaxSlots - 1)) * kAmaxStride, amax_l);
-    }
-}
-
-// The same operation as a PERSISTENT, software-pipelined kernel (default; E3DGE_DEC2_BLUR=1 selects the one above).  The
-// one-shot form is load -> barrier -> compute -> barrier -> store per workgroup with three workgroups per CU: at most ~40 KB per
-// CU are in flight and it streamed 3.0-3.1 TB/s whatever the staging / store pattern (round-3 measurements).  Here a 512-thread
-// workgroup walks 8-row tiles with tile k + 1 arriving by LDS-DMA (per-lane source address, 24 pieces of 1 KiB dealt out between
-// the channel computations of tile k) and the entries leaving LDS-transposed (1 KiB per store instruction); 70 KB of LDS, so two
-// workgroups share a CU and cover each other's waits (cold T rows return after ~3 k cycles under load: one tile of prefetch
-// per workgroup is not enough on its own -- measured with E3DGE_PK_TIMING).  A thread finishes 4 adjacent pixels of 2 channels.
-constexpr int kPb2Rows = 8, kPb2U = kPb2Rows + 3, kPb2Threads = 512;
-constexpr int kPb2StageBytes = 8 * kPb2U * kPbPitch * 4, kPb2EntryBytes = 2 * kPb2Rows * kPbCols * 16;
-constexpr int kPb2Lds = 2 * kPb2StageBytes + kPb2EntryBytes + 4096;        // + bias table (C <= 1024)
-
-__global__ void __launch_bounds__(kPb2Threads) pk_blur2_kernel(const PkBlurK a, int n_tiles, int tiles_y2) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_pb[];
-    unsigned char* const eb_lds = smem_pb + 2 * kPb2StageBytes;
-    float* const bias_s = reinterpret_cast<float*>(eb_lds + kPb2EntryBytes);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = a.C >> 3, R = a.R, TR = R + 3, TP = R + 4;
-    const int my_tiles = (n_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    if (my_tiles <= 0) return;
-
-    const float nw = a.noise ? a.noise_w[0] : 0.0f;
-    const float nza = a.noise ? fabsf(nw) * amax_read(a.noise_amax, lane) : 0.0f;
-    const float bound = a.act_scale * (amax_read(a.t_amax, lane) * 1.001f + nza + a.bias_amax) * 1.001f;
-    const unsigned eb = scale_exponent(bound);
-    const float kmul = a.act_scale * pow2_bits(268u - eb), kinv = 1.0f / pow2_bits(268u - eb);
-    if (blockIdx.x == 0 && tid == 0) a.out_meta[0] = (int)eb;
-    for (int i = tid; i < a.C; i += kPb2Threads) bias_s[i] = a.bias ? a.bias[i] : 0.0f;
-    float kf[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) kf[p][q] = a.fir[(3 - p) * 4 + (3 - q)];
-
-    struct Tile { int b, g, oy0, ox0; };
-    auto tile_at = [&](int k) {
-        int L = xcd_logical((int)blockIdx.x + k * (int)gridDim.x, n_tiles);
-        Tile t;
-        const int tx_i = L % a.tiles_x; L /= a.tiles_x;
-        const int ty_i = L % tiles_y2; L /= tiles_y2;
-        t.g = L % G; t.b = L / G;
-        t.oy0 = ty_i * kPb2Rows; t.ox0 = tx_i * kPbCols;
-        return t;
-    };
-    constexpr int NGR = kPbPitch / 4, NE = 8 * kPb2U * NGR, NPC = (NE + 63) / 64, NPW = (NPC + 7) / 8;   // 1496 groups of four floats, 24 pieces
-    // this wave's pieces j_lo <= j < j_hi (piece wave + 8 j) of tile t; T rows oy0 - 1 .., columns ox0 - 2 .. (T(y, x) lives at
-    // [y + 1][x + 2]: every group of four is one aligned 16-byte element; the T buffer carries its own zero border)
-    auto issue = [&](const Tile& t, int buf, int j_lo, int j_hi) {
-        const float* tb = a.t + ((int64_t)t.b * a.C + 8 * t.g) * TR * TP;
-        const uint32_t dst = lds_u32(smem_pb + buf * kPb2StageBytes);
-        for (int j = j_lo; j < j_hi; ++j) {
-            const int pc = wave + 8 * j;
-            if (pc >= NPC) break;
-            const int e = pc * 64 + lane;
-            if (e < NE) {
-                const int ch = e / (kPb2U * NGR), rem = e - ch * (kPb2U * NGR);
-                const int r = rem / NGR, cg = rem - r * NGR;
-                const int row = min(t.oy0 + r, TR - 1), cc = min(t.ox0 + 4 * cg, TP - 4);
-                dma_piece(tb, (uint32_t)((ch * TR + row) * TP + cc) * 4u, dst + pc * 1024);
-            }
-        }
-    };
-    const int cq = tid >> 7, t7 = tid & 127, tx = t7 & 15, ty = t7 >> 4;       // channel quarter (2 channels), 4-pixel group, row
-    auto load_noise = [&](const Tile& t, float (&nz)[4]) {
-        const int oy = min(t.oy0 + ty, R - 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ox = min(t.ox0 + 4 * tx + j, R - 1);
-            nz[j] = a.noise ? a.noise[(int64_t)(a.noise_batch > 1 ? t.b : 0) * R * R + (int64_t)oy * R + ox] : 0.0f;
-        }
-    };
-
-    Tile t_cur = tile_at(0), t_nx = t_cur;
-    float nz[4], nz_next[4] = {0.f, 0.f, 0.f, 0.f};
-    issue(t_cur, 0, 0, NPW);
-    load_noise(t_cur, nz_next);
-    float amax_l = 0.0f;
-    PK_T_INIT;
-    const int nsteps = my_tiles;
-    for (int k = 0; k < my_tiles; ++k) {
-        // tile k (and its noise) has landed, tile k - 1's stores are out; after the barrier nobody reads the buffers reused below
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        PK_T(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { asm volatile("" : "+v"(nz_next[j])); nz[j] = __fmul_rn(nw, nz_next[j]); }
-        const bool has_next = k + 1 < my_tiles;
-        if (has_next) {
-            t_nx = tile_at(k + 1);
-            issue(t_nx, (k + 1) & 1, 0, 1);
-        }
-        PK_T(1);
-        // ---- compute tile k: 4 pixels x 2 channels per thread ----
-        const float* u = reinterpret_cast<const float*>(smem_pb + (k & 1) * kPb2StageBytes);
-        const bool ok_row = t_cur.oy0 + ty < R;
-        float v[2][4];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int ch = 2 * cq + e;
-            float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ky = 0; ky < 4; ++ky) {
-                const float* row = u + (ch * kPb2U + ty + ky) * kPbPitch + 4 * tx;
-                const f32x4 q0 = *reinterpret_cast<const f32x4*>(row), q1 = *reinterpret_cast<const f32x4*>(row + 4);
-                const float in[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
-#pragma unroll
-                for (int kx = 0; kx < 4; ++kx)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = fmaf(in[j + kx + 1], kf[ky][kx], acc[j]);     // u column c <-> x = ox0 - 2 + c
-            }
-            const float bv = bias_s[8 * t_cur.g + ch];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float tv = acc[j];
-                if (a.noise) tv = __fadd_rn(tv, nz[j]);
-                tv = tv + bv;
-                tv = fmaxf(tv, tv * a.slope) * kmul;                   // lrelu (0 <= slope <= 1) * act_scale * 2^k
-                if (ok_row && t_cur.ox0 + 4 * tx + j < R) amax_l = fmaxf(amax_l, fabsf(tv));
-                v[e][j] = tv;
-            }
-            if (has_next) issue(t_nx, (k + 1) & 1, 1 + e * (NPW / 2), e == 1 ? NPW : 1 + (NPW / 2));
-        }
-        if (has_next) load_noise(t_nx, nz_next);
-        PK_T(2);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                                  // word cq of the pixel's hi and lo entries
-            unsigned hw, lw;
-            SPLIT2_TO(v[0][j], v[1][j], hw, lw);
-            const int pix = ty * kPbCols + 4 * tx + j;
-            *reinterpret_cast<unsigned*>(eb_lds + (size_t)pix * 16 + 4 * cq) = hw;
-            *reinterpret_cast<unsigned*>(eb_lds + (size_t)(kPb2Rows * kPbCols + pix) * 16 + 4 * cq) = lw;
-        }
-        __syncthreads();
-        {   // entries [plane][row][pixel] come back in linear order: 1 KiB per store instruction
-            const int64_t plane = (int64_t)(R + 2) * (R + 2);
-            u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(a.y) + ((int64_t)(t_cur.b * G + t_cur.g) * 2) * plane;
-#pragma unroll
-            for (int it = 0; it < 2 * kPb2Rows * kPbCols / kPb2Threads; ++it) {
-                const int e = tid + it * kPb2Threads;
-                const int hl = e / (kPb2Rows * kPbCols), rem = e - hl * (kPb2Rows * kPbCols);
-                const int r = rem / kPbCols, c = rem - r * kPbCols;
-                if (t_cur.oy0 + r < R && t_cur.ox0 + c < R)
-                    dst[hl * plane + (int64_t)(t_cur.oy0 + r + 1) * (R + 2) + t_cur.ox0 + c + 1] = reinterpret_cast<const u32x4*>(eb_lds)[e];
-            }
-        }
-        PK_T(3);
-        t_cur = t_nx;
-    }
-    if (a.out_amax) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) amax_l = fmaxf(amax_l, __shfl_xor(amax_l, off, kWave));
-        if (lane == 0) atomic_max_nonneg(a.out_amax + (((int)blockIdx.x * 8 + wave) & (kAmaxSlots - 1)) * kAmaxStride, amax_l * kinv);
-    }
-    PK_T_DONE(8);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // ToRGB on a packed activation (stylesdf_model.py:531-541): 1x1 modulated conv without demodulation (table wm = (scale W) s
 // from the weights launch) + bias + the FIR-up-sampled skip image.  Bound: HBM (4 B per input element).  A thread owns one
 // pixel and a slice of the channel groups (16-byte entries, coalesced across pixels); slices fold through LDS in order.
@@ -1909,60 +1241,11 @@ static int launch_s1(PkConvK k, hipStream_t st, const char* what) {
     return check_launch(what);
 }
 
-constexpr int kUpNpixMax = 528;
-template <int NCT, int NPT, int WCO, int WQ>
-static int launch_up(PkConvK k, hipStream_t st, const char* what) {
-    constexpr int Q = 32 * NPT * WQ, NCTB = NCT * WCO;
-    constexpr int lds = 2 * (4 * kUpNpixMax * 16 + NCTB * kPkSlab);
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    E3DGE_REQUIRE(k.Co % (32 * NCTB) == 0, "%s: Co=%d not a multiple of %d", what, k.Co, 32 * NCTB);
-    k.co_blocks = k.Co / (32 * NCTB);
-    // column blocks: the fewest equal-width blocks whose patch (rows spanned by Q consecutive positions + 1, block width + 1
-    // columns) fits the LDS plane.  Q = 256: 65 -> one block, 129 -> one, 257 -> 129 + 128, 513 -> 4 x 103 + 101.
-    auto fits = [&](int wdt) {
-        int rows = (Q - 1) / wdt + 3;
-        if (rows > k.H + 2) rows = k.H + 2;
-        return rows * (wdt + 1) <= kUpNpixMax;
-    };
-    k.nblk = 0;
-    for (int nb = 1; nb <= k.W + 1 && nb <= 256; ++nb) {
-        const int cw = (k.W + 1 + nb - 1) / nb, cwl = k.W + 1 - (nb - 1) * cw;
-        if (cwl >= 1 && fits(cw) && fits(cwl)) { k.nblk = nb; k.cw = cw; k.cwl = cwl; break; }
-    }
-    E3DGE_REQUIRE(k.nblk > 0, "%s: no column blocking of %d positions fits the LDS plane", what, k.W + 1);
-    k.tpf = ((k.H + 1) * k.cw + Q - 1) / Q;
-    k.tpl = ((k.H + 1) * k.cwl + Q - 1) / Q;
-    const int64_t n_tiles = (int64_t)k.B * k.co_blocks * ((int64_t)(k.nblk - 1) * k.tpf + k.tpl);
-    E3DGE_REQUIRE(n_tiles < ((int64_t)1 << 30), "%s: too many tiles", what);
-    k.n_tiles = (int)n_tiles;
-    auto fn = &pkconv_up_kernel<NCT, NPT, WCO, WQ, kUpNpixMax>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(E3DGE_ERR_LAUNCH, "hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
-    int grid = 256 * ((160 * 1024) / lds >= 2 ? 2 : 1);
-    if (grid > k.n_tiles) grid = k.n_tiles;
-    fn<<<dim3((unsigned)grid), dim3(64 * WCO * WQ), lds, st>>>(k);
-    return check_launch(what);
+static int shape_override(const char* name) {      // E3DGE_DEC2_S1 / E3DGE_DEC2_UPBLUR_SHAPE = variant index (tuning runs); -1: automatic
+    const char* v = getenv(name);
+    return (v && *v) ? atoi(v) : -1;
 }
 
-template <int NPT>
-static int launch_upblur_t(PkConvK k, const float* fir, hipStream_t st) {
-    constexpr int TH = 8 * NPT - 2, lds = 2 * (4 * (TH + 3) * kUbPC * 16 + kPkSlab) + 4096;
-    static_assert(lds <= 160 * 1024 && 8 * 16 * NPT * 64 * 4 <= lds - 4096, "LDS budget");
-    k.co_blocks = k.Co / 32;
-    k.tiles_y = (k.H + TH - 1) / TH;
-    k.tiles_x = (k.W + kUbTW - 1) / kUbTW;
-    const int64_t n_tiles = (int64_t)k.B * k.co_blocks * k.tiles_y * k.tiles_x;
-    E3DGE_REQUIRE(n_tiles < ((int64_t)1 << 30), "dec2 convT+blur: too many tiles");
-    k.n_tiles = (int)n_tiles;
-    auto fn = &pkconv_upblur_kernel<NPT>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(E3DGE_ERR_LAUNCH, "hipFuncSetAttribute(dec2 convT+blur): %s", hipGetErrorString(e));
-    const int wgs = (160 * 1024) / lds >= 2 ? 512 : 256;
-    const int grid = k.n_tiles < wgs ? k.n_tiles : wgs;
-    fn<<<dim3((unsigned)grid), dim3(512), lds, st>>>(k, fir);
-    return check_launch("dec2 convT+blur");
-}
-static int shape_override(const char* name);
 template <int NPT, int NW, int TC>
 static int launch_upblur2_t(PkConvK k, const float* g, hipStream_t st) {
     constexpr int PRW = NW * NPT * (32 / TC), TH = PRW - 2, TW = TC - 2;
@@ -1992,49 +1275,30 @@ static int upblur_rounds(const PkConvK& k, int th, int tw, int slots) {
     const int64_t n = (int64_t)k.B * (k.Co / 32) * ((k.H + th - 1) / th) * ((k.W + tw - 1) / tw);
     return (int)((n + slots - 1) / slots);
 }
-static int shape_override(const char* name);
-// fir1d: the 1-D factor of the blur kernel when the plan says it is rank one (second-generation kernel), else NULL
-static int launch_upblur(PkConvK k, const float* fir, const float* fir1d, hipStream_t st) {
+// fir1d: (g0, g1) of the blur kernel's symmetric 1-D factor (g0, g1, g1, g0)
+static int launch_upblur(PkConvK k, const float* fir1d, hipStream_t st) {
     E3DGE_REQUIRE(k.Co % 32 == 0 && k.Co <= 1024 && k.y && k.out_meta, "dec2 convT+blur: bad arguments");
-    if (fir1d && shape_override("E3DGE_DEC2_UPBLUR_GEN") != 1) {
-        // tile shapes: 0 = eight waves x 2 position rows (14 x 30 stored positions, one workgroup per CU), 1 = eight waves x 1 row
-        // (6 x 30), 2 = FOUR waves x 2 rows (6 x 30, 77 KB of LDS: two workgroups per CU, whose barriers and operand fetches
-        // interleave), 3 = four waves x 2 MFMA tiles of 2 x 16 positions (14 x 14 stored, same LDS).  Automatic: 2 or 3, whichever
-        // needs fewer rounds of 512 resident workgroups (64^2: 200 instead of 264 tiles -- one per CU; 512^2: 1,369 instead of
-        // 1,548 -- three rounds instead of four), 3 on a tie (9 % fewer halo positions).
-        // 4 = EIGHT waves x 1 MFMA tile of 2 x 16 (the same 14 x 14 tile, one workgroup per CU): when there are no more tiles than
-        // CUs a four-wave workgroup has its SIMDs to itself and its LDS-DMA issue (10 pieces per wave and chunk, ~150 cycles each)
-        // is no longer covered by a partner's MFMAs -- 61 cycles per MFMA measured at the 64^2 level; with two waves of the SAME
-        // workgroup per SIMD it is (59.6 vs 70.0 us there, same box).
-        int v = shape_override("E3DGE_DEC2_UPBLUR_SHAPE");
-        if (v < 0) {
-            if (upblur_rounds(k, 14, 14, 256) <= 1) v = 4;
-            else v = upblur_rounds(k, 14, 14, 512) <= upblur_rounds(k, 6, 30, 512) ? 3 : 2;
-        }
-        switch (v) {
-            case 0: return launch_upblur2_t<2, 8, 32>(k, fir1d, st);
-            case 1: return launch_upblur2_t<1, 8, 32>(k, fir1d, st);
-            case 2: return launch_upblur2_t<2, 4, 32>(k, fir1d, st);
-            case 4: return launch_upblur2_t<1, 8, 16>(k, fir1d, st);
-            default: return launch_upblur2_t<2, 4, 16>(k, fir1d, st);
-        }
+    // tile shapes: 0 = eight waves x 2 position rows (14 x 30 stored positions, one workgroup per CU), 1 = eight waves x 1 row
+    // (6 x 30), 2 = FOUR waves x 2 rows (6 x 30, 77 KB of LDS: two workgroups per CU, whose barriers and operand fetches
+    // interleave), 3 = four waves x 2 MFMA tiles of 2 x 16 positions (14 x 14 stored, same LDS).  Automatic: 2 or 3, whichever
+    // needs fewer rounds of 512 resident workgroups (64^2: 200 instead of 264 tiles -- one per CU; 512^2: 1,369 instead of
+    // 1,548 -- three rounds instead of four), 3 on a tie (9 % fewer halo positions).
+    // 4 = EIGHT waves x 1 MFMA tile of 2 x 16 (the same 14 x 14 tile, one workgroup per CU): when there are no more tiles than
+    // CUs a four-wave workgroup has its SIMDs to itself and its LDS-DMA issue (10 pieces per wave and chunk, ~150 cycles each)
+    // is no longer covered by a partner's MFMAs -- 61 cycles per MFMA measured at the 64^2 level; with two waves of the SAME
+    // workgroup per SIMD it is (59.6 vs 70.0 us there, same box).
+    int v = shape_override("E3DGE_DEC2_UPBLUR_SHAPE");
+    if (v < 0) {
+        if (upblur_rounds(k, 14, 14, 256) <= 1) v = 4;
+        else v = upblur_rounds(k, 14, 14, 512) <= upblur_rounds(k, 6, 30, 512) ? 3 : 2;
     }
-    // tiles of 14 x 30 positions (two position rows per wave).  The 6 x 30 form (E3DGE_DEC2_UPBLUR_NPT=1) gives the 64^2 level 264
-    // tiles instead of 120 for the 256 CUs but re-streams every weight slab twice as often: 115 vs 96 us there, slower everywhere.
-    return shape_override("E3DGE_DEC2_UPBLUR_NPT") == 1 ? launch_upblur_t<1>(k, fir, st) : launch_upblur_t<2>(k, fir, st);
-}
-
-// fuse the blur into the transposed convolution?  Measured at every level of the 1024^2 / channel-multiplier-2 decoder
-// (tools/dec2_check.py, one MI355X): 93 vs 75 + 19 us (64 -> 128), 68 vs 63 + 28, 90 vs 71 + 46, 108 vs 70 + 84 (512 -> 1024):
-// never slower, so it is the default; E3DGE_DEC2_UPBLUR=0 keeps the two-kernel form (T in HBM) for A/B and tests.
-static bool use_upblur(int) {
-    const char* v = getenv("E3DGE_DEC2_UPBLUR");
-    return !(v && *v && atoi(v) == 0);
-}
-
-static int shape_override(const char* name) {      // E3DGE_DEC2_S1 / E3DGE_DEC2_UP = variant index (tuning runs); -1: automatic
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : -1;
+    switch (v) {
+        case 0: return launch_upblur2_t<2, 8, 32>(k, fir1d, st);
+        case 1: return launch_upblur2_t<1, 8, 32>(k, fir1d, st);
+        case 2: return launch_upblur2_t<2, 4, 32>(k, fir1d, st);
+        case 4: return launch_upblur2_t<1, 8, 16>(k, fir1d, st);
+        default: return launch_upblur2_t<2, 4, 16>(k, fir1d, st);
+    }
 }
 
 // can the last convolution also do ToRGB?  (one co-block, every channel of a pixel in one wave: the 32- and 64-channel tiles)
@@ -2068,22 +1332,6 @@ static int conv_s1(PkConvK k, hipStream_t st) {
         case 2: return launch_s1<2, 1, 2, 1, 8, 1>(k, st, "dec2 conv<64co,8x64>");
         case 3: return launch_s1<1, 1, 2, 1, 8, 1>(k, st, "dec2 conv<32co,8x64>");
         default: return launch_s1<1, 2, 2, 1, 4, 1>(k, st, "dec2 conv<32co,8x64,4w>");
-    }
-}
-
-static int conv_up(PkConvK k, hipStream_t st) {
-    int v = shape_override("E3DGE_DEC2_UP");
-    if (v < 0) {      // measured per layer (tools/dec2_check.py --sweep, 1024^2 / channel multiplier 2)
-        if (k.Co % 64 != 0) v = 3;
-        else if ((int64_t)k.H * k.W <= 64 * 64) v = 3;
-        else v = 1;
-    }
-    if (k.Co % 64 != 0 && v != 2 && v != 3) v = 2;
-    switch (v) {
-        case 0: return launch_up<1, 1, 2, 4>(k, st, "dec2 convT<64co,128q>");
-        case 1: return launch_up<2, 1, 1, 8>(k, st, "dec2 convT<64co,256q>");
-        case 2: return launch_up<1, 2, 1, 4>(k, st, "dec2 convT<32co,256q,4w>");
-        default: return launch_up<1, 1, 1, 8>(k, st, "dec2 convT<32co,256q>");
     }
 }
 
@@ -2121,10 +1369,6 @@ extern "C" int64_t e3dge_dec2_act_words(int batch, int channels, int res) {
     if (batch <= 0 || channels <= 0 || res <= 0) return 0;
     return (int64_t)batch * ((channels + 7) / 8) * 2 * (res + 2) * (res + 2) * 4;
 }
-extern "C" int64_t e3dge_dec2_tbuf_floats(int batch, int co, int in_res) {
-    if (batch <= 0 || co <= 0 || in_res <= 0) return 0;
-    return (int64_t)batch * co * (2 * in_res + 3) * (2 * in_res + 4);
-}
 extern "C" int e3dge_dec2_num_launches(int n_up) { return 6 + 4 * n_up; }
 
 extern "C" int e3dge_dec2_prepack_weights(float* wpre, const float* weight, float scale, int co, int ci, e3dge_stream_t stream) {
@@ -2154,6 +1398,8 @@ extern "C" int e3dge_dec2_forward(const E3dgeDec2Plan* P, e3dge_stream_t stream)
     E3DGE_REQUIRE(P != nullptr, "dec2_forward: null plan");
     E3DGE_REQUIRE(P->batch >= 0 && P->n_up >= 0 && P->n_up <= E3DGE_DEC2_MAX_UP && P->in_res >= 4 && P->in_ch > 0 && P->in_ch % 16 == 0,
                   "dec2_forward: bad sizes (batch %d, n_up %d, in_res %d, in_ch %d)", P->batch, P->n_up, P->in_res, P->in_ch);
+    E3DGE_REQUIRE(P->n_up == 0 || P->fir_blur_separable != 0,
+                  "dec2_forward: fir_blur_separable == 0 (the blur kernel has no symmetric rank-one factor; such decoders take the planar path)");
     if (P->batch == 0) return E3DGE_OK;
     E3DGE_REQUIRE(P->features && P->mod_table && P->latent && P->amax && P->meta && P->fir_blur && P->fir_up, "dec2_forward: null pointer");
     int rc = check_conv(P->conv1, "conv1");
@@ -2163,7 +1409,7 @@ extern "C" int e3dge_dec2_forward(const E3dgeDec2Plan* P, e3dge_stream_t stream)
     E3DGE_REQUIRE(P->rgb1.ci == P->conv1.co, "dec2_forward: rgb1.ci != conv1.co");
     for (int u = 0, prev = P->conv1.co; u < P->n_up; ++u) {
         if ((rc = check_conv(P->up[u], "up")) != 0 || (rc = check_conv(P->conv[u], "conv")) != 0) return rc;
-        E3DGE_REQUIRE(P->tbuf[u] && P->act[2 + 2 * u] && P->act[3 + 2 * u] && P->rgb[u].out && P->rgb[u].wm && P->rgb[u].weight && P->rgb[u].style && P->rgb[u].bias,
+        E3DGE_REQUIRE(P->act[2 + 2 * u] && P->act[3 + 2 * u] && P->rgb[u].out && P->rgb[u].wm && P->rgb[u].weight && P->rgb[u].style && P->rgb[u].bias,
                       "dec2_forward: level %d workspace / ToRGB pointer missing", u);
         E3DGE_REQUIRE(P->up[u].ci == prev && P->conv[u].ci == P->up[u].co && P->rgb[u].ci == P->conv[u].co, "dec2_forward: level %d channel chain", u);
         E3DGE_REQUIRE((int64_t)(1 + (P->up[u].co + 7) / 8) * 8 * ((int64_t)P->in_res << (u + 1)) * ((int64_t)P->in_res << (u + 1)) * P->batch < ((int64_t)1 << 31),
@@ -2258,52 +1504,17 @@ extern "C" int e3dge_dec2_forward(const E3dgeDec2Plan* P, e3dge_stream_t stream)
     for (int u = 0; u < P->n_up; ++u) {
         const E3dgeDec2Conv& cu = P->up[u];
         const E3dgeDec2Conv& cc = P->conv[u];
-        float* am_t = P->amax + (int64_t)E3DGE_AMAX_FLOATS * (2 + 3 * u);
-        float* am_u = am_t + E3DGE_AMAX_FLOATS;
+        float* am_u = P->amax + (int64_t)E3DGE_AMAX_FLOATS * (3 + 3 * u);      // (amax buffer [2 + 3u] is not written)
         float* am_v = am_u + E3DGE_AMAX_FLOATS;
-        if (use_upblur(res)) {   // transposed conv + blur + noise + bias + lrelu -> packed in one launch, T stays on chip
+        {   // transposed conv + blur + noise + bias + lrelu -> packed in one launch, T stays on chip
             PkConvK k = conv_args(cu, res);
             k.knorm = sqrtf(4.0f * (float)cu.ci);
             k.x = reinterpret_cast<const unsigned char*>(P->act[prev_act]); k.in_meta = P->meta + prev_act;
             k.in_amax = P->amax + (int64_t)E3DGE_AMAX_FLOATS * (prev_act == 1 ? 1 : 4 + 3 * (u - 1));
             k.y = reinterpret_cast<unsigned char*>(P->act[2 + 2 * u]); k.out_meta = P->meta + 2 + 2 * u; k.out_amax = am_u;
-            DEC2_STEP(launch_upblur(k, P->fir_blur, P->fir_blur_separable ? P->fir_blur_1d : nullptr, st));
+            DEC2_STEP(launch_upblur(k, P->fir_blur_1d, st));
             mark(true);                   // (keeps the kernel_ms slots aligned: this level's blur entry reads 0)
             res *= 2;
-        } else {
-        {   // transposed conv -> T
-            PkConvK k = conv_args(cu, res);
-            k.noise = nullptr; k.noise_w = nullptr; k.noise_amax = nullptr;
-            k.x = reinterpret_cast<const unsigned char*>(P->act[prev_act]); k.in_meta = P->meta + prev_act;
-            k.in_amax = P->amax + (int64_t)E3DGE_AMAX_FLOATS * (prev_act == 1 ? 1 : 4 + 3 * (u - 1));
-            k.t = P->tbuf[u]; k.out_amax = am_t;
-            DEC2_STEP(conv_up(k, st));
-        }
-        res *= 2;
-        {   // blur + noise + bias + lrelu -> packed
-            PkBlurK k{};
-            k.t = P->tbuf[u]; k.y = reinterpret_cast<unsigned char*>(P->act[2 + 2 * u]); k.fir = P->fir_blur;
-            k.noise = cu.noise; k.noise_w = cu.noise_w; k.noise_amax = cu.noise_amax; k.bias = cu.bias; k.bias_amax = cu.bias_amax;
-            k.t_amax = am_t; k.out_meta = P->meta + 2 + 2 * u; k.out_amax = am_u;
-            k.slope = P->negative_slope; k.act_scale = P->act_scale;
-            k.B = B; k.C = cu.co; k.R = res; k.noise_batch = cu.noise_batch;
-            k.tiles_x = (res + kPbCols - 1) / kPbCols; k.tiles_y = (res + kPbRows - 1) / kPbRows;
-            const int64_t blocks = (int64_t)k.tiles_x * k.tiles_y * (cu.co / 8) * B;
-            if (shape_override("E3DGE_DEC2_BLUR") == 1) {
-                pk_blur_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(k);
-            } else {
-                if (!(cu.co <= 1024 && blocks < ((int64_t)1 << 30))) return finish(fail(E3DGE_ERR_INVALID_ARG, "dec2 blur: too many channels / tiles"));
-                auto fn = &pk_blur2_kernel;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, kPb2Lds);
-                if (e != hipSuccess) return finish(fail(E3DGE_ERR_LAUNCH, "hipFuncSetAttribute(dec2 blur): %s", hipGetErrorString(e)));
-                const int tiles_y2 = (res + kPb2Rows - 1) / kPb2Rows;
-                const int64_t tiles2 = (int64_t)k.tiles_x * tiles_y2 * (cu.co / 8) * B;
-                if (!(tiles2 < ((int64_t)1 << 30))) return finish(fail(E3DGE_ERR_INVALID_ARG, "dec2 blur: too many tiles"));
-                const int grid = tiles2 < 512 ? (int)tiles2 : 512;        // two 70-KB workgroups per CU
-                fn<<<dim3((unsigned)grid), dim3(kPb2Threads), kPb2Lds, st>>>(k, (int)tiles2, tiles_y2);
-            }
-            DEC2_STEP(check_launch("dec2 blur"));
-        }
         }
         // ToRGB in the convolution's epilogue whenever one tile covers every output channel (32 / 64): at the last level the activation
         // is then never stored; at an earlier level (round 4) it is stored AND reduced -- the stand-alone ToRGB re-read all of it

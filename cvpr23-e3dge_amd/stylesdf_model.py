@@ -127,6 +127,22 @@ import weakref
 
 _DEC2_STATES = weakref.WeakKeyDictionary()          # Decoder -> {(batch, res, device, stream): workspace + E3dgeDec2Plan}
 _DEC2_NOISE_AMAX = weakref.WeakKeyDictionary()      # Decoder -> {noise tensor version: amax buffer}
+_DEC2_BLUR_FACTOR = weakref.WeakKeyDictionary()     # Decoder -> (blur kernel tensor, its version, blur_factor of it)
+
+
+def blur_factor(kernel):
+    """(g0, g1, g1, g0) when the 4x4 blur kernel is outer(g, g) with a symmetric g up to fp32 round-off (make_kernel([1,3,3,1])
+    * 4 is), else None.  The packed decoder's up-sampling kernel applies the blur as these two 1-D passes."""
+    k2 = kernel.detach().double().cpu()
+    tot = float(k2.sum())
+    if tuple(k2.shape) != (4, 4) or not tot > 0:
+        return None
+    g = k2.sum(1) / tot ** 0.5
+    kmax = float(k2.abs().max())
+    if not (float((torch.outer(g, g) - k2).abs().max()) <= 1e-6 * kmax and float((k2 - k2.t()).abs().max()) <= 1e-6 * kmax and
+            float((g - g.flip(0)).abs().max()) <= 1e-7 * float(g.abs().max())):
+        return None
+    return tuple(float(v) for v in g)
 
 
 def decoder_backend():
@@ -679,12 +695,23 @@ class Decoder(nn.Module):
                 return False
         if features.shape[1] != self.conv1.conv.in_channel:
             return False
+        if self.to_rgbs and self._blur_factor() is None:     # the planar path applies any 4x4 blur kernel as it is
+            return False
         B, res = features.shape[0], features.shape[2]
-        # 32-bit byte offsets inside one packed tensor / element offsets inside a T buffer
+        # 32-bit byte offsets inside one packed tensor
         top = res << len(self.to_rgbs)
         if B * max(self.channels.get(top, 16), 16) * (top + 4) * (top + 4) * 4 >= 2 ** 31:
             return False
         return all(n is None or (n.device == features.device and n.dtype == torch.float32) for n in noise)
+
+    def _blur_factor(self):
+        """blur_factor of the first up-sampling layer's Blur kernel (the plan hands it to every level), cached per (tensor,
+        version): _dec2_ok asks on every forward, and the kernel is a device buffer."""
+        k = self.convs[0].conv.blur.kernel
+        hit = _DEC2_BLUR_FACTOR.get(self)
+        if hit is None or hit[0] is not k or hit[1] != k._version:
+            hit = _DEC2_BLUR_FACTOR[self] = (k, k._version, blur_factor(k))
+        return hit[2]
 
     def _dec2_bwd_ok(self):
         """Can the packed pipeline differentiate itself (e3dge_dec2_backward)?  Every 3x3 layer needs 32-channel multiples on both
@@ -722,7 +749,7 @@ class Decoder(nn.Module):
 
     def _dec2_state(self, B, res, device):
         """Workspace + plan of the packed pipeline for one (batch, input resolution, device, stream): packed activation
-        buffers (zero-filled ONCE: their borders are the convolutions' zero padding and no kernel writes them), T buffers,
+        buffers (zero-filled ONCE: their borders are the convolutions' zero padding and no kernel writes them),
         per-sample weight images, ToRGB tables, amax / meta blocks, and the E3dgeDec2Plan struct with every static pointer
         filled in.  Rebuilt when a parameter tensor is replaced."""
         lib = _lib.load()
@@ -780,9 +807,6 @@ class Decoder(nn.Module):
             up_c, cv, tr = self.convs[2 * u], self.convs[2 * u + 1], self.to_rgbs[u]
             fill_conv(plan.up[u], up_c, views[2 + 3 * u])
             fill_conv(plan.conv[u], cv, views[3 + 3 * u])
-            tb = torch.zeros(lib.e3dge_dec2_tbuf_floats(B, up_c.conv.out_channel, r), **f32)
-            keep.append(tb)
-            plan.tbuf[u] = _lib.ptr(tb)
             r *= 2
             acts += [packed(up_c.conv.out_channel, r), packed(cv.conv.out_channel, r)]
             outs.append(fill_rgb(plan.rgb[u], tr, views[4 + 3 * u], r))
@@ -794,18 +818,11 @@ class Decoder(nn.Module):
         fir_up = (self.to_rgbs[0].upsample.kernel if n_up else fir_blur).detach().contiguous()
         keep += [amax, meta, fir_blur, fir_up]
         plan.amax, plan.meta, plan.fir_blur, plan.fir_up = _lib.ptr(amax), _lib.ptr(meta), _lib.ptr(fir_blur), _lib.ptr(fir_up)
-        # the blur kernel is make_kernel(1-D list) * 4 = outer(g, g): hand the kernel its 1-D factor when that holds exactly
-        # enough (fp32 round-off of the outer product), otherwise the 4x4 form is applied as it is
-        k2 = fir_blur.detach().double().cpu()
-        tot = float(k2.sum())
-        if tuple(k2.shape) == (4, 4) and tot > 0:
-            g1 = k2.sum(1) / tot ** 0.5
-            if float((torch.outer(g1, g1) - k2).abs().max()) <= 1e-6 * float(k2.abs().max()) and \
-                    float((k2 - k2.t()).abs().max()) <= 1e-6 * float(k2.abs().max()) and \
-                    float((g1 - g1.flip(0)).abs().max()) <= 1e-7 * float(g1.abs().max()):      # symmetric factor (g0, g1, g1, g0)
-                for i in range(4):
-                    plan.fir_blur_1d[i] = float(g1[i])
-                plan.fir_blur_separable = 1
+        g = self._blur_factor() if n_up else None        # (None: e3dge_dec2_forward refuses the plan; _dec2_ok keeps such decoders off it)
+        if g is not None:
+            for i in range(4):
+                plan.fir_blur_1d[i] = g[i]
+            plan.fir_blur_separable = 1
         st = dict(key=pkey, plan=plan, keep=keep, acts=acts, outs=outs, meta=meta, amax=amax, n_launch=lib.e3dge_dec2_num_launches(n_up))
         states.pop(slot, None)
         while len(states) >= 4:

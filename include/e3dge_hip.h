@@ -249,8 +249,7 @@ typedef struct E3dgeDec2Plan {
     E3dgeDec2Conv conv[E3DGE_DEC2_MAX_UP];         /* stride-1 StyledConv of level u (convs[2u+1])                         */
     E3dgeDec2Rgb rgb[E3DGE_DEC2_MAX_UP];
     uint32_t* act[2 * E3DGE_DEC2_MAX_UP + 2];      /* packed workspaces: [0] features, [1] conv1 out, [2+2u] blur out, [3+2u] conv out */
-    float* tbuf[E3DGE_DEC2_MAX_UP];                /* (batch, co, 2H+3, 2W+4) fp32, zero-filled once: transposed-conv outputs */
-    float* amax;                                   /* (3 n_up + 2) amax buffers (zeroed by the call): [0] features, [1] conv1 out, [2+3u] T, [3+3u] blur out, [4+3u] conv out */
+    float* amax;                                   /* (3 n_up + 2) amax buffers (zeroed by the call): [0] features, [1] conv1 out, [2+3u] not written, [3+3u] blur out, [4+3u] conv out */
     int32_t* meta;                                 /* (2 n_up + 2) ints: eb of act[i]                                      */
     const float* fir_blur;                         /* 4x4 taps of the up-sampling convs' Blur (make_kernel * 4)            */
     const float* fir_up;                           /* 4x4 taps of ToRGB's Upsample                                        */
@@ -258,17 +257,16 @@ typedef struct E3dgeDec2Plan {
     float* kernel_ms;                              /* host array, n_kernel_ms floats, or NULL: HIP-event time of every launch (makes the call synchronous) */
     int32_t n_kernel_ms, reserved1;
     /* ABI 11: when the blur kernel is rank one with a SYMMETRIC factor (make_kernel([1,3,3,1]) is), fir_blur = outer(fir_blur_1d,
-     * fir_blur_1d), fir_blur_1d = (g0, g1, g1, g0) and fir_blur_separable != 0: the fused up-sampling kernel then applies the two 1-D passes (horizontal in registers,
-     * vertical through LDS).  With fir_blur_separable == 0 the 4x4 taps are applied as they are (first-generation kernel). */
+     * fir_blur_1d), fir_blur_1d = (g0, g1, g1, g0) and fir_blur_separable != 0: the fused up-sampling kernel applies the two 1-D passes (horizontal in registers,
+     * vertical through LDS).  ABI 15: with n_up > 0, fir_blur_separable == 0 is rejected (E3DGE_ERR_INVALID_ARG); such a decoder takes the planar path. */
     float fir_blur_1d[4];
     int32_t fir_blur_separable;
     /* ABI 12: != 0 keeps the packed activation of the LAST convolution too (normally it only exists inside the fused ToRGB epilogue):
      * e3dge_dec2_backward reads the sign of every stored activation for lrelu'. */
     int32_t save_for_backward;
 } E3dgeDec2Plan;
-/* 32-bit words of a packed tensor / floats of a T buffer / floats of a wpre image */
+/* 32-bit words of a packed tensor */
 int64_t e3dge_dec2_act_words(int batch, int channels, int res);
-int64_t e3dge_dec2_tbuf_floats(int batch, int co, int in_res);
 /* weight (co, ci, 3, 3) -> wpre[t][c][tap][lane][j] = scale * weight[32t + (lane & 31)][16c + 8 (lane >> 5) + j][tap] */
 int e3dge_dec2_prepack_weights(float* wpre, const float* weight, float scale, int co, int ci, e3dge_stream_t stream);
 /* launches per forward with n_up levels (= number of kernel_ms entries written): 6 + 4 n_up */

@@ -121,34 +121,46 @@ int main(void) {
     assert lib.e3dge_decoder_styles(None, 1, 1, 0, None, 1, 1, 1, None) == -1
 
 
-def test_dec2_structs_layout_matches_c():
+def test_dec2_structs_match_c_in_every_plan_field():
+    C, R, P = _lib.Dec2Conv, _lib.Dec2Rgb, _lib.Dec2Plan
+    plan_fields = [f[0] for f in P._fields_]          # every field of the plan, in order
     src = r'''
 #include <stdio.h>
 #include <stddef.h>
 #include "e3dge_hip.h"
 int main(void) {
   printf("%zu %zu %zu %zu\n", sizeof(E3dgeDec2Conv), offsetof(E3dgeDec2Conv, bias_amax), offsetof(E3dgeDec2Conv, noise_batch), sizeof(E3dgeDec2Rgb));
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %d %zu %zu\n", sizeof(E3dgeDec2Plan), offsetof(E3dgeDec2Plan, conv1), offsetof(E3dgeDec2Plan, up),
-         offsetof(E3dgeDec2Plan, rgb), offsetof(E3dgeDec2Plan, act), offsetof(E3dgeDec2Plan, amax), offsetof(E3dgeDec2Plan, negative_slope),
-         offsetof(E3dgeDec2Plan, kernel_ms), E3DGE_DEC2_MAX_UP, offsetof(E3dgeDec2Plan, fir_blur_1d), offsetof(E3dgeDec2Plan, fir_blur_separable));
-  return 0; }'''
+  printf("%zu %d\n", sizeof(E3dgeDec2Plan), E3DGE_DEC2_MAX_UP);
+''' + "".join(f'  printf("%zu\\n", offsetof(E3dgeDec2Plan, {n}));\n' for n in plan_fields) + "  return 0; }"
     with tempfile.TemporaryDirectory() as d:
         c = os.path.join(d, "t.c")
         open(c, "w").write(src)
         exe = os.path.join(d, "t")
         subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
         got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    C, R, P = _lib.Dec2Conv, _lib.Dec2Rgb, _lib.Dec2Plan
-    assert got == [ctypes.sizeof(C), C.bias_amax.offset, C.noise_batch.offset, ctypes.sizeof(R), ctypes.sizeof(P), P.conv1.offset, P.up.offset,
-                   P.rgb.offset, P.act.offset, P.amax.offset, P.negative_slope.offset, P.kernel_ms.offset, _lib.DEC2_MAX_UP,
-                   P.fir_blur_1d.offset, P.fir_blur_separable.offset]
+    assert got == [ctypes.sizeof(C), C.bias_amax.offset, C.noise_batch.offset, ctypes.sizeof(R), ctypes.sizeof(P), _lib.DEC2_MAX_UP] + \
+        [getattr(P, n).offset for n in plan_fields]
     lib = _lib.load()
     assert lib.e3dge_dec2_forward(None, None) == -1
     assert lib.e3dge_dec2_forward(ctypes.byref(P(batch=1, n_up=7, in_res=64, in_ch=256)), None) == -1       # more levels than the plan holds
     assert lib.e3dge_dec2_num_launches(4) == 22
-    assert lib.e3dge_dec2_act_words(1, 32, 1024) == 4 * 2 * 1026 * 1026 * 4 and lib.e3dge_dec2_tbuf_floats(2, 32, 512) == 2 * 32 * 1027 * 1028
+    # a plan without the blur kernel's 1-D factor is refused before any pointer is looked at (every pointer here is null)
+    assert lib.e3dge_dec2_forward(ctypes.byref(P(batch=1, n_up=4, in_res=64, in_ch=256, fir_blur_separable=0)), None) == -1
+    assert b"fir_blur_separable == 0" in lib.e3dge_last_error()
+    assert lib.e3dge_dec2_act_words(1, 32, 1024) == 4 * 2 * 1026 * 1026 * 4
     assert lib.e3dge_dec2_pack(None, None, None, None, 1, 12, 8, None) == -1
     assert lib.e3dge_hitprob_points(None, None, None, None, None, None, None, None, 1, 4, 4, 1, None) == -1
+
+
+def test_blur_factor_accepts_only_symmetric_rank_one_kernels():
+    from e3dge_amd.stylesdf_model import blur_factor, make_kernel
+    k = make_kernel([1, 3, 3, 1]) * 4                 # Blur of an up-sampling ModulatedConv2d (upsample_factor 2)
+    g = blur_factor(k)
+    assert g is not None and g[0] == g[3] and g[1] == g[2]
+    assert float((torch.outer(torch.tensor(g), torch.tensor(g)) - k.double()).abs().max()) <= 1e-6
+    not_rank_one = make_kernel([[1, 3, 3, 1], [3, 9, 9, 3], [3, 9, 9, 3], [1, 3, 3, 2]])     # symmetric, rank two
+    assert blur_factor(not_rank_one * 4) is None
+    assert blur_factor(make_kernel([1, 2, 3, 4]) * 4) is None          # rank one, but the factor is not symmetric
 
 
 def test_dec2_backward_structs_layout_matches_c():

@@ -20,6 +20,7 @@ from oracle import decoder_ref
 import e3dge_amd  # noqa: F401
 from e3dge_amd import _lib
 from e3dge_amd import synthetic as syn
+from e3dge_amd.stylesdf_model import _DEC2_STATES, make_kernel
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -63,23 +64,16 @@ def gen256():
     return g.to(DEV).eval(), sd
 
 
-UPBLUR_FORMS = {                    # name -> (E3DGE_DEC2_UPBLUR, E3DGE_DEC2_UPBLUR_GEN, E3DGE_DEC2_UPBLUR_SHAPE)
-    "auto": ("1", None, None),      # second generation, tile shape picked per level
-    "gen2_8w_14x30": ("1", None, "0"), "gen2_8w_6x30": ("1", None, "1"), "gen2_4w_6x30": ("1", None, "2"), "gen2_4w_14x14": ("1", None, "3"),
-    "gen2_8w_14x14": ("1", None, "4"),
-    "gen1": ("1", "1", None),       # first generation (4x4 FIR from the LDS patch); also what a non-separable kernel takes
-    "two_kernels": ("0", None, None),
+UPBLUR_FORMS = {                    # name -> E3DGE_DEC2_UPBLUR_SHAPE
+    "auto": None,                   # tile shape picked per level
+    "gen2_8w_14x30": "0", "gen2_8w_6x30": "1", "gen2_4w_6x30": "2", "gen2_4w_14x14": "3", "gen2_8w_14x14": "4",
 }
 
 
 @pytest.mark.parametrize("form", list(UPBLUR_FORMS))
 def test_every_stage_against_the_planar_kernels(gen256, form, monkeypatch):
-    """Up-sampling layer forms: transposed conv + blur in one kernel (T / H stay in LDS) in both generations and every tile
-    shape of the second, and the two-kernel form with T in HBM."""
-    upblur, gen, shape = UPBLUR_FORMS[form]
-    monkeypatch.setenv("E3DGE_DEC2_UPBLUR", upblur)
-    if gen is not None:
-        monkeypatch.setenv("E3DGE_DEC2_UPBLUR_GEN", gen)
+    """The up-sampling layer (transposed conv + blur in one kernel, T / H stay in LDS) in every tile shape."""
+    shape = UPBLUR_FORMS[form]
     if shape is not None:
         monkeypatch.setenv("E3DGE_DEC2_UPBLUR_SHAPE", shape)
     g, sd = gen256
@@ -108,7 +102,7 @@ def test_every_stage_against_the_planar_kernels(gen256, form, monkeypatch):
         img = dec._forward_packed(feats, wd, noise, kernel_ms=ms)
         names = dec.dec2_launch_names()
         assert len(ms) == _lib.load().e3dge_dec2_num_launches(len(dec.to_rgbs)) == len(names)
-        assert all((t == 0) == (upblur == "1" and n.endswith(".blur")) for n, t in zip(names, ms)), list(zip(names, ms))
+        assert all((t == 0) == n.endswith(".blur") for n, t in zip(names, ms)), list(zip(names, ms))
         errs = {}
         for k, r in enumerate(ref):
             got = dec.dec2_unpack(1 + k, feats.shape)
@@ -151,6 +145,28 @@ def test_image_against_the_oracle_small_shapes(B, res, size, per_sample_noise):
     record(f"dec2_oracle_B{B}_res{res}_size{size}", **e)
     assert tuple(img.shape) == (B, 3, size, size)
     assert e['vs_f32'] <= IMG_ATOL and e['vs_f64'] <= max(IMG_ATOL, 3 * e['f32_vs_f64'])
+
+
+def test_non_separable_blur_kernel_takes_the_planar_path():
+    """A blur kernel without a symmetric rank-one factor: no packed plan is built, and Decoder.forward returns exactly what the
+    planar path returns."""
+    g, _ = full_state_dict(size=64, cm=1, res=16)
+    dec = g.to(DEV).eval().decoder
+    _, wd = syn.synthetic_inputs(2, seed=5, device=DEV)
+    wd = wd[:, :dec.n_latent].contiguous()
+    feats = (0.7 * torch.randn(2, 256, 16, 16, device=DEV, generator=torch.Generator(DEV).manual_seed(11))).contiguous()
+    noise = [getattr(dec.noises, f"noise_{i}") for i in range(dec.num_layers)]
+    k = make_kernel([[1, 3, 3, 1], [3, 9, 9, 3], [3, 9, 9, 3], [1, 3, 3, 2]]) * 4      # symmetric, rank two
+    with torch.no_grad():
+        assert dec._dec2_ok(feats, wd, noise, None)         # make_kernel([1, 3, 3, 1]): the packed path
+        for c in dec.convs:
+            if c.conv.upsample:
+                c.conv.blur.kernel.copy_(k)
+        assert not dec._dec2_ok(feats, wd, noise, None)
+        img, _ = dec(feats, [wd], input_is_latent=True, noise=noise, randomize_noise=False)
+        planar = _planar(dec, feats, wd, noise)
+    assert not _DEC2_STATES.get(dec)
+    assert torch.equal(img, planar)
 
 
 def test_input_magnitude_does_not_matter(gen256):

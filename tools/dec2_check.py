@@ -148,22 +148,22 @@ def main():
         emit(what="kernel_ms_median", **tag, names=dec.dec2_launch_names(), ms=med, total=round(sum(med), 4))
         if a.sweep:
             names = dec.dec2_launch_names()
-            for var, key in (("E3DGE_DEC2_S1", "conv"), ("E3DGE_DEC2_UP", "convT")):
-                for v in range(5 if key == "conv" else 4):
-                    os.environ[var] = str(v)
-                    try:
-                        acc = []
-                        for _ in range(max(5, a.iters // 2)):
-                            m = []
-                            out = dec._forward_packed(feats, wd, noise, kernel_ms=m)
-                            acc.append(m)
-                        med = [sorted(col)[len(col) // 2] for col in zip(*acc)]
-                        sel = {n: round(t, 4) for n, t in zip(names, med) if (key == "conv" and n.endswith("conv")) or (key == "conv" and n == "conv1") or (key == "convT" and n.endswith("convT"))}
-                        emit(what="sweep", var=var, variant=v, **tag, ms=sel, img_err=float((out - ref_img).abs().max()))
-                    except RuntimeError as e:
-                        emit(what="sweep", var=var, variant=v, **tag, error=str(e)[:200])
-                    finally:
-                        os.environ.pop(var, None)
+            var = "E3DGE_DEC2_S1"
+            for v in range(5):
+                os.environ[var] = str(v)
+                try:
+                    acc = []
+                    for _ in range(max(5, a.iters // 2)):
+                        m = []
+                        out = dec._forward_packed(feats, wd, noise, kernel_ms=m)
+                        acc.append(m)
+                    med = [sorted(col)[len(col) // 2] for col in zip(*acc)]
+                    sel = {n: round(t, 4) for n, t in zip(names, med) if n.endswith("conv") or n == "conv1"}
+                    emit(what="sweep", var=var, variant=v, **tag, ms=sel, img_err=float((out - ref_img).abs().max()))
+                except RuntimeError as e:
+                    emit(what="sweep", var=var, variant=v, **tag, error=str(e)[:200])
+                finally:
+                    os.environ.pop(var, None)
 
 
 if __name__ == "__main__":
