@@ -9,7 +9,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E3DGE_LIB_PATH") or os.path.join(_HERE, "lib", "libe3dge_hip.so")   # override: kernel A/B variants
-ABI_VERSION = 15
+ABI_VERSION = 16
 PREC_F32, PREC_F16X3, PREC_F16X3_V1, PREC_F16X3_G2 = 0, 1, 2, 3
 AMAX_FLOATS = 64 * 32           # E3DGE_AMAX_FLOATS: one amax buffer (include/e3dge_hip.h)
 
@@ -38,14 +38,22 @@ class RenderBwdArgs(ctypes.Structure):
                                    "d_weights", "tex_alpha")] + [
         ("sigmoid_beta", _f32), ("batch", _i32), ("height", _i32), ("width", _i32), ("n_samples", _i32),
         ("force_background", _i32), ("precision", _i32)] + [(n, _vp) for n in ("d_rgb_pts", "d_sdf_pts", "partials", "dfilm", "dstyles",
-                                                                                "d_tex_alpha", "d_tex_beta")] + [("phase", _i32)]
+                                                                                "d_tex_alpha", "d_tex_beta")] + [("phase", _i32)] + [
+        (n, _vp) for n in ("d_lin", "lin_amax", "d_sigmoid_beta")]
 
 
 class SirenBwdArgs(ctypes.Structure):
     """Mirror of struct E3dgeSirenBwdArgs (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("packed", "film", "args", "d_feat", "d_rgb", "d_sdf", "tang", "rsave", "wg", "wb", "tex_alpha")] + [
         ("batch", _i32), ("precision", _i32), ("n_pts", _i64), ("box_scale", _f32)] + [
-        (n, _vp) for n in ("partials", "dfilm", "dstyles", "d_pts", "d_tex_alpha", "d_tex_beta")]
+        (n, _vp) for n in ("partials", "dfilm", "dstyles", "d_pts", "d_tex_alpha", "d_tex_beta", "d_lin", "lin_amax")]
+
+
+class SirenWgradArgs(ctypes.Structure):
+    """Mirror of struct E3dgeSirenWgradArgs (include/e3dge_hip.h, ABI 16)."""
+    _fields_ = [(n, _vp) for n in ("args", "d_lin", "lin_amax", "d_sdf", "d_rgb", "pts", "viewdirs", "d_w", "d_w_view_dirs", "d_w_first",
+                                   "d_w_sigma", "d_b_sigma", "d_w_rgb", "d_b_rgb", "ws")] + [
+        ("ws_floats", _i64), ("n_pts", _i64), ("batch", _i32), ("samples", _i32), ("precision", _i32), ("box_scale", _f32)]
 
 
 class ModconvArgs(ctypes.Structure):
@@ -183,6 +191,8 @@ SIGNATURES = {
     "e3dge_tex_modulations_bwd": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "e3dge_wgrad_ws_floats": (_i64, [_i32, _i32, _i64]),
     "e3dge_wgrad": (_i32, [_vp, _vp]),
+    "e3dge_siren_wgrad_ws_floats": (_i64, [_i32, _i64]),
+    "e3dge_siren_wgrad": (_i32, [ctypes.POINTER(SirenWgradArgs), _vp]),
     "e3dge_local_query": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp]),
     "e3dge_local_query_bwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp]),
     "e3dge_local_query_sort_ws_ints": (_i64, [_i32, _i64, _i32, _i32]),

@@ -279,8 +279,14 @@ __device__ __forceinline__ void sincos_hw16(float x, float& sn, float& cs) {
 
 // EIK / TEX / DPTS as in siren_bwd_kernel.  EIK: a.tang holds the PRODUCTS ta_l r_l (e3dge_siren_tangent_tr), a.rsave is unused.
 // Partial sums: slice (workgroup, sub-tile) of a.partials, [9][2][256] = sum(da a [+ ta r cos a]), sum(da) per layer and feature.
-template <bool EIK, bool TEX, bool DPTS>
+// LIN (ABI 16, renderer parameter gradients; not with EIK / TEX): every g_l = gamma_l * adj(a_l) the chain forms (fp32, before it is
+// split into the next GEMM's operand) also goes to a.d_lin, slab-major like the arguments, and each layer's max |g_l| into the amax
+// buffer a.lin_amax + l * E3DGE_AMAX_FLOATS -- the operands of e3dge_siren_wgrad.  Only lanes of real points store (padded lanes address
+// the clamped row npts - 1).  The stores are NOT counted by the vmcnt scheme above: a count is a lower bound of the operations younger
+// than the awaited one, so an extra operation in the queue only makes a wait stricter.
+template <bool EIK, bool TEX, bool DPTS, bool LIN = false>
 __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK a) {
+    static_assert(!LIN || (!EIK && !TEX), "parameter gradients: first order, first pass only");
     constexpr int NS = EIK ? 2 : 1;                // streams: arguments [, ta r]; no regular stores (d_pts / d_tex / partial slices are extras)
     constexpr int kSlots = t3_slots(NS), kDist = kSlots - 1, kRingF = t3_ring_floats(NS);
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -406,6 +412,25 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
             for (int w = 1; w < 8; ++w) s += sp[w * 2 * kWidth];
             my_slice[layer * 2 * kWidth + (tid & 1) * kWidth + (tid >> 1)] = s;
         };
+        // LIN: this lane's 4 values of g_layer, tile t (the point is recomputed from the thread index: nothing of it lives across a tile)
+        auto store_lin = [&](int layer_s, int t, const f32x4v& v) {
+            if constexpr (LIN) {
+                int tid_s = tid_k;
+                asm volatile("" : "+v"(tid_s));
+                const int p_s = sub * kTilePts + 16 * (tid_s >> 6) + (tid_s & 15);
+                if (p_s < npts)
+                    st4(a.d_lin + base_row * (9 * kWidth) + t3_row_floats(p_s, (tid_s >> 4) & 3, 9) + layer_s * kT3LayerF + kT3TileF * t, v);
+            }
+        };
+        auto publish_amax = [&](int layer_s) {
+            if constexpr (LIN) {
+                float m = gmax;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+                if ((tid_k & 63) == 0)
+                    atomic_max_nonneg(a.lin_amax + layer_s * E3DGE_AMAX_FLOATS + (((int)blockIdx.x * 8 + (tid_k >> 6)) & (kAmaxSlots - 1)) * kAmaxStride, m);
+            }
+        };
         auto next_operand = [&]() {
             inv_scale = scale_split16(out, inH, inL, gmax);
             gmax = 0.0f;
@@ -448,8 +473,10 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
                         gmax = fmaxf(gmax, fabsf(out[t][r]));
                     }
                     reduce_store(t, rb, rg);
+                    store_lin(8, t, out[t]);
                 }
             }
+            publish_amax(8);
             next_operand();
             t3_barrier();
             fold(8);
@@ -502,6 +529,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
             auto epi_finish = [&](int tp) {
                 if (tex_here && valid) { st4(dta + 16 * tp, e_da); st4(dtb + 16 * tp, e_db); }
                 reduce_store(tp, rb, rg);
+                store_lin(Lm1, tp, out[tp]);
             };
             t3_static_for<k16Tiles>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
@@ -537,6 +565,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
 #pragma unroll
             for (int r = 0; r < 4; ++r) epi_val(k16Tiles - 1, r);
             epi_finish(k16Tiles - 1);
+            publish_amax(Lm1);
             if (Gb + 1 < kBigLayers) next_operand();
             t3_barrier();
             fold(Lm1);

@@ -40,6 +40,10 @@ struct SirenBwdK {
     float* d_tex_beta;       // (batch, n_pts, 256) out: dL/dbeta = dh8'
     long long n_pts;
     int batch, subtiles_per_wg, wgs_per_img;
+    // ABI 16, precision f16x3_g2 only (siren16_bwd_kernel<.., LIN>): g_l = gamma_l * adj(a_l) of all nine layers, slab-major like `args`,
+    // and one amax buffer per layer (zeroed by the caller) -- the operands of e3dge_siren_wgrad.  Null = off.
+    float* d_lin;
+    float* lin_amax;
 };
 
 constexpr int kBwdLdsW = 0;
@@ -913,6 +917,7 @@ struct CompositeBwdK {
     const float* d_weights;  // (rays, S) or null: gradient arriving at the compositing weights (hit_prob)
     float* d_rgb_pts;        // (rays, S, 3) out
     float* d_sdf_pts;        // (rays, S) out
+    float* d_beta;           // (rays) out or null: this ray's share of dL/d sigmoid_beta
     float sigmoid_beta;
     int S, force_bg;
     long long n_rays, rays_per_img;
@@ -1027,6 +1032,7 @@ __global__ void __launch_bounds__(kThreads) composite_bwd_kernel(const Composite
                 const float dal = dwe * Ts - suffix / (1.0f - al + 1e-10f);
                 suffix = fmaf(dwe, al * Ts, suffix);
                 ws[s * kCbStride + 7] = dal * ws[s * kCbStride + 3];
+                if (a.d_beta) ws[s * kCbStride + 1] = dal;           // (alpha_s is not read again)
             }
         }
         __syncthreads();
@@ -1042,6 +1048,24 @@ __global__ void __launch_bounds__(kThreads) composite_bwd_kernel(const Composite
                     const float sc = sigmoid_f32(ws[s * kCbStride + 4 + c]);
                     a.d_rgb_pts[gpt * 3 + c] = 2.0f * drgb[c] * w * sc * (1.0f - sc);
                 }
+            }
+            if (a.d_beta) {
+                // dL/d beta = sum_s dL/dalpha_s delta_s e_s d sigma_s / d beta,  d sigma / d beta = sg (1 - sg) sdf / beta^3 - sg / beta^2
+                // (the same e == 0 convention as d alpha / d sdf above); lanes over samples, then a fixed xor tree
+                float acc = 0.0f;
+                for (int s = lane; s < S; s += kWave) {
+                    const long long gpt = ray * S + s;
+                    const float sdf = a.sdf[gpt];
+                    const float sg = sigmoid_f32(-sdf * inv_beta);
+                    const float delta = a.dists[gpt];
+                    const float e = __expf(-sg * inv_beta * delta);
+                    const float ib2 = inv_beta * inv_beta;
+                    const float dsig = fmaf(sg * (1.0f - sg) * sdf, ib2 * inv_beta, -sg * ib2);
+                    acc += (e == 0.0f) ? 0.0f : ws[s * kCbStride + 1] * delta * e * dsig;
+                }
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+                if (lane == 0) a.d_beta[ray] = acc;
             }
         }
         __syncthreads();
@@ -1183,6 +1207,14 @@ static int launch_bwd(SirenBwdK k, const float* wg, const float* wb, float* dfil
     E3DGE_REQUIRE(!(tex && k.tang), "siren_bwd: the eikonal double backward is not available on the tex-FiLM pass");
     E3DGE_REQUIRE(((reinterpret_cast<uintptr_t>(k.tex_alpha) | reinterpret_cast<uintptr_t>(k.d_tex_alpha) | reinterpret_cast<uintptr_t>(k.d_tex_beta)) & 15) == 0,
                   "siren_bwd: tex pointers must be 16-B aligned");
+    const bool lin = k.d_lin != nullptr;
+    if (lin) {
+        E3DGE_REQUIRE(gen2, "siren_bwd: d_lin (parameter gradients) needs precision E3DGE_PREC_F16X3_G2, got %d", k.precision);
+        E3DGE_REQUIRE(kT3Blocked, "siren_bwd: d_lin needs the slab-major saved state (this build has E3DGE_T3_BLOCKED=0)");
+        E3DGE_REQUIRE(k.lin_amax != nullptr, "siren_bwd: d_lin needs lin_amax (9 amax buffers, zeroed)");
+        E3DGE_REQUIRE(!tex && k.tang == nullptr, "siren_bwd: d_lin is first order on the first pass only (no tang, no tex_alpha)");
+        E3DGE_REQUIRE((reinterpret_cast<uintptr_t>(k.d_lin) & 15) == 0, "siren_bwd: d_lin must be 16-B aligned");
+    }
     typedef void (*KernelFn)(const SirenBwdK);
     // [dpts][eik][f16], then the two tex variants
     static const KernelFn fns[10] = {
@@ -1198,8 +1230,9 @@ static int launch_bwd(SirenBwdK k, const float* wg, const float* wb, float* dfil
         &siren16_bwd_kernel<false, false, false>, &siren16_bwd_kernel<true, false, false>,
         &siren16_bwd_kernel<false, false, true>, &siren16_bwd_kernel<true, false, true>,
         &siren16_bwd_kernel<false, true, false>};
+    static const KernelFn fns16_lin[2] = {&siren16_bwd_kernel<false, false, false, true>, &siren16_bwd_kernel<false, false, true, true>};
     const bool eik = k.tang != nullptr, dpts = k.d_pts != nullptr;
-    const KernelFn fn = gen2 ? fns16[tex ? 4 : 2 * dpts + eik] : fns[tex ? 8 + f16 : 4 * dpts + 2 * eik + f16];
+    const KernelFn fn = lin ? fns16_lin[dpts] : gen2 ? fns16[tex ? 4 : 2 * dpts + eik] : fns[tex ? 8 + f16 : 4 * dpts + 2 * eik + f16];
     const int lds_bytes = gen2 ? b16_lds_bytes(eik ? 2 : 1, dpts) : kBwdLdsBytes;
     k.precision = f16 ? E3DGE_PREC_F16X3 : E3DGE_PREC_F32;
     {   // the attribute is per device (and cheap): set it on the launch's device every time
@@ -1234,6 +1267,7 @@ extern "C" int e3dge_siren_bwd(const E3dgeSirenBwdArgs* r, e3dge_stream_t stream
     k.partials = r->partials; k.n_pts = r->n_pts; k.batch = r->batch; k.samples = 1; k.tang = r->tang; k.rsave = r->rsave;
     k.precision = r->precision; k.d_pts = r->d_pts; k.box_scale = r->box_scale;
     k.tex_alpha = r->tex_alpha; k.d_tex_alpha = r->d_tex_alpha; k.d_tex_beta = r->d_tex_beta;
+    k.d_lin = r->d_lin; k.lin_amax = r->lin_amax;
     return launch_bwd(k, r->wg, r->wb, r->dfilm, r->dstyles, as_stream(stream));
 }
 
@@ -1245,6 +1279,8 @@ extern "C" int e3dge_siren_render_bwd(const E3dgeRenderBwdArgs* r, e3dge_stream_
     E3DGE_REQUIRE(r->packed && r->film && r->args && r->sdf && r->dists && r->points && r->weights && r->t_vals &&
                   r->near && r->far && r->d_rgb_pts && r->d_sdf_pts, "siren_render_bwd: null pointer");
     E3DGE_REQUIRE(r->sigmoid_beta != 0.0f, "siren_render_bwd: sigmoid_beta must be non-zero");
+    E3DGE_REQUIRE(r->d_lin == nullptr || r->precision == E3DGE_PREC_F16X3_G2,
+                  "siren_render_bwd: d_lin (parameter gradients) needs precision E3DGE_PREC_F16X3_G2, got %d", r->precision);
     E3DGE_REQUIRE(((reinterpret_cast<uintptr_t>(r->d_feat_map) | reinterpret_cast<uintptr_t>(r->args)) & 15) == 0,
                   "siren_render_bwd: args/d_feat_map must be 16-B aligned");
     hipStream_t st = as_stream(stream);
@@ -1254,7 +1290,7 @@ extern "C" int e3dge_siren_render_bwd(const E3dgeRenderBwdArgs* r, e3dge_stream_
     c.t_vals = r->t_vals; c.near = r->near; c.far = r->far;
     c.d_rgbmap = r->d_rgb_map; c.d_featmap = r->d_feat_map; c.d_xyzmap = r->d_xyz_map; c.d_depthmap = r->d_depth_map;
     c.d_sdf_in = r->d_sdf; c.d_weights = r->d_weights; c.d_rgb_pts = r->d_rgb_pts; c.d_sdf_pts = r->d_sdf_pts;
-    c.sigmoid_beta = r->sigmoid_beta; c.S = r->n_samples; c.force_bg = r->force_background;
+    c.sigmoid_beta = r->sigmoid_beta; c.S = r->n_samples; c.force_bg = r->force_background; c.d_beta = r->d_sigmoid_beta;
     c.n_rays = HW * r->batch; c.rays_per_img = HW;
     c.args_blocked = (r->precision == E3DGE_PREC_F16X3_G2 && kT3Blocked) ? 1 : 0;
     const size_t lds = (size_t)4 * r->n_samples * kCbStride * sizeof(float);
@@ -1277,6 +1313,7 @@ extern "C" int e3dge_siren_render_bwd(const E3dgeRenderBwdArgs* r, e3dge_stream_
     k.d_featmap = r->d_feat_map; k.weights = r->weights; k.samples = r->n_samples;
     k.partials = r->partials; k.n_pts = HW * r->n_samples; k.batch = r->batch; k.tang = r->tang; k.rsave = r->rsave; k.precision = r->precision;
     k.tex_alpha = r->tex_alpha; k.d_tex_alpha = r->d_tex_alpha; k.d_tex_beta = r->d_tex_beta;
+    k.d_lin = r->d_lin; k.lin_amax = r->lin_amax;
     return launch_bwd(k, r->wg, r->wb, r->dfilm, r->dstyles, st);
 }
 

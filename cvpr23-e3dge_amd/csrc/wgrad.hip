@@ -34,6 +34,9 @@ struct WgradK {
     float* ws; float* ws_col;
     long long n_rows, slab;
     int lda, off_a, m, ldb, off_b, n, relu_b, mb, nb, gap_at, gap, ld_xcol, cols;       // cols: bit 0 = column sums, bit 1 = xcol
+    // SRC = 1 (e3dge_siren_wgrad): rows are the padded points of the SIREN's slab-major saved state, n16 per image of which the first n_valid
+    // are real; blockIdx.y = y picks layer y + 1 of d_lin (a) against sin(layer y of the arguments) (b), ws_layer floats of workspace each
+    long long n16, n_valid, ws_layer;
 };
 
 struct __attribute__((packed, aligned(4))) WgU4 { float v[4]; };             // 16-byte access at 4-byte alignment (rows of any pitch)
@@ -90,7 +93,11 @@ __device__ __forceinline__ int wg_xcd_logical(int t, int n) {
 template <int MI, int NJ>
 constexpr int wg_lds_bytes() { return 2 * 2 * (64 * MI + 128 * NJ) * kWgPitch; }
 
-template <int MI, int NJ, int MINB>
+// SRC = 0: row operands as described above.  SRC = 1: the SIREN's parameter gradients dW_l = sum_p g_l[p] (x) sin(a_{l-1}[p]) (ABI 16,
+// DESIGN.md 4.6c) -- both operands slab-major ([slab of 16 points][9 layers][16 tiles][q][point][4]): thread (pp, fq)'s 16 bytes of a step
+// are contiguous, the 16 points of a step are one slab.  Padded rows are SELECTED to zero (the buffers are uninitialised there: 0 * NaN);
+// operand b is a sine, |b| <= 1: fixed scale.
+template <int MI, int NJ, int MINB, int SRC = 0>
 __global__ void __launch_bounds__(kWgThreads, MINB) wgrad_kernel(const WgradK a) {
     constexpr int BM = 64 * MI, BN = 128 * NJ, HALF_A = BM * kWgPitch, HALF_B = BN * kWgPitch, STAGE = 2 * (HALF_A + HALF_B);
     extern __shared__ __attribute__((aligned(16))) unsigned char wg_lds[];
@@ -101,7 +108,9 @@ __global__ void __launch_bounds__(kWgThreads, MINB) wgrad_kernel(const WgradK a)
     const int blk = L % nblk, slab = L / nblk;
     const int bm = blk / a.nb, bn = blk % a.nb;
     const long long p_begin = (long long)slab * a.slab, p_end = min(a.n_rows, p_begin + a.slab);
-    const unsigned ea = scale_exponent(amax_read(a.amax_a, lane)), eb = scale_exponent(amax_read(a.amax_b, lane));
+    const int lay = SRC ? (int)blockIdx.y : 0;
+    const unsigned ea = scale_exponent(amax_read(SRC ? a.amax_a + (lay + 1) * E3DGE_AMAX_FLOATS : a.amax_a, lane));
+    const unsigned eb = SRC ? scale_exponent(1.0f) : scale_exponent(amax_read(a.amax_b, lane));
     const float sa = __uint_as_float((268u - ea) << 23), sb = __uint_as_float((268u - eb) << 23);       // 2^(141 - e)
     const int wy = wave >> 2, wx = wave & 3;
     const int m_left = a.m - BM * bm, n_left = a.n - BN * bn;
@@ -120,8 +129,16 @@ __global__ void __launch_bounds__(kWgThreads, MINB) wgrad_kernel(const WgradK a)
 
     WgSrc src_a, src_b;
     const int f0b = BN * bn, f0b_phys = f0b + (a.gap && f0b >= a.gap_at ? a.gap : 0);
-    wg_src_init(src_a, a.a + a.off_a, a.lda, a.m, BM * bm, BM * bm, BM, p_begin, pp, fq);
-    wg_src_init(src_b, a.b + a.off_b, a.ldb, a.n, f0b, f0b_phys, BN, p_begin, pp, fq);
+    long long row_in = 0;                                     // SRC = 1: the step's first row within its image
+    if constexpr (SRC == 1) {
+        const long long o = (p_begin >> 4) * (9 * kSlabLayerF) + (fq >> 2) * kSlabTileF + ((fq & 3) * 16 + 2 * pp) * 4;
+        src_a = WgSrc{a.a + (lay + 1) * kSlabLayerF + o, 9 * kSlabLayerF, 4};
+        src_b = WgSrc{a.b + lay * kSlabLayerF + o, 9 * kSlabLayerF, 4};
+        row_in = p_begin % a.n16;
+    } else {
+        wg_src_init(src_a, a.a + a.off_a, a.lda, a.m, BM * bm, BM * bm, BM, p_begin, pp, fq);
+        wg_src_init(src_b, a.b + a.off_b, a.ldb, a.n, f0b, f0b_phys, BN, p_begin, pp, fq);
+    }
     const float* xc = a.xcol ? a.xcol + (p_begin + 2 * pp) * (long long)a.ld_xcol : nullptr;
     // slice of step s: register set s & 1, LDS stage s & 1 (the step loop is unrolled by two: both are compile-time)
     f32x4 ra[2][2], rb[2][2];
@@ -131,6 +148,24 @@ __global__ void __launch_bounds__(kWgThreads, MINB) wgrad_kernel(const WgradK a)
 
     auto load = [&](long long p0, auto set_c) {
         constexpr int set = decltype(set_c)::value;
+        if constexpr (SRC == 1) {                             // (called for consecutive steps: row_in advances by one slab per call)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const bool ok = row_in + 2 * pp + e < a.n_valid;
+                const f32x4 x = *reinterpret_cast<const f32x4*>(src_a.row + 4 * e);
+                const f32x4 y = *reinterpret_cast<const f32x4*>(src_b.row + 4 * e);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ra[set][e][j] = ok ? x[j] : 0.0f;
+                    rb[set][e][j] = ok ? sin_f32(y[j]) : 0.0f;
+                }
+            }
+            src_a.row += src_a.ld;
+            src_b.row += src_b.ld;
+            row_in += kWgPts;
+            if (row_in >= a.n16) row_in -= a.n16;
+            return;
+        }
         if (p0 + kWgPts <= p_end) { wg_load<false>(ra[set], src_a, p0, p_end, pp); wg_load<false>(rb[set], src_b, p0, p_end, pp); }
         else { wg_load<true>(ra[set], src_a, p0, p_end, pp); wg_load<true>(rb[set], src_b, p0, p_end, pp); }
         if (cols & 2) {
@@ -205,7 +240,7 @@ __global__ void __launch_bounds__(kWgThreads, MINB) wgrad_kernel(const WgradK a)
     // partial block -> workspace [slab][block][wave][i][j][r / 4][lane][r & 3]: a wave-instruction stores one contiguous KiB (row-major
     // blocks cost 128-byte pieces: 82 us per 256 x 256 layer, a third of it these stores).  The fold sums slot by slot and decodes
     // (row, column) only for the final store: register r of tile (i, j) is row 32 (MI wy + i) + row_of(r, half), column 32 (NJ wx + j) + col.
-    f32x4* __restrict__ out = reinterpret_cast<f32x4*>(a.ws + ((long long)slab * nblk + blk) * (BM * BN)) + (wave * MI * NJ) * 256 + lane;
+    f32x4* __restrict__ out = reinterpret_cast<f32x4*>(a.ws + (SRC ? lay * a.ws_layer : 0) + ((long long)slab * nblk + blk) * (BM * BN)) + (wave * MI * NJ) * 256 + lane;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -234,8 +269,10 @@ __global__ void __launch_bounds__(kWgThreads, MINB) wgrad_kernel(const WgradK a)
 struct WgFoldK {
     float* c; const float* ws; const float* ws_col; float* colsum; float* ccol; const float* amax_a; const float* amax_b;
     int ldc, m, n, mb, nb, bm_sz, bn_sz, n_slabs, gap_at, gap, ld_ccol, n_mat;
+    long long ws_layer;      // SRC = 1: blockIdx.y = layer block (see WgradK), c advances by m * ldc per layer
 };
 constexpr int kWgFoldWaves = 16;
+template <int SRC = 0>
 __global__ void __launch_bounds__(64 * kWgFoldWaves) wgrad_fold_kernel(const WgFoldK a) {
     const int lane = threadIdx.x & 63;
     if ((int)blockIdx.x >= a.n_mat) {
@@ -264,7 +301,9 @@ __global__ void __launch_bounds__(64 * kWgFoldWaves) wgrad_fold_kernel(const WgF
     // slabs w, w + 16, ... (loads 8 deep), then the 16 sums in a fixed tree.  Slots of tiles outside (m, n) were never written:
     // they are skipped by the same wave-uniform test the producer used.
     __shared__ f32x4 red[kWgFoldWaves][64];
-    const unsigned ea = scale_exponent(amax_read(a.amax_a, lane)), eb = scale_exponent(amax_read(a.amax_b, lane));
+    const int lay = SRC ? (int)blockIdx.y : 0;
+    const unsigned ea = scale_exponent(amax_read(SRC ? a.amax_a + (lay + 1) * E3DGE_AMAX_FLOATS : a.amax_a, lane));
+    const unsigned eb = SRC ? scale_exponent(1.0f) : scale_exponent(amax_read(a.amax_b, lane));
     const int ee = (int)ea + (int)eb - 282;                                           // 1 / (sa sb) = 2^ee, |ee| can exceed the fp32 exponent range:
     const float f1 = __uint_as_float((unsigned)(127 + ee / 2) << 23), f2 = __uint_as_float((unsigned)(127 + (ee - ee / 2)) << 23);   // two factors
     const int w = threadIdx.x >> 6;
@@ -275,7 +314,8 @@ __global__ void __launch_bounds__(64 * kWgFoldWaves) wgrad_fold_kernel(const WgF
     const int row0 = a.bm_sz * bm + 32 * (MI * wy + i), col0 = a.bn_sz * bn + 32 * (NJ * wx + j);
     if (row0 >= a.m || col0 >= a.n) return;
     const long long bsz = (long long)a.bm_sz * a.bn_sz;
-    const f32x4* __restrict__ p = reinterpret_cast<const f32x4*>(a.ws + (long long)blk * bsz) + piece * 64 + lane;
+    const f32x4* __restrict__ p = reinterpret_cast<const f32x4*>(a.ws + (SRC ? lay * a.ws_layer : 0) + (long long)blk * bsz) + piece * 64 + lane;
+    float* const c_out = a.c + (SRC ? (long long)lay * a.m * a.ldc : 0);
     const long long stride = (long long)a.mb * a.nb * bsz / 4;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int s = w;
@@ -297,7 +337,7 @@ __global__ void __launch_bounds__(64 * kWgFoldWaves) wgrad_fold_kernel(const WgF
         if (x < a.n) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (y0 + e < a.m) a.c[(long long)(y0 + e) * a.ldc + x + (a.gap && x >= a.gap_at ? a.gap : 0)] = v[e] * f1 * f2;
+                if (y0 + e < a.m) c_out[(long long)(y0 + e) * a.ldc + x + (a.gap && x >= a.gap_at ? a.gap : 0)] = v[e] * f1 * f2;
         }
     }
 }
@@ -385,6 +425,232 @@ extern "C" int e3dge_wgrad(const E3dgeWgrad* g, e3dge_stream_t stream) {
     f.gap_at = g->b_gap_at; f.gap = gap; f.ld_ccol = g->ld_ccol;
     f.n_mat = ge.mb * ge.nb * 8 * (ge.bm_sz / 64) * (ge.bn_sz / 128) * 4;
     const int n_col = k.cols ? (g->m + 63) / 64 : 0;
-    wgrad_fold_kernel<<<dim3((unsigned)(f.n_mat + n_col)), dim3(64 * kWgFoldWaves), 0, st>>>(f);
+    wgrad_fold_kernel<0><<<dim3((unsigned)(f.n_mat + n_col)), dim3(64 * kWgFoldWaves), 0, st>>>(f);
     return check_launch("wgrad(fold)");
+}
+
+// =====================================================================================================================================
+// e3dge_siren_wgrad (ABI 16): the SIREN renderer's weight gradients from the training backward's g_l (d_lin) and the
+// forward's saved arguments.  The eight 256 x 256 products (pts_linears.1..7, views_linears' h_7 columns) are wgrad_kernel<.., 1>, one
+// layer per blockIdx.y; the narrow rest -- W_0 (256 x 3), views_linears' three view-direction columns, both heads and their biases --
+// is siren_wgrad_small_kernel: VALU, one pass over slabs of g_0, g_8, a_7, a_8.
+// =====================================================================================================================================
+namespace e3dge {
+
+constexpr int kSwSmallFloats = 10 * kWidth + 4;      // per-workgroup partial: w0 [256][3] | w_view dirs [256][3] | w_sigma | w_rgb [3][256] | b_sigma | b_rgb [3]
+constexpr int kSwSmallMaxWg = 1024;
+constexpr int kSwLayers = 8;
+constexpr int kSwMaxSlabs = 32;                      // per layer: 8 x 32 workgroups = one round of one workgroup per CU
+
+struct SirenWgradSmallK {
+    const float* args; const float* d_lin; const float* d_sdf; const float* d_rgb; const float* pts; const float* viewdirs;
+    float* ws;
+    long long n_pts, n16, n_slabs;
+    int slabs_per_wg, samples;
+    float box_scale;
+};
+
+// thread t: the 16 floats [16 (t & 15), + 16) of 16-feature tile t >> 4 of a slab layer = points 4 (t & 3) .. + 3, features 16 (t >> 4) + 4 q + j,
+// q = (t & 15) >> 2.  The scalars of the slab's 16 points go through LDS, padded points as zeros (and their streams are selected away).
+__global__ void __launch_bounds__(256) siren_wgrad_small_kernel(const SirenWgradSmallK a) {
+    __shared__ float sc[16][11];                      // x0[3] | view dir[3] | d_sdf | d_rgb[3] | valid
+    const int t = threadIdx.x, tile = t >> 4, idx = t & 15, n0 = 4 * (idx & 3), q = idx >> 2;
+    float w0[4][3] = {}, wv[4][3] = {}, wsg[4] = {}, wr[4][3] = {};
+    float bs = 0.0f, br[3] = {0.f, 0.f, 0.f};
+    const long long s_begin = (long long)blockIdx.x * a.slabs_per_wg;
+    const long long s_end = min(a.n_slabs, s_begin + a.slabs_per_wg);
+    for (long long slab = s_begin; slab < s_end; ++slab) {
+        __syncthreads();                              // the previous slab's scalars have been read
+        if (t < 16) {
+            const long long row = slab * 16 + t, b = row / a.n16, p = row - b * a.n16;
+            const bool ok = p < a.n_pts;
+            const long long gp = b * a.n_pts + (ok ? p : 0);
+            float v[10] = {};
+            if (ok) {
+                for (int c = 0; c < 3; ++c) v[c] = a.pts[gp * 3 + c] * a.box_scale;
+                if (a.viewdirs) for (int c = 0; c < 3; ++c) v[3 + c] = a.viewdirs[(gp / a.samples) * 3 + c];
+                if (a.d_sdf) v[6] = a.d_sdf[gp];
+                if (a.d_rgb) for (int c = 0; c < 3; ++c) v[7 + c] = a.d_rgb[gp * 3 + c];
+            }
+            for (int c = 0; c < 10; ++c) sc[t][c] = v[c];
+            sc[t][10] = ok ? 1.0f : 0.0f;
+        }
+        __syncthreads();
+        const long long base = slab * (9 * kSlabLayerF) + tile * kSlabTileF + 16 * idx;
+        f32x4 g0[4], g8[4], a7[4], a8[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            g0[k] = *reinterpret_cast<const f32x4*>(a.d_lin + base + 4 * k);
+            g8[k] = *reinterpret_cast<const f32x4*>(a.d_lin + base + 8 * kSlabLayerF + 4 * k);
+            a7[k] = *reinterpret_cast<const f32x4*>(a.args + base + 7 * kSlabLayerF + 4 * k);
+            a8[k] = *reinterpret_cast<const f32x4*>(a.args + base + 8 * kSlabLayerF + 4 * k);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float* s = sc[n0 + k];
+            const bool ok = s[10] != 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float x0 = ok ? g0[k][j] : 0.0f, x8 = ok ? g8[k][j] : 0.0f;
+                const float h7 = ok ? sin_f32(a7[k][j]) : 0.0f, h8 = ok ? sin_f32(a8[k][j]) : 0.0f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    w0[j][c] = fmaf(x0, s[c], w0[j][c]);
+                    wv[j][c] = fmaf(x8, s[3 + c], wv[j][c]);
+                    wr[j][c] = fmaf(s[7 + c], h8, wr[j][c]);
+                }
+                wsg[j] = fmaf(s[6], h7, wsg[j]);
+            }
+        }
+        if (t == 0) {
+            for (int n = 0; n < 16; ++n) { bs += sc[n][6]; br[0] += sc[n][7]; br[1] += sc[n][8]; br[2] += sc[n][9]; }
+        }
+    }
+    // the four threads of a feature quad (t & 3) in a fixed xor tree, then one writer per quad
+#pragma unroll
+    for (int off = 1; off < 4; off <<= 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                w0[j][c] += __shfl_xor(w0[j][c], off, kWave);
+                wv[j][c] += __shfl_xor(wv[j][c], off, kWave);
+                wr[j][c] += __shfl_xor(wr[j][c], off, kWave);
+            }
+            wsg[j] += __shfl_xor(wsg[j], off, kWave);
+        }
+    }
+    float* const o = a.ws + (long long)blockIdx.x * kSwSmallFloats;
+    if ((idx & 3) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int f = 16 * tile + 4 * q + j;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                o[f * 3 + c] = w0[j][c];
+                o[3 * kWidth + f * 3 + c] = wv[j][c];
+                o[7 * kWidth + c * kWidth + f] = wr[j][c];
+            }
+            o[6 * kWidth + f] = wsg[j];
+        }
+    }
+    if (t == 0) { o[10 * kWidth] = bs; o[10 * kWidth + 1] = br[0]; o[10 * kWidth + 2] = br[1]; o[10 * kWidth + 3] = br[2]; }
+}
+
+// out element i = sum over the small kernel's workgroups in fixed order: 64 consecutive elements per block, wave w of 16 sums the
+// workgroups w, w + 16, ... (loads 8 deep), then the 16 sums in a fixed tree (one thread walking all partials took 53 us)
+struct SirenWgradSmallFoldK {
+    const float* ws; float* d_w_first; float* d_w_view; float* d_w_sigma; float* d_w_rgb; float* d_b_sigma; float* d_b_rgb;
+    int n_wg;
+};
+__global__ void __launch_bounds__(64 * kWgFoldWaves) siren_wgrad_small_fold_kernel(const SirenWgradSmallFoldK a) {
+    __shared__ float red[kWgFoldWaves][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + lane;
+    float s = 0.0f;
+    if (i < kSwSmallFloats) {
+        const float* __restrict__ p = a.ws + i;
+        int g = w;
+        for (; g + 7 * kWgFoldWaves < a.n_wg; g += 8 * kWgFoldWaves) {
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = p[(long long)(g + k * kWgFoldWaves) * kSwSmallFloats];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += v[k];
+        }
+        for (; g < a.n_wg; g += kWgFoldWaves) s += p[(long long)g * kSwSmallFloats];
+    }
+    red[w][lane] = s;
+    __syncthreads();
+    if (w != 0 || i >= kSwSmallFloats) return;
+    float t = 0.0f;
+#pragma unroll
+    for (int q = 0; q < kWgFoldWaves; q += 4) t += (red[q][lane] + red[q + 1][lane]) + (red[q + 2][lane] + red[q + 3][lane]);
+    if (i < 3 * kWidth) a.d_w_first[i] = t;
+    else if (i < 6 * kWidth) a.d_w_view[i - 3 * kWidth] = t;
+    else if (i < 7 * kWidth) a.d_w_sigma[i - 6 * kWidth] = t;
+    else if (i < 10 * kWidth) a.d_w_rgb[i - 7 * kWidth] = t;
+    else if (i == 10 * kWidth) a.d_b_sigma[0] = t;
+    else a.d_b_rgb[i - 10 * kWidth - 1] = t;
+}
+
+struct SirenWgradGeom { long long n16, rows, big_slab; int big_slabs; long long small_slabs; int small_wg, slabs_per_wg; };
+static SirenWgradGeom siren_wgrad_geometry(int batch, int64_t n_pts) {
+    SirenWgradGeom g{};
+    g.n16 = (n_pts + 15) / 16 * 16;
+    g.rows = g.n16 * batch;
+    long long s = (g.rows + 255) / 256;                    // a slab of the big products is at least 256 points
+    if (s > kSwMaxSlabs) s = kSwMaxSlabs;
+    if (s < 1) s = 1;
+    g.big_slab = ((g.rows + s - 1) / s + kWgPts - 1) / kWgPts * kWgPts;
+    g.big_slabs = (int)((g.rows + g.big_slab - 1) / g.big_slab);
+    g.small_slabs = g.rows / 16;
+    g.small_wg = (int)(g.small_slabs < kSwSmallMaxWg ? g.small_slabs : kSwSmallMaxWg);
+    g.slabs_per_wg = (int)((g.small_slabs + g.small_wg - 1) / g.small_wg);
+    g.small_wg = (int)((g.small_slabs + g.slabs_per_wg - 1) / g.slabs_per_wg);
+    return g;
+}
+
+}  // namespace e3dge
+
+extern "C" int64_t e3dge_siren_wgrad_ws_floats(int batch, int64_t n_pts) {
+    if (batch <= 0 || n_pts <= 0) return 0;
+    const SirenWgradGeom g = siren_wgrad_geometry(batch, n_pts);
+    return (int64_t)kSwLayers * g.big_slabs * kWidth * kWidth + (int64_t)g.small_wg * kSwSmallFloats;
+}
+
+extern "C" int e3dge_siren_wgrad(const E3dgeSirenWgradArgs* r, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(r != nullptr, "siren_wgrad: null args");
+#if defined(E3DGE_T3_BLOCKED) && !E3DGE_T3_BLOCKED
+    // (A/B builds with point-major saved state: the backward's d_lin and the arguments are not slab-major, which this launch reads)
+    return fail(E3DGE_ERR_UNSUPPORTED, "siren_wgrad: built with E3DGE_T3_BLOCKED=0 -- the contraction reads the slab-major layout only");
+#endif
+    E3DGE_REQUIRE(r->precision == E3DGE_PREC_F16X3_G2, "siren_wgrad: precision %d -- the parameter gradients exist for E3DGE_PREC_F16X3_G2 only", r->precision);
+    E3DGE_REQUIRE(r->batch >= 0 && r->n_pts >= 0 && r->samples >= 1, "siren_wgrad: bad sizes (batch %d, n_pts %lld, samples %d)", r->batch, (long long)r->n_pts, r->samples);
+    E3DGE_REQUIRE(r->d_w && r->d_w_view_dirs && r->d_w_first && r->d_w_sigma && r->d_b_sigma && r->d_w_rgb && r->d_b_rgb, "siren_wgrad: null output");
+    hipStream_t st = as_stream(stream);
+    if (r->batch == 0 || r->n_pts == 0) {
+        hipError_t e = hipSuccess;
+        float* outs[7] = {r->d_w, r->d_w_view_dirs, r->d_w_first, r->d_w_sigma, r->d_b_sigma, r->d_w_rgb, r->d_b_rgb};
+        const size_t n[7] = {(size_t)kSwLayers * kWidth * kWidth, 3 * kWidth, 3 * kWidth, kWidth, 1, 3 * kWidth, 3};
+        for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipMemsetAsync(outs[i], 0, n[i] * 4, st);
+        return e == hipSuccess ? E3DGE_OK : fail(E3DGE_ERR_LAUNCH, "siren_wgrad: hipMemset: %s", hipGetErrorString(e));
+    }
+    E3DGE_REQUIRE(r->args && r->d_lin && r->lin_amax && r->pts && r->ws, "siren_wgrad: null input (args, d_lin, lin_amax, pts, ws)");
+    E3DGE_REQUIRE(r->viewdirs == nullptr || r->n_pts % r->samples == 0, "siren_wgrad: n_pts %lld is not a multiple of samples %d", (long long)r->n_pts, r->samples);
+    E3DGE_REQUIRE(((reinterpret_cast<uintptr_t>(r->args) | reinterpret_cast<uintptr_t>(r->d_lin) | reinterpret_cast<uintptr_t>(r->ws)) & 15) == 0,
+                  "siren_wgrad: args / d_lin / ws must be 16-B aligned");
+    E3DGE_REQUIRE(r->ws_floats >= e3dge_siren_wgrad_ws_floats(r->batch, r->n_pts), "siren_wgrad: workspace too small");
+    const SirenWgradGeom g = siren_wgrad_geometry(r->batch, r->n_pts);
+    WgradK k{};
+    k.a = r->d_lin; k.amax_a = r->lin_amax; k.b = r->args; k.amax_b = nullptr; k.ws = r->ws; k.n_rows = g.rows; k.slab = g.big_slab;
+    k.lda = 0; k.off_a = 0; k.m = kWidth; k.ldb = 0; k.off_b = 0; k.n = kWidth; k.relu_b = 0; k.mb = 1; k.nb = 1; k.cols = 0;
+    k.n16 = g.n16; k.n_valid = r->n_pts; k.ws_layer = (long long)g.big_slabs * kWidth * kWidth;
+    {
+        constexpr int lds = wg_lds_bytes<4, 2>();
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<4, 2, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return fail(E3DGE_ERR_LAUNCH, "hipFuncSetAttribute(siren_wgrad): %s", hipGetErrorString(e));
+        wgrad_kernel<4, 2, 1, 1><<<dim3((unsigned)g.big_slabs, kSwLayers), dim3(kWgThreads), lds, st>>>(k);
+        int rc = check_launch("siren_wgrad");
+        if (rc) return rc;
+    }
+    WgFoldK f{};
+    f.c = r->d_w; f.ws = r->ws; f.amax_a = r->lin_amax; f.amax_b = nullptr;
+    f.ldc = kWidth; f.m = kWidth; f.n = kWidth; f.mb = 1; f.nb = 1; f.bm_sz = 256; f.bn_sz = 256; f.n_slabs = g.big_slabs;
+    f.n_mat = 8 * 4 * 2 * 4; f.ws_layer = k.ws_layer;
+    wgrad_fold_kernel<1><<<dim3((unsigned)f.n_mat, kSwLayers), dim3(64 * kWgFoldWaves), 0, st>>>(f);
+    int rc = check_launch("siren_wgrad(fold)");
+    if (rc) return rc;
+    SirenWgradSmallK s{};
+    s.args = r->args; s.d_lin = r->d_lin; s.d_sdf = r->d_sdf; s.d_rgb = r->d_rgb; s.pts = r->pts; s.viewdirs = r->viewdirs;
+    s.ws = r->ws + (int64_t)kSwLayers * g.big_slabs * kWidth * kWidth;
+    s.n_pts = r->n_pts; s.n16 = g.n16; s.n_slabs = g.small_slabs; s.slabs_per_wg = g.slabs_per_wg; s.samples = r->samples; s.box_scale = r->box_scale;
+    siren_wgrad_small_kernel<<<dim3((unsigned)g.small_wg), dim3(256), 0, st>>>(s);
+    rc = check_launch("siren_wgrad(small)");
+    if (rc) return rc;
+    SirenWgradSmallFoldK sf{};
+    sf.ws = s.ws; sf.d_w_first = r->d_w_first; sf.d_w_view = r->d_w_view_dirs; sf.d_w_sigma = r->d_w_sigma; sf.d_w_rgb = r->d_w_rgb;
+    sf.d_b_sigma = r->d_b_sigma; sf.d_b_rgb = r->d_b_rgb; sf.n_wg = g.small_wg;
+    siren_wgrad_small_fold_kernel<<<dim3((kSwSmallFloats + 63) / 64), dim3(64 * kWgFoldWaves), 0, st>>>(sf);
+    return check_launch("siren_wgrad(small fold)");
 }

@@ -1097,6 +1097,8 @@ class Generator(nn.Module):
         # overrides (base_setup.py:53-56); same here.
         self.renderer = VolumeFeatureRenderer(renderer_opt, style_dim=self.style_dim,
                                               out_im_res=model_opt.renderer_spatial_output_dim)
+        # the reference decides the same way whether the renderer's weights get gradients (:812, :959); off = the frozen fast path
+        self.renderer.train_renderer = self.train_renderer
         self.renderer_n_latent = _opt_get(renderer_opt, 'depth', 8) + 1
         if self.full_pipeline:
             self.decoder = Decoder(model_opt)

@@ -14,8 +14,14 @@ What differs: nothing is evaluated in PyTorch.  One `e3dge_film_params` launch t
 (gamma, beta) pairs, one `e3dge_siren_render_fwd` launch does rays -> samples -> MLP -> composite; the eikonal terms,
 `sample_mode` and the training direction (gradient to the styles, to the second pass's texture FiLM and to query
 points) are further HIP launches.  Options the kernels do not cover (stratified perturbation, density
-mode, mesh extraction, gradients to the frozen generator weights) raise NotImplementedError instead of silently taking
-another path.
+mode, mesh extraction) raise NotImplementedError instead of silently taking another path.
+
+Renderer parameters: with `VolumeFeatureRenderer.train_renderer = True` (Generator sets it from
+`not freeze_renderer`, as the reference's `train_renderer` does) the first-order backward of `render` and `run_network` also
+returns the gradients of every SIREN parameter and of `sigmoid_beta`: the training backward stores g_l = gamma_l * dL/da_l, the
+contraction e3dge_siren_wgrad turns it into the weight gradients, the FiLM biases and style linears follow from d(film) on the host
+side.  Precision f16x3_g2 only; the eikonal term and the texture-FiLM pass with trainable weights are refused.  Off (the default),
+trainable SIREN parameters under a backward raise NotImplementedError, as before.
 """
 import ctypes
 import os
@@ -282,6 +288,20 @@ class SirenGenerator(nn.Module):
         self._fingerprint = None
         self.mfma_mode = default_mfma_mode()
         self.bwd_mode = default_bwd_mode()
+        self.train_params = False          # set through VolumeFeatureRenderer.train_renderer
+
+    def trainable_params(self, what, eikonal=False, tex=False):
+        """() when the renderer is not trained (train_params off) or no parameter requires grad; else siren_trainable_params(self) --
+        after refusing what the parameter gradients do not cover."""
+        if not self.train_params or not any(p.requires_grad for p in _lib.params_of(self)):
+            return ()
+        if eikonal:
+            raise NotImplementedError(f"{what}: trainable renderer parameters together with the eikonal term (second-order parameter "
+                                      "gradients) are not covered")
+        if tex:
+            raise NotImplementedError(f"{what}: trainable renderer parameters on the texture-FiLM pass are not covered")
+        _require_param_mode(self, what)
+        return tuple(siren_trainable_params(self))
 
     # -- device caches -------------------------------------------------------------------------------
     def _film_layers(self):
@@ -424,10 +444,12 @@ class SirenGenerator(nn.Module):
         reference gets by keeping the surface point in the graph (:921-930).  View directions get no gradient."""
         _lib.require_gpu(pts, "pts")
         live = pts.shape[0] and pts.shape[1]
-        if torch.is_grad_enabled() and (styles.requires_grad or pts.requires_grad) and live:
-            self.require_frozen("query_points")
+        params = self.trainable_params("query_points", want_eikonal) if torch.is_grad_enabled() and live else ()
+        if torch.is_grad_enabled() and (styles.requires_grad or pts.requires_grad or params) and live:
+            if not params:
+                self.require_frozen("query_points")
             sdf, raw, eik = _PointsQuery.apply(styles, self, pts, None if viewdirs is None else viewdirs.detach(),
-                                               box_scale, mfma_mode, bool(want_eikonal))
+                                               box_scale, mfma_mode, bool(want_eikonal), *params)
             raw = raw if want_raw else None
             return (sdf, raw, eik) if want_eikonal else (sdf, raw)
         film = self.film_params(styles)
@@ -507,7 +529,7 @@ def tangent_arguments(siren, film, args, v, box_scale, images=None, rsave=None, 
 
 
 def siren_backward(siren, film, args, d_feat, d_rgb, d_sdf, tang=None, rsave=None, want_d_pts=False, box_scale=1.0,
-                   tex_alpha=None, images=None):
+                   tex_alpha=None, images=None, lin=None):
     """dL/d(styles) (B,9,256) and dL/d(film) (B,9,2,256) from the per-point output gradients (e3dge_siren_bwd).
     args (B,N,9,256) are the forward launch's saved pre-sine arguments; any of d_feat (B,N,256), d_rgb (B,N,3),
     d_sdf (B,N) may be None.  tang + rsave add the gradient of a loss on the eikonal term.  Returns
@@ -532,10 +554,74 @@ def siren_backward(siren, film, args, d_feat, d_rgb, d_sdf, tang=None, rsave=Non
         tex_alpha=_lib.ptr(tex_alpha), batch=B, precision=siren.check_mode(siren.bwd_mode), n_pts=N, box_scale=float(box_scale),
         partials=_lib.ptr(partials), dfilm=_lib.ptr(dfilm), dstyles=_lib.ptr(dstyles), d_pts=_lib.ptr(d_pts),
         d_tex_alpha=_lib.ptr(d_ta), d_tex_beta=_lib.ptr(d_tb))
+    if lin is not None:                            # (d_lin, lin_amax) of lin_buffers(): the renderer's parameter gradients follow
+        a.d_lin, a.lin_amax = _lib.ptr(lin[0]), _lib.ptr(lin[1])
     with _lib.on_device(dev):
         rc = lib.e3dge_siren_bwd(ctypes.byref(a), _lib.stream_of(args))
     _lib.check(rc, "e3dge_siren_bwd")
     return dstyles, dfilm, d_pts, (None if d_ta is None else (d_ta, d_tb))
+
+
+# ---- renderer parameter gradients (ABI 16) ----------------------------------------------------------------------
+def siren_trainable_params(siren):
+    """The SIREN's parameters in a fixed order (pts_linears.0..7, views_linears: weight, bias, gamma.weight, gamma.bias, beta.weight,
+    beta.bias; then rgb_linear, sigma_linear: weight, bias) -- the extra autograd inputs of _RenderQuery / _PointsQuery."""
+    out = []
+    for l in siren._film_layers():
+        out += [l.weight, l.bias, l.gamma.weight, l.gamma.bias, l.beta.weight, l.beta.bias]
+    return out + [siren.rgb_linear.weight, siren.rgb_linear.bias, siren.sigma_linear.weight, siren.sigma_linear.bias]
+
+
+def _require_param_mode(siren, what):
+    siren.device_image()                                   # (check_mode reads the weight range the image build records)
+    if siren.check_mode(siren.bwd_mode) != _lib.PREC_F16X3_G2:
+        raise NotImplementedError(f"{what}: gradients of the renderer's parameters exist for backward mode 'f16x3_g2' only "
+                                  f"(mode {siren.bwd_mode!r}, or the fp32 fallback for weights with |w| >= 256)")
+
+
+def lin_buffers(B, N, device):
+    """(d_lin, lin_amax): the backward's parameter-gradient outputs -- g_l of the nine layers, laid out like the saved arguments, and
+    nine zeroed amax buffers."""
+    return (saved_state_buffer(B, N, 9, device), torch.zeros(9 * _lib.AMAX_FLOATS, device=device, dtype=torch.float32))
+
+
+def siren_param_grads(siren, film, styles, dfilm, args, d_lin, lin_amax, d_sdf, d_rgb, pts, viewdirs, samples, box_scale):
+    """Gradients of siren_trainable_params(siren), in that order, from one training backward: e3dge_siren_wgrad for the weights and
+    heads, d(film) and the styles for the FiLM biases and the gamma / beta style linears (LinearLayer: out = std_init (W s + b) + bias_init)."""
+    B, N = args.shape[0], args.shape[1]
+    dev = args.device
+    W = siren.W
+    lib = _lib.load()
+    f32 = dict(device=dev, dtype=torch.float32)
+    d_w = torch.empty((8, W, W), **f32)
+    d_wv, d_w0 = torch.empty((W, 3), **f32), torch.empty((W, 3), **f32)
+    d_ws, d_bs = torch.empty((1, W), **f32), torch.empty(1, **f32)
+    d_wr, d_br = torch.empty((3, W), **f32), torch.empty(3, **f32)
+    n_ws = lib.e3dge_siren_wgrad_ws_floats(B, N)
+    ws = torch.empty(max(n_ws, 1), **f32)
+    c = lambda t: None if t is None else t.contiguous().float()
+    d_sdf, d_rgb, pts, viewdirs = c(d_sdf), c(d_rgb), c(pts), c(viewdirs)
+    a = _lib.SirenWgradArgs(
+        args=_lib.ptr(args), d_lin=_lib.ptr(d_lin), lin_amax=_lib.ptr(lin_amax), d_sdf=_lib.ptr(d_sdf), d_rgb=_lib.ptr(d_rgb),
+        pts=_lib.ptr(pts), viewdirs=_lib.ptr(viewdirs), d_w=_lib.ptr(d_w), d_w_view_dirs=_lib.ptr(d_wv), d_w_first=_lib.ptr(d_w0),
+        d_w_sigma=_lib.ptr(d_ws), d_b_sigma=_lib.ptr(d_bs), d_w_rgb=_lib.ptr(d_wr), d_b_rgb=_lib.ptr(d_br), ws=_lib.ptr(ws),
+        ws_floats=n_ws, n_pts=N, batch=B, samples=int(samples), precision=siren.check_mode(siren.bwd_mode), box_scale=float(box_scale))
+    with _lib.on_device(dev):
+        rc = lib.e3dge_siren_wgrad(ctypes.byref(a), _lib.stream_of(args))
+    _lib.check(rc, "e3dge_siren_wgrad")
+    st = styles.detach().float()
+    st = st.unsqueeze(1).expand(-1, 9, -1) if st.ndim == 2 else st            # (B, 9, 256)
+    dg, db = dfilm[:, :, 0], dfilm[:, :, 1]                                    # (B, 9, 256)
+    d_bias = (film[:, :, 0] * db).sum(0)                                       # d b_l = sum_b gamma_l[b] d beta_l[b]
+    d_gw = 15.0 * torch.einsum('bln,blk->lnk', dg, st)
+    d_gb = 15.0 * dg.sum(0)
+    d_bw = 0.25 * torch.einsum('bln,blk->lnk', db, st)
+    d_bb = 0.25 * db.sum(0)
+    weights = [d_w0] + [d_w[i] for i in range(7)] + [torch.cat([d_w[7], d_wv], 1)]
+    out = []
+    for l in range(9):
+        out += [weights[l], d_bias[l], d_gw[l], d_gb[l], d_bw[l], d_bb[l]]
+    return out + [d_wr, d_br, d_ws, d_bs]
 
 
 class _PointsQuery(torch.autograd.Function):
@@ -545,8 +631,9 @@ class _PointsQuery(torch.autograd.Function):
     get no gradient (they are fixed samples).  The backward is not itself differentiable (once_differentiable)."""
 
     @staticmethod
-    def forward(ctx, styles, siren, pts, viewdirs, box_scale, mfma_mode, want_eik):
+    def forward(ctx, styles, siren, pts, viewdirs, box_scale, mfma_mode, want_eik, *params):
         B, N = pts.shape[0], pts.shape[1]
+        ctx.n_params = len(params)                     # trainable renderer: siren_trainable_params(siren), gradients returned in order
         ctx.set_materialize_grads(False)               # (unused outputs arrive as None in backward, not as zero tensors: a fill each)
         args = saved_state_buffer(B, N, 9, pts.device, siren.W)
         film = siren.film_params(styles)
@@ -558,13 +645,14 @@ class _PointsQuery(torch.autograd.Function):
         else:
             eik, rsave = torch.empty(0, device=pts.device), torch.empty(0, device=pts.device)
         ctx.want_eik = want_eik
-        ctx.save_for_backward(film, args, rsave)
+        extra = (styles.detach(), pts.detach(), viewdirs if viewdirs is not None else torch.empty(0, device=pts.device)) if params else ()
+        ctx.save_for_backward(film, args, rsave, *extra)
         return sdf, raw, eik
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_sdf, d_raw, d_eik):
-        film, args, rsave = ctx.saved_tensors
+        film, args, rsave = ctx.saved_tensors[:3]
         d_rgb = d_feat = None
         ds = d_sdf
         if d_raw is not None:
@@ -573,11 +661,17 @@ class _PointsQuery(torch.autograd.Function):
         tang = rs = None
         if ctx.want_eik and d_eik is not None:
             tang, rs = tangent_arguments(ctx.siren, film, args, d_eik, ctx.box_scale, ctx.images, rsave)
-        dstyles, _, d_pts, _ = siren_backward(ctx.siren, film, args, d_feat, d_rgb, ds, tang, rs,
-                                              want_d_pts=ctx.needs_input_grad[2], box_scale=ctx.box_scale, images=ctx.images)
+        lin = lin_buffers(args.shape[0], args.shape[1], args.device) if ctx.n_params else None
+        dstyles, dfilm, d_pts, _ = siren_backward(ctx.siren, film, args, d_feat, d_rgb, ds, tang, rs,
+                                                  want_d_pts=ctx.needs_input_grad[2], box_scale=ctx.box_scale, images=ctx.images, lin=lin)
+        pgrads = ()
+        if ctx.n_params:
+            styles, pts, vd = ctx.saved_tensors[3:]
+            pgrads = tuple(siren_param_grads(ctx.siren, film, styles, dfilm, args, lin[0], lin[1], ds, d_rgb, pts,
+                                             vd if vd.numel() else None, 1, ctx.box_scale))
         if ctx.styles_ndim == 2:                   # one W shared by the nine layers (reference :189-191)
             dstyles = dstyles.sum(1)
-        return (dstyles if ctx.needs_input_grad[0] else None), None, d_pts, None, None, None, None
+        return ((dstyles if ctx.needs_input_grad[0] else None), None, d_pts, None, None, None, None) + pgrads
 
 
 _DIFF_KEYS = ('gen_thumb_imgs', 'features', 'xyz', 'depth', 'sdf', 'hit_prob', 'eikonal_term')
@@ -640,10 +734,10 @@ class _RenderQuery(torch.autograd.Function):
     pre-sine arguments, e3dge_siren_render_bwd for the way back.  Cameras, near / far get no gradient."""
 
     @staticmethod
-    def differentiable(renderer, styles, focal, c2w, near, far, want_eik=False, tex_conditions=None):
+    def differentiable(renderer, styles, focal, c2w, near, far, want_eik=False, tex_conditions=None, params=()):
         ta, tb = tex_conditions if tex_conditions is not None else (None, None)
         shared = _EikShared() if want_eik else None
-        vals = _RenderQuery.apply(styles, renderer, focal, c2w, near, far, bool(want_eik), ta, tb, shared)
+        vals = _RenderQuery.apply(styles, renderer, focal, c2w, near, far, bool(want_eik), ta, tb, shared, *params)
         out = dict(zip(_DIFF_KEYS + _AUX_KEYS, vals))
         if not want_eik:
             out['eikonal_term'] = None
@@ -655,8 +749,10 @@ class _RenderQuery(torch.autograd.Function):
         return renderer._render_dict(out, c2w, near, far)
 
     @staticmethod
-    def forward(ctx, styles, renderer, focal, c2w, near, far, want_eik, tex_alpha, tex_beta, shared=None):
+    def forward(ctx, styles, renderer, focal, c2w, near, far, want_eik, tex_alpha, tex_beta, shared=None, *params):
+        # params (trainable renderer): siren_trainable_params(renderer.siren) + [sigmoid_beta], or [sigmoid_beta] alone; gradients in that order
         B, H, S = c2w.shape[0], renderer.out_im_res, renderer.N_samples
+        ctx.n_params = len(params)
         # seven differentiable outputs, a stage-1 loss touches three: without this autograd hands backward a zero tensor for each of the
         # others (a fill + a transposing copy per output, and the kernels then read and add the zeros)
         ctx.set_materialize_grads(False)
@@ -695,8 +791,9 @@ class _RenderQuery(torch.autograd.Function):
             shared.images = renderer.siren.device_image()
             shared.rsave = rsave if want_eik else None
         ta = tex[0].contiguous() if tex is not None else torch.empty(0, device=c2w.device)
+        extra = (styles.detach(), out['viewdirs']) if len(params) > 1 else ()
         ctx.save_for_backward(film, args, out['sdf'], out['dists'], out['points'], out['hit_prob'],
-                              near.reshape(B).contiguous().float(), far.reshape(B).contiguous().float(), rsave, ta)
+                              near.reshape(B).contiguous().float(), far.reshape(B).contiguous().float(), rsave, ta, *extra)
         aux = tuple(out[k] for k in _AUX_KEYS)
         ctx.mark_non_differentiable(*aux)
         return tuple(out[k] for k in _DIFF_KEYS) + aux
@@ -704,7 +801,7 @@ class _RenderQuery(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, d_rgb, d_feat, d_xyz, d_depth, d_sdf, d_hit, d_eik, *unused):
-        film, args, sdf, dists, points, weights, near, far, rsave, ta = ctx.saved_tensors
+        film, args, sdf, dists, points, weights, near, far, rsave, ta = ctx.saved_tensors[:10]
         r = ctx.renderer
         siren = r.siren
         B, H, S = film.shape[0], r.out_im_res, r.N_samples
@@ -749,6 +846,13 @@ class _RenderQuery(torch.autograd.Function):
             force_background=int(bool(r.force_background)), precision=siren.check_mode(siren.bwd_mode), d_rgb_pts=_lib.ptr(d_rgb_pts), d_sdf_pts=_lib.ptr(d_sdf_pts),
             partials=_lib.ptr(partials), dfilm=_lib.ptr(dfilm), dstyles=_lib.ptr(dstyles), d_tex_alpha=_lib.ptr(d_ta),
             d_tex_beta=_lib.ptr(d_tb))
+        lin = d_beta = None
+        if ctx.n_params:                                                     # trainable renderer (eikonal / tex passes were refused)
+            d_beta = torch.empty(B * H * H, device=dev, dtype=torch.float32)
+            a.d_sigmoid_beta = _lib.ptr(d_beta)
+        if ctx.n_params > 1:                                                 # (1 = sigmoid_beta alone: no d_lin, no contraction)
+            lin = lin_buffers(B, n_pts, dev)
+            a.d_lin, a.lin_amax = _lib.ptr(lin[0]), _lib.ptr(lin[1])
         with _lib.on_device(dev):
             if wait_for is None:
                 rc = lib.e3dge_siren_render_bwd(ctypes.byref(a), _lib.stream_of(film))
@@ -760,9 +864,16 @@ class _RenderQuery(torch.autograd.Function):
                     a.phase = 2
                     rc = lib.e3dge_siren_render_bwd(ctypes.byref(a), _lib.stream_of(film))
         _lib.check(rc, "e3dge_siren_render_bwd")
+        pgrads = ()
+        if ctx.n_params > 1:
+            styles, viewdirs = ctx.saved_tensors[10:]
+            pgrads = tuple(siren_param_grads(siren, film, styles, dfilm, args, lin[0], lin[1], d_sdf_pts, d_rgb_pts, points, viewdirs,
+                                             S, r.box_scale))
+        if ctx.n_params:
+            pgrads += (d_beta.sum().reshape(1),)
         if ctx.styles_ndim == 2:
             dstyles = dstyles.sum(1)
-        return (dstyles if ctx.needs_input_grad[0] else None), None, None, None, None, None, None, d_ta, d_tb, None
+        return ((dstyles if ctx.needs_input_grad[0] else None), None, None, None, None, None, None, d_ta, d_tb, None) + pgrads
 
 
 def _resblock_backward_torch(x, w0, b0, w1, ws, dy):
@@ -1157,6 +1268,9 @@ class VolumeFeatureRenderer(nn.Module):
         if isinstance(tex_conditions, _LazyTex) and (torch.is_grad_enabled() or return_eikonal or not self._reuse_enabled(None)):
             tex_conditions = tex_conditions.materialize()          # (only the record path can use the fused head + FiLM launch)
         tex_grad = tex_conditions is not None and not isinstance(tex_conditions, _LazyTex) and (tex_conditions[0].requires_grad or tex_conditions[1].requires_grad)
+        params = self._trainable_params(tex_conditions is not None, return_eikonal) if torch.is_grad_enabled() and c2w.shape[0] else ()
+        if params:
+            return _RenderQuery.differentiable(self, styles, focal, c2w, near, far, False, None, params)
         if torch.is_grad_enabled() and (styles.requires_grad or tex_grad) and c2w.shape[0]:
             self.siren.require_frozen("VolumeFeatureRenderer.render")
             if self.sigmoid_beta.requires_grad:
@@ -1187,6 +1301,33 @@ class VolumeFeatureRenderer(nn.Module):
         if B:
             out['eikonal_term'] = sdf_gradient(self.siren, film, args, self.box_scale)[0].reshape(B, H, H, S, 3)
         return out
+
+    @property
+    def train_renderer(self):
+        """Opt-in (default False): backward passes also return the gradients of the SIREN parameters and of sigmoid_beta (whichever
+        require grad).  Off, trainable renderer parameters under a backward raise NotImplementedError."""
+        return self.__dict__.get('_train_renderer', False)
+
+    @train_renderer.setter
+    def train_renderer(self, on):
+        self.__dict__['_train_renderer'] = bool(on)
+        self.siren.train_params = bool(on)
+
+    def _trainable_params(self, tex, eikonal):
+        """() unless train_renderer is on and a renderer parameter requires grad; then the SIREN's parameters and sigmoid_beta, or
+        sigmoid_beta alone when no SIREN parameter requires grad (its gradient comes from the compositing backward, in any precision)."""
+        if not self.train_renderer:
+            return ()
+        sb = self.sigmoid_beta
+        ps = self.siren.trainable_params("VolumeFeatureRenderer.render", eikonal, tex)
+        if not ps and not sb.requires_grad:
+            return ()
+        if not ps:                                           # only sigmoid_beta trains: the compositing backward alone
+            if eikonal or tex:
+                raise NotImplementedError("VolumeFeatureRenderer.render: a trainable sigmoid_beta together with the eikonal term or the "
+                                          "texture-FiLM pass is not covered")
+            return (sb,)
+        return ps + (sb,)
 
     # ---- backbone hand-over between the two renders of an evaluated image -------------------------------------------------
     def _reuse_key(self, styles, focal, c2w, near, far):

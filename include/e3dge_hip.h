@@ -499,6 +499,10 @@ typedef struct E3dgeSirenBwdArgs {
     float box_scale;
     float* partials; float* dfilm; float* dstyles;
     float* d_pts; float* d_tex_alpha; float* d_tex_beta;
+    /* ABI 16 (renderer parameter gradients, see e3dge_siren_wgrad below; NULL = off): */
+    float* d_lin;      /* (batch, n_pts, 9, 256) out, laid out like `args` (E3DGE_PREC_F16X3_G2: slab-major): g_l = gamma_l * dL/d a_l of
+                          every layer and point.  Rows of padded points are not written. */
+    float* lin_amax;   /* 9 amax buffers (9 * E3DGE_AMAX_FLOATS floats, zeroed by the caller): max |g_l| per layer */
 } E3dgeSirenBwdArgs;
 int e3dge_siren_bwd(const E3dgeSirenBwdArgs* args, e3dge_stream_t stream);
 
@@ -545,8 +549,40 @@ typedef struct E3dgeRenderBwdArgs {
     int phase;               /* ABI 14: 0 = both launches; 1 = only the backward of the compositing (reads the d_*_map / d_sdf / d_weights inputs, writes
                                 d_rgb_pts / d_sdf_pts; needs neither tang nor rsave); 2 = only the network backward on what phase 1 left in those buffers.
                                 Lets a caller run phase 1 beside e3dge_siren_tangent(_tr) on another stream and wait for the tangent before phase 2. */
+    /* ABI 16 (NULL = off): d_lin, lin_amax as in E3dgeSirenBwdArgs (phase 0 / 2), with n_pts = H*W*S;
+     * d_sigmoid_beta (rays) out (phase 0 / 1): each ray's share of dL/d sigmoid_beta -- sum them for the gradient. */
+    float* d_lin; float* lin_amax; float* d_sigmoid_beta;
 } E3dgeRenderBwdArgs;
 int e3dge_siren_render_bwd(const E3dgeRenderBwdArgs* args, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * ABI 16: gradients of the SIREN renderer's own weights (the reference trains them: Generator.train_renderer =
+ * not freeze_renderer, stylesdf_model.py:812; PTI fine-tunes the whole generator, projectors.py:447-640).
+ * Precision E3DGE_PREC_F16X3_G2 only: the backward launches above return E3DGE_ERR_INVALID_ARG for any other precision when
+ * d_lin is set.  First order only (no tang / rsave, no texture FiLM pass).
+ * Inputs: `args` (the forward's saved arguments) and `d_lin` / `lin_amax` (the backward's new outputs), both (batch, n_pts, 9, 256)
+ * slab-major; d_sdf (batch, n_pts) and d_rgb (batch, n_pts, 3): the gradients at the head outputs (d_sdf_pts / d_rgb_pts of a
+ * render backward, the caller's d_sdf / d_rgb of e3dge_siren_bwd; NULL = 0); pts (batch, n_pts, 3) the un-warped points and
+ * box_scale as given to the forward; viewdirs: (batch, n_pts / samples, 3) per ray (samples = S of a render), per point
+ * (samples = 1), or NULL (= 0, run_network without view directions).
+ * Outputs (all written, never accumulated into):
+ *   d_w[8]        (8, 256, 256)  dL/d W_l of pts_linears.1..7 and, last, the first 256 columns of views_linears.weight
+ *   d_w_view_dirs (256, 3)       dL/d views_linears.weight[:, 256:259]
+ *   d_w_first     (256, 3)       dL/d pts_linears.0.weight
+ *   d_w_sigma (256), d_b_sigma (1), d_w_rgb (3, 256), d_b_rgb (3)   the two heads
+ * The FiLM layers' own biases and the gamma / beta style-linear parameters follow from dfilm on the host side.
+ * ws: e3dge_siren_wgrad_ws_floats(batch, n_pts) floats of scratch, 16-B aligned (args and d_lin too).  Fixed-order split-K folds: bit-reproducible. */
+typedef struct E3dgeSirenWgradArgs {
+    const float* args; const float* d_lin; const float* lin_amax;
+    const float* d_sdf; const float* d_rgb; const float* pts; const float* viewdirs;
+    float* d_w; float* d_w_view_dirs; float* d_w_first; float* d_w_sigma; float* d_b_sigma; float* d_w_rgb; float* d_b_rgb;
+    float* ws;
+    int64_t ws_floats, n_pts;
+    int batch, samples, precision;
+    float box_scale;
+} E3dgeSirenWgradArgs;
+int64_t e3dge_siren_wgrad_ws_floats(int batch, int64_t n_pts);
+int e3dge_siren_wgrad(const E3dgeSirenWgradArgs* args, e3dge_stream_t stream);
 
 
 
