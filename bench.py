@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the BASELINE.json metric on MI355X: rendered rays/s at 64x64 rays x 24 samples.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 starts the N ranks itself (one process per GPU through torch.distributed.run, rendezvous on
 127.0.0.1) when it was not already launched by torchrun, and fails loudly if fewer than N GPUs are visible; when the driver
@@ -16,9 +16,11 @@ with no data-path collective (weak scaling); `value` = rays rendered by all rank
 Before the W warm-up steps the same launches run untimed for --prewarm-ms (default 250 ms, reported as `prewarm_ms`): the
 GPU clocks down during the seconds of host-side setup and the first ~50-100 ms of load run slower; W and K are unchanged.
 
-Extra objects on the JSON line:
+A plain run sets up, pre-warms, runs the W warm-up and K timed steps, writes --dump-outputs and prints the line;
+beside the headline keys it carries one object:
   roofline      dominant kernel of the headline (default) mode: algorithmic FLOPs per launch / its mean duration measured
                 with HIP events on the launch stream inside the timed region.
+Everything else runs only with --full, after the headline and in the same process; its objects on the line:
   modes         the same K-step measurement for BOTH contraction modes, f16x3 (default) and strict f32.
   sustained     the K-step block repeated for >= 1 s: median and spread of rays/s (the K-step line alone is ~0.1 s).
   c3            BASELINE configs[2]: per-image evaluation (pass #1, texture head, pass #2, decoder 64^2 -> 1024^2, 8 metric
@@ -195,6 +197,9 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1, help="images per GPU per step (metric config: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg as well (other modes, sustained, C3, C4, surface, inversion, "
+                         "training steps, CPU baseline); the --no-* options below drop legs from such a run")
     ap.add_argument("--c3-images", type=int, default=0,
                     help="images per rank in the C3 leg (0 = the whole evaluation set split over the ranks: ceil(2824 / N))")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -205,7 +210,9 @@ def parse_args():
     ap.add_argument("--no-c3", action="store_true")
     ap.add_argument("--no-modes", action="store_true")
     ap.add_argument("--no-sustained", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="only the K-step headline measurement (profiling runs)")
+    ap.add_argument("--headline-only", action="store_true",
+                    help="only the K-step headline measurement, also with --full (what a run without --full does; kept for the "
+                         "profiling scripts under tools/ and the commands recorded under profiles/)")
     ap.add_argument("--prewarm-ms", type=float, default=250.0,
                     help="untimed load before the W warm-up steps (and before every informational leg): the GPU clocks down "
                          "during the seconds of host-side setup and needs ~50-100 ms of load to come back")
@@ -241,7 +248,7 @@ def self_launch(args):
 
 def main():
     args = parse_args()
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_inversion = args.no_train_step = args.no_c4 = args.no_c3 = args.no_surface = True
         args.no_modes = args.no_sustained = True
     if args.gpus < 1:

@@ -10,7 +10,7 @@ G3="SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_BRANCH
 i=0
 for grp in "$G1" "$G2" "$G3"; do
   i=$((i+1))
-  E3DGE_MFMA_MODE=f32 timeout 200 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/fwd_$i" -o pmc -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-inversion --no-train-step > "$OUT/fwd_$i.log" 2>&1; echo "fwd $i rc=$?"
+  E3DGE_MFMA_MODE=f32 timeout 200 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/fwd_$i" -o pmc -- python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-inversion --no-train-step > "$OUT/fwd_$i.log" 2>&1; echo "fwd $i rc=$?"
   timeout 200 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/bwd_$i" -o pmc -- python $R/tools/bwd_bench.py 1 5 > "$OUT/bwd_$i.log" 2>&1; echo "bwd $i rc=$?"
 done
 python - "$OUT" <<'PY'
