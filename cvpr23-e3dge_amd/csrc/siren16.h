@@ -46,8 +46,10 @@ constexpr int k16LdsW = 0;
 constexpr int k16LdsFilm = k16LdsW + k16NBuf * k16ChunkFloats;        // [9][2][256]
 constexpr int k16LdsHead = k16LdsFilm + 9 * 2 * kWidth;               // w_sigma[256], w_rgb[3][256], b_sigma, b_rgb[3]
 constexpr int k16LdsW0 = k16LdsHead + kHeadFloats;                    // [3][256] first-layer weights, column-major
-constexpr int k16LdsWvt = k16LdsW0 + 3 * kWidth;                      // [3][256] view-direction columns of the view layer, x128
-constexpr int k16LdsFeat = k16LdsWvt + 3 * kWidth;                    // [kRMax][kFPitch]
+// [2][256][4] per-feature record of the view layer, one ds_read_b128 per half: (gamma, beta, w_r, w_g), (w_b, view-direction
+// columns x, y, z x128) -- gamma / beta as in the FiLM block (bias folded in, 1/128 divided out), w_rgb a copy of the head's
+constexpr int k16LdsVrec = k16LdsW0 + 3 * kWidth;
+constexpr int k16LdsFeat = k16LdsVrec + 2 * 4 * kWidth;               // [kRMax][kFPitch]
 constexpr int k16LdsPart = k16LdsFeat + kRMax * kFPitch;              // [8 waves][2 slots][256]
 constexpr int k16LdsAlpha = ((k16LdsPart + 8 * k16Slots * kWidth + 3) / 4) * 4;
 constexpr int k16LdsWgt = k16LdsAlpha + kTilePts;
@@ -60,7 +62,7 @@ constexpr int k16LdsVd = k16LdsWq + 8 * k16Slots * 16;                // [8 wave
 constexpr int k16LdsFloats = k16LdsVd + 8 * 16 * 4;
 constexpr int k16LdsBytes = k16LdsFloats * 4;
 static_assert(k16LdsBytes <= 160 * 1024, "LDS budget");
-static_assert((k16LdsFilm % 4) == 0 && (k16LdsHead % 4) == 0 && (k16LdsW0 % 4) == 0 && (k16LdsWvt % 4) == 0, "alignment");
+static_assert((k16LdsFilm % 4) == 0 && (k16LdsHead % 4) == 0 && (k16LdsW0 % 4) == 0 && (k16LdsVrec % 4) == 0, "alignment");
 
 // one 16-byte store of saved state (E3DGE_NT_STORES=1: non-temporal -- an A/B of round 6)
 #ifndef E3DGE_NT_STORES
@@ -276,7 +278,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
     float* const film_s = smem + k16LdsFilm;
     float* const head_s = smem + k16LdsHead;
     float* const w0_s = smem + k16LdsW0;
-    float* const wvt_s = smem + k16LdsWvt;
+    float* const vrec_s = smem + k16LdsVrec;
     float* const feat_acc = smem + k16LdsFeat;
     float* const part = smem + k16LdsPart;
     float* const alpha_s = smem + k16LdsAlpha;
@@ -319,19 +321,65 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
     if (CACHE == 2) pipe.init(wbuf, packed + kOffBig16b + (int64_t)(kBigLayers - 1) * k16Tiles * k16ChunkFloats, tid_k >> 6, tid_k & 63, k16Tiles);
     else pipe.init(wbuf, packed + kOffBig16b, tid_k >> 6, tid_k & 63);
     pipe.prime();
-    // FiLM block with the layer bias folded into the offset and the weights' factor 128 divided out of gamma (layers >= 1)
-    for (int i = tid_k; i < 9 * kWidth; i += k16Threads) {
-        const int l = i >> 8, n = i & 255;
-        const float gm = film_g[(l * 2 + 0) * kWidth + n], bt = film_g[(l * 2 + 1) * kWidth + n];
-        film_s[(l * 2 + 0) * kWidth + n] = (l >= 1) ? gm * (1.0f / kW16Scale) : gm;
-        film_s[(l * 2 + 1) * kWidth + n] = __fadd_rn(__fmul_rn(gm, packed[kOffBias + l * kWidth + n]), bt);
+    // The tables: this thread's share of every global read is issued first, into registers, and only then written to the LDS --
+    // one L2 round trip for the whole prologue instead of one per loop iteration (film_g was just written by another kernel,
+    // possibly on another XCD).
+    constexpr int kFilmIt = (9 * kWidth + k16Threads - 1) / k16Threads;
+    constexpr int kHeadIt = (kHeadFloats + k16Threads - 1) / k16Threads;
+    constexpr int kColIt = (3 * kWidth + k16Threads - 1) / k16Threads;
+    float ld_gm[kFilmIt], ld_bt[kFilmIt], ld_bias[kFilmIt], ld_head[kHeadIt], ld_w0[kColIt], ld_vt[kColIt];
+#pragma unroll
+    for (int j = 0; j < kFilmIt; ++j) {
+        const int i = tid_k + j * k16Threads, l = i >> 8, n = i & 255;
+        ld_gm[j] = ld_bt[j] = ld_bias[j] = 0.0f;
+        if (i < 9 * kWidth) {
+            ld_gm[j] = film_g[(l * 2 + 0) * kWidth + n];
+            ld_bt[j] = film_g[(l * 2 + 1) * kWidth + n];
+            ld_bias[j] = packed[kOffBias + l * kWidth + n];
+        }
     }
-    for (int i = tid_k; i < kHeadFloats; i += k16Threads) head_s[i] = packed[kOffWSigma + i];
-    for (int i = tid_k; i < 3 * kWidth; i += k16Threads) {
-        const int c = i >> 8, n = i & 255;           // fragment images of layer 0 / the view tail: [t][m][lane], k = 2m + half
+#pragma unroll
+    for (int j = 0; j < kHeadIt; ++j) {
+        const int i = tid_k + j * k16Threads;
+        ld_head[j] = (i < kHeadFloats) ? packed[kOffWSigma + i] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < kColIt; ++j) {
+        const int i = tid_k + j * k16Threads, c = i >> 8, n = i & 255;   // fragment images of layer 0 / the view tail: [t][m][lane], k = 2m + half
         const int src = ((n >> 5) * 2 + (c >> 1)) * 64 + (c & 1) * 32 + (n & 31);
-        w0_s[i] = packed[kOffFirst + src];
-        wvt_s[i] = packed[kOffVTail + src] * kW16Scale;
+        ld_w0[j] = ld_vt[j] = 0.0f;
+        if (i < 3 * kWidth) { ld_w0[j] = packed[kOffFirst + src]; ld_vt[j] = packed[kOffVTail + src]; }
+    }
+    // FiLM block with the layer bias folded into the offset and the weights' factor 128 divided out of gamma (layers >= 1); the
+    // view layer's (l = 8) values also go to its record
+#pragma unroll
+    for (int j = 0; j < kFilmIt; ++j) {
+        const int i = tid_k + j * k16Threads, l = i >> 8, n = i & 255;
+        if (i < 9 * kWidth) {
+            const float gm = ld_gm[j], bt = ld_bt[j];
+            const float g_s = (l >= 1) ? gm * (1.0f / kW16Scale) : gm;
+            const float b_s = __fadd_rn(__fmul_rn(gm, ld_bias[j]), bt);
+            film_s[(l * 2 + 0) * kWidth + n] = g_s;
+            film_s[(l * 2 + 1) * kWidth + n] = b_s;
+            if (l == 8) { vrec_s[4 * n + 0] = g_s; vrec_s[4 * n + 1] = b_s; }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kHeadIt; ++j) {
+        const int i = tid_k + j * k16Threads;
+        if (i < kHeadFloats) {
+            head_s[i] = ld_head[j];
+            const int c = (i >> 8) - 1, n = i & 255;     // w_rgb[c][n] (head floats 256 .. 1023)
+            if (c >= 0 && c < 3) vrec_s[(c == 2 ? 4 * kWidth : 0) + 4 * n + (c == 2 ? 0 : 2 + c)] = ld_head[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kColIt; ++j) {
+        const int i = tid_k + j * k16Threads, c = i >> 8, n = i & 255;
+        if (i < 3 * kWidth) {
+            w0_s[i] = ld_w0[j];
+            vrec_s[4 * kWidth + 4 * n + 1 + c] = ld_vt[j] * kW16Scale;
+        }
     }
     float cw[12] = {0}, focal = 1.f, nearv = 0.f, farv = 0.f;
     if (MODE == 0) {
@@ -689,66 +737,86 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) prgb[c][r] = 0.0f;
         {
-            const float* __restrict__ film_v = film + 8 * 2 * kWidth;
-            const float* __restrict__ wrgb = head_s + kWidth;
-            f32x4v pv = zero4();
-            float e_gm = 0.f, e_bt = 0.f, e_w0 = 0.f, e_w1 = 0.f, e_w2 = 0.f, fa0 = 0.f, fa1 = 0.f;
-            int e_n = 0;
-            auto epi_begin = [&](int tp) {
-                e_n = 16 * tp + col;
-                e_gm = film_v[e_n]; e_bt = film_v[kWidth + e_n];
-                e_w0 = wrgb[e_n]; e_w1 = wrgb[kWidth + e_n]; e_w2 = wrgb[2 * kWidth + e_n];
-                fa0 = fa1 = 0.f;
-            };
-            auto epi_r = [&](int r) {
-                const float varg = fmaf(e_gm, pv[r], e_bt);
-                const float h = sin_f32(varg);
-                const int pr = slab_p0 + 4 * q + r;
-                if (SAVE && pr < npts) a.save_args[saved_elem_floats(sblk, srow_block + pr, 8, e_n, 9)] = varg;
-                prgb[0][r] = fmaf(e_w0, h, prgb[0][r]);
-                prgb[1][r] = fmaf(e_w1, h, prgb[1][r]);
-                prgb[2][r] = fmaf(e_w2, h, prgb[2][r]);
-                if (MODE == 0) {
-                    fa0 = fmaf(q0[r], h, fa0);
-                    fa1 = fmaf(q1[r], h, fa1);
-                } else if (a.raw) {
-                    if (pr < npts) a.raw[((int64_t)b * a.n_pts + pt0 + pr) * 260 + 4 + e_n] = h;
-                }
-            };
-            auto epi_end = [&]() {
-                if (MODE == 0) {
-                    fa0 = sum_over_q(fa0);
-                    fa1 = sum_over_q(fa1);
-                    if (q == 0) {
-                        float* pp = part + (wave * k16Slots) * kWidth + e_n;
-                        if (slab_nslots > 0) pp[0] = fa0;
-                        if (slab_nslots > 1) pp[kWidth] = fa1;
+            // The 16 tiles unrolled (static LDS buffer t % k16NBuf, as in layers 1..7).  Tile t's epilogue -- view-direction columns,
+            // FiLM, sine, rgb / feature partials -- runs staged over the k-steps of tile t+1, the four values of a lane side by side;
+            // every operation, and the order of every accumulation, is that of the one-value-at-a-time form.
+            const f32x4v* __restrict__ vra = reinterpret_cast<const f32x4v*>(vrec_s) + col;               // (gamma, beta, w_r, w_g)
+            const f32x4v* __restrict__ vrb = reinterpret_cast<const f32x4v*>(vrec_s + 4 * kWidth) + col;  // (w_b, columns x, y, z)
+            f32x4v ra = zero4(), rb = zero4(), pacc = zero4(), paccb = zero4(), pv = zero4(), varg = zero4(), kf = zero4(), hv = zero4();
+            float fa0 = 0.f, fa1 = 0.f;
+            auto epi = [&](int tp, int g) {          // stage g of tile tp's epilogue (record of tile tp in ra / rb)
+                const int e_n = 16 * tp + col;
+                if (g == 0) {
+                    const f32x4v s4 = pacc + paccb;
+                    // view-direction columns (fp32, already x128 like the streamed weights)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pv[r] = fmaf(rb[3], dvz[r], fmaf(rb[2], dvy[r], fmaf(rb[1], dvx[r], s4[r])));
+                } else if (g == 1) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) varg[r] = fmaf(ra[0], pv[r], ra[1]);
+#ifndef E3DGE_POLY_SINE      // sin_hw_f32 in stages, as in layers 1..7
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) kf[r] = rintf(varg[r] * 0.15915494f);
+                } else if (g == 2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) kf[r] = fmaf(varg[r], 6.4206382e-09f, fmaf(varg[r], 0.15915494f, -kf[r]));
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) hv[r] = __builtin_amdgcn_sinf(kf[r]);
+#else
+                } else if (g == 2) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) hv[r] = sin_poly_f32(varg[r]);
+#endif
+                } else if (g == 3) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int pr = slab_p0 + 4 * q + r;
+                        if (SAVE && pr < npts) a.save_args[saved_elem_floats(sblk, srow_block + pr, 8, e_n, 9)] = varg[r];
+                        if (MODE != 0 && a.raw && pr < npts) a.raw[((int64_t)b * a.n_pts + pt0 + pr) * 260 + 4 + e_n] = hv[r];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        prgb[0][r] = fmaf(ra[2], hv[r], prgb[0][r]);
+                        prgb[1][r] = fmaf(ra[3], hv[r], prgb[1][r]);
+                        prgb[2][r] = fmaf(rb[0], hv[r], prgb[2][r]);
+                    }
+                } else if (g == 4) {
+                    if (MODE == 0) {
+                        fa0 = fa1 = 0.f;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { fa0 = fmaf(q0[r], hv[r], fa0); fa1 = fmaf(q1[r], hv[r], fa1); }
+                    }
+                } else if (g == 5) {
+                    if (MODE == 0) {
+                        fa0 = sum_over_q(fa0);
+                        fa1 = sum_over_q(fa1);
+                        if (q == 0) {
+                            float* pp = part + (wave * k16Slots) * kWidth + e_n;
+                            if (slab_nslots > 0) pp[0] = fa0;
+                            if (slab_nslots > 1) pp[kWidth] = fa1;
+                        }
                     }
                 }
             };
-#pragma unroll 1
-            for (int t = 0; t < k16Tiles; ++t) {
+            auto load_rec = [&](int t) { ra = vra[16 * t]; rb = vrb[16 * t]; };     // after stage 3: the last use of the previous record
+            auto view_tile = [&](int t, int sbuf) {
                 f32x4v acc = zero4(), accb = zero4();
-                if (t == 0) {
-                    tile16<true>(pipe, lane, inH, inL, acc, accb, ringH, ringL, [](int) {}, [&]() { fwd_hook(2); });
-                } else {
-                    epi_begin(t - 1);
-                    tile16<true>(pipe, lane, inH, inL, acc, accb, ringH, ringL, [&](int g) { if (g >= 1 && g <= 4) epi_r(g - 1); }, [&]() { fwd_hook(2); });
-                    epi_end();
-                }
+                tile16<true>(pipe, lane, inH, inL, acc, accb, ringH, ringL, [&](int g) {
+                    if (t > 0 && g <= 5) epi(t - 1, g);
+                    if (g == 4) load_rec(t);
+                }, [&]() { fwd_hook(2); }, sbuf);
                 pipe.advance();
-                acc = acc + accb;
-                // view-direction columns (fp32, already x128 like the streamed weights)
-                const int n = 16 * t + col;
-                const float t0 = wvt_s[n], t1 = wvt_s[kWidth + n], t2 = wvt_s[2 * kWidth + n];
+                pacc = acc; paccb = accb;
+            };
+            if constexpr (MODE == 0 && !SAVE) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = fmaf(t2, dvz[r], fmaf(t1, dvy[r], fmaf(t0, dvx[r], acc[r])));
-                pv = acc;
+                for (int t = 0; t < k16Tiles; ++t) view_tile(t, t % k16NBuf);
+            } else {      // (unrolled, the per-tile store addresses of the saved arguments / raw outputs push these past 256 VGPRs)
+#pragma unroll 1
+                for (int t = 0; t < k16Tiles; ++t) view_tile(t, -1);
             }
-            epi_begin(k16Tiles - 1);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) epi_r(r);
-            epi_end();
+            for (int g = 0; g <= 5; ++g) epi(k16Tiles - 1, g);
         }
 
         PHASE16(4);
