@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("E3DGE_LIB_PATH") or os.path.join(_HERE, "lib", "libe3
 ABI_VERSION = 16
 PREC_F32, PREC_F16X3, PREC_F16X3_V1, PREC_F16X3_G2 = 0, 1, 2, 3
 AMAX_FLOATS = 64 * 32           # E3DGE_AMAX_FLOATS: one amax buffer (include/e3dge_hip.h)
+MC_MAX_TRIS = 16                # E3DGE_MC_MAX_TRIS: triangles per case in e3dge_marching_cubes_tables (include/e3dge_hip.h)
 
 _c_float_p = ctypes.c_void_p     # device pointers travel as integers
 _i32, _i64, _f32, _vp = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
@@ -204,6 +205,10 @@ SIGNATURES = {
     "e3dge_hitprob_points": (_i32, [_vp] * 8 + [_i32, _i64, _i32, _i32, _vp]),
     "e3dge_hitprob_composite": (_i32, [_vp] * 6 + [_f32, _i32, _i32, _i64, _i32, _i32, _vp]),
     "e3dge_align_volume": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "e3dge_marching_cubes_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "e3dge_marching_cubes_count": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp]),
+    "e3dge_marching_cubes_emit": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "e3dge_marching_cubes_tables": (_i32, [_vp, _vp]),
     "e3dge_selftest_mfma": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "e3dge_selftest_mfma16": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "e3dge_selftest_mfma16x16": (_i32, [_vp, _vp, _vp, _i32, _vp]),

@@ -241,3 +241,46 @@ def stage2_fuse_state(template):
 def stage2_head_state(template):
     """Texture-head parameters: a small FiLM perturbation (the reference zero-initialises fc_1, which would test nothing)."""
     return {k: 0.05 * synthetic_tensor(STAGE2_HEAD_PREFIX + k, v.shape) for k, v in template.items()}
+
+
+# ---- analytic SDF volumes for marching cubes (tests/test_marching_cubes.py, tools/gen_golden_marching_cubes.py) ------------------------
+# name -> (h, w, d) of the aligned_sdf layout (1, h, w, d, 1).  Values come from float64 + - * / sqrt (floor for the quantised case) on
+# index coordinates in skimage's axes (x = w, y = h, z = d), cast to float32 once: the same bits with any numpy.
+MC_VOLUMES = {
+    'blob': (40, 40, 40),          # offset ellipsoid, genus 0
+    'torus': (48, 48, 48),         # genus 1
+    'twoblobs': (36, 36, 36),      # two spheres 0.06 apart: ambiguous faces in the neck
+    'quantised': (32, 32, 32),     # a sphere rounded to steps of 0.5: many exact zeros
+    'border': (40, 56, 48),        # a sphere cut by two faces of the box (open mesh), non-cubic
+    'noise': (24, 24, 24),         # random values inside, 1 on the border (closed, every kind of cell)
+}
+
+
+def mc_volume(name):
+    """The named analytic volume as float32 (h, w, d) numpy, i.e. aligned_sdf[0, ..., 0]."""
+    h, w, d = MC_VOLUMES[name]
+    x, y, z = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64), np.arange(d, dtype=np.float64), indexing='xy')
+    # meshgrid 'xy' gives arrays of shape (h, w, d) with x varying along w, y along h, z along d
+
+    def sphere(cx, cy, cz, r):
+        return np.sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy) + (z - cz) * (z - cz)) - r
+
+    if name == 'blob':
+        qx, qy, qz = (x - 19.3) / 12.5, (y - 21.7) / 9.3, (z - 18.4) / 14.1
+        f = (np.sqrt(qx * qx + qy * qy + qz * qz) - 1.0) * 10.0
+    elif name == 'torus':
+        dx, dy, dz = x - 23.6, y - 24.2, z - 23.9
+        ring = np.sqrt(dx * dx + dy * dy) - 13.3
+        f = np.sqrt(ring * ring + dz * dz) - 5.1
+    elif name == 'twoblobs':
+        f = np.minimum(sphere(12.2, 13.1, 17.9, 7.6), sphere(23.4, 23.9, 17.6, 7.9))
+    elif name == 'quantised':
+        f = np.floor(sphere(15.5, 16.0, 15.7, 10.5) * 2.0 + 0.5) / 2.0
+    elif name == 'border':
+        f = sphere(-3.0, 5.0, 20.0, 22.0)
+    elif name == 'noise':
+        f = np.random.RandomState(7).uniform(-1.0, 1.0, size=(h, w, d))
+        f[0], f[-1], f[:, 0], f[:, -1], f[:, :, 0], f[:, :, -1] = 1, 1, 1, 1, 1, 1
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(f.astype(np.float32))

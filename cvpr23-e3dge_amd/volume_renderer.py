@@ -1546,16 +1546,25 @@ class VolumeFeatureRenderer(nn.Module):
 
         render_out = self.render(focal, cam_poses, near, far, styles, tex_conditions=tex, return_eikonal=return_eikonal)
         if return_mesh:
-            # surface extraction (:1703-1731): the rendered SDF volume onto the regular grid in HIP; marching cubes itself is
-            # third-party CPU code -- 'mesh' is filled when scikit-image / trimesh are installed, 'aligned_sdf' always
+            # surface extraction (:1703-1731): the rendered SDF volume onto the regular grid and marching cubes, both in HIP
+            # ('aligned_sdf', 'mesh_verts', 'mesh_faces').  'mesh' is the reference's skimage / trimesh mesh when those are installed,
+            # otherwise built from the HIP arrays
             from . import mesh_utils
-            render_out['aligned_sdf'] = mesh_utils.align_volume(render_out['sdf'].detach())
+            aligned = render_out['aligned_sdf'] = mesh_utils.align_volume(render_out['sdf'].detach())
             try:
-                mesh, verts, faces = mesh_utils.marching_cubes_mesh(render_out['aligned_sdf'])
-                render_out['mesh'], render_out['shaded_mesh'] = mesh, mesh
-            except (ImportError, ValueError) as e:           # ValueError: no zero crossing (the reference prints and goes on)
+                mverts, mfaces = mesh_utils.marching_cubes(aligned)
+            except (ValueError, mesh_utils.NoSurfaceError) as e:   # no zero crossing (the reference prints and goes on)
+                render_out['mesh_verts'] = torch.empty(0, 3, dtype=torch.float32, device=aligned.device)
+                render_out['mesh_faces'] = torch.empty(0, 3, dtype=torch.int32, device=aligned.device)
                 render_out['mesh'] = render_out['shaded_mesh'] = None
                 render_out['mesh_error'] = str(e)
+            else:
+                render_out['mesh_verts'], render_out['mesh_faces'] = mverts, mfaces
+                if mesh_utils.third_party_available():
+                    mesh = mesh_utils.marching_cubes_mesh(aligned)[0]
+                else:
+                    mesh = mesh_utils.mesh_from_hip(mverts, mfaces)
+                render_out['mesh'], render_out['shaded_mesh'] = mesh, mesh
         if return_surface_eikonal:
             # normal at the integrated surface point (:921-930).  As in the reference the point stays in the graph: the
             # term's gradient reaches the styles through the network AND through d xyz / d styles (the Hessian-vector

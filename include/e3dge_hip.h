@@ -685,6 +685,40 @@ int e3dge_image_metric_row(float* row, const float* sums, int batch, float l2_la
 int e3dge_align_volume(float* out, const float* volume, const float* xs, const float* ys, const float* zs, const float* coef,
                        int batch, int height, int width, int depth, int channels, e3dge_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Surface extraction, marching cubes: replaces the CPU step after align_volume, the reference's
+ * _extract_mesh_with_marching_cubes (project/utils/volume_renderer.py:1733-1758, the same code as project/utils/mesh_utils.py:48-70):
+ *     verts, faces = skimage.measure.marching_cubes(sdf[0, ..., 0].permute(1, 0, 2), 0)
+ *     verts[:, a] = (verts[:, a] / n_a - 0.5) * 0.24,  n = (w, h, d);  verts[:, 2] *= -1;  verts[:, 1] *= -1
+ * The volume is read through strides in skimage's axes (x, y, z) = the (w, h, d) axes of aligned_sdf (b, h, w, d, c): value (x, y, z) at
+ * sdf[x * sx + y * sy + z * sz] (strides in floats); nx, ny, nz >= 2 and nx * ny * nz <= 2^31 / E3DGE_MC_MAX_TRIS - 1.
+ *   vertices  exactly one per grid edge whose end points straddle 0 (a value > 0 is positive, 0 counts as negative); on the edge from
+ *             the lower corner a at index i to b the coordinate is float32(i + t), t = (0 - a) / (b - a) in double (skimage's own
+ *             values; Lewiner's extra cell-interior vertices are not made).  scene != 0: then the transform above in fp32, in that order.
+ *             Order: by point p = (x * ny + y) * nz + z, then the point's +x, +y, +z edge.
+ *   faces     int32 vertex indices, wound as skimage's default gradient_direction='descent' (the right-hand normal points to the positive
+ *             side); watertight and consistently oriented, degenerate triangles kept.  Order: by cell (numbered by its lowest point p),
+ *             then the triangle order of the case table (e3dge_marching_cubes_tables).  On an ambiguous face the positive corners are
+ *             separated, so tilings differ from Lewiner's there.
+ * Three calls, no allocation, no synchronisation:
+ *   e3dge_marching_cubes_ws_bytes   workspace bytes for the grid (-1: bad sizes)
+ *   e3dge_marching_cubes_count      totals (2 ints, device) = {V, F}; {-1, -1} when 0 lies outside [min, max] of the volume (skimage's
+ *                                   "Surface level must be within volume data range."); V = 0 otherwise means no surface
+ *   e3dge_marching_cubes_emit       on the same stream, with the same workspace, volume and sizes: verts (n_verts, 3) float32, faces
+ *                                   (n_faces, 3) int32; the caller passes the totals it read back, nothing is written past them
+ *   e3dge_marching_cubes_tables     host only: n_tris (256), tri_edges (256, E3DGE_MC_MAX_TRIS, 3) (-1 past n_tris[c]).  Case c has bit k
+ *                                   set iff corner k = (k & 1, (k >> 1) & 1, (k >> 2) & 1) is positive; edge e = 4 * axis + j runs along
+ *                                   axis (0 x, 1 y, 2 z) from its lower corner, whose offsets on the other two axes are (j & 1, j >> 1)
+ *                                   in increasing axis order; the lower corner's point owns the edge's vertex.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_MC_MAX_TRIS 16
+int64_t e3dge_marching_cubes_ws_bytes(int nx, int ny, int nz);
+int e3dge_marching_cubes_count(int* totals, void* ws, int64_t ws_bytes, const float* sdf, int nx, int ny, int nz, int64_t sx, int64_t sy,
+                               int64_t sz, e3dge_stream_t stream);
+int e3dge_marching_cubes_emit(float* verts, int* faces, int64_t n_verts, int64_t n_faces, const void* ws, int64_t ws_bytes, const float* sdf,
+                              int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int scene, e3dge_stream_t stream);
+int e3dge_marching_cubes_tables(int* n_tris, int* tri_edges);
+
 /* Layout self-test: runs a 32x32xK fp32-MFMA product with the fragment conventions the render kernel
  * relies on and writes it to c (32*32 floats, row-major) for the caller to compare with a @ b^T.
  * a: (32, k) row-major, b: (32, k) row-major, k multiple of 8, k <= 256. */
