@@ -126,6 +126,18 @@ class Wgrad(ctypes.Structure):
         (n, _i32) for n in ("ld_xcol", "ld_ccol", "b_gap_at", "b_gap")]
 
 
+MESH_MAX_FACES_PER_PIXEL = 8    # E3DGE_MESH_MAX_FACES_PER_PIXEL
+
+
+class MeshRenderArgs(ctypes.Structure):
+    """Mirror of struct E3dgeMeshRenderArgs (include/e3dge_hip.h)."""
+    _fields_ = [(n, _vp) for n in ("verts", "faces", "normals", "colors")] + [("n_verts", _i64), ("n_faces", _i64), ("camera", _f32 * 12),
+               ("tan_half_fov", _f32), ("znear", _f32), ("zfar", _f32)] + [
+        (n, _f32 * 3) for n in ("light_location", "ambient_color", "diffuse_color", "specular_color", "background_color")] + [
+        ("blur_radius", _f32), ("sigma", _f32), ("gamma", _f32), ("image_size", _i32), ("faces_per_pixel", _i32)] + [
+        (n, _vp) for n in ("image", "zbuf", "pix_to_face", "status", "ws")] + [("ws_bytes", _i64), ("bin_capacity", _i64)]
+
+
 # include/e3dge_hip_experimental.h: -DE3DGE_EXPERIMENTAL builds (tools/build_variant.sh) carry two more precision modes; no extra symbols
 EXPERIMENTAL_SIGNATURES = {}
 
@@ -209,6 +221,11 @@ SIGNATURES = {
     "e3dge_marching_cubes_count": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp]),
     "e3dge_marching_cubes_emit": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "e3dge_marching_cubes_tables": (_i32, [_vp, _vp]),
+    "e3dge_depth_mesh": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "e3dge_vertex_normals_ws_bytes": (_i64, [_i64]),
+    "e3dge_vertex_normals": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "e3dge_mesh_render_ws_bytes": (_i64, [_i64, _i64, _i32, _i64]),
+    "e3dge_mesh_render": (_i32, [ctypes.POINTER(MeshRenderArgs), _vp]),
     "e3dge_selftest_mfma": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "e3dge_selftest_mfma16": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "e3dge_selftest_mfma16x16": (_i32, [_vp, _vp, _vp, _i32, _vp]),

@@ -9,9 +9,17 @@
     SurfaceMesh(vertices, faces)                     the part of trimesh.Trimesh the reference's runners use (.vertices, .faces,
                                                      .export(..., file_type='obj'))
 
+Surface renderings (mesh_utils.py:107-173 and trainer.py:1482-1534, 2254-2346 of the reference; csrc/mesh_render.hip):
+    depth_mesh(xyz) / xyz2mesh(xyz)                  the renderer's xyz map as a triangle mesh: device tensors / the reference's return
+    vertex_normals(verts, faces)                     angle-weighted vertex normals (what trimesh's .vertex_normals feeds pytorch3d)
+    MeshCamera(azim, elev, fov, ...)                 create_cameras (camera_utils.py:158-179) on the host: twelve floats
+    create_mesh_renderer / create_depth_mesh_renderer   the pytorch3d Phong renderer as one HIP rasteriser (e3dge_mesh_render)
+    render_depth_mesh(xyz, viewpoint) / render_surface_mesh(verts, faces, viewpoint)   the runner's two geometry images
+
 The renderer calls align_volume for `return_mesh=True` (volume_renderer.py:1703-1731 of the reference) and returns the aligned
 volume as 'aligned_sdf', and marching_cubes' result as 'mesh_verts' / 'mesh_faces'.  'mesh' comes from marching_cubes_mesh when
 scikit-image and trimesh are installed, otherwise from the HIP result."""
+import ctypes
 import functools
 
 import numpy as np
@@ -186,3 +194,236 @@ def third_party_available():
     except ImportError:
         return False
     return True
+
+
+# ---- surface renderings -----------------------------------------------------------------------------------------------------------------
+def depth_mesh_faces(h, w):
+    """The face list of depth_mesh on the host, in the order include/e3dge_hip.h documents: cell (r, c) in row-major order gives
+    (r w + c, (r+1) w + c, r w + c + 1) then ((r+1) w + c, (r+1) w + c + 1, r w + c + 1).  (2 (h-1)(w-1), 3) int32."""
+    r, c = np.meshgrid(np.arange(h - 1), np.arange(w - 1), indexing="ij")
+    a = (r * w + c).reshape(-1)
+    b = a + w
+    return np.stack([np.stack([a, b, a + 1], 1), np.stack([b, b + 1, a + 1], 1)], 1).reshape(-1, 3).astype(np.int32)
+
+
+def depth_mesh(xyz):
+    """xyz (1, 3, h, w) float32 on the GPU (the renderer's 'xyz') -> verts (h w, 3) float32, faces (2 (h-1)(w-1), 3) int32: xyz2mesh
+    (mesh_utils.py:107-126) with one fixed diagonal per cell and the reference's winding.  One launch, no host round trip."""
+    _lib.require_gpu(xyz, "depth_mesh: xyz")
+    if xyz.dim() != 4 or xyz.shape[0] != 1 or xyz.shape[1] != 3:
+        raise RuntimeError(f"depth_mesh expects (1, 3, h, w), got {tuple(xyz.shape)}")
+    _, _, h, w = xyz.shape
+    src = xyz.detach().contiguous()
+    verts = torch.empty(h * w, 3, dtype=torch.float32, device=src.device)
+    faces = torch.empty(2 * (h - 1) * (w - 1), 3, dtype=torch.int32, device=src.device)
+    with _lib.on_device(src.device):
+        _lib.check(_lib.load().e3dge_depth_mesh(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(src), h, w, _lib.stream_of(src)), "e3dge_depth_mesh")
+    return verts, faces
+
+
+def xyz2mesh(xyz):
+    """The reference's xyz2mesh: a trimesh.Trimesh when trimesh imports, otherwise a SurfaceMesh (as mesh_from_hip decides).  Accepts a
+    numpy array or a CPU tensor like the reference; the mesh is built on the GPU."""
+    if not isinstance(xyz, torch.Tensor):
+        xyz = torch.from_numpy(np.asarray(xyz))
+    if not xyz.is_cuda:
+        if not torch.cuda.is_available():
+            raise RuntimeError("xyz2mesh builds the mesh on the GPU (HIP); this build has no CPU path")
+        xyz = xyz.cuda()
+    return mesh_from_hip(*depth_mesh(xyz.float()))
+
+
+def _mesh_args(verts, faces, what):
+    _lib.require_gpu(verts, f"{what}: verts")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError(f"{what}: verts must be (V, 3), got {tuple(verts.shape)}")
+    if not isinstance(faces, torch.Tensor) or faces.device != verts.device or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError(f"{what}: faces must be an (F, 3) tensor on the device of verts")
+    return verts.detach().contiguous(), faces.detach().to(torch.int32).contiguous()
+
+
+def vertex_normals(verts, faces):
+    """(V, 3) float32 unit normals: the sum over a vertex's faces of the unit face normal weighted by the face's corner angle at the
+    vertex, normalised; (0, 0, 0) for a vertex without faces.  Bit-reproducible (include/e3dge_hip.h, e3dge_vertex_normals)."""
+    verts, faces = _mesh_args(verts, faces, "vertex_normals")
+    lib = _lib.load()
+    nv, nf = verts.shape[0], faces.shape[0]
+    nbytes = lib.e3dge_vertex_normals_ws_bytes(nv)
+    out = torch.empty_like(verts)
+    with _lib.on_device(verts.device):
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=verts.device)
+        _lib.check(lib.e3dge_vertex_normals(_lib.ptr(out), _lib.ptr(verts), _lib.ptr(faces), nv, nf, _lib.ptr(ws), nbytes,
+                                            _lib.stream_of(verts)), "e3dge_vertex_normals")
+    return out
+
+
+class MeshCamera:
+    """create_cameras (camera_utils.py:158-179) on the host: a camera at distance `dist` from the origin, looking at it, `azim` / `elev`
+    in degrees, `fov` the FULL field of view in degrees.  View coordinates: +x left, +y up, +z into the scene; NDC = view.xy / (view.z
+    tan(fov / 2)); the centre of pixel (row i, column j) of an S x S image is (1 - (2 j + 1) / S, 1 - (2 i + 1) / S).  The same rays as
+    generate_camera_params + get_rays at (azim, elev) with fov = 2 fov_ang.  float64 on the host; `floats()` is what the kernel takes."""
+
+    def __init__(self, azim, elev, fov, dist=1.0, znear=0.01, zfar=100.0):
+        a, e = np.deg2rad(float(azim)), np.deg2rad(float(elev))
+        self.fov, self.dist, self.znear, self.zfar = float(fov), float(dist), float(znear), float(zfar)
+        self.position = self.dist * np.array([np.cos(e) * np.sin(a), np.sin(e), np.cos(e) * np.cos(a)])
+        unit = lambda v: v / np.linalg.norm(v)
+        self.z_ax = unit(-self.position)
+        self.x_ax = unit(np.cross(np.array([0.0, 1.0, 0.0]), self.z_ax))
+        self.y_ax = np.cross(self.z_ax, self.x_ax)
+        self.tan_half_fov = float(np.tan(np.deg2rad(self.fov) / 2))
+
+    def view(self, points):
+        """(..., 3) world points -> view coordinates (float64)."""
+        d = np.asarray(points, np.float64) - self.position
+        return np.stack([d @ self.x_ax, d @ self.y_ax, d @ self.z_ax], -1)
+
+    def project(self, points):
+        """(..., 3) world points -> (x_n, y_n, view z)."""
+        v = self.view(points)
+        return np.stack([v[..., 0] / (v[..., 2] * self.tan_half_fov), v[..., 1] / (v[..., 2] * self.tan_half_fov), v[..., 2]], -1)
+
+    def pixels(self, points, image_size):
+        """(..., 3) world points -> fractional (row, column): a pixel's centre maps to its integer index."""
+        p = self.project(points)
+        return np.stack([((1 - p[..., 1]) * image_size - 1) / 2, ((1 - p[..., 0]) * image_size - 1) / 2], -1)
+
+    def floats(self):
+        """C, x_ax, y_ax, z_ax: the twelve float32 of E3dgeMeshRenderArgs.camera."""
+        return np.concatenate([self.position, self.x_ax, self.y_ax, self.z_ax]).astype(np.float32)
+
+
+def _rgb(value, name):
+    v = np.asarray(value, np.float32).reshape(-1)
+    if v.size != 3:
+        raise ValueError(f"{name} must be ((r, g, b),), got {value!r}")
+    return v
+
+
+class MeshRenderer:
+    """What create_mesh_renderer returns: renderer(verts, faces, normals=None, colors=None) -> image (1, S, S, 4).  `rasterize` also
+    returns zbuf (S, S, K) and pix_to_face (S, S, K)."""
+    SIGMA = GAMMA = 1e-4                # pytorch3d's BlendParams defaults, as is the white background
+    BACKGROUND = (1.0, 1.0, 1.0)
+
+    def __init__(self, camera, image_size=256, blur_radius=1e-6, light_location=((-0.5, 1., 5.),), faces_per_pixel=5,
+                 ambient_color=((0.5, 0.5, 0.5),), diffuse_color=((0.3, 0.3, 0.3),), specular_color=((0.2, 0.2, 0.2),)):
+        if not isinstance(camera, MeshCamera):
+            raise TypeError("create_mesh_renderer takes a MeshCamera (mesh_utils.MeshCamera(azim, elev, fov))")
+        if not 1 <= int(faces_per_pixel) <= _lib.MESH_MAX_FACES_PER_PIXEL:
+            raise ValueError(f"faces_per_pixel = {faces_per_pixel}: the HIP rasteriser keeps 1..{_lib.MESH_MAX_FACES_PER_PIXEL} fragments "
+                             "per pixel in registers")
+        if int(image_size) < 1:
+            raise ValueError(f"image_size = {image_size}")
+        self.camera, self.image_size, self.blur_radius = camera, int(image_size), float(blur_radius)
+        self.faces_per_pixel = int(faces_per_pixel)
+        self.light_location = _rgb(light_location, "light_location")
+        self.ambient_color, self.diffuse_color = _rgb(ambient_color, "ambient_color"), _rgb(diffuse_color, "diffuse_color")
+        self.specular_color = _rgb(specular_color, "specular_color")
+        self.bin_factor = 4
+
+    def _args(self):
+        a = _lib.MeshRenderArgs()
+        a.camera[:] = self.camera.floats().tolist()
+        a.tan_half_fov, a.znear, a.zfar = self.camera.tan_half_fov, self.camera.znear, self.camera.zfar
+        for name in ("light_location", "ambient_color", "diffuse_color", "specular_color"):
+            getattr(a, name)[:] = getattr(self, name).tolist()
+        a.background_color[:] = self.BACKGROUND
+        a.blur_radius, a.sigma, a.gamma = self.blur_radius, self.SIGMA, self.GAMMA
+        a.image_size, a.faces_per_pixel = self.image_size, self.faces_per_pixel
+        return a
+
+    def rasterize(self, verts, faces, normals=None, colors=None, bin_capacity=None):
+        """(image (S, S, 4), zbuf (S, S, K), pix_to_face (S, S, K)).  The status word is read back after the launch (one 8-byte copy):
+        when the per-tile face lists did not fit `bin_capacity` entries (default: 4 per face + 64 per tile) the call is repeated once
+        with what they need; a `bin_capacity` given by the caller is not grown -- the call raises instead."""
+        verts, faces = _mesh_args(verts, faces, "mesh renderer")
+        if normals is None:
+            normals = vertex_normals(verts, faces)
+        for t, name in ((normals, "normals"), (colors, "colors")):
+            if t is not None:
+                _lib.require_gpu(t, f"mesh renderer: {name}")
+                if t.shape != verts.shape or t.device != verts.device:
+                    raise RuntimeError(f"mesh renderer: {name} must be (V, 3) on the device of verts, got {tuple(t.shape)}")
+        normals = normals.detach().contiguous()
+        colors = None if colors is None else colors.detach().contiguous()
+        lib, dev, S, K = _lib.load(), verts.device, self.image_size, self.faces_per_pixel
+        nv, nf = verts.shape[0], faces.shape[0]
+        tiles = ((S + 15) // 16) ** 2
+        fixed = bin_capacity is not None
+        cap = int(bin_capacity) if fixed else self.bin_factor * nf + 64 * tiles
+        image = torch.empty(S, S, 4, dtype=torch.float32, device=dev)
+        zbuf = torch.empty(S, S, K, dtype=torch.float32, device=dev)
+        pix = torch.empty(S, S, K, dtype=torch.int32, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        a = self._args()
+        a.verts, a.faces, a.normals, a.colors = _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(normals), _lib.ptr(colors)
+        a.n_verts, a.n_faces = nv, nf
+        a.image, a.zbuf, a.pix_to_face, a.status = _lib.ptr(image), _lib.ptr(zbuf), _lib.ptr(pix), _lib.ptr(status)
+        with _lib.on_device(dev):
+            for attempt in range(2):
+                cap = min(cap, nf * tiles)
+                nbytes = lib.e3dge_mesh_render_ws_bytes(nv, nf, S, cap)
+                if nbytes < 0:
+                    raise RuntimeError("mesh renderer: " + lib.e3dge_last_error().decode(errors="replace"))
+                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+                a.ws, a.ws_bytes, a.bin_capacity = _lib.ptr(ws), nbytes, cap
+                _lib.check(lib.e3dge_mesh_render(ctypes.byref(a), _lib.stream_of(verts)), "e3dge_mesh_render")
+                need, _ = status.tolist()
+                if need <= cap:
+                    return image, zbuf, pix
+                if fixed:
+                    break
+                cap = need
+        raise RuntimeError(f"mesh renderer: the tile lists need {need} entries, bin_capacity is {cap}")
+
+    def __call__(self, verts, faces, normals=None, colors=None):
+        return self.rasterize(verts, faces, normals, colors)[0].unsqueeze(0)
+
+
+class DepthMeshRenderer(MeshRenderer):
+    """create_depth_mesh_renderer's return: renderer(verts, faces, ...) -> (image (1, S, S, 4), zbuf (1, S, S, K))."""
+
+    def __call__(self, verts, faces, normals=None, colors=None):
+        image, zbuf, _ = self.rasterize(verts, faces, normals, colors)
+        return image.unsqueeze(0), zbuf.unsqueeze(0)
+
+
+def create_mesh_renderer(camera, image_size=256, blur_radius=1e-6, light_location=((-0.5, 1., 5.),), faces_per_pixel=5, **light_kwargs):
+    """The reference's create_mesh_renderer (mesh_utils.py:145-173): pytorch3d's MeshRasterizer + SoftPhongShader with PointLights
+    (ambient_color 0.5, diffuse_color 0.3, specular_color 0.2 unless given, each ((r, g, b),)), as one HIP rasteriser.  `camera`: a
+    MeshCamera."""
+    return MeshRenderer(camera, image_size, blur_radius, light_location, faces_per_pixel, **light_kwargs)
+
+
+def create_depth_mesh_renderer(camera, image_size=256, blur_radius=1e-6, light_location=((-0.5, 1., 5.),), faces_per_pixel=5,
+                               **light_kwargs):
+    """The reference's create_depth_mesh_renderer: the same renderer returning (image, zbuf).  The reference asks for 17 faces per pixel
+    there (it only serves noise projection, which this package does not have): more than 8 is refused."""
+    return DepthMeshRenderer(camera, image_size, blur_radius, light_location, faces_per_pixel, **light_kwargs)
+
+
+def _viewpoint_camera(viewpoint, fov_ang):
+    v = viewpoint.detach().cpu().numpy() if isinstance(viewpoint, torch.Tensor) else np.asarray(viewpoint)
+    v = v.reshape(-1).astype(np.float64)
+    if v.size != 2:
+        raise ValueError(f"viewpoint must be one (azim, elev) pair in radians, got shape {v.shape}")
+    return MeshCamera(azim=np.rad2deg(v[0]), elev=np.rad2deg(v[1]), fov=2 * fov_ang, dist=1)
+
+
+_RUNNER_LIGHTS = dict(specular_color=((0.2, 0.2, 0.2),), ambient_color=((0.1, 0.1, 0.1),), diffuse_color=((0.65, .65, .65),))
+
+
+def render_depth_mesh(xyz, viewpoint, fov_ang=6.0, image_size=512):
+    """The geometry image of AERunner.render_depth_mesh (trainer.py:2295-2331): the depth mesh of `xyz` (1, 3, h, w), shaded from
+    `viewpoint` = (azim, elev) in radians as generate_camera_params returns it -> (S, S, 3) float32 in 0..255 on the device.  The
+    runner's background mask (:2283-2289, 2332-2337) is the caller's."""
+    verts, faces = depth_mesh(xyz)
+    r = create_mesh_renderer(_viewpoint_camera(viewpoint, fov_ang), image_size=image_size, light_location=((0.0, 0.0, 5.0),), **_RUNNER_LIGHTS)
+    return 255 * r(verts, faces)[0, ..., :3]
+
+
+def render_surface_mesh(verts, faces, viewpoint, fov_ang=6.0, image_size=512, colors=None):
+    """AERunner.render_trimesh (trainer.py:1482-1534) for a marching-cubes mesh on the device -> (S, S, 3) float32 in 0..255."""
+    r = create_mesh_renderer(_viewpoint_camera(viewpoint, fov_ang), image_size=image_size, light_location=((0.0, 3.0, 5.0),), **_RUNNER_LIGHTS)
+    return 255 * r(verts, faces, colors=colors)[0, ..., :3]

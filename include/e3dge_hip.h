@@ -719,6 +719,69 @@ int e3dge_marching_cubes_emit(float* verts, int* faces, int64_t n_verts, int64_t
                               int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int scene, e3dge_stream_t stream);
 int e3dge_marching_cubes_tables(int* n_tris, int* tri_edges);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * Surface renderings (csrc/mesh_render.hip): the depth mesh of an xyz map, vertex normals, and a mesh rasteriser with Phong shading --
+ * what the reference gets from xyz2mesh (project/utils/mesh_utils.py:107-126), trimesh's vertex_normals and pytorch3d's MeshRasterizer +
+ * SoftPhongShader (create_mesh_renderer, mesh_utils.py:145-173).  Additions to ABI 16.  No allocation, no synchronisation.
+ *
+ * e3dge_depth_mesh      xyz (3, h, w) float32 -> verts (h w, 3): vertex r w + c = xyz[:, r, c]; faces (2 (h-1)(w-1), 3) int32: cell (r, c),
+ *                       cells in row-major order, gives (r w + c, (r+1) w + c, r w + c + 1) then ((r+1) w + c, (r+1) w + c + 1, r w + c + 1):
+ *                       one fixed diagonal; every face has signed area -1/2 in (column, row) index space, the winding the reference's
+ *                       faces have after its column swap (its diagonal is Qhull's choice per cell).
+ * e3dge_vertex_normals  normals (V, 3) float32 = normalise( sum over the vertex's faces of corner angle x unit face normal ), the normal
+ *                       (v1 - v0) x (v2 - v0); faces of zero area (or with an index outside [0, V)) add nothing; a vertex without faces or
+ *                       with a zero sum gets (0, 0, 0).  The terms are computed in float64 and summed as 2^40 fixed-point integers:
+ *                       bit-reproducible.  ws: e3dge_vertex_normals_ws_bytes(V) bytes.
+ * e3dge_mesh_render     one mesh, one camera, one point light, material all ones with shininess 64.  camera = C (3), x_ax (3), y_ax (3),
+ *                       z_ax (3): view coordinates p_v = ((p - C).x_ax, (p - C).y_ax, (p - C).z_ax), +x left, +y up, +z into the scene; NDC
+ *                       x_n = p_v.x / (p_v.z t), y_n = p_v.y / (p_v.z t), t = tan_half_fov; the centre of pixel (row i, column j) is
+ *                       q = (1 - (2 j + 1) / S, 1 - (2 i + 1) / S).  Per pixel, for every face with |area| > 1e-8 (area = (x2 - x0)(y1 - y0) -
+ *                       (y2 - y0)(x1 - x0) in NDC) and all three p_v.z >= znear / 2:
+ *                         b0 = ((qx - x1)(y2 - y1) - (qy - y1)(x2 - x1)) / area, b1, b2 cyclically; inside = all b > 0;
+ *                         d2 = min over the three edges of the squared distance from q to the segment (an edge shorter than 1e-4: to its end
+ *                         point); covered = inside or d2 < blur_radius; d = inside ? -d2 : d2;
+ *                         b'_k = (b_k / z_k) / sum_m (b_m / z_m), clamped to [0, 1], divided by max(their sum, 1e-5); z = sum b'_k z_k
+ *                         (the NDC coordinates, b, b' and z are evaluated in float64 from the float32 vertices and camera: a face on the
+ *                         silhouette is 1e-4 NDC wide with a depth range that is not small, and float32 coordinates and edge functions lose
+ *                         its depth to rounding and cancellation; z_k, d2 and everything after the fragment's depth are float32);
+ *                       the K = faces_per_pixel covered fragments with the smallest z >= 0 are kept, equal z: the lower face index first.
+ *                       Each is shaded at P = sum b'_k vertex_k, N = normalise(sum b'_k normal_k) (normalise: x / max(|x|, 1e-6)):
+ *                         L = normalise(light - P), c = N.L, V = normalise(C - P), R = 2 c N - L,
+ *                         colour = (ambient + diffuse max(c, 0)) texel + specular (c > 0 ? max(V.R, 0) : 0)^64, texel = sum b'_k colour_k
+ *                         (colors NULL: 1);
+ *                       and blended:  p_k = 1 / (1 + exp(d_k / sigma)),  m = max((zfar - z_min) / (zfar - znear), 1e-10) with z_min the
+ *                         nearest kept z,  w_k = p_k exp(((z_min - z_k) / (zfar - znear)) / gamma)  -- the exponent is formed from the view-space
+ *                         depths, not as the difference of two rounded (zfar - z) / (zfar - znear) (only when m is the clamp 1e-10 is it
+ *                         (zfar - z_k) / (zfar - znear) - 1e-10) --  delta = max(exp((1e-10 - m) / gamma), 1e-10),
+ *                         rgb = (sum w_k colour_k + delta background) / (sum w_k + delta),  alpha = 1 - prod (1 - p_k).
+ *                       image (S, S, 4) float32; zbuf (S, S, K) float32, near to far, -1 where empty; pix_to_face (S, S, K) int32, -1 where
+ *                       empty; a pixel without fragments is (background, 0).
+ *                       Faces are binned by 16 x 16-pixel tile into lists of bin_capacity entries in all.  status (2 ints, device) =
+ *                       {entries needed, bin_capacity}: when the first exceeds the second the outputs are NOT written -- the caller reads
+ *                       status and calls again with a larger capacity and workspace.  ws: e3dge_mesh_render_ws_bytes(V, F, S, bin_capacity)
+ *                       bytes (-1: bad sizes; F x tiles must stay below 2^31).
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_MESH_MAX_FACES_PER_PIXEL 8
+typedef struct E3dgeMeshRenderArgs {
+    const float* verts; const int32_t* faces; const float* normals; const float* colors;
+    int64_t n_verts, n_faces;
+    float camera[12];
+    float tan_half_fov, znear, zfar;
+    float light_location[3], ambient_color[3], diffuse_color[3], specular_color[3], background_color[3];
+    float blur_radius, sigma, gamma;
+    int32_t image_size, faces_per_pixel;
+    float* image; float* zbuf; int32_t* pix_to_face;
+    int32_t* status;
+    void* ws;
+    int64_t ws_bytes, bin_capacity;
+} E3dgeMeshRenderArgs;
+int e3dge_depth_mesh(float* verts, int32_t* faces, const float* xyz, int h, int w, e3dge_stream_t stream);
+int64_t e3dge_vertex_normals_ws_bytes(int64_t n_verts);
+int e3dge_vertex_normals(float* normals, const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, void* ws, int64_t ws_bytes,
+                         e3dge_stream_t stream);
+int64_t e3dge_mesh_render_ws_bytes(int64_t n_verts, int64_t n_faces, int image_size, int64_t bin_capacity);
+int e3dge_mesh_render(const E3dgeMeshRenderArgs* args, e3dge_stream_t stream);
+
 /* Layout self-test: runs a 32x32xK fp32-MFMA product with the fragment conventions the render kernel
  * relies on and writes it to c (32*32 floats, row-major) for the caller to compare with a @ b^T.
  * a: (32, k) row-major, b: (32, k) row-major, k multiple of 8, k <= 256. */
