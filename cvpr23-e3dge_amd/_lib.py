@@ -138,12 +138,12 @@ class MeshRenderArgs(ctypes.Structure):
         (n, _vp) for n in ("image", "zbuf", "pix_to_face", "status", "ws")] + [("ws_bytes", _i64), ("bin_capacity", _i64)]
 
 
-# include/e3dge_hip_experimental.h: -DE3DGE_EXPERIMENTAL builds (tools/build_variant.sh) carry two more precision modes; no extra symbols
+# include/e3dge_hip_experimental.h: -DE3DGE_EXPERIMENTAL builds (tools/build_variant.sh) carry one more precision mode; no extra symbols
 EXPERIMENTAL_SIGNATURES = {}
 
 
 def has_experimental():
-    """Was the loaded library built with -DE3DGE_EXPERIMENTAL (modes f16x3_v1 / f16x3_g2)?"""
+    """Was the loaded library built with -DE3DGE_EXPERIMENTAL (mode f16x3_v1; f16x3_g2 is in every build)?"""
     return bool(load().e3dge_build_flags() & 1)
 
 

@@ -24,18 +24,10 @@ constexpr int kPkSlab = 9 * 2 * 1024;            // bytes of one weight slab: (3
 // -DE3DGE_PK_TIMING: waves 0 and NW-1 of workgroup 0 accumulate shader-cycle deltas per phase of a step (0: vmcnt + barrier,
 // 1: DMA issue, 2: fragment reads + MFMAs, 3: epilogue) and leave them in the unused floats of the output amax buffer's first
 // line (tools/dec2_check.py --timing).
-#ifndef E3DGE_PK_OVL
-#define E3DGE_PK_OVL 0
-#endif
-#ifndef E3DGE_PK_S1_PM
-#define E3DGE_PK_S1_PM 1         // stride-1 conv: product-major MFMA order (0 = three dependent MFMAs per accumulator in a row)
-#endif
-#ifndef E3DGE_PK_ISSUE_TAPS
-#define E3DGE_PK_ISSUE_TAPS 6    // the LDS-DMA pieces of the next step go out behind the MFMAs of this many taps (stride-1 and fused up-sampling kernels)
-#endif
-#ifndef E3DGE_PK_EPI_VALU
-#define E3DGE_PK_EPI_VALU 8      // VALU instructions of a finished tile's epilogue scheduled behind each MFMA of the next tile
-#endif
+// the LDS-DMA pieces of the next step go out behind the MFMAs of this many taps (stride-1 and fused up-sampling kernels); behind 1 / 3 / 9
+// taps measured within 1 % (the wait at the step's top is barrier skew, not DMA latency)
+constexpr int kPkIssueTaps = 6;
+constexpr int kPkEpiValu = 8;    // VALU instructions of a finished tile's epilogue scheduled behind each MFMA of the next tile
 #ifdef E3DGE_PK_TIMING
 #define PK_T(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; } while (0)
 #define PK_T_INIT unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter(); const unsigned long long tbegin = tlast
@@ -405,7 +397,7 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
     //                          planes' leftover pieces over the waves), lane's patch entry packed (row << 8 | column) in a register
     // and the sources of step + 1 are computed ONCE at the top of a step (Src, pinned in scalar registers).
     constexpr int NWS = (NWP + NW - 1) / NW, PR = (NPP + NW - 1) / NW, ROT = NW >= 4 ? NW / 4 : 1;
-    constexpr int NSLOT = NWS + 4 * PR, PPT = (NSLOT + E3DGE_PK_ISSUE_TAPS - 1) / E3DGE_PK_ISSUE_TAPS;
+    constexpr int NSLOT = NWS + 4 * PR, PPT = (NSLOT + kPkIssueTaps - 1) / kPkIssueTaps;
     uint32_t wvo[NWS];
 #pragma unroll
     for (int j = 0; j < NWS; ++j) {
@@ -541,9 +533,10 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
     // program order behind the MFMAs they would not overlap at all -- a wave issues in order, and its partner on the SIMD runs
     // the same phase (measured: moving the epilogue into the MFMA phase without the interleave changed nothing).
     constexpr int NH = 4 * NCT * NPT;
-    // E3DGE_PK_OVL: 0 never, 1 whenever two accumulator sets fit (NCT NPT <= 2; four tiles + their copy + the slices' temporaries
-    // spill 252-348 B), 2 only for the fused-ToRGB kernels
-    constexpr bool OVL = E3DGE_PK_OVL == 1 ? NCT * NPT <= 2 : (E3DGE_PK_OVL == 2 ? (RGB && NCT * NPT <= 2) : false);
+    // The overlapped form (the finished tile's slices threaded between the next tile's MFMAs) is off: it measured SLOWER, 86 -> 92-94 us
+    // on the last conv and 101 vs 95 us in the fused-ToRGB kernel, and four tiles + their copy + the slices' temporaries spilled 252-348 B.
+    // Its code path stays for now: taking it out moved instructions in the stride-1 kernels, which is not this change's business.
+    constexpr bool OVL = false;
     unsigned shw[2], slw[2];                         // words of the pair's first group, kept until the second is done
     float m8 = 0.0f;
     auto epi_slice = [&](int h) {
@@ -717,7 +710,7 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
                         bh[py * NPX + px] = *reinterpret_cast<const u32x4*>(xb + pix * 16);
                         bl[py * NPX + px] = *reinterpret_cast<const u32x4*>(xb + XPLANE + pix * 16);
                     }
-#if E3DGE_PK_S1_PM        // product-major: consecutive MFMAs go to different accumulators (cf. pkconv_upblur2_kernel)
+                // product-major: consecutive MFMAs go to different accumulators (cf. pkconv_upblur2_kernel)
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
@@ -730,17 +723,6 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
                 for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
                     for (int pt = 0; pt < NPT; ++pt) acc[ct][pt] = mfma16(ah[ct], bl[pt], acc[ct][pt]);
-#else
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                    for (int pt = 0; pt < NPT; ++pt) {
-                        f32x16& d = acc[ct][pt];
-                        d = mfma16(ah[ct], bh[pt], d);
-                        d = mfma16(al[ct], bh[pt], d);
-                        d = mfma16(ah[ct], bl[pt], d);
-                    }
-#endif
                 if (EPI) {                               // this tap's slices of the finished tile, threaded between its MFMAs
 #pragma unroll
                     for (int h = 0; h < NH; ++h)
@@ -748,7 +730,7 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
 #pragma unroll
                     for (int i = 0; i < 3 * NCT * NPT; ++i) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                   // one MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x002, E3DGE_PK_EPI_VALU, 0);   // then this many VALU instructions of the slices
+                        __builtin_amdgcn_sched_group_barrier(0x002, kPkEpiValu, 0);   // then this many VALU instructions of the slices
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -896,7 +878,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) pkconv_upblur2_kerne
     // epilogue -- three registers each, which is what spilled in the 2 x 16 form.  The 64-bit sources of a chunk are computed once
     // (Src), not behind every tap.
     constexpr int NWS = (NWP + NW - 1) / NW, PR = (NPP + NW - 1) / NW, ROT = NW / 4;
-    constexpr int NSLOT = NWS + 4 * PR, PPT = (NSLOT + E3DGE_PK_ISSUE_TAPS - 1) / E3DGE_PK_ISSUE_TAPS;
+    constexpr int NSLOT = NWS + 4 * PR, PPT = (NSLOT + kPkIssueTaps - 1) / kPkIssueTaps;
     uint32_t pkv[4];                                     // (round 0; later rounds are derived from it when they are issued)
     int rws[4];
     unsigned vmask = 0;

@@ -291,7 +291,7 @@ template <int NCT>
 __global__ void __launch_bounds__(256) pkconv_down_kernel(const PkConvK a) {
     constexpr int NW = 4, NT = 256, TH = 4, TW = 32, PH = TH + 1, PW = TW + 1, NPIX = PH * PW, NPP = (NPIX + 63) / 64;
     constexpr int NPL = 16, XPLANE = NPIX * 16, XST = NPL * XPLANE, WST = NCT * kPkSlab, STAGE = XST + WST;
-    constexpr int NXS = (NPL / NW) * NPP, NWP = NCT * 18, NWS = (NWP + NW - 1) / NW, NSLOT = NXS + NWS, PPT = (NSLOT + E3DGE_PK_ISSUE_TAPS - 1) / E3DGE_PK_ISSUE_TAPS;
+    constexpr int NXS = (NPL / NW) * NPP, NWP = NCT * 18, NWS = (NWP + NW - 1) / NW, NSLOT = NXS + NWS, PPT = (NSLOT + kPkIssueTaps - 1) / kPkIssueTaps;
     static_assert(NPL % NW == 0, "planes are dealt out four per round");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_pk[];
     float* const tab = reinterpret_cast<float*>(smem_pk + 2 * STAGE);        // [3][32 NCT]: (scale W) s of this workgroup's channels

@@ -32,34 +32,8 @@ constexpr int kMcFragBytes = 64 * 16;                 // one A fragment: 64 lane
 constexpr int kMcSlabBytes = 9 * 2 * kMcFragBytes;    // (co-tile, chunk): 9 taps x (hi, lo) = 18,432 B
 constexpr int kMcThreads = 512;                       // 8 waves: two per SIMD
 constexpr int kMcMaxCi = 1024;                        // style vector staged in LDS
-// How far ahead the input patches are loaded (1 or 2 steps), per tile shape: A = 4x32 px, B = 4x64, C = 8x64 / 64 co,
-// D = 8x64 / 32 co, TA / TD = the two transposed shapes.  Two steps ahead costs NIT*8 more registers but lets the two wave
-// groups run their phases in opposite order (see run_step).
-#ifndef E3DGE_MC_AH_A
-#define E3DGE_MC_AH_A 1
-#endif
-#ifndef E3DGE_MC_AH_B
-#define E3DGE_MC_AH_B 1
-#endif
-#ifndef E3DGE_MC_AH_C
-#define E3DGE_MC_AH_C 1
-#endif
-#ifndef E3DGE_MC_AH_D
-#define E3DGE_MC_AH_D 1
-#endif
-#ifndef E3DGE_MC_AH_TA
-#define E3DGE_MC_AH_TA 1
-#endif
-#ifndef E3DGE_MC_AH_TD
-#define E3DGE_MC_AH_TD 1
-#endif
-#ifndef E3DGE_MC_TAPGROUP
-#define E3DGE_MC_TAPGROUP 3
-#endif
-#ifndef E3DGE_MC_SKEW
-#define E3DGE_MC_SKEW 1
-#endif
-constexpr bool kMcSkew = E3DGE_MC_SKEW != 0;      // (with kMcAhead == 2) opposite phase order for waves 0-3 / 4-7              // input patches are loaded this many steps ahead (1 or 2)
+// The input patches are loaded ONE step ahead in every tile shape.  Two steps ahead (NIT*8 more registers) let the two wave groups
+// run their issue / convert / compute phases in opposite order: built and measured in round 2, no gain beyond noise.
 #ifdef E3DGE_MC_TIMING
 #define MC_T(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; } while (0)
 #else
@@ -90,11 +64,12 @@ struct ModconvK {
 // A workgroup = 8 waves = TH rows x CG co-groups; a wave owns NCT co-tiles x NPT pixel tiles (32 px) of its row.
 // Pipeline over the steps (tile, 16-channel chunk) of a persistent workgroup:
 //   step s computes from LDS buffers [s & 1]; at its top the weight DMA of step s+1 and the global loads of the input
-//   patch of step s+2 (two steps ahead: HBM latency is longer than one step's MFMAs) are issued; at its end the patch of
-//   step s+1, loaded one step earlier, is modulated, split into f16 hi/lo and written to LDS buffer [(s+1) & 1].
+//   patch of step s+1 are issued; at its end that patch is modulated, split into f16 hi/lo and written to LDS buffer [(s+1) & 1].
+// (kMcAhead, steps the loads run ahead, is kept as a parameter because it is part of the kernels' names; 1 is the only schedule)
 template <bool UP, int TH, int NPT, int CG, int NCT, int kMcAhead>
 __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
     static_assert(TH * CG == 8, "8 waves");
+    static_assert(kMcAhead == 1, "the input patches are loaded one step ahead");
     constexpr int TW = 32 * NPT;
     constexpr int PH = UP ? TH + 1 : TH + 2, PW = UP ? TW + 1 : TW + 2;      // patch with halo
     constexpr int NPIX = PH * PW;
@@ -123,8 +98,8 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
         ty = t % a.tiles_y; t /= a.tiles_y;
         cb = t % a.co_blocks; b = t / a.co_blocks;
     };
-    // Position of a step: tile k (of this workgroup) and chunk c, with the tile's coordinates.  Three cursors walk the steps
-    // (current, +1 for the weight DMA and the LDS stores, +kMcAhead for the global loads) and are ADVANCED, not recomputed:
+    // Position of a step: tile k (of this workgroup) and chunk c, with the tile's coordinates.  The cursors that walk the steps
+    // (current, +1 for the weight DMA and the LDS stores, and its copy for the global loads) are ADVANCED, not recomputed:
     // step / n_chunks and the three divisions of tile_of for each of them were ~10 scalar divisions per step -- 13 SALU
     // instructions per MFMA in the counters (profiles/r2_pmc_issue_modconv.txt), all in the issue stream of the same waves.
     struct Pos { int k, c, b, cb, ty, tx; };
@@ -240,17 +215,15 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
         }
     };
 
-    // ---- prologue: step 0 into buffers 0 (and, two steps ahead, step 1 on its way) ----------------------------------
+    // ---- prologue: step 0 into buffers 0 ----------------------------------------------------------------------------
     Pos p_cur = pos_at(0);                               // the step being computed
     Pos p_nx1 = p_cur; advance(p_nx1);                   // step + 1
     Pos p_nxa = p_nx1;                                   // step + kMcAhead
-    if (kMcAhead == 2) advance(p_nxa);
     int b_lds = p_cur.b;
     load_style(b_lds);
     load_epilogue_consts(p_cur);
     issue_weights(p_cur, 0);
     load_input(p_cur, true, preg[0]);
-    if (kMcAhead == 2 && nsteps > 1) load_input(p_nx1, false, preg[1]);
     __syncthreads();                                   // s_lds visible
     store_input(p_cur, true, 0, preg[0]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -262,14 +235,13 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
 
     f32x16 acc[NPH][NCT][NPT];
     float amax_wg = 0.0f;
-    // pr_load: registers the prefetch of this step goes to; pr_store: registers holding the patch of step+1
     auto run_step = [&](int step, float (&pr_load)[NIT][8], const float (&pr_store)[NIT][8]) {
         const int cur = step & 1;
         const int k = p_cur.k, c = p_cur.c;
-        const bool has1 = step + 1 < nsteps, hasp = step + kMcAhead < nsteps;
+        const bool has1 = step + 1 < nsteps;
         if (has1) issue_weights(p_nx1, cur ^ 1);
         auto do_issue = [&]() {
-            if (hasp) load_input(p_nxa, false, pr_load);
+            if (has1) load_input(p_nxa, false, pr_load);
             MC_T(0);
         };
         auto do_compute = [&]() {
@@ -313,7 +285,7 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
                             d = mfma16(ah[ct], bl[pt], d);
                         }
                     // the scheduler otherwise hoists the fragment reads of all nine taps (72 x 4 registers) and spills
-                    if (tap % E3DGE_MC_TAPGROUP == E3DGE_MC_TAPGROUP - 1) __builtin_amdgcn_sched_barrier(0);
+                    if (tap % 3 == 2) __builtin_amdgcn_sched_barrier(0);
                 }
             }
             MC_T(1);
@@ -368,37 +340,19 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
             }
             MC_T(3);
         };
-        // Two steps ahead the staging of a step does not depend on this step's loads, so the two wave groups (one wave per
-        // SIMD each) run the phases in opposite order: while waves 0-3 issue loads and convert, waves 4-7 own the matrix
-        // pipe, and vice versa -- the MFMA phase of one group covers the VMEM / VALU / LDS-store phase of the other.
-        if (kMcAhead == 2 && kMcSkew && wave >= 4) {
-            do_compute();
-            do_issue();
-            do_convert();
-        } else {
-            do_issue();
-            if (kMcAhead == 2 && kMcSkew) { do_convert(); do_compute(); }
-            else { do_compute(); do_convert(); }
-        }
-        // weights of step s+1 (DMA, issued before this step's prefetch loads) must have landed.  Two steps ahead, the NIT*8
-        // loads just issued may stay in flight (vmcnt retires in order: "at most NIT*8 outstanding" = everything older is done)
-        if (kMcAhead == 2 && hasp) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NIT * 8) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        do_issue();
+        do_compute();
+        do_convert();
+        // weights of step s+1 (DMA, issued before this step's prefetch loads) must have landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         MC_T(4);
         __syncthreads();
         MC_T(5);
         p_cur = p_nx1;
         advance(p_nx1);
-        if (kMcAhead == 2) advance(p_nxa); else p_nxa = p_nx1;
+        p_nxa = p_nx1;
     };
-    if (kMcAhead == 2) {
-        for (int step = 0; step < nsteps; step += 2) {
-            run_step(step, preg[0], preg[1]);           // loads step+2 -> preg[0]; stores step+1 from preg[1]
-            if (step + 1 < nsteps) run_step(step + 1, preg[1], preg[0]);
-        }
-    } else {
-        for (int step = 0; step < nsteps; ++step) run_step(step, preg[0], preg[0]);   // loaded at the top, stored at the end
-    }
+    for (int step = 0; step < nsteps; ++step) run_step(step, preg[0], preg[0]);   // the patch of step+1: loaded at the top, stored at the end
 #ifdef E3DGE_MC_TIMING
     if (blockIdx.x == 0 && tid == 0 && a.out_amax) {   // profiling build: cycle sums in the unused floats of slot 0's line
         for (int i = 0; i < 6; ++i) a.out_amax[1 + i] = (float)tacc[i];
@@ -559,7 +513,7 @@ decoder_demod_kernel(const E3dgeModLayer* __restrict__ tab, int n_layers, int to
     }
 }
 
-template <bool UP, int TH, int NPT, int CG, int NCT, int AH>
+template <bool UP, int TH, int NPT, int CG, int NCT>
 static int launch_modconv(ModconvK k, hipStream_t st, const char* what) {
     constexpr int TW = 32 * NPT;
     constexpr int PH = UP ? TH + 1 : TH + 2, PW = UP ? TW + 1 : TW + 2;
@@ -573,7 +527,7 @@ static int launch_modconv(ModconvK k, hipStream_t st, const char* what) {
     const int64_t n_tiles = (int64_t)k.B * k.co_blocks * k.tiles_y * k.tiles_x;
     E3DGE_REQUIRE(n_tiles < ((int64_t)1 << 30), "%s: too many tiles", what);
     k.n_tiles = (int)n_tiles;
-    auto fn = &modconv_kernel<UP, TH, NPT, CG, NCT, AH>;
+    auto fn = &modconv_kernel<UP, TH, NPT, CG, NCT, 1>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return fail(E3DGE_ERR_LAUNCH, "hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
     const int wgs_per_cu = (160 * 1024) / lds >= 2 ? 2 : 1;
@@ -702,12 +656,12 @@ extern "C" int e3dge_modconv3x3(const E3dgeModconvArgs* r, e3dge_stream_t stream
     const int64_t px = (int64_t)r->height * r->width;
     // tile shapes by layer size, so that the small early layers still spread over the 256 CUs
     if (!r->upsample) {
-        if (r->co % 64 != 0) return launch_modconv<false, 8, 2, 1, 1, E3DGE_MC_AH_D>(k, st, "modconv3x3<8x64,32co>");
-        if (px <= 64 * 64) return launch_modconv<false, 4, 1, 2, 1, E3DGE_MC_AH_A>(k, st, "modconv3x3<4x32,64co>");
+        if (r->co % 64 != 0) return launch_modconv<false, 8, 2, 1, 1>(k, st, "modconv3x3<8x64,32co>");
+        if (px <= 64 * 64) return launch_modconv<false, 4, 1, 2, 1>(k, st, "modconv3x3<4x32,64co>");
         // (above 128^2 an 8 x 64 tile with two co-tiles per wave measured a few % faster in round 2, but its instantiation spills 60 B;
         // this planar path is the fallback of the packed pipeline now, so the 4 x 64 shape serves every larger size: no scratch anywhere)
-        return launch_modconv<false, 4, 2, 2, 1, E3DGE_MC_AH_B>(k, st, "modconv3x3<4x64,64co>");
+        return launch_modconv<false, 4, 2, 2, 1>(k, st, "modconv3x3<4x64,64co>");
     }
-    if (r->co % 64 == 0) return launch_modconv<true, 4, 1, 2, 1, E3DGE_MC_AH_TA>(k, st, "modconv3x3T<4x32,64co>");
-    return launch_modconv<true, 8, 1, 1, 1, E3DGE_MC_AH_TD>(k, st, "modconv3x3T<8x32,32co>");
+    if (r->co % 64 == 0) return launch_modconv<true, 4, 1, 2, 1>(k, st, "modconv3x3T<4x32,64co>");
+    return launch_modconv<true, 8, 1, 1, 1>(k, st, "modconv3x3T<8x32,32co>");
 }

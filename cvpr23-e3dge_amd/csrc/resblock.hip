@@ -27,14 +27,8 @@ constexpr int kRbTilesOut = kRbOut / 32;  // 16
 constexpr int kRbCSteps = kRbStepsIn / 2;                   // 10 k-steps per chunk
 constexpr int kRbChunkFloats = kRbCSteps * 2 * 64 * 4;      // [k-step][hi|lo][lane][4 words] = 5120 floats = 20 KiB
 constexpr int kRbPieces = kRbChunkFloats * 4 / (4 * 64 * 16);   // 5 LDS-DMA pieces (16 B per lane) per wave and chunk
-#ifndef E3DGE_RB_NBUF
-#define E3DGE_RB_NBUF 5
-#endif
-constexpr int kRbNBuf = E3DGE_RB_NBUF;                      // LDS weight buffers
-#ifndef E3DGE_RB_RING
-#define E3DGE_RB_RING 2
-#endif
-constexpr int kRbRing = E3DGE_RB_RING;                      // k-steps of (hi, lo) weight fragments held: 1 consumed + the rest in flight
+constexpr int kRbNBuf = 5;                                  // LDS weight buffers
+constexpr int kRbRing = 2;                                  // k-steps of (hi, lo) weight fragments held: 1 consumed + the rest in flight
 constexpr int kRbChunksG1 = kRbTilesIn * 2;                 // W_0: per out tile chunk A (k 0..159), chunk B (k 160..319)
 constexpr int kRbChunksG2 = kRbTilesOut * 4;                // per out tile: W_s A, W_s B, W_1 A, W_1 B
 constexpr int kRbChunks = kRbChunksG1 + kRbChunksG2;        // 84

@@ -261,14 +261,14 @@ __global__ void __launch_bounds__(kThreads) siren_kernel(const SirenK a) {
                 for (int t = 0; t < kNT; ++t) {
                     f32x16 acc = zero16();
                     if (t == 0) {
-                        acc = big_tile<false, 0>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), chunk_sync, issue_piece);
+                        acc = big_tile<false>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), chunk_sync, issue_piece);
                     } else {
                         // FiLM (gamma, beta') of the 4 registers being processed, and of the NEXT 4 (fetched from LDS one quad
                         // ahead: a read issued right before its use exposes the LDS latency four times per tile)
                         const float* __restrict__ fl = film_l + 32 * (t - 1) + 4 * half;
                         f32x4 g4 = *reinterpret_cast<const f32x4*>(fl), b4 = *reinterpret_cast<const f32x4*>(fl + kWidth);
                         f32x4 g4n = g4, b4n = b4, sarg;
-                        acc = big_tile<false, E3DGE_SPREAD_STD>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, [&](int r) {
+                        acc = big_tile<false>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, [&](int r) {
                             if ((r & 3) == 0 && r < 12) {
                                 g4n = *reinterpret_cast<const f32x4*>(fl + 8 * ((r >> 2) + 1));
                                 b4n = *reinterpret_cast<const f32x4*>(fl + kWidth + 8 * ((r >> 2) + 1));
@@ -542,10 +542,10 @@ __global__ void __launch_bounds__(kThreads) siren_kernel(const SirenK a) {
                 f32x16 acc = zero16();
                 if (!F16) {
                     if (t == 0) {
-                        acc = big_tile<true, 0>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), chunk_sync, issue_piece);
+                        acc = big_tile<true>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), chunk_sync, issue_piece);
                     } else {
                         epi_begin(t - 1);
-                        acc = big_tile<true, E3DGE_SPREAD_VIEW>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, epi_r, chunk_sync, issue_piece);
+                        acc = big_tile<true>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, epi_r, chunk_sync, issue_piece);
                         epi_end();
                     }
                     acc = mfma32(a0, wvt[(t * 2 + 0) * 64 + lane], acc);

@@ -30,16 +30,11 @@ constexpr int k16ChunkFloats = 16 * kWidth;      // one tile x K = 256: 16 KiB
 constexpr int k16Chunks = kBigLayers * k16Tiles; // 128 chunks per 128-point sub-tile
 // One workgroup barrier per tile.  (Per two tiles with a fifth LDS buffer measured the same, 0.3140 vs 0.3145 ms: the wait at
 // the barrier is where the two waves of a SIMD queue for the matrix pipe, not a cost of the barrier -- removed)
-#ifndef E3DGE_16_ABL
-#define E3DGE_16_ABL 0      // timing ablations (wrong results): 4 = no workgroup barrier in the weight pipe, 8 = no
-                            // transmittance scan, 16 = no colour compositing scan, 32 = no ordered merge of the feature partials
-#endif
 constexpr int k16NBuf = 4;                       // LDS weight buffers
 constexpr int k16Slots = 2;                      // rays a 16-point slab can touch when S >= 16
-#ifndef E3DGE_16_RING
-#define E3DGE_16_RING 2     // 2, 4 and 8 measure the same (0.320 / 0.320 / 0.323 ms): the fragment reads are not latency-exposed
-#endif
-constexpr int k16Ring = E3DGE_16_RING;           // k-steps of (hi, lo) fragments held in registers (must divide 8)
+// k-steps of (hi, lo) fragments held in registers (must divide 8).  2, 4 and 8 measured the same (0.320 / 0.320 / 0.323 ms):
+// the fragment reads are not latency-exposed
+constexpr int k16Ring = 2;
 
 // ---- LDS carve (floats) ----
 constexpr int k16LdsW = 0;
@@ -64,16 +59,9 @@ constexpr int k16LdsBytes = k16LdsFloats * 4;
 static_assert(k16LdsBytes <= 160 * 1024, "LDS budget");
 static_assert((k16LdsFilm % 4) == 0 && (k16LdsHead % 4) == 0 && (k16LdsW0 % 4) == 0 && (k16LdsVrec % 4) == 0, "alignment");
 
-// one 16-byte store of saved state (E3DGE_NT_STORES=1: non-temporal -- an A/B of round 6)
-#ifndef E3DGE_NT_STORES
-#define E3DGE_NT_STORES 1
-#endif
+// one 16-byte store of saved state: non-temporal (against plain stores an A/B of round 6)
 __device__ __forceinline__ void save_st4(float* p, const f32x4v& v) {
-#if E3DGE_NT_STORES
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4v*>(p));
-#else
-    *reinterpret_cast<f32x4v*>(p) = v;
-#endif
 }
 __device__ __forceinline__ f32x4v mfma16x16(u32x4 a, u32x4 b, f32x4v c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
@@ -186,9 +174,7 @@ struct ChunkPipe16 {
 #ifdef E3DGE_PHASE_TIMING
         const unsigned long long c1 = __builtin_readcyclecounter();
 #endif
-#if !(E3DGE_16_ABL & 4)
         __syncthreads();
-#endif
 #ifdef E3DGE_PHASE_TIMING
         t_vm += c1 - c0; t_bar += __builtin_readcyclecounter() - c1;
 #endif
@@ -653,7 +639,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
             const int sub_lo = sub * kTilePts;
             const int sub_hi = min(sub_lo + kTilePts, npts);
             const int r_first = sub_lo / S, r_last = (sub_hi - 1) / S;
-            for (int i = __builtin_amdgcn_readfirstlane(wave); i <= ((E3DGE_16_ABL & 8) ? -1 : r_last - r_first); i += 8) {
+            for (int i = __builtin_amdgcn_readfirstlane(wave); i <= r_last - r_first; i += 8) {
                 const int rl = r_first + i;
                 const int s_lo = max(0, sub_lo - rl * S), s_hi = min(S, sub_hi - rl * S);
                 float* st = state + rl * kStateStride;
@@ -842,7 +828,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
             const int sub_lo = sub * kTilePts;
             const int sub_hi = min(sub_lo + kTilePts, npts);
             const int r_first = sub_lo / S, r_last = (sub_hi - 1) / S;
-            for (int i = __builtin_amdgcn_readfirstlane(wave); i <= ((E3DGE_16_ABL & 16) ? -1 : r_last - r_first); i += 8) {   // a wave per ray, a lane per sample
+            for (int i = __builtin_amdgcn_readfirstlane(wave); i <= r_last - r_first; i += 8) {   // a wave per ray, a lane per sample
                 const int rl = r_first + i;
                 const int s_lo = max(0, sub_lo - rl * S), s_hi = min(S, sub_hi - rl * S);
                 float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
@@ -859,7 +845,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
                     st[6] = __fadd_rn(st[6], c0); st[7] = __fadd_rn(st[7], c1); st[8] = __fadd_rn(st[8], c2);
                 }
             }
-            if (tid < kWidth && !(E3DGE_16_ABL & 32)) {   // ordered merge of the feature partials: slab by slab, ray slot by ray slot
+            if (tid < kWidth) {   // ordered merge of the feature partials: slab by slab, ray slot by ray slot
                 const int n = tid;
                 float pv[8 * k16Slots];                      // (all sixteen loads in flight at once; unused slots are never added)
 #pragma unroll

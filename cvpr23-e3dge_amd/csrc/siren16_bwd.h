@@ -50,25 +50,16 @@ template <int N, class F> __device__ __forceinline__ void t3_static_for(F&& f) {
 
 // ring slots of 1 KiB per wave and stream; a stream tile is fetched (slots - 1) tiles ahead of the tile being consumed.  One stream:
 // eight slots (64 KiB of ring); two streams: four each (LDS: 64 KiB of weight buffers + 64 KiB of ring + tables).
-#ifndef E3DGE_T3_SLOTS1
-#define E3DGE_T3_SLOTS1 8
-#endif
-constexpr int t3_slots(int ns) { return ns == 1 ? E3DGE_T3_SLOTS1 : 4; }
+constexpr int t3_slots(int ns) { return ns == 1 ? 8 : 4; }
 constexpr int t3_ring_floats(int ns) { return 8 * t3_slots(ns) * 256; }      // one stream, eight waves
 static_assert(k16Tiles % t3_slots(1) == 0 && k16Tiles % t3_slots(2) == 0, "static slot index = tile index mod slots");
-// Who issues what (E3DGE_T3_SPLIT, default OFF -- an experiment that is kept because its result decides where the time is NOT).
-// vmcnt retires in order, so a wave that waits for its (L2-resident, two tiles old) weight pieces also waits for every older stream
-// load of its own: with one queue per wave the streams' latency budget is three tiles whatever the ring depth.  E3DGE_T3_SPLIT=1
-// separates the queues BY WAVE -- waves 0-3 issue the whole weight chunk (4 pieces each), waves 4-7 the stream tiles of waves w-4
-// and w (any wave may DMA into any LDS address), every wave waits for its own operations and the tile's barrier publishes all of
-// them; a stream's budget is then its ring depth (7 tiles with one stream).  Measured (MI355X, 64x64x18, tools/r6_chain_abl.sh):
-// sdf chain 0.439 vs 0.444 ms, tangent 0.437 vs 0.439, second-order backward 0.492 vs 0.480 -- nothing: the streams were not
-// latency-bound, they were ACCESS-PATTERN-bound (sixteen 64-byte pieces per instruction; the slab-major layout above takes the same
-// kernels to 0.325 / 0.321 / 0.468 ms, and 0.237 / 0.235 / 0.431 with cache-resident rows).
-#ifndef E3DGE_T3_SPLIT
-#define E3DGE_T3_SPLIT 0
-#endif
-constexpr bool kT3Split = E3DGE_T3_SPLIT != 0;
+// Who issues what: every wave issues its own eighth of the weight chunk and its own stream tiles, one queue per wave.  vmcnt retires in
+// order, so a wave that waits for its (L2-resident, two tiles old) weight pieces also waits for every older stream load of its own: the
+// streams' latency budget is three tiles whatever the ring depth.  Round 6 tried separating the queues BY WAVE -- waves 0-3 issued the
+// whole weight chunk, waves 4-7 the stream tiles of waves w-4 and w, a stream's budget then being its ring depth (7 tiles with one
+// stream).  Measured (MI355X, 64x64x18): sdf chain 0.439 vs 0.444 ms, tangent 0.437 vs 0.439, second-order backward 0.492 vs 0.480 --
+// nothing: the streams were not latency-bound, they were ACCESS-PATTERN-bound (sixteen 64-byte pieces per instruction; the slab-major
+// layout below took the same kernels to 0.325 / 0.321 / 0.468 ms, and 0.237 / 0.235 / 0.431 with cache-resident rows).  Removed.
 
 // backward kernel: weights | ring (1 or 2 streams) | gamma [9][256] | w_sigma [256] | wave slices [8][256][2] | W0 [3][256] (d_pts)
 constexpr int kB16LdsW = 0;
@@ -91,40 +82,21 @@ constexpr int c16_lds_bytes(int ns) { return (c16_lds_head(ns) + kWidth) * 4; }
 static_assert(c16_lds_bytes(2) <= 160 * 1024 && c16_lds_bytes(1) <= 160 * 1024, "LDS budget (chain)");
 
 constexpr int kB16Ring = 2;                       // k-steps of weight fragments held (registers are the scarce resource here)
-// Timing ablations (tools/build_variant.sh -DE3DGE_T3_ABL=bits; results are wrong with any bit set):
-//   1 = no stream DMA (the epilogues read whatever the ring holds)      2 = no stores of the chain kernels
-//   16 = hot rows: every lane streams (and stores) the workgroup's first row -- the same instruction mix against cache-resident data
-#ifndef E3DGE_T3_ABL
-#define E3DGE_T3_ABL 0
-#endif
-// Layout of the saved state (pre-sine arguments (.., 9, 256), r_l / ta_l r_l (.., 8, 256)):
-//   point-major (kT3Blocked = false): row p = the L x 256 floats of point p.  A wave's tile access touches 16 rows: 64 B in each.
-//   slab-major  (kT3Blocked = true) : 16 consecutive points form a slab [L layers][16 tiles][lane (q, n) = 16 q + n][4 floats]: the
-//       16 points x 16 features of one (layer, tile) are 1 KiB contiguous in exactly the order the 64 lanes hold them -- every stream
-//       DMA and every store of a wave is ONE contiguous KiB (8 full lines, one DRAM page) instead of sixteen 64-byte pieces.
-//       Same number of bytes (rows padded to a multiple of 16 per image); slab s starts where row 16 s starts.
-#ifndef E3DGE_T3_BLOCKED
-#define E3DGE_T3_BLOCKED 1      // (0 = point-major, as the first-generation kernels: A/B builds; the forward then must not be asked for slabs)
-#endif
-constexpr bool kT3Blocked = E3DGE_T3_BLOCKED != 0;
-constexpr int kT3LayerF = kT3Blocked ? 16 * kWidth : kWidth;      // floats between consecutive layers of a point / slab
-constexpr int kT3TileF = kT3Blocked ? kWidth : 16;                // floats between consecutive 16-feature tiles
+// Layout of the saved state (pre-sine arguments (.., 9, 256), r_l / ta_l r_l (.., 8, 256)): slab-major (siren_common.h).  16 consecutive
+// points form a slab [L layers][16 tiles][lane (q, n) = 16 q + n][4 floats]: the 16 points x 16 features of one (layer, tile) are 1 KiB
+// contiguous in exactly the order the 64 lanes hold them -- every stream DMA and every store of a wave is ONE contiguous KiB (8 full
+// lines, one DRAM page) instead of the sixteen 64-byte pieces of the point-major rows these kernels read until round 6.
+// Same number of bytes (rows padded to a multiple of 16 per image); slab s starts where row 16 s starts.
+constexpr int kT3LayerF = kSlabLayerF;            // floats between consecutive layers of a slab
+constexpr int kT3TileF = kSlabTileF;              // floats between consecutive 16-feature tiles
 // float offset of lane (n = pl & 15 of the slab, q)'s 4 values of (layer 0, tile 0), relative to the workgroup's first row; L layers per row
 __device__ __forceinline__ uint32_t t3_row_floats(int pl, int q, int L) {
-    return kT3Blocked ? (uint32_t)((pl >> 4) * L * (16 * kWidth) + (q * 16 + (pl & 15)) * 4) : (uint32_t)(pl * L * kWidth + q * 4);
+    return (uint32_t)((pl >> 4) * L * (16 * kWidth) + (q * 16 + (pl & 15)) * 4);
 }
-constexpr int kT3StreamOps = (E3DGE_T3_ABL & 1) ? 0 : 1;      // counted operations per stream and tile / per store and tile
-constexpr int kT3StoreOps = (E3DGE_T3_ABL & 2) ? 0 : 1;
 
 __device__ __forceinline__ f32x4v ld4(const float* p) { return *reinterpret_cast<const f32x4v*>(p); }
 __device__ __forceinline__ void st4(float* p, const f32x4v& v) { *reinterpret_cast<f32x4v*>(p) = v; }
-__device__ __forceinline__ void st4_chain(float* p, const f32x4v& v) {      // the per-tile store of the chain kernels (see E3DGE_T3_ABL)
-#if !(E3DGE_T3_ABL & 2)
-    save_st4(p, v);
-#else
-    if (v[0] == 1.2345e-30f) *reinterpret_cast<f32x4v*>(p) = v;
-#endif
-}
+__device__ __forceinline__ void st4_chain(float* p, const f32x4v& v) { save_st4(p, v); }      // the per-tile store of the chain kernels
 
 // ---- the in-order memory queue (see the header comment) ----
 #ifdef E3DGE_T3_STRICT      // debugging: every counted wait drains the queue (a result that differs from the default build is a race)
@@ -137,112 +109,24 @@ template <int N> __device__ __forceinline__ void t3_wait() {
 #endif
 // workgroup barrier that does not touch vmcnt (the compiler's own adds s_waitcnt vmcnt(0) when it has stores in flight)
 __device__ __forceinline__ void t3_barrier() {
-#if !(E3DGE_16_ABL & 4)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
 }
 // One stream tile (16 points x 16 features of one layer = 1 KiB) of this wave into ring slot TILE & 3.  `gbase` (scalar) = the
 // stream at the workgroup's first point, `voff` = the lane's byte offset (point row + layer + 16 q), the tile's 64 bytes go into
 // the instruction's immediate -- which the hardware adds to the LDS address as well, so it is taken off the slot base.
-// Issue roles as scalar flags, computed by SALU instructions only: (wave < 4, wave >= 4).  `wave_s` must come straight from
-// __builtin_amdgcn_readfirstlane (then it IS an SGPR; a C++ select on it may be evaluated in the VALU, and an "s" asm operand silently
-// accepts the resulting VGPR).  An earlier form read the flag back with v_readfirstlane inside an asm statement: the compiler cannot
-// see the VALU-writes-SGPR / SALU-reads hazards of gfx950 in there, the flags came out inverted or stale on the MI355X and waves 0-3
-// issued the stream tiles of waves -4..-1 (tools/ubench/asm_if.hip reproduces it in isolation).
-__device__ __forceinline__ void t3_roles(int wave_s, int& w_role, int& s_role) {
-    int w, st;
-    asm volatile("s_cmp_lt_u32 %2, 4\n\ts_cselect_b32 %0, 1, 0\n\ts_cselect_b32 %1, 0, 1" : "=s"(w), "=s"(st) : "s"(wave_s) : "scc");
-    w_role = w; s_role = st;
-}
-// Role-conditional forms: the scalar test and the branch live INSIDE the asm statement, so the compiler keeps seeing one straight-line
-// tile (a C++ `if (role)` around the DMA split every unrolled tile into basic blocks and cost the chain kernels 60 registers).
-#ifndef E3DGE_NT_LOADS
-#define E3DGE_NT_LOADS 0
-#endif
-#if E3DGE_NT_LOADS
-#define E3DGE_T3_NT " nt"
-#else
-#define E3DGE_T3_NT ""
-#endif
-template <int OFF_BYTES>
-__device__ __forceinline__ void glds16_saddr_if(int flag, const void* sbase, uint32_t voff, uint32_t lds_addr) {
-    asm volatile("s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 .Lt3skip%=\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%4" E3DGE_T3_NT "\n.Lt3skip%=:"
-                 :: "s"(flag), "v"(voff), "s"(sbase), "s"(lds_addr), "n"(OFF_BYTES) : "memory", "scc");
-}
-__device__ __forceinline__ void glds16_saddr_x4_if(int flag, const void* sbase, uint32_t voff, uint32_t lds_addr) {     // four 1-KiB pieces
-    asm volatile("s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 .Lt3skip%=\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:0" E3DGE_T3_NT "\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024" E3DGE_T3_NT "\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:2048" E3DGE_T3_NT "\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072" E3DGE_T3_NT "\n.Lt3skip%=:"
-                 :: "s"(flag), "v"(voff), "s"(sbase), "s"(lds_addr) : "memory", "scc");
-}
-// s_waitcnt vmcnt(A) if flag else vmcnt(B)
-template <int A, int B> __device__ __forceinline__ void t3_wait_by_role(int flag) {
-#ifdef E3DGE_T3_STRICT
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    static_assert(A >= 0 && A < 64 && B >= 0 && B < 64, "vmcnt is six bits");
-    asm volatile("s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 .Lt3w%=\n\ts_waitcnt vmcnt(%1)\n\ts_branch .Lt3e%=\n.Lt3w%=:\n\ts_waitcnt vmcnt(%2)\n.Lt3e%=:"
-                 :: "s"(flag), "n"(A), "n"(B) : "memory", "scc");
-#endif
-}
 template <int TILE, int SLOTS>
-__device__ __forceinline__ void t3_issue(int flag, const void* gbase, uint32_t voff, uint32_t ring_lds) {
+__device__ __forceinline__ void t3_issue_tile(const void* gbase, uint32_t voff, uint32_t ring_lds) {
     // (the immediate is 12 bits: slab-major tiles are 1 KiB apart, so only tile & 3 fits and the rest goes into the lane offset)
-    constexpr int kImm = kT3Blocked ? (TILE & 3) * 1024 : TILE * 64;
-    constexpr uint32_t kAdd = kT3Blocked ? (uint32_t)(TILE >> 2) * 4096u : 0u;
-    if (kT3Split) glds16_saddr_if<kImm>(flag, gbase, voff + kAdd, ring_lds + (uint32_t)((TILE & (SLOTS - 1)) * 1024 - kImm));
-    else glds16_saddr<kImm>(gbase, voff + kAdd, ring_lds + (uint32_t)((TILE & (SLOTS - 1)) * 1024 - kImm));
+    constexpr int kT = TILE & 15;
+    constexpr int kImm = (kT & 3) * 1024;
+    constexpr uint32_t kAdd = (uint32_t)(kT >> 2) * 4096u;
+    glds16_saddr<kImm>(gbase, voff + kAdd, ring_lds + (uint32_t)((kT & (SLOTS - 1)) * 1024 - kImm));
 }
-// flag (scalar): this wave issues stream tiles (always 1 without the role split)
-template <int TILE, int SLOTS>
-__device__ __forceinline__ void t3_issue_tile(int flag, const void* gbase, uint32_t voff, uint32_t ring_lds) {
-    if (E3DGE_T3_ABL & 1) return;
-    if (E3DGE_T3_ABL & 16) voff &= (kT3Blocked ? 1023u : 63u);
-    t3_issue<(TILE & 15), SLOTS>(flag, gbase, voff, ring_lds);
-}
-// The weight pipe of the 8-wave kernels with the issue roles above: `active` waves (0-3 when split: a quarter of the chunk each in four
-// pieces; every wave an eighth in two pieces otherwise) issue, every wave keeps the bookkeeping.
-struct T3WeightPipe : ChunkPipe16 {
-    int active;
-    __device__ __forceinline__ void init3(float* wbuf_, const float* image, int wave_u, int lane, int count_ = k16Chunks) {     // wave_u: from readfirstlane
-        int s_unused;
-        active = 1;
-        if (kT3Split) t3_roles(wave_u, active, s_unused);
-        init(wbuf_, image, kT3Split ? 2 * (wave_u & 3) : wave_u, lane, count_);     // split: img / lds_base at wave_u * 4 KiB
-    }
-    __device__ __forceinline__ void issue3() {
-        const char* s = img + (size_t)idx * (k16ChunkFloats * 4);
-        const uint32_t d = lds_base + (uint32_t)buf * (k16ChunkFloats * 4);
-        if (kT3Split) {
-            glds16_saddr_x4_if(active, s, voff, d);
-        } else {
-            glds16_saddr<0>(s, voff, d);
-            glds16_saddr<1024>(s, voff, d);
-        }
-        idx = (idx + 1 == count) ? 0 : idx + 1;
-        buf = (buf + 1 == k16NBuf) ? 0 : buf + 1;
-    }
-    __device__ __forceinline__ void prime3() { issue3(); issue3(); issue3(); }
-};
-constexpr int kT3WOps = kT3Split ? 4 : 2;         // weight pieces per issuing wave and tile
-// Counted waits of the hook of tile t (see the header comment).  NS streams, NO stores per tile and wave, D = stream distance.
-//   one queue per wave: the weight chunk of tile t+1 (hook t-2) is awaited; younger = streams of hook t-2, stores, all of hook t-1
-//   split, weight waves: younger = stores of two gaps + the four pieces of hook t-1
-//   split, stream waves: the streams of hook t-D are awaited; younger = D-1 hooks of 2 NS stream tiles + the stores of D gaps
+// Counted wait of the hook of tile t (see the header comment).  NS streams, NO stores per tile and wave: the weight chunk of tile t+1
+// (hook t-2) is awaited; younger = streams of hook t-2, stores, all of hook t-1.
 // (tile 0 of a layer has no interleaved epilogue: the gap between hooks 0 and 1 holds no store)
-template <int NS, int NO, int D> __device__ __forceinline__ void t3_hook_wait(int t, int w_role) {     // w_role: scalar 0 / 1
-    constexpr int S = NS * kT3StreamOps, O = NO * kT3StoreOps;
-    if (!kT3Split) {
-        if (t == 2) t3_wait<2 + 2 * S + O>(); else t3_wait<2 + 2 * S + 2 * O>();
-    } else {
-        constexpr int kS = (D - 1) * 2 * S;
-        if (t == 2 && t == D) t3_wait_by_role<4 + O, kS + (D - 1) * O>(w_role);
-        else if (t == 2) t3_wait_by_role<4 + O, kS + D * O>(w_role);
-        else if (t == D) t3_wait_by_role<4 + 2 * O, kS + (D - 1) * O>(w_role);
-        else t3_wait_by_role<4 + 2 * O, kS + D * O>(w_role);
-    }
+template <int NS, int NO> __device__ __forceinline__ void t3_hook_wait(int t) {
+    if (t == 2) t3_wait<2 + 2 * NS + NO>(); else t3_wait<2 + 2 * NS + 2 * NO>();
 }
 __device__ __forceinline__ uint32_t lds_addr_of(const float* p) {
     return (uint32_t)(size_t)(__attribute__((address_space(3))) const float*)p;
@@ -314,13 +198,11 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
     }
 
     const int wave_u = __builtin_amdgcn_readfirstlane(tid_k >> 6);
-    int w_role = 0, s_role = 1;                                               // weight waves issue no streams (scalar flags)
-    if (kT3Split) t3_roles(wave_u, w_role, s_role);
     const int64_t base_pt = (int64_t)b * a.n_pts + pt0;                       // the workgroup's first point in the caller's (point-major) tensors
-    const int64_t base_row = (int64_t)b * saved_rows_per_image(kT3Blocked, a.n_pts) + pt0;      // ... and its row in the saved state
+    const int64_t base_row = (int64_t)b * saved_rows_per_image(true, a.n_pts) + pt0;      // ... and its row in the saved state
     const char* const g_args = reinterpret_cast<const char*>(a.args + base_row * (9 * kWidth));
     const char* const g_tr = EIK ? reinterpret_cast<const char*>(a.tang + base_row * (8 * kWidth)) : nullptr;
-    // ring bases (LDS byte address of slot 0) of the waves this wave fetches for: itself (B) and, when split, wave - 4 (A)
+    // ring base (LDS byte address of slot 0) of this wave
     const uint32_t ring_b = lds_addr_of(smem + kB16LdsRing) + (uint32_t)wave_u * (kSlots * 1024u);
     constexpr uint32_t kStream1 = (uint32_t)kRingF * 4u;                      // byte distance of the second stream's ring
     // row (relative to the workgroup's first) of this lane's column in wave `w` of sub-tile `sub`; rows beyond the tensor read the last valid row
@@ -328,7 +210,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
         const int p = sub * kTilePts + 16 * w + (tid_x & 15);
         return p < npts ? p : npts - 1;
     };
-    // the stream tiles of (sub-tile, layer, tile) for the waves this wave serves
+    // the stream tiles of (sub-tile, layer, tile) of this wave
     auto issue_streams = [&](auto tile_c, int sub, int layer) {
         constexpr int tile = decltype(tile_c)::value;
         int tid_i = tid_k;
@@ -337,18 +219,13 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
         asm volatile("" : "+s"(ring_o));            // (the per-tile slot addresses are loop invariants the compiler would hoist into ~60 SGPRs)
         const int q0 = (tid_i >> 4) & 3;
         const int rb = row_of(sub, tid_i >> 6, tid_i);
-        t3_issue_tile<tile, kSlots>(s_role, g_args, 4u * (t3_row_floats(rb, q0, 9) + (uint32_t)layer * kT3LayerF), ring_o);
-        if (EIK) t3_issue_tile<tile, kSlots>(s_role, g_tr, 4u * (t3_row_floats(rb, q0, 8) + (uint32_t)layer * kT3LayerF), ring_o + kStream1);
-        if (kT3Split) {
-            const int ra = row_of(sub, (tid_i >> 6) - 4, tid_i);
-            t3_issue_tile<tile, kSlots>(s_role, g_args, 4u * (t3_row_floats(ra, q0, 9) + (uint32_t)layer * kT3LayerF), ring_o - 4u * (kSlots * 1024u));
-            if (EIK) t3_issue_tile<tile, kSlots>(s_role, g_tr, 4u * (t3_row_floats(ra, q0, 8) + (uint32_t)layer * kT3LayerF), ring_o - 4u * (kSlots * 1024u) + kStream1);
-        }
+        t3_issue_tile<tile, kSlots>(g_args, 4u * (t3_row_floats(rb, q0, 9) + (uint32_t)layer * kT3LayerF), ring_o);
+        if (EIK) t3_issue_tile<tile, kSlots>(g_tr, 4u * (t3_row_floats(rb, q0, 8) + (uint32_t)layer * kT3LayerF), ring_o + kStream1);
     };
 
-    T3WeightPipe pipe;
-    pipe.init3(wbuf, packed + kOffBigT16b, wave_u, tid_k & 63);
-    pipe.prime3();
+    ChunkPipe16 pipe;
+    pipe.init(wbuf, packed + kOffBigT16b, wave_u, tid_k & 63);
+    pipe.prime();
     t3_static_for<kDist>([&](auto tc) { issue_streams(tc, 0, 7); });          // the first tiles of the first sub-tile (layer 7)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -536,9 +413,9 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
                 // after k-step 1: the counted wait, the barrier (publishes every wave's finished DMA), the next weight chunk, then the
                 // streams kDist tiles ahead
                 auto hook = [&]() {
-                    t3_hook_wait<NS, 0, kDist>(t, w_role);
+                    t3_hook_wait<NS, 0>(t);
                     t3_barrier();
-                    pipe.issue3();
+                    pipe.issue_chunk();
                     constexpr int tn = (t + kDist) & 15;
                     if (t + kDist < k16Tiles) issue_streams(std::integral_constant<int, tn>{}, sub, Lm1);
                     else issue_streams(std::integral_constant<int, tn>{}, sub_x, lay_x);
@@ -638,17 +515,15 @@ __global__ void __launch_bounds__(k16Threads) siren16_chain_kernel(const SirenCh
     constexpr int kChainChunks = 7 * k16Tiles;
     constexpr int kFirstGemmLayer = TANGENT ? 1 : 6;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid_k >> 6);
-    int w_role = 0, s_role = 1;
-    if (kT3Split) t3_roles(wave_u, w_role, s_role);
     const int64_t base_pt = (int64_t)b * a.n_pts + pt0;
-    const int64_t base_row = (int64_t)b * saved_rows_per_image(kT3Blocked, a.n_pts) + pt0;
+    const int64_t base_row = (int64_t)b * saved_rows_per_image(true, a.n_pts) + pt0;
     const char* const g_args = reinterpret_cast<const char*>(a.args + base_row * (9 * kWidth));
     const char* const g_r = TR ? reinterpret_cast<const char*>(a.rmul + base_row * (8 * kWidth)) : nullptr;
     const uint32_t ring_b = lds_addr_of(smem + kC16LdsRing) + (uint32_t)wave_u * (kSlots * 1024u);
     constexpr uint32_t kStream1 = (uint32_t)kRingF * 4u;
     auto row_of = [&](int sub, int w, int tid_x) {
         const int p = sub * kTilePts + 16 * w + (tid_x & 15);
-        return (E3DGE_T3_ABL & 16) ? 0 : (p < npts ? p : npts - 1);
+        return p < npts ? p : npts - 1;
     };
     auto issue_streams = [&](auto tile_c, int sub, int layer) {
         constexpr int tile = decltype(tile_c)::value;     // see siren16_bwd_kernel
@@ -658,19 +533,14 @@ __global__ void __launch_bounds__(k16Threads) siren16_chain_kernel(const SirenCh
         asm volatile("" : "+s"(ring_o));
         const int q0 = (tid_i >> 4) & 3;
         const int rb = row_of(sub, tid_i >> 6, tid_i);
-        t3_issue_tile<tile, kSlots>(s_role, g_args, 4u * (t3_row_floats(rb, q0, 9) + (uint32_t)layer * kT3LayerF), ring_o);
-        if (TR) t3_issue_tile<tile, kSlots>(s_role, g_r, 4u * (t3_row_floats(rb, q0, 8) + (uint32_t)layer * kT3LayerF), ring_o + kStream1);
-        if (kT3Split) {
-            const int ra = row_of(sub, (tid_i >> 6) - 4, tid_i);
-            t3_issue_tile<tile, kSlots>(s_role, g_args, 4u * (t3_row_floats(ra, q0, 9) + (uint32_t)layer * kT3LayerF), ring_o - 4u * (kSlots * 1024u));
-            if (TR) t3_issue_tile<tile, kSlots>(s_role, g_r, 4u * (t3_row_floats(ra, q0, 8) + (uint32_t)layer * kT3LayerF), ring_o - 4u * (kSlots * 1024u) + kStream1);
-        }
+        t3_issue_tile<tile, kSlots>(g_args, 4u * (t3_row_floats(rb, q0, 9) + (uint32_t)layer * kT3LayerF), ring_o);
+        if (TR) t3_issue_tile<tile, kSlots>(g_r, 4u * (t3_row_floats(rb, q0, 8) + (uint32_t)layer * kT3LayerF), ring_o + kStream1);
     };
 
-    T3WeightPipe pipe;
+    ChunkPipe16 pipe;
     // tangent: hidden layers 1..7 are the first 7 layers of the forward image; sdf chain: skip the view layer's transposed chunks
-    pipe.init3(wbuf, packed + (TANGENT ? kOffBig16b : kOffBigT16b + (int64_t)k16Tiles * k16ChunkFloats), wave_u, tid_k & 63, kChainChunks);
-    pipe.prime3();
+    pipe.init(wbuf, packed + (TANGENT ? kOffBig16b : kOffBigT16b + (int64_t)k16Tiles * k16ChunkFloats), wave_u, tid_k & 63, kChainChunks);
+    pipe.prime();
     t3_static_for<kDist>([&](auto tc) { issue_streams(tc, 0, kFirstGemmLayer); });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -694,7 +564,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_chain_kernel(const SirenCh
         // Rows beyond the tensor are exact clones of the last valid row: same loads, same arithmetic, the same values stored to the
         // same addresses -- every store of this kernel is unconditional (the counted waits rely on it).
         const int p = sub * kTilePts + 16 * wave + col;
-        const int pc = (E3DGE_T3_ABL & 16) ? 0 : (p < npts ? p : (npts - 1));
+        const int pc = p < npts ? p : (npts - 1);
         const int64_t gpt = base_pt + pc;
         const float* __restrict__ ap = a.args + base_row * (9 * kWidth) + t3_row_floats(pc, q, 9);
         const float* __restrict__ rp = TR ? a.rmul + base_row * (8 * kWidth) + t3_row_floats(pc, q, 8) : nullptr;
@@ -772,9 +642,9 @@ __global__ void __launch_bounds__(k16Threads) siren16_chain_kernel(const SirenCh
             t3_static_for<k16Tiles>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
                 auto hook = [&]() {                                      // see siren16_bwd_kernel; one store per tile here
-                    t3_hook_wait<NS, 1, kDist>(t, w_role);
+                    t3_hook_wait<NS, 1>(t);
                     t3_barrier();
-                    pipe.issue3();
+                    pipe.issue_chunk();
                     constexpr int tn = (t + kDist) & 15;
                     if (t + kDist < k16Tiles) issue_streams(std::integral_constant<int, tn>{}, sub, l);
                     else issue_streams(std::integral_constant<int, tn>{}, sub_x, lay_x);

@@ -197,22 +197,13 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
     f32x16 in[kNT], out[kNT];
     u32x4 inH[2 * kNT], inL[2 * kNT];
     float inv_scale = 1.0f;                       // F16: undoes the operand scaling of the GEMM being consumed
-    // F16: running max |g| of the layer being produced (this lane's 128 values).  With the two extra streams of the EIK
-    // variant one more live register tips the allocator into spilling inside the MFMA stream, so that variant takes
-    // the max in a separate pass over out[] instead.
-    // Round 3: the running maximum is off for every variant (E3DGE_BWD_RUNMAX=1 restores it where EIK is off): with it the three
-    // default-mode variants without the eikonal streams spilled 36 / 116 / 192 bytes per lane; the separate pass costs
-    // 128 v_max per layer and wave.
-#ifndef E3DGE_BWD_RUNMAX
-#define E3DGE_BWD_RUNMAX 0
-#endif
-    constexpr bool kRunMax = E3DGE_BWD_RUNMAX != 0 && F16 && !EIK;
-    float gmax = 0.0f;
+    // F16: max |g| of the layer being produced is taken in a separate pass over out[] (scale_split; 128 v_max per layer and wave).
+    // Until round 3 the epilogues kept a running maximum instead: one more live register, with which the three default-mode variants
+    // without the eikonal streams spilled 36 / 116 / 192 bytes per lane inside the MFMA stream.
     // g_L of a finished layer (out[], fp32) becomes the B operand of the next GEMM
     auto next_operand = [&]() {
         if (F16) {
-            inv_scale = kRunMax ? scale_split(out, inH, inL, gmax) : scale_split(out, inH, inL);
-            gmax = 0.0f;
+            inv_scale = scale_split(out, inH, inL);
         } else {
 #pragma unroll
             for (int tt = 0; tt < kNT; ++tt) {
@@ -330,7 +321,6 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                         rb[4 * q + j] = da;
                         rg[4 * q + j] = da * ((ar[j] - b4[j]) * i4[j]);
                         out[t][4 * q + j] = g4[j] * da;
-                        if (kRunMax) gmax = fmaxf(gmax, fabsf(out[t][4 * q + j]));
                     }
                 }
                 asm volatile("" : "+a"(out[t]));                       // results wait in AGPRs: the VGPRs stay free for the loads
@@ -403,30 +393,18 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                             da = fmaf(dh, cs, -sn * tr);
                             dg_extra = tr * i4[j] * cs;
                         } else {
-#ifndef E3DGE_BWD_ABL_NO_COS
                             da = dh * cos_hw_f32(ar[q][j]);
-#else
-                            da = dh * ar[q][j];
-#endif
                         }
                         rb[4 * q + j] = da;
                         rg[4 * q + j] = fmaf(da, (ar[q][j] - b4[j]) * i4[j], dg_extra);
                         dst[4 * q + j] = g4[j] * da;
-                        if (kRunMax) gmax = fmaxf(gmax, fabsf(dst[4 * q + j]));
                     }
                     if (tex_here && valid) {
                         *reinterpret_cast<f32x4*>(dta + o) = da4;
                         *reinterpret_cast<f32x4*>(dtb + o) = db4;
                     }
                 }
-#ifndef E3DGE_BWD_ABL_NO_REDUCE
                 reduce_tile(Lm1, tp, rb, rg);
-#else
-                float keep = 0.f;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) keep += rb[i] + rg[i];
-                dst[0] += keep * 1e-30f;
-#endif
             };
             f32x4 e_al = {0.f, 0.f, 0.f, 0.f}, e_da = e_al, e_db = e_al;
             auto epi_step = [&](int tp, int r, f32x16& dst) {           // tp, r: compile-time constants at every call site
@@ -461,7 +439,6 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                 rbh[r & 7] = da;
                 rgh[r & 7] = fmaf(da, (ar - e_b[j]) * e_i[j], dg_extra);
                 dst[r] = e_g[j] * da;
-                if (kRunMax) gmax = fmaxf(gmax, fabsf(dst[r]));
                 if (tex_here && j == 3 && valid) {
                     const int o = 32 * tp + 8 * q + 4 * half;
                     *reinterpret_cast<f32x4*>(dta + o) = e_da;
@@ -499,12 +476,8 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                         return;
                     }
                     if (t > 0) {
-#ifndef E3DGE_BWD_ABL_NO_ARGLOAD
 #pragma unroll
                         for (int q = 0; q < 4; ++q) argb[q] = *reinterpret_cast<const f32x4*>(apl + 32 * (t - 1) + 8 * q + 4 * half);
-#else
-                        for (int q = 0; q < 4; ++q) argb[q] = f32x4{0.1f * t, 0.2f, 0.3f + q, 0.4f};
-#endif
                     }
                     if (t == kNT - 1) {
 #pragma unroll
@@ -522,7 +495,7 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                 f32x16 acc = zero16();
                 [[maybe_unused]] const unsigned long long c0 = BT_NOW();
                 if (!F16) {
-                    acc = big_tile<false, 0>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), sync_and_fetch, issue_piece);
+                    acc = big_tile<false>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), sync_and_fetch, issue_piece);
                 } else {
                     f32x16 accb = zero16();
                     if (t == 0) {
@@ -837,7 +810,7 @@ __global__ void __launch_bounds__(kThreads) siren_chain_kernel(const SirenChainK
                 };
                 f32x16 acc = zero16();
                 if (!F16) {
-                    acc = big_tile<false, 0>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), sync_and_fetch, issue_piece);
+                    acc = big_tile<false>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), sync_and_fetch, issue_piece);
                 } else {
                     f32x16 accb = zero16();
                     if (t == 0 || !kInter) {
@@ -1210,7 +1183,6 @@ static int launch_bwd(SirenBwdK k, const float* wg, const float* wb, float* dfil
     const bool lin = k.d_lin != nullptr;
     if (lin) {
         E3DGE_REQUIRE(gen2, "siren_bwd: d_lin (parameter gradients) needs precision E3DGE_PREC_F16X3_G2, got %d", k.precision);
-        E3DGE_REQUIRE(kT3Blocked, "siren_bwd: d_lin needs the slab-major saved state (this build has E3DGE_T3_BLOCKED=0)");
         E3DGE_REQUIRE(k.lin_amax != nullptr, "siren_bwd: d_lin needs lin_amax (9 amax buffers, zeroed)");
         E3DGE_REQUIRE(!tex && k.tang == nullptr, "siren_bwd: d_lin is first order on the first pass only (no tang, no tex_alpha)");
         E3DGE_REQUIRE((reinterpret_cast<uintptr_t>(k.d_lin) & 15) == 0, "siren_bwd: d_lin must be 16-B aligned");
@@ -1292,7 +1264,7 @@ extern "C" int e3dge_siren_render_bwd(const E3dgeRenderBwdArgs* r, e3dge_stream_
     c.d_sdf_in = r->d_sdf; c.d_weights = r->d_weights; c.d_rgb_pts = r->d_rgb_pts; c.d_sdf_pts = r->d_sdf_pts;
     c.sigmoid_beta = r->sigmoid_beta; c.S = r->n_samples; c.force_bg = r->force_background; c.d_beta = r->d_sigmoid_beta;
     c.n_rays = HW * r->batch; c.rays_per_img = HW;
-    c.args_blocked = (r->precision == E3DGE_PREC_F16X3_G2 && kT3Blocked) ? 1 : 0;
+    c.args_blocked = r->precision == E3DGE_PREC_F16X3_G2 ? 1 : 0;
     const size_t lds = (size_t)4 * r->n_samples * kCbStride * sizeof(float);
     {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&composite_bwd_kernel),

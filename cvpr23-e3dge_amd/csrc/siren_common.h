@@ -39,21 +39,13 @@ constexpr int kFPitch = kWidth + 1;             // padded pitch of the feature a
 constexpr int kMaxSlots = 3;                    // rays a 32-point slab can touch when S >= 16
 constexpr int kMinSamples = 16;
 
-// VALU instructions of the pipelined epilogue forced behind each MFMA with sched_group_barrier (0 = leave the
-// placement to the compiler).  Measured on MI355X (round 1, tools/build_variant.sh A/B): 0 -> 0.949 ms, 2..4 ->
+// The fp32 tiles (big_tile) leave the placement of the pipelined epilogue's VALU instructions to the compiler.  Forcing
+// n of them behind each MFMA with sched_group_barrier was measured on MI355X (round 1): none -> 0.949 ms, 2..4 ->
 // 1.00-1.02 ms, with one or two accumulators alike: on gfx950 the fp32 MFMA and the fp32 VALU do not execute
 // concurrently for one wave (PMC: MFMA-busy + VALU-active + waits = wave cycles in every variant), so spreading
-// only adds issue bubbles.  The lever that works is FEWER VALU instructions, not better placement.
-#ifndef E3DGE_SPREAD_STD
-#define E3DGE_SPREAD_STD 0
-#endif
-#ifndef E3DGE_SPREAD_VIEW
-#define E3DGE_SPREAD_VIEW 0
-#endif
-// f16x3 path: VALU instructions scheduled behind each f16 MFMA (there the pipes DO overlap; 0 = compiler's placement)
-#ifndef E3DGE_SPREAD16
-#define E3DGE_SPREAD16 5
-#endif
+// only added issue bubbles.  The lever that works is FEWER VALU instructions, not better placement.
+// f16x3 path: VALU instructions scheduled behind each f16 MFMA (there the pipes DO overlap)
+constexpr int kSpread16 = 5;
 
 // ---- packed weight image (floats) ----
 constexpr int64_t kOffBig = 0;                                       // [8 layers][8 t][8 c][4 q][64 lane][4]
@@ -238,7 +230,6 @@ struct ChunkPipe {
 #endif
     }
     __device__ __forceinline__ void issue_piece(int i) {     // i is a compile-time constant at every call site
-#ifndef E3DGE_ABL_NODMA
         const char* s = src + (i >> 2) * 4096;
         const uint32_t d = lds_dst + (uint32_t)(i >> 2) * 4096u;
         switch (i & 3) {
@@ -247,7 +238,6 @@ struct ChunkPipe {
             case 2: glds16_saddr<2048>(s, voff, d); break;
             default: glds16_saddr<3072>(s, voff, d); break;
         }
-#endif
         if (i == 7) {
             idx = (idx + 1 == first + count) ? first : idx + 1;
             src = img + (size_t)idx * (kChunkFloats * 4);
@@ -341,7 +331,7 @@ struct NoEpilogue { __device__ __forceinline__ void operator()(int) const {} };
 constexpr int kRing = 4;          // weight fragments held in registers (2 being consumed + 2 in flight)
 constexpr int kSyncPair = 2;      // MFMA-group pair (even index) after which the chunk barrier happens; DMA pieces follow
 
-template <bool TRANSPOSED, int VALU_PER_MFMA, class Epi, class Sync, class Dma>
+template <bool TRANSPOSED, class Epi, class Sync, class Dma>
 __device__ __forceinline__ f32x16 big_tile(const float* __restrict__ wchunk, const float* __restrict__ wnext,
                                            int lane, const f32x16 (&in)[kNT], f32x16 acc, f32x4 (&ring)[kRing],
                                            Epi&& epi, Sync&& sync, Dma&& dma) {
@@ -368,13 +358,6 @@ __device__ __forceinline__ f32x16 big_tile(const float* __restrict__ wchunk, con
         if (gp == kSyncPair) sync();
         if (gp > kSyncPair && gp <= kSyncPair + 16) dma((gp - kSyncPair) / 2 - 1);   // one DMA piece per group pair
         epi(gp >> 1);
-        if (VALU_PER_MFMA > 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);               // 1 MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, VALU_PER_MFMA, 0);   // n VALU
-            }
-        }
     }
     return acc;
 }
@@ -382,15 +365,9 @@ __device__ __forceinline__ f32x16 big_tile(const float* __restrict__ wchunk, con
 // The same contraction on the f16 matrix pipe: fp32 operands split into f16 hi + lo, three products per k-step
 // (hi*hi, lo_w*hi_a, hi_w*lo_a) into one fp32 accumulator.  16 k-steps of K=16 per tile = 48 MFMAs of 32
 // cycles (1536 vs 8192 for fp32), and this pipe runs concurrently with the VALU, so the epilogue hides under it.
-#ifndef E3DGE_RING16
-#define E3DGE_RING16 4
-#endif
-constexpr int kRing16 = E3DGE_RING16;   // k-steps whose (hi, lo) weight fragments are held: 1 consumed + the rest in flight
+constexpr int kRing16 = 4;        // k-steps whose (hi, lo) weight fragments are held: 1 consumed + the rest in flight
 constexpr int kSyncStep16 = 2;    // k-step after which the chunk barrier + next DMA issue happen
 
-// Ablation switches for tools/ablate.sh (timing experiments only -- results are wrong when any is defined):
-//   E3DGE_ABL_NOEPI  drop the pipelined epilogue VALU     E3DGE_ABL_NODMA  drop the weight DMA
-//   E3DGE_ABL_NOLDS  drop the weight-fragment LDS reads   E3DGE_ABL_NOSYNC drop the chunk barrier
 template <bool TRANSPOSED, class Epi, class Sync, class Dma>
 __device__ __forceinline__ void big_tile_f16(const float* __restrict__ wchunk, const float* __restrict__ wnext,
                                              int lane, const u32x4 (&aH)[2 * kNT], const u32x4 (&aL)[2 * kNT],
@@ -403,10 +380,8 @@ __device__ __forceinline__ void big_tile_f16(const float* __restrict__ wchunk, c
 #pragma unroll
     for (int g = 0; g < kSteps; ++g) {
         const int ga = g + kRing16 - 1;
-#ifndef E3DGE_ABL_NOLDS
         ringH[ga % kRing16] = (ga < kSteps) ? wp[(ga * 2 + 0) * 64] : wn[((ga - kSteps) * 2 + 0) * 64];
         ringL[ga % kRing16] = (ga < kSteps) ? wp[(ga * 2 + 1) * 64] : wn[((ga - kSteps) * 2 + 1) * 64];
-#endif
         __builtin_amdgcn_sched_barrier(0);
         const u32x4 wh = ringH[g % kRing16], wl = ringL[g % kRing16];
         // Two accumulators used alternately (a b a | b a b | ...): an instruction issued between two MFMAs that chain
@@ -423,24 +398,16 @@ __device__ __forceinline__ void big_tile_f16(const float* __restrict__ wchunk, c
             x1 = mfma16(aH[g], wl, x1);
             x0 = mfma16(aL[g], wh, x0);
         }
-#ifndef E3DGE_ABL_NOSYNC
         if (g == kSyncStep16) sync();
-#endif
-#ifndef E3DGE_ABL_NODMA
         if (g > kSyncStep16 && g <= kSyncStep16 + 8) dma(g - kSyncStep16 - 1);            // one DMA piece per k-step
-#endif
-#ifndef E3DGE_ABL_NOEPI
         epi(g);
-#endif
-        if (E3DGE_SPREAD16 > 0) {
-            // f16 MFMAs co-execute with the VALU when the fillers sit BETWEEN consecutive MFMAs (about five single-issue
-            // instructions hide per 32-cycle MFMA): lay the epilogue out as {MFMA, n VALU, LDS read} x 3 per k-step
+        // f16 MFMAs co-execute with the VALU when the fillers sit BETWEEN consecutive MFMAs (about five single-issue
+        // instructions hide per 32-cycle MFMA): lay the epilogue out as {MFMA, n VALU, LDS read} x 3 per k-step
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, E3DGE_SPREAD16, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
+        for (int i = 0; i < 3; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, kSpread16, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
     }
 }

@@ -601,10 +601,6 @@ extern "C" int64_t e3dge_siren_wgrad_ws_floats(int batch, int64_t n_pts) {
 
 extern "C" int e3dge_siren_wgrad(const E3dgeSirenWgradArgs* r, e3dge_stream_t stream) {
     E3DGE_REQUIRE(r != nullptr, "siren_wgrad: null args");
-#if defined(E3DGE_T3_BLOCKED) && !E3DGE_T3_BLOCKED
-    // (A/B builds with point-major saved state: the backward's d_lin and the arguments are not slab-major, which this launch reads)
-    return fail(E3DGE_ERR_UNSUPPORTED, "siren_wgrad: built with E3DGE_T3_BLOCKED=0 -- the contraction reads the slab-major layout only");
-#endif
     E3DGE_REQUIRE(r->precision == E3DGE_PREC_F16X3_G2, "siren_wgrad: precision %d -- the parameter gradients exist for E3DGE_PREC_F16X3_G2 only", r->precision);
     E3DGE_REQUIRE(r->batch >= 0 && r->n_pts >= 0 && r->samples >= 1, "siren_wgrad: bad sizes (batch %d, n_pts %lld, samples %d)", r->batch, (long long)r->n_pts, r->samples);
     E3DGE_REQUIRE(r->d_w && r->d_w_view_dirs && r->d_w_first && r->d_w_sigma && r->d_b_sigma && r->d_w_rgb && r->d_b_rgb, "siren_wgrad: null output");

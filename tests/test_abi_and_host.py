@@ -34,6 +34,25 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.e3dge_siren_packed_floats() == (64 * 8192 + 2 * 1024 + 9 * 256 + 4 * 256 + 4) + 5 * 64 * 8192
 
 
+def test_variant_build_links_every_source_of_the_library(lib):
+    """A variant library comes from build.SOURCES / build.FLAGS like the default one, so ctypes finds every symbol _lib binds.  One small
+    source is recompiled with a define nothing reads; the other objects are those the `lib` fixture's build left in lib/."""
+    from e3dge_amd import build
+    path = build.build_variant("hosttest", ["-DE3DGE_HOST_TEST_NOTHING_READS_THIS=1"], only="hitprob", verbose=False)
+    try:
+        assert path == os.path.join(build.LIBDIR, "variants", "lib_hosttest.so")
+        variant = ctypes.CDLL(path)
+        missing = [name for name in _lib.SIGNATURES if not hasattr(variant, name)]
+        assert not missing, missing
+        variant.e3dge_abi_version.restype = ctypes.c_int
+        assert variant.e3dge_abi_version() == _lib.ABI_VERSION
+        assert not [f for f in os.listdir(os.path.dirname(path)) if f.endswith(".o")]      # the variant's own object is temporary
+    finally:
+        os.remove(path)
+    with pytest.raises(ValueError):
+        build.build_variant("hosttest", only="no_such_source", verbose=False)
+
+
 def test_render_args_struct_layout_matches_c():
     src = r'''
 #include <stdio.h>
