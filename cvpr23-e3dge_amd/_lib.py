@@ -4,8 +4,10 @@ The library is built in-tree by `build.py` (hipcc --offload-arch=gfx950) and shi
 loaded lazily on first use.  Nothing here falls back to another implementation: a missing library or a
 failing call raises RuntimeError."""
 import ctypes
+import operator
 import os
 import threading
+import weakref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E3DGE_LIB_PATH") or os.path.join(_HERE, "lib", "libe3dge_hip.so")   # override: kernel A/B variants
@@ -335,9 +337,54 @@ def forget_params(module):
     module.__dict__.pop('_e3dge_param_slots', None)
 
 
-def param_key(module):
-    """((data_ptr, _version), ...) of the module's parameters: what the weight-image caches are keyed on."""
-    return tuple((q.data_ptr(), q._version) for q in params_of(module))
+STRICT_WEIGHT_CACHE = os.environ.get("E3DGE_STRICT_WEIGHT_CACHE", "0") not in ("", "0")
+_WEIGHT_CACHE = weakref.WeakKeyDictionary()      # module -> {slot name: [(sources, signature, extra, fingerprint, value), ...], oldest first}
+
+
+def _fingerprint(sources):
+    """Norm and sum of every floating-point source: what E3DGE_STRICT_WEIGHT_CACHE=1 compares on every hit to catch writes through
+    `.data` (device reductions and a host synchronisation per lookup)."""
+    import torch
+    with torch.no_grad():
+        flat = [t.detach().reshape(-1) for t in sources if t.is_floating_point()]
+        return torch.stack(list(torch._foreach_norm(flat)) + [t.sum() for t in flat]) if flat else torch.zeros(0)
+
+
+def cached(module, slot, sources, build, extra=(), limit=1):
+    """The value `build()` made from the tensors `sources` (parameters, buffers, or other cached values this one was derived from --
+    every tensor whose contents or pointer the value carries), kept for `module` under the name `slot`; the one cache of every packed
+    weight image, table and plan.  Entries live in a module-level weak map, never on the module: deepcopy, state_dict and pickling do not
+    see them.  A hit needs the SAME tensor objects (the entry holds them, so their storage cannot be freed and handed to another tensor:
+    (data_ptr, _version) alone is recycled by the caching allocator) with unchanged data_ptr (`Module._apply` swaps `.data` under the same
+    Parameter) and _version (optimizer steps, load_state_dict, in-place ops), and an equal `extra` tuple (device, batch, resolution,
+    stream).  Writes through `.data` bump no version: call invalidate(), or run with E3DGE_STRICT_WEIGHT_CACHE=1.  `limit` > 1 keeps that
+    many entries of different `extra`, evicting the oldest first -- a captured graph may still replay the older ones."""
+    try:
+        entries = _WEIGHT_CACHE[module][slot]
+    except KeyError:
+        entries = _WEIGHT_CACHE.setdefault(module, {}).setdefault(slot, [])
+    sig = [(t.data_ptr(), t._version) for t in sources]
+    for e in entries:
+        if e[1] == sig and e[2] == extra and all(map(operator.is_, e[0], sources)):
+            if not STRICT_WEIGHT_CACHE or (e[3] is not None and e[3].equal(_fingerprint(sources))):
+                return e[4]
+    value = build()
+    keep = [e for e in entries if e[2] != extra]              # (an entry of the same `extra` is replaced)
+    entries[:] = keep[max(0, len(keep) - (limit - 1)):]
+    entries.append((list(sources), sig, extra, _fingerprint(sources) if STRICT_WEIGHT_CACHE else None, value))
+    return value
+
+
+def latest(module, slot):
+    """The newest value cached for (module, slot), or None: for what a build records beside the image (the SIREN's weight range)."""
+    entries = _WEIGHT_CACHE.get(module, {}).get(slot)
+    return entries[-1][4] if entries else None
+
+
+def invalidate(module):
+    """Drop every cached value of `module` and of all its sub-modules (needed only after writes through `.data`)."""
+    for m in module.modules():
+        _WEIGHT_CACHE.pop(m, None)
 
 
 class on_device:

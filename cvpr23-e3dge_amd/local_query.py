@@ -16,14 +16,11 @@ needed, as torch modules (library GEMMs) otherwise.  The hourglass image filters
 path."""
 import ctypes
 import os
-import weakref
 
 import torch
 from torch import nn
 
 from . import _lib
-
-_FUSE_IMAGES = weakref.WeakKeyDictionary()          # Fuse_sft_MLP -> packed weight images of its nine 256 x 256 blocks
 
 
 def fuse_autograd_backend():
@@ -288,13 +285,16 @@ class Fuse_sft_MLP(nn.Module):
                 self.scale[0].weight, self.scale[0].bias, self.scale[2].weight, self.scale[2].bias,
                 self.shift[0].weight, self.shift[0].bias, self.shift[2].weight, self.shift[2].bias]
 
+    def invalidate(self):
+        """Drop the packed weight images (needed after writes through `.data`; see SirenGenerator.invalidate)."""
+        _lib.invalidate(self)
+
     def _images(self, device):
         """Packed weight images (e3dge_ws_pack) of the nine 256 x 256 blocks, bias / mask-column vectors; rebuilt when a
-        parameter changes.  Kept outside the module (weak map): modules stay deep-copyable and state_dict-clean."""
-        key = _lib.param_key(self) + (str(device),)
-        hit = _FUSE_IMAGES.get(self)
-        if hit is not None and hit['key'] == key:
-            return hit
+        parameter changes (_lib.cached)."""
+        return _lib.cached(self, 'images', _lib.params_of(self), lambda: self._build_images(device), (str(device),))
+
+    def _build_images(self, device):
         lib = _lib.load()
         enc, n_in = self.encode_enc, self.encode_enc.fc_0.in_features
         has_col = n_in == 513
@@ -307,16 +307,14 @@ class Fuse_sft_MLP(nn.Module):
                 _lib.check(lib.e3dge_ws_pack(_lib.ptr(t), _lib.ptr(w), 1, _lib.stream_of(w)), "e3dge_ws_pack")
             return t
         f0, sc = enc.fc_0.weight, enc.shortcut.weight
-        hit = dict(key=key, b_off=b_off, has_col=has_col,
-                   f0a=img(f0[:, :256]), f0b=img(f0[:, b_off:]), f1=img(enc.fc_1.weight), sa=img(sc[:, :256]), sb=img(sc[:, b_off:]),
-                   sc1=img(self.scale[0].weight), sc2=img(self.scale[2].weight), sh1=img(self.shift[0].weight), sh2=img(self.shift[2].weight),
-                   f0col=f0[:, 256].detach().contiguous() if has_col else None, scol=sc[:, 256].detach().contiguous() if has_col else None,
-                   b0=enc.fc_0.bias.detach().contiguous(), b1=enc.fc_1.bias.detach().contiguous(),
-                   bsc1=self.scale[0].bias.detach().contiguous(), bsc2=self.scale[2].bias.detach().contiguous(),
-                   bsh1=self.shift[0].bias.detach().contiguous(), bsh2=self.shift[2].bias.detach().contiguous(),
-                   slope=float(self.scale[1].negative_slope))
-        _FUSE_IMAGES[self] = hit
-        return hit
+        return dict(b_off=b_off, has_col=has_col,
+                    f0a=img(f0[:, :256]), f0b=img(f0[:, b_off:]), f1=img(enc.fc_1.weight), sa=img(sc[:, :256]), sb=img(sc[:, b_off:]),
+                    sc1=img(self.scale[0].weight), sc2=img(self.scale[2].weight), sh1=img(self.shift[0].weight), sh2=img(self.shift[2].weight),
+                    f0col=f0[:, 256].detach().contiguous() if has_col else None, scol=sc[:, 256].detach().contiguous() if has_col else None,
+                    b0=enc.fc_0.bias.detach().contiguous(), b1=enc.fc_1.bias.detach().contiguous(),
+                    bsc1=self.scale[0].bias.detach().contiguous(), bsc2=self.scale[2].bias.detach().contiguous(),
+                    bsh1=self.shift[0].bias.detach().contiguous(), bsh2=self.shift[2].bias.detach().contiguous(),
+                    slope=float(self.scale[1].negative_slope))
 
     def _images_t(self, device):
         """Packed images of the TRANSPOSED 256 x 256 blocks (d input = d output @ W is the layer of W^T): built on the first backward."""

@@ -17,6 +17,7 @@ import ctypes
 import math
 import os
 import random
+import types
 
 import numpy as np
 import torch
@@ -125,9 +126,8 @@ class EqualLinear(nn.Module):
 
 import weakref
 
-_DEC2_STATES = weakref.WeakKeyDictionary()          # Decoder -> {(batch, res, device, stream): workspace + E3dgeDec2Plan}
 _DEC2_NOISE_AMAX = weakref.WeakKeyDictionary()      # Decoder -> {noise tensor version: amax buffer}
-_DEC2_BLUR_FACTOR = weakref.WeakKeyDictionary()     # Decoder -> (blur kernel tensor, its version, blur_factor of it)
+_DEC2_STATES = types.SimpleNamespace(get=lambda dec: _lib.latest(dec, 'dec2_state'))   # (tests ask whether a decoder has built a plan)
 
 
 def blur_factor(kernel):
@@ -167,7 +167,7 @@ def decoder_autograd_backend():
     backward taken with create_graph=True (a second differentiation through the decoder; not something the reference's encoder training
     does) is re-routed by the node itself to the library path, whose custom ops are twice differentiable as the reference's are
     (round 6; it raised before).  Parameter writes through `.data` between a forward and its backward bump no version counter and are
-    not seen by either path: call `invalidate()` and run the forward again."""
+    not seen by either path: call `Decoder.invalidate()` (or `Generator.invalidate()`) and run the forward again."""
     v = os.environ.get("E3DGE_DECODER_AUTOGRAD", "auto")
     if v not in ("auto", "packed", "library"):
         raise RuntimeError(f"E3DGE_DECODER_AUTOGRAD must be 'auto', 'packed' or 'library', got {v!r}")
@@ -317,22 +317,14 @@ class ModulatedConv2d(nn.Module):
 
     def invalidate(self):
         """Drop the packed weight images (needed after writes through `.data`; see SirenGenerator.invalidate)."""
-        self._img = self._img_key = None
-        self._wpre = self._wpre_key = None
-        self._wpre_t = self._wpre_t_key = None
-
-    def _apply(self, fn, *a, **k):
-        self._img = self._img_key = None
-        self._wpre = self._wpre_key = None
-        self._wpre_t = self._wpre_t_key = None
-        return super()._apply(fn, *a, **k)
+        _lib.invalidate(self)
 
     def device_wpre_t(self):
         """scale * W in the TRANSPOSED fragment order (rows = input channels, taps flipped for the stride-1 layers): what the
         backward's weights launch streams (e3dge_dec2_prepack_weights_t; the data gradient of :331-361 of the reference)."""
         w = self.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        if getattr(self, '_wpre_t', None) is None or self._wpre_t_key != key:
+
+        def build():
             Co, Ci = self.out_channel, self.in_channel
             wpre = torch.empty(Co * Ci * 9, device=w.device, dtype=torch.float32)
             wc = w.detach().reshape(Co, Ci, 9).contiguous()
@@ -340,29 +332,29 @@ class ModulatedConv2d(nn.Module):
                 rc = _lib.load().e3dge_dec2_prepack_weights_t(_lib.ptr(wpre), _lib.ptr(wc), float(self.scale), Co, Ci,
                                                               0 if self.upsample else 1, _lib.stream_of(wc))
             _lib.check(rc, "e3dge_dec2_prepack_weights_t")
-            self._wpre_t, self._wpre_t_key = wpre, key
-        return self._wpre_t
+            return wpre
+        return _lib.cached(self, 'wpre_t', (w,), build)
 
     def device_wpre(self):
         """scale * W re-arranged in MFMA A-fragment element order (fp32): what the per-forward weights launch of the packed
         decoder pipeline streams (e3dge_dec2_prepack_weights)."""
         w = self.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        if getattr(self, '_wpre', None) is None or self._wpre_key != key:
+
+        def build():
             Co, Ci = self.out_channel, self.in_channel
             wpre = torch.empty(Co * Ci * 9, device=w.device, dtype=torch.float32)
             wc = w.detach().reshape(Co, Ci, 9).contiguous()
             with torch.cuda.device(w.device):
                 rc = _lib.load().e3dge_dec2_prepack_weights(_lib.ptr(wpre), _lib.ptr(wc), float(self.scale), Co, Ci, _lib.stream_of(wc))
             _lib.check(rc, "e3dge_dec2_prepack_weights")
-            self._wpre, self._wpre_key = wpre, key
-        return self._wpre
+            return wpre
+        return _lib.cached(self, 'wpre', (w,), build)
 
     def device_image(self):
         """(image, wsq): the MFMA fragment image of scale * W (f16 hi/lo) and the per-(co,ci) squared norms."""
         w = self.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        if getattr(self, '_img', None) is None or self._img_key != key:
+
+        def build():
             lib = _lib.load()
             Co, Ci = self.out_channel, self.in_channel
             img = torch.empty(lib.e3dge_modconv_packed_words(Co, Ci), device=w.device, dtype=torch.int32)
@@ -376,8 +368,8 @@ class ModulatedConv2d(nn.Module):
             if wmax >= 400.0:                      # the image stores 128 * scale * w as f16
                 raise RuntimeError(f"modulated-conv weights up to {wmax:g} (after the 1/sqrt(fan_in) scale) do not fit the "
                                    "f16 image; set E3DGE_MODCONV=library for this checkpoint")
-            self._img, self._img_key = (img, wsq), key
-        return self._img
+            return img, wsq
+        return _lib.cached(self, 'image', (w,), build)
 
     def forward_fused(self, input, style, noise=None, noise_weight=None, bias=None, negative_slope=0.2, act_scale=1.0,
                       act=False, in_amax=None, out_amax=None, pre=None):
@@ -617,16 +609,10 @@ class Decoder(nn.Module):
     def _style_table(self, B, device):
         layers = self._mod_layers()
         wsqs = [m.device_image()[1] if m.kernel_size == 3 else None for m, _ in layers]
-        key = (B, str(device)) + tuple((m.modulation.weight.data_ptr(), m.modulation.weight._version, m.modulation.bias.data_ptr(),
-                                        m.modulation.bias._version, 0 if w is None else w.data_ptr()) for (m, _), w in zip(layers, wsqs))
-        # one table (and one output buffer) per stream: two forwards in flight on different streams must not share it
-        slot = (B, str(device), torch.cuda.current_stream(device).cuda_stream)
-        tabs = self.__dict__.setdefault('_tabs', {})
-        hit = tabs.get(slot)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        if True:
-            import ctypes
+        # the table stores the pointers of every modulation layer's parameters and of the squared-norm tables: all are its sources
+        sources = [t for (m, _), w in zip(layers, wsqs) for t in (m.modulation.weight, m.modulation.bias, w) if t is not None]
+
+        def build():
             pad4 = lambda n: (n + 3) // 4 * 4
             total = sum(pad4(B * m.in_channel) + (pad4(B * m.out_channel) + pad4(B) if w is not None else 0) for (m, _), w in zip(layers, wsqs))
             buf = torch.empty(total, device=device, dtype=torch.float32)
@@ -648,11 +634,10 @@ class Decoder(nn.Module):
                 row_start += m.in_channel
                 co_start += m.out_channel if w is not None else 0
             raw = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).to(device)
-            tabs.pop(slot, None)
-            while len(tabs) >= 8:                      # evict the oldest slot only: a captured graph may still replay the others
-                tabs.pop(next(iter(tabs)))
-            tabs[slot] = (key, (raw, buf, views, len(layers), row_start, co_start))
-        return tabs[slot][1]
+            return raw, buf, views, len(layers), row_start, co_start
+        # one table (and one output buffer) per stream: two forwards in flight on different streams must not share it.  Eight are kept,
+        # the oldest evicted first: a captured graph may still replay the others
+        return _lib.cached(self, 'style_table', sources, build, (B, str(device), torch.cuda.current_stream(device).cuda_stream), limit=8)
 
     def _all_modulations(self, latent):
         """[(s, demod, s_amax)] per modulated conv of the forward, or None when the fused path is not taken."""
@@ -705,13 +690,15 @@ class Decoder(nn.Module):
         return all(n is None or (n.device == features.device and n.dtype == torch.float32) for n in noise)
 
     def _blur_factor(self):
-        """blur_factor of the first up-sampling layer's Blur kernel (the plan hands it to every level), cached per (tensor,
-        version): _dec2_ok asks on every forward, and the kernel is a device buffer."""
+        """blur_factor of the first up-sampling layer's Blur kernel (the plan hands it to every level), cached: _dec2_ok asks on every
+        forward, and the kernel is a device buffer."""
         k = self.convs[0].conv.blur.kernel
-        hit = _DEC2_BLUR_FACTOR.get(self)
-        if hit is None or hit[0] is not k or hit[1] != k._version:
-            hit = _DEC2_BLUR_FACTOR[self] = (k, k._version, blur_factor(k))
-        return hit[2]
+        return _lib.cached(self, 'blur_factor', (k,), lambda: blur_factor(k))
+
+    def invalidate(self):
+        """Drop every packed weight image, style table and plan of the decoder and its layers (needed after writes through `.data`;
+        see SirenGenerator.invalidate)."""
+        _lib.invalidate(self)
 
     def _dec2_bwd_ok(self):
         """Can the packed pipeline differentiate itself (e3dge_dec2_backward)?  Every 3x3 layer needs 32-channel multiples on both
@@ -751,22 +738,20 @@ class Decoder(nn.Module):
         """Workspace + plan of the packed pipeline for one (batch, input resolution, device, stream): packed activation
         buffers (zero-filled ONCE: their borders are the convolutions' zero padding and no kernel writes them),
         per-sample weight images, ToRGB tables, amax / meta blocks, and the E3dgeDec2Plan struct with every static pointer
-        filled in.  Rebuilt when a parameter tensor is replaced."""
-        lib = _lib.load()
-        layers = self._mod_layers()
-        convs3 = [self.conv1] + list(self.convs)
-        rgbs = [self.to_rgb1] + list(self.to_rgbs)
+        filled in.  Its sources: every parameter, the style table and the pre-packed weights it points into.  Four are kept, the oldest
+        evicted first (a captured graph may still replay the others)."""
         tab = self._style_table(B, device)                 # has its own cache; rebuilt when a modulation layer / wsq changes
-        pkey = (id(tab[0]),) + _lib.param_key(self)
-        slot = (B, res, str(device), torch.cuda.current_stream(device).cuda_stream)
-        states = _DEC2_STATES.setdefault(self, {})      # module level (weak): ctypes plans must not sit on a deep-copyable module
-        hit = states.get(slot)
-        if hit is not None and hit['key'] == pkey:
-            return hit
+        wpres = {sc: sc.conv.device_wpre() for sc in [self.conv1] + list(self.convs)}
+        return _lib.cached(self, 'dec2_state', _lib.params_of(self) + [tab[0]] + list(wpres.values()),
+                           lambda: self._build_dec2_state(B, res, device, tab, wpres),
+                           (B, res, str(device), torch.cuda.current_stream(device).cuda_stream), limit=4)
+
+    def _build_dec2_state(self, B, res, device, tab, wpres):
+        lib = _lib.load()
         n_up = len(self.to_rgbs)
         raw, buf, views, n_mod, rows, cos = tab
         f32 = dict(device=device, dtype=torch.float32)
-        keep = [raw, buf]
+        keep = [raw, buf, *wpres.values()]                 # every tensor whose pointer the plan stores
         plan = _lib.Dec2Plan()
         plan.batch, plan.n_up, plan.in_res, plan.in_ch = B, n_up, res, self.conv1.conv.in_channel
         plan.mod_table = _lib.ptr(raw)
@@ -779,7 +764,7 @@ class Decoder(nn.Module):
             wimg = torch.empty(B * lib.e3dge_modconv_packed_words(m.out_channel, m.in_channel), device=device, dtype=torch.int32)
             bias = sc.activate.bias.detach()
             keep.extend([wimg, bias])
-            dst.wpre, dst.style, dst.demod, dst.wimg = _lib.ptr(m.device_wpre()), _lib.ptr(view[0]), _lib.ptr(view[1]), _lib.ptr(wimg)
+            dst.wpre, dst.style, dst.demod, dst.wimg = _lib.ptr(wpres[sc]), _lib.ptr(view[0]), _lib.ptr(view[1]), _lib.ptr(wimg)
             dst.noise_w, dst.bias = _lib.ptr(sc.noise.weight), _lib.ptr(bias)
             dst.bias_amax = float(bias.abs().max().item())
             dst.ci, dst.co = m.in_channel, m.out_channel
@@ -823,12 +808,7 @@ class Decoder(nn.Module):
             for i in range(4):
                 plan.fir_blur_1d[i] = g[i]
             plan.fir_blur_separable = 1
-        st = dict(key=pkey, plan=plan, keep=keep, acts=acts, outs=outs, meta=meta, amax=amax, n_launch=lib.e3dge_dec2_num_launches(n_up))
-        states.pop(slot, None)
-        while len(states) >= 4:
-            states.pop(next(iter(states)))
-        states[slot] = st
-        return st
+        return dict(plan=plan, keep=keep, acts=acts, outs=outs, meta=meta, amax=amax, n_launch=lib.e3dge_dec2_num_launches(n_up))
 
     def _forward_packed(self, features, latent, noise, kernel_ms=None, save=False):
         """Decoder.forward body on the packed pipeline; `kernel_ms` (list) receives the HIP-event time of every launch
@@ -1116,6 +1096,13 @@ class Generator(nn.Module):
 
     def get_latent(self, input):
         return self.style(input)
+
+    def invalidate(self):
+        """Drop everything derived from the parameters anywhere in the generator: the renderer's records and host copies
+        (VolumeFeatureRenderer.invalidate) and every packed weight image, table and plan of the renderer, the decoder and any other
+        sub-module.  Needed after writes through `.data` (the reference's EMA accumulate()); see SirenGenerator.invalidate."""
+        self.renderer.invalidate()
+        _lib.invalidate(self)
 
     def styles_and_noise_forward(self, styles, inject_index=None, truncation=1, truncation_latent=None,
                                  input_is_latent=False):

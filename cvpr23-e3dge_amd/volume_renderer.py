@@ -130,7 +130,6 @@ def release_record_buffers(renderer, pinned_only=False):
             pool.pop(k)
 
 
-_WMAX_STATE = weakref.WeakKeyDictionary()                              # ResnetBlockFC -> pinned host scalar + event of the deferred weight-range check
 _BACKBONE = weakref.WeakKeyDictionary()                                # renderer -> {key, buf (record), out (first pass's tensors)}
 _SIDE_STREAMS = {}                                                     # per device (module level: modules stay deep-copyable)
 
@@ -153,13 +152,11 @@ def _overlap_decoder():
 
 # backward-type launches additionally know the 8-wave x 16-point layout (E3DGE_PREC_F16X3_G2, csrc/siren16_bwd.h)
 BWD_MODES = dict(MFMA_MODES, f16x3_g2=_lib.PREC_F16X3_G2)
-_STRICT_CACHE = os.environ.get("E3DGE_STRICT_WEIGHT_CACHE", "0") not in ("", "0")
 
 
 def default_mfma_mode():
     """How the 256-wide contractions run (see include/e3dge_hip.h): 'f16x3' (split-f16 on the f16 matrix pipe, fp32
     accumulate -- same parity bounds, ~4x faster) unless E3DGE_MFMA_MODE=f32 asks for the fp32 MFMA kernel."""
-    import os
     mode = os.environ.get("E3DGE_MFMA_MODE", "f16x3")
     if mode not in MFMA_MODES:
         raise RuntimeError(f"E3DGE_MFMA_MODE must be one of {sorted(MFMA_MODES)}, got {mode!r}")
@@ -170,7 +167,6 @@ def default_bwd_mode():
     """The same choice for the backward-type kernels (E3DGE_BWD_MODE).  Default: 'f16x3_g2' beside the f16x3 forward -- the 8-wave
     kernels of csrc/siren16_bwd.h (block-scaled split-f16 like 'f16x3', saved state slab-major, second-order inputs as the products
     ta r; round 6) --, 'f32' beside the f32 forward.  'f16x3' = the first-generation 4-wave kernels."""
-    import os
     fwd = default_mfma_mode()
     mode = os.environ.get("E3DGE_BWD_MODE", "f16x3_g2" if fwd == "f16x3" else fwd)
     if mode not in BWD_MODES:
@@ -283,9 +279,6 @@ class SirenGenerator(nn.Module):
         self.views_linears = FiLMSiren(input_ch_views + W, W, style_dim=style_dim)
         self.rgb_linear = LinearLayer(W, 3, freq_init=True)
         self.sigma_linear = LinearLayer(W, 1, freq_init=True)
-        self._cache_key = None
-        self._cache = None
-        self._fingerprint = None
         self.mfma_mode = default_mfma_mode()
         self.bwd_mode = default_bwd_mode()
         self.train_params = False          # set through VolumeFeatureRenderer.train_renderer
@@ -307,40 +300,24 @@ class SirenGenerator(nn.Module):
     def _film_layers(self):
         return list(self.pts_linears) + [self.views_linears]
 
-    def _key(self):
-        return _lib.param_key(self)
-
     def invalidate(self):
-        """Drop the packed weight image.  The cache is keyed on (data_ptr, _version) of every parameter, which catches
-        optimizer steps, `load_state_dict`, `.to()` and in-place ops on the parameter itself -- but NOT writes through
-        `.data` (`p.data.mul_()`, the reference's EMA `accumulate()` in utils/training_utils.py:45 and ranger.py:178 do
-        that; they leave `_version` untouched).  Call this after such an update, or set E3DGE_STRICT_WEIGHT_CACHE=1 to
-        have every call compare a device-side fingerprint of the weights (one extra reduction + a host sync per call)."""
-        self._cache = self._cache_key = self._fingerprint = None
+        """Drop the packed weight image.  The cache (_lib.cached) follows every parameter's identity, data pointer and version, which
+        catches optimizer steps, `load_state_dict`, `.to()`, a replaced Parameter and in-place ops on the parameter itself -- but NOT
+        writes through `.data` (`p.data.mul_()`, the reference's EMA `accumulate()` in utils/training_utils.py:45 and ranger.py:178 do
+        that; they leave the version untouched).  Call this after such an update, or set E3DGE_STRICT_WEIGHT_CACHE=1 to
+        have every call compare a device-side fingerprint of the weights (extra reductions + a host sync per call)."""
+        _lib.invalidate(self)
 
     def _apply(self, fn, *a, **k):
-        self.invalidate()
         _lib.forget_params(self)
         return super()._apply(fn, *a, **k)
 
-    def train(self, mode=True):
-        self.invalidate()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self.invalidate()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _weights_fingerprint(self):
-        with torch.no_grad():
-            return torch.stack(torch._foreach_norm([p.detach().reshape(-1) for p in self.parameters()]))
-
     def device_image(self):
         """(packed, wg, bg, wb, bb): rebuilt only when a parameter changed (or moved); see invalidate()."""
-        key = self._key()
-        if self._cache is not None and key == self._cache_key:
-            if not _STRICT_CACHE or torch.equal(self._weights_fingerprint(), self._fingerprint):
-                return self._cache
+        return _lib.cached(self, 'image', _lib.params_of(self), self._build_image)[0]
+
+    def _build_image(self):
+        """[device_image(), max |w| of the 256-wide layers, has check_mode warned about it]."""
         w0 = self.pts_linears[0].weight
         _lib.require_gpu(w0, "SirenGenerator parameters")
         lib = _lib.load()
@@ -369,24 +346,23 @@ class SirenGenerator(nn.Module):
             _lib.check(rc, "e3dge_siren_pack_weights")
             # The f16x3 images carry the weights times 128 as f16 (max 65504): a checkpoint with |w| >= 256 in the
             # 256-wide layers (trained ones are ~0.01) cannot use them; check_mode() then selects the fp32 MFMA kernels.
-            self._wmax = float(torch.maximum(w_hidden.abs().max(), w_view.abs().max()).item())
+            wmax = float(torch.maximum(w_hidden.abs().max(), w_view.abs().max()).item())
             layers = self._film_layers()
             wg = torch.stack([l.gamma.weight.detach() for l in layers]).contiguous()
             bg = torch.stack([l.gamma.bias.detach() for l in layers]).contiguous()
             wb = torch.stack([l.beta.weight.detach() for l in layers]).contiguous()
             bb = torch.stack([l.beta.bias.detach() for l in layers]).contiguous()
-            self._fingerprint = self._weights_fingerprint() if _STRICT_CACHE else None
-        self._cache, self._cache_key = (packed, wg, bg, wb, bb), key
-        return self._cache
+        return [(packed, wg, bg, wb, bb), wmax, False]
 
     def check_mode(self, mode):
         """Precision selector for a launch.  Weights outside the f16x3 image's range (|w| >= 256, see device_image) fall
         back to the fp32 MFMA kernels for this module, with one warning."""
-        if mode != "f32" and getattr(self, "_wmax", 0.0) >= 256.0:
-            if not getattr(self, '_warned_range', False):
-                warnings.warn(f"SIREN weights up to {self._wmax:g} do not fit the f16x3 weight image (|w| < 256); "
+        built = _lib.latest(self, 'image')
+        if mode != "f32" and built is not None and built[1] >= 256.0:
+            if not built[2]:
+                warnings.warn(f"SIREN weights up to {built[1]:g} do not fit the f16x3 weight image (|w| < 256); "
                               "this module uses the fp32 MFMA kernels instead")
-                self._warned_range = True
+                built[2] = True
             mode = "f32"
         return BWD_MODES[mode]
 
@@ -975,26 +951,15 @@ class ResnetBlockFC(nn.Module):
         self.shortcut = nn.Linear(size_in, size_out, bias=False)
         for t in (self.fc_0.bias, self.fc_0.weight, self.fc_1.bias, self.fc_1.weight, self.shortcut.weight):
             nn.init.zeros_(t)                                        # :88-93 (and resnetfc.py:36)
-        self._cache_key = None
-        self._cache = None
 
     def invalidate(self):
         """Drop the packed weight images (needed after writes through `.data`; see SirenGenerator.invalidate)."""
-        self._cache = self._cache_key = None
-        self._cache_bwd = self._cache_bwd_key = None
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate()
-        return super()._apply(fn, *a, **k)
-
-    def train(self, mode=True):
-        self.invalidate()
-        return super().train(mode)
+        _lib.invalidate(self)
 
     def device_image(self):
         ps = [self.fc_0.weight, self.fc_0.bias, self.fc_1.weight, self.fc_1.bias, self.shortcut.weight]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
-        if key != self._cache_key or self._cache is None:
+
+        def build():
             dev = ps[0].device
             _lib.require_gpu(ps[0], "ResnetBlockFC weights")
             lib = _lib.load()
@@ -1007,14 +972,14 @@ class ResnetBlockFC(nn.Module):
             wmax = max(float(t.abs().max().item()) for t in (c[0], c[2], c[4]))
             if wmax >= 500.0:              # the image stores 128 * w as f16
                 raise RuntimeError(f"texture-head weights up to {wmax:g} do not fit the f16x3 weight image (|w| < 500)")
-            self._cache, self._cache_key = packed, key
-        return self._cache
+            return packed
+        return _lib.cached(self, 'image', ps, build)
 
     def device_image_bwd(self):
         """The backward's weight image (W_0, W_1^T, W_s^T, W_0^T chunks + b_0), rebuilt when a parameter changes."""
         ps = [self.fc_0.weight, self.fc_0.bias, self.fc_1.weight, self.shortcut.weight]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in ps)
-        if key != getattr(self, "_cache_bwd_key", None) or getattr(self, "_cache_bwd", None) is None:
+
+        def build():
             dev = ps[0].device
             _lib.require_gpu(ps[0], "ResnetBlockFC weights")
             lib = _lib.load()
@@ -1028,7 +993,7 @@ class ResnetBlockFC(nn.Module):
             # step, and three blocking .item() reads per rebuild sat in front of every backward (round-5 advisor finding).  The first
             # image is checked synchronously; after that the maximum is reduced on the device, copied to pinned host memory without
             # blocking, and examined at the NEXT rebuild (by then the copy has long finished) -- weights drift, they do not jump.
-            st = _WMAX_STATE.setdefault(self, {})          # (module-level: modules stay deep-copyable / picklable)
+            st = _lib.cached(self, 'wmax_check', (), dict)  # (pinned host scalar + event; no sources: it outlives the images)
             self._check_pending_wmax(st)
             wmax_dev = torch.stack([t.abs().max() for t in (c[0], c[2], c[3])]).max()
             if "host" not in st:
@@ -1038,8 +1003,8 @@ class ResnetBlockFC(nn.Module):
                 st["host"].copy_(wmax_dev.reshape(1), non_blocking=True)
                 st["event"] = torch.cuda.Event()
                 st["event"].record(torch.cuda.current_stream(dev))
-            self._cache_bwd, self._cache_bwd_key = packed, key
-        return self._cache_bwd
+            return packed
+        return _lib.cached(self, 'image_bwd', ps, build)
 
     @staticmethod
     def _raise_if_out_of_range(wmax):
@@ -1460,29 +1425,19 @@ class VolumeFeatureRenderer(nn.Module):
         """Host copy of the learned sigmoid_beta, refreshed only when the parameter changes (a `.item()` per
         call would put a device synchronisation in front of every render).  Writes through `.data` need invalidate()."""
         p = self.sigmoid_beta
-        key = (p.data_ptr(), p._version)
-        if getattr(self, '_sb_key', None) != key or _STRICT_CACHE:
-            self._sb_val, self._sb_key = float(p.detach().item()), key
-        return self._sb_val
+        return _lib.cached(self, 'sigmoid_beta', (p,), lambda: float(p.detach().item()))
 
     def invalidate(self):
         """Forget every host / device copy derived from the parameters (packed SIREN image, texture-head image,
         sigmoid_beta).  Needed only after updates that bypass autograd's version counter (`p.data.mul_()`, the reference's
         EMA accumulate(), utils/training_utils.py:45); optimizer steps, load_state_dict, .to() and train()/eval() are
         detected without it."""
-        self._sb_key = None
+        _lib.invalidate(self)                                 # (this module's and every sub-module's: SIREN, texture head)
         _BACKBONE.pop(self, None)                             # (the first pass's layer-7 record was computed from the old values)
         pool = _RECORD_BUFS.get(self)
         if pool:                                              # storage a captured graph points into stays; the rest is released
             for k in [k for k, e in pool.items() if not e[1]]:
                 pool.pop(k)
-        for m in self.modules():
-            if m is not self and hasattr(m, 'invalidate'):
-                m.invalidate()
-
-    def train(self, mode=True):
-        self._sb_key = None
-        return super().train(mode)
 
     # ---- deferred synchronisation (the generator runs the decoder between begin_deferred() and finish_deferred()) ------------------------
     def begin_deferred(self):

@@ -467,3 +467,82 @@ def test_mid_level_torgb_in_the_epilogue_matches_the_stand_alone_launch(monkeypa
     err, scale = float((img - img0).abs().max()), float(img0.abs().max())
     record("dec2_mid_torgb", err=err, img_max=scale)
     assert err <= 1e-5 * max(scale, 1.0)
+
+
+# ---- writes through `.data` and invalidate(): the decoder's and Fuse_sft_MLP's packed images, and the generator as a whole ------------
+# Two runs of these forwards on the same inputs are bit-equal, and so is a freshly constructed module with the same weights (checked on
+# the commit before the shared weight cache), hence torch.equal throughout.
+def _small_generator(state=None):
+    g, sd = full_state_dict(size=64, cm=1, res=16)
+    if state is not None:
+        g.load_state_dict(state)
+    return g.to(DEV).eval()
+
+
+def _state_of(module):
+    return {k: v.detach().cpu().clone() for k, v in module.state_dict().items()}
+
+
+def test_decoder_data_write_is_served_stale_until_invalidate():
+    """The packed forward reads each 3x3 modulated convolution's weight from a pre-packed copy (the modulation linears themselves are read
+    in place, so there is nothing stale to see there): a write through `.data` to one modulated layer's weight changes nothing until
+    Decoder.invalidate(), after which the image is the one a freshly built decoder with the edited weights gives."""
+    dec = _small_generator().decoder
+    _, wd = syn.synthetic_inputs(2, seed=5, device=DEV)
+    wd = wd[:, :dec.n_latent].contiguous()
+    feats = (0.7 * torch.randn(2, 256, 16, 16, device=DEV, generator=torch.Generator(DEV).manual_seed(11))).contiguous()
+    run = lambda d: d(feats, [wd], input_is_latent=True, noise=[getattr(d.noises, f"noise_{i}") for i in range(d.num_layers)],
+                      randomize_noise=False)[0].clone()
+    with torch.no_grad():
+        assert dec._dec2_ok(feats, wd, [getattr(dec.noises, f"noise_{i}") for i in range(dec.num_layers)], None)
+        base = run(dec)
+        dec.convs[1].conv.weight.data.mul_(1.5)
+        assert torch.equal(run(dec), base)
+        dec.invalidate()
+        new = run(dec)
+        assert not torch.equal(new, base)
+        fresh = _small_generator().decoder
+        fresh.load_state_dict(_state_of(dec))
+        assert torch.equal(new, run(fresh))
+
+
+def test_fuse_sft_mlp_data_write_is_served_stale_until_invalidate():
+    from e3dge_amd.local_query import Fuse_sft_MLP
+    m = _fuse_module(257, seed=9).to(DEV)
+    torch.manual_seed(2)
+    x = torch.randn(2, 500, 513, device=DEV)
+    x[..., 256] = (torch.rand(2, 500, device=DEV) > 0.4).float()
+    run = lambda mod: mod.fuse(x, x[..., 257:], w=0.7).clone()
+    with torch.no_grad():
+        base = run(m)
+        m.scale[0].weight.data.mul_(1.5)
+        assert torch.equal(run(m), base)
+        m.invalidate()
+        new = run(m)
+        assert not torch.equal(new, base)
+        m2 = Fuse_sft_MLP(257, 256)
+        m2.load_state_dict(_state_of(m))
+        assert torch.equal(new, run(m2.to(DEV)))
+
+
+def test_generator_invalidate_reaches_the_renderer_and_the_decoder():
+    from e3dge_amd.camera_utils import generate_camera_params
+    g = _small_generator()
+    wr, wd = syn.synthetic_inputs(2, seed=5, device=DEV)
+    wd = wd[:, :g.decoder.n_latent].contiguous()
+    poses, focal, near, far, _ = generate_camera_params(16, DEV, locations=torch.tensor([[0.1, -0.05], [0.0, 0.2]], device=DEV))
+
+    def run(gen):
+        o = gen([wr, wd], poses, focal, near, far, input_is_latent=True, randomize_noise=False)
+        return o['gen_thumb_imgs'].clone(), o['gen_imgs'].clone()
+    with torch.no_grad():
+        thumb0, img0 = run(g)
+        g.renderer.siren.pts_linears[2].weight.data.mul_(1.01)
+        g.decoder.convs[1].conv.weight.data.mul_(1.5)
+        thumb1, img1 = run(g)
+        assert torch.equal(thumb1, thumb0) and torch.equal(img1, img0)
+        g.invalidate()
+        thumb2, img2 = run(g)
+        assert not torch.equal(thumb2, thumb0) and not torch.equal(img2, img0)
+        thumb3, img3 = run(_small_generator(_state_of(g)))
+        assert torch.equal(thumb2, thumb3) and torch.equal(img2, img3)
