@@ -140,6 +140,15 @@ class MeshRenderArgs(ctypes.Structure):
         (n, _vp) for n in ("image", "zbuf", "pix_to_face", "status", "ws")] + [("ws_bytes", _i64), ("bin_capacity", _i64)]
 
 
+NOISE_PROJECT_FACES_PER_PIXEL, NOISE_PROJECT_MAX_MAPS = 17, 4    # E3DGE_NOISE_PROJECT_FACES_PER_PIXEL, E3DGE_NOISE_PROJECT_MAX_MAPS
+
+
+class NoiseProjectArgs(ctypes.Structure):
+    """Mirror of struct E3dgeNoiseProjectArgs (include/e3dge_hip.h)."""
+    _fields_ = [(n, _vp) for n in ("verts", "faces", "vert_noise", "prev")] + [("n_verts", _i64), ("n_faces", _i64), ("camera", _f32 * 12)] + [
+        (n, _f32) for n in ("tan_half_fov", "znear", "zfar", "blur_radius", "sigma", "gamma")] + [("image_size", _i32), ("n_maps", _i32)] + [
+        (n, _vp) for n in ("out", "valid", "status", "ws")] + [("ws_bytes", _i64), ("bin_capacity", _i64)]
+
 # include/e3dge_hip_experimental.h: -DE3DGE_EXPERIMENTAL builds (tools/build_variant.sh) carry one more precision mode; no extra symbols
 EXPERIMENTAL_SIGNATURES = {}
 
@@ -228,6 +237,9 @@ SIGNATURES = {
     "e3dge_vertex_normals": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "e3dge_mesh_render_ws_bytes": (_i64, [_i64, _i64, _i32, _i64]),
     "e3dge_mesh_render": (_i32, [ctypes.POINTER(MeshRenderArgs), _vp]),
+    "e3dge_mesh_subdivide": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "e3dge_noise_project_ws_bytes": (_i64, [_i64, _i64, _i32, _i64]),
+    "e3dge_noise_project": (_i32, [ctypes.POINTER(NoiseProjectArgs), _vp]),
     "e3dge_selftest_mfma": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "e3dge_selftest_mfma16": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "e3dge_selftest_mfma16x16": (_i32, [_vp, _vp, _vp, _i32, _vp]),

@@ -15,6 +15,9 @@
 //              independent of it) -> raster: one 256-thread workgroup per 16 x 16-pixel tile, one pixel per thread (each wave an 8 x 16
 //              pixel block), face records staged through LDS 256 at a time and read by broadcast, the K nearest fragments of a pixel in
 //              registers (K a template parameter), shading and blending at the end of the same kernel.
+// noise        the reference's NoiseInjection.project_noise (project/models/stylesdf_model.py:365-466): the same binning stages and
+//              fragment walk at K = 17, blending up to four scalar vertex fields instead of a Phong colour.
+// subdivide    midpoint subdivision (trimesh.remesh.subdivide), one launch per level; the caller ranks the edge keys.
 #include "common.h"
 
 namespace e3dge {
@@ -211,36 +214,44 @@ mr_face_kernel(MrParams P, int2* __restrict__ ftile, unsigned* __restrict__ coun
         for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(count + ty * P.tiles + tx, 1u);
 }
 
-// One block: exclusive scan of the tile counts; status = {entries needed, capacity}.
+// One block: exclusive scan of the tile counts; status = {entries needed, capacity}.  Carry = unsigned: the totals fit 32 bits by the
+// caller's check (faces x tiles < 2^31).  Carry = mr_u64 (noise projection: no such bound): `entries needed` saturates at 2^31 - 1 --
+// above every capacity the entry accepts -- and so do the offsets, so that offset + cursor neither wraps nor passes the fill's guard.
+template <typename Carry>
 __global__ void __launch_bounds__(kMrThreads)
 mr_scan_kernel(const unsigned* __restrict__ count, unsigned* __restrict__ offset, int n_tiles, int* __restrict__ status, int capacity) {
-    __shared__ unsigned lds[kMrThreads / kWave];
+    __shared__ Carry lds[kMrThreads / kWave];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    unsigned carry = 0;
+    Carry carry = 0;
     for (int b0 = 0; b0 < n_tiles; b0 += kMrThreads) {
         const int b = b0 + threadIdx.x;
-        const unsigned v = b < n_tiles ? count[b] : 0u;
-        unsigned inc = v;
+        const Carry v = b < n_tiles ? count[b] : 0u;
+        Carry inc = v;
 #pragma unroll
         for (int o = 1; o < kWave; o <<= 1) {
-            const unsigned up = __shfl_up(inc, o, kWave);
+            const Carry up = __shfl_up(inc, o, kWave);
             if (lane >= o) inc += up;
         }
         if (lane == kWave - 1) lds[wave] = inc;
         __syncthreads();
-        unsigned base = 0, tot = 0;
+        Carry base = 0, tot = 0;
 #pragma unroll
         for (int w = 0; w < kMrThreads / kWave; ++w) {
-            const unsigned s = lds[w];
-            base += w < wave ? s : 0u;
+            const Carry s = lds[w];
+            base += w < wave ? s : (Carry)0;
             tot += s;
         }
         __syncthreads();
-        if (b < n_tiles) offset[b] = carry + base + inc - v;
+        if (b < n_tiles) {
+            const Carry o = carry + base + inc - v;
+            if constexpr (sizeof(Carry) == 8) offset[b] = (unsigned)(o < (Carry)0x7fffffff ? o : (Carry)0x7fffffff);
+            else offset[b] = o;
+        }
         carry += tot;
     }
     if (threadIdx.x == 0) {
-        status[0] = (int)carry;
+        if constexpr (sizeof(Carry) == 8) status[0] = (int)(carry < (Carry)0x7fffffff ? carry : (Carry)0x7fffffff);
+        else status[0] = (int)carry;
         status[1] = capacity;
     }
 }
@@ -326,22 +337,15 @@ __device__ __forceinline__ void mr_normalize(float& x, float& y, float& z) {
     z /= l;
 }
 
+// The K nearest covered fragments of pixel centre (qx, qy) among the faces of `tile`, ordered by (z, face index): lz / ld / lf, empty
+// slots (inf, 0, kMrEmpty).  Every thread of the workgroup calls it (face records are staged through `rec` 256 at a time); threads
+// that are not `live` only stage.  The insertion is unrolled over K: every index into the three arrays is a compile-time constant, so
+// they stay in registers (a runtime index would move them to scratch).
 template <int K>
-__global__ void __launch_bounds__(kMrThreads)
-mr_raster_kernel(MrParams P, const int* __restrict__ status, const unsigned* __restrict__ count, const unsigned* __restrict__ offset,
-                 const int* __restrict__ entries, const int* __restrict__ faces, const MrVert* __restrict__ vcache,
-                 const float* __restrict__ verts, const float* __restrict__ normals, const float* __restrict__ colors,
-                 float* __restrict__ image, float* __restrict__ zbuf, int* __restrict__ pix_to_face) {
-    __shared__ MrRecord rec[kMrThreads];
-    if (status[0] > status[1]) return;              // the lists did not fit: the caller reads status and launches again
-    const int tile = blockIdx.x, tx = tile % P.tiles, ty = tile / P.tiles;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int j = tx * kMrTile + (lane & 7) + 8 * (wave & 1), i = ty * kMrTile + (lane >> 3) + 8 * (wave >> 1);
-    const bool live = i < P.S && j < P.S;
-    const float qx = 1.0f - (float)(2 * j + 1) / (float)P.S, qy = 1.0f - (float)(2 * i + 1) / (float)P.S;
-
-    float lz[K], ld[K];
-    int lf[K];
+__device__ __forceinline__ void mr_nearest_fragments(const MrParams& P, MrRecord* rec, int tile, bool live, float qx, float qy,
+                                                     const unsigned* __restrict__ count, const unsigned* __restrict__ offset,
+                                                     const int* __restrict__ entries, const int* __restrict__ faces,
+                                                     const MrVert* __restrict__ vcache, float (&lz)[K], float (&ld)[K], int (&lf)[K]) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         lz[k] = __builtin_inff();
@@ -383,6 +387,25 @@ mr_raster_kernel(MrParams P, const int* __restrict__ status, const unsigned* __r
         }
         __syncthreads();
     }
+}
+
+template <int K>
+__global__ void __launch_bounds__(kMrThreads)
+mr_raster_kernel(MrParams P, const int* __restrict__ status, const unsigned* __restrict__ count, const unsigned* __restrict__ offset,
+                 const int* __restrict__ entries, const int* __restrict__ faces, const MrVert* __restrict__ vcache,
+                 const float* __restrict__ verts, const float* __restrict__ normals, const float* __restrict__ colors,
+                 float* __restrict__ image, float* __restrict__ zbuf, int* __restrict__ pix_to_face) {
+    __shared__ MrRecord rec[kMrThreads];
+    if (status[0] > status[1]) return;              // the lists did not fit: the caller reads status and launches again
+    const int tile = blockIdx.x, tx = tile % P.tiles, ty = tile / P.tiles;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int j = tx * kMrTile + (lane & 7) + 8 * (wave & 1), i = ty * kMrTile + (lane >> 3) + 8 * (wave >> 1);
+    const bool live = i < P.S && j < P.S;
+    const float qx = 1.0f - (float)(2 * j + 1) / (float)P.S, qy = 1.0f - (float)(2 * i + 1) / (float)P.S;
+
+    float lz[K], ld[K];
+    int lf[K];
+    mr_nearest_fragments<K>(P, rec, tile, live, qx, qy, count, offset, entries, faces, vcache, lz, ld, lf);
     if (!live) return;
 
     const int64_t pix = (int64_t)i * P.S + j;
@@ -449,16 +472,128 @@ int mr_launch_raster(const MrParams& P, const E3dgeMeshRenderArgs& a, const MrWo
     return check_launch("mesh_render_raster");
 }
 
+// ---- noise projection ------------------------------------------------------------------------------------------------------------------
+// The rasteriser's fragment walk at K = 17, then the blend of up to four scalar vertex fields that share the rasterisation (the
+// decoder's noise maps of one size): colour = the interpolated field, ambient 1, no diffuse or specular term, background 1.  Per pixel
+// 3 x 17 registers of (z, d, face); the texels are read at the end, once per kept fragment.
+constexpr int kNpK = E3DGE_NOISE_PROJECT_FACES_PER_PIXEL, kNpMaxMaps = E3DGE_NOISE_PROJECT_MAX_MAPS;
+
+__global__ void __launch_bounds__(kMrThreads)
+np_raster_kernel(MrParams P, const int* __restrict__ status, const unsigned* __restrict__ count, const unsigned* __restrict__ offset,
+                 const int* __restrict__ entries, const int* __restrict__ faces, const MrVert* __restrict__ vcache,
+                 const float* __restrict__ vert_noise, int64_t n_verts, int n_maps, const float* __restrict__ prev,
+                 float* __restrict__ out, unsigned char* __restrict__ valid) {
+    __shared__ MrRecord rec[kMrThreads];
+    if (status[0] > status[1]) return;              // the lists did not fit: the caller reads status and launches again
+    const int tile = blockIdx.x, tx = tile % P.tiles, ty = tile / P.tiles;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int j = tx * kMrTile + (lane & 7) + 8 * (wave & 1), i = ty * kMrTile + (lane >> 3) + 8 * (wave >> 1);
+    const bool live = i < P.S && j < P.S;
+    const float qx = 1.0f - (float)(2 * j + 1) / (float)P.S, qy = 1.0f - (float)(2 * i + 1) / (float)P.S;
+
+    float lz[kNpK], ld[kNpK];
+    int lf[kNpK];
+    mr_nearest_fragments<kNpK>(P, rec, tile, live, qx, qy, count, offset, entries, faces, vcache, lz, ld, lf);
+    if (!live) return;
+
+    const int64_t pix = (int64_t)i * P.S + j, plane = (int64_t)P.S * P.S;
+    float num[kNpMaxMaps] = {0.0f, 0.0f, 0.0f, 0.0f}, den = 0.0f, zmax = -1.0f;
+    const float range = P.zfar - P.znear;
+    const float m_raw = (P.zfar - lz[0]) / range;
+    const bool clamped = !(m_raw >= 1e-10f);
+    const float m = clamped ? 1e-10f : m_raw;
+#pragma unroll
+    for (int k = 0; k < kNpK; ++k) {
+        if (lf[k] == kMrEmpty) continue;
+        const int64_t f = lf[k];
+        const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+        const MrRecord r = mr_record(vcache[i0], vcache[i1], vcache[i2], (int)f, P.blur);
+        double b0, b1, b2;
+        mr_bary(r, qx, qy, b0, b1, b2);
+        mr_persp_clip(r, b0, b1, b2);
+        const float w0 = (float)b0, w1 = (float)b1, w2 = (float)b2;
+        const float prob = 1.0f / (1.0f + expf(-(-ld[k] / P.sigma)));
+        const float e = clamped ? (P.zfar - lz[k]) / range - m : (lz[0] - lz[k]) / range;
+        const float w = prob * expf(e / P.gamma);
+#pragma unroll
+        for (int c = 0; c < kNpMaxMaps; ++c) {
+            if (c < n_maps) {
+                const float* __restrict__ vn = vert_noise + c * n_verts;
+                num[c] += w * (w0 * vn[i0] + w1 * vn[i1] + w2 * vn[i2]);
+            }
+        }
+        den += w;
+        zmax = fmaxf(zmax, lz[k]);
+    }
+    const bool ok = zmax > 0.0f;                    // the reference's zbuf.max(-1) > 0
+    valid[pix] = ok ? 1 : 0;
+    const float delta = fmaxf(expf((1e-10f - m) / P.gamma), 1e-10f);
+#pragma unroll
+    for (int c = 0; c < kNpMaxMaps; ++c)
+        if (c < n_maps) out[c * plane + pix] = ok ? (num[c] + delta) / (den + delta) : prev[c * plane + pix];
+}
+
+// ---- midpoint subdivision ----------------------------------------------------------------------------------------------------------------
+// One launch: thread i copies vertex i (i < V), writes the midpoint of edge i - V (V <= i < V + E) and the four faces of face i (i < F).
+__global__ void __launch_bounds__(kMrThreads)
+subdivide_kernel(float* __restrict__ out_verts, int* __restrict__ out_faces, const float* __restrict__ verts, const int* __restrict__ faces,
+                 const int64_t* __restrict__ edge_keys, const int* __restrict__ side_rank, int64_t n_verts, int64_t n_faces, int64_t n_edges) {
+    const int64_t i = (int64_t)blockIdx.x * kMrThreads + threadIdx.x;
+    if (i < n_verts) {
+        for (int a = 0; a < 3; ++a) out_verts[i * 3 + a] = verts[i * 3 + a];
+    } else if (i < n_verts + n_edges) {
+        const int64_t key = edge_keys[i - n_verts];
+        const int64_t lo = key / n_verts, hi = key % n_verts;
+        const bool ok = key >= 0 && lo < n_verts;      // a key that is no vertex pair: a vertex at the origin, nothing read
+        for (int a = 0; a < 3; ++a) out_verts[i * 3 + a] = ok ? 0.5f * (verts[lo * 3 + a] + verts[hi * 3 + a]) : 0.0f;
+    }
+    if (i < n_faces) {
+        const int a = faces[i * 3], b = faces[i * 3 + 1], c = faces[i * 3 + 2];
+        const int ab = (int)n_verts + side_rank[i * 3], bc = (int)n_verts + side_rank[i * 3 + 1], ca = (int)n_verts + side_rank[i * 3 + 2];
+        int* __restrict__ o = out_faces + i * 12;
+        o[0] = a;  o[1] = ab;  o[2] = ca;
+        o[3] = ab; o[4] = b;   o[5] = bc;
+        o[6] = ca; o[7] = bc;  o[8] = c;
+        o[9] = ab; o[10] = bc; o[11] = ca;
+    }
+}
+
 constexpr int kMrMaxSize = 16384;                   // tile indices are packed into 16 bits
 
-int mr_check_sizes(int64_t n_verts, int64_t n_faces, int image_size, int64_t bin_capacity) {
+int mr_check_sizes(const char* what, int64_t n_verts, int64_t n_faces, int image_size, int64_t bin_capacity, bool narrow) {
     E3DGE_REQUIRE(n_verts >= 0 && n_faces >= 0 && n_verts < ((int64_t)1 << 31) && n_faces < ((int64_t)1 << 31),
-                  "mesh_render: %lld vertices, %lld faces", (long long)n_verts, (long long)n_faces);
-    E3DGE_REQUIRE(image_size >= 1 && image_size <= kMrMaxSize, "mesh_render: image_size %d outside 1..%d", image_size, kMrMaxSize);
+                  "%s: %lld vertices, %lld faces", what, (long long)n_verts, (long long)n_faces);
+    E3DGE_REQUIRE(image_size >= 1 && image_size <= kMrMaxSize, "%s: image_size %d outside 1..%d", what, image_size, kMrMaxSize);
     const int64_t t = (image_size + kMrTile - 1) / kMrTile;
-    E3DGE_REQUIRE(n_faces * t * t < ((int64_t)1 << 31), "mesh_render: %lld faces x %lld tiles exceed the 32-bit bin offsets",
+    // narrow: 32-bit totals in the scan; otherwise the scan carries 64 bits and saturates at 2^31 - 1, which no capacity reaches
+    E3DGE_REQUIRE(!narrow || n_faces * t * t < ((int64_t)1 << 31), "%s: %lld faces x %lld tiles exceed the 32-bit bin offsets", what,
                   (long long)n_faces, (long long)(t * t));
-    E3DGE_REQUIRE(bin_capacity >= 0 && bin_capacity < ((int64_t)1 << 31), "mesh_render: bin capacity %lld", (long long)bin_capacity);
+    E3DGE_REQUIRE(bin_capacity >= 0 && bin_capacity < ((int64_t)1 << 31) - (narrow ? 0 : 1), "%s: bin capacity %lld", what, (long long)bin_capacity);
+    return E3DGE_OK;
+}
+
+// vertices -> faces -> scan -> fill: the per-tile face lists both raster kernels read.
+template <typename Carry>
+int mr_bin_faces(const MrParams& P, const MrWorkspace& w, const float* verts, const int* faces, int64_t n_verts, int64_t n_faces,
+                 int64_t n_tiles, int* status, int64_t bin_capacity, hipStream_t s) {
+    // count, offset and cursor are adjacent: one clear
+    if (hipMemsetAsync(w.count, 0, (size_t)(3 * mr_align(n_tiles * 4)), s) != hipSuccess) return check_launch("mesh_render_clear");
+    int e;
+    if (n_verts > 0) {
+        mr_vertex_kernel<<<dim3((unsigned)((n_verts + kMrThreads - 1) / kMrThreads)), dim3(kMrThreads), 0, s>>>(P, w.vcache, verts, n_verts);
+        if ((e = check_launch("mesh_render_vertices")) != E3DGE_OK) return e;
+    }
+    const unsigned fblocks = (unsigned)((n_faces + kMrThreads - 1) / kMrThreads);
+    if (n_faces > 0) {
+        mr_face_kernel<<<dim3(fblocks), dim3(kMrThreads), 0, s>>>(P, w.ftile, w.count, faces, w.vcache, n_verts, n_faces);
+        if ((e = check_launch("mesh_render_faces")) != E3DGE_OK) return e;
+    }
+    mr_scan_kernel<Carry><<<dim3(1), dim3(kMrThreads), 0, s>>>(w.count, w.offset, (int)n_tiles, status, (int)bin_capacity);
+    if ((e = check_launch("mesh_render_scan")) != E3DGE_OK) return e;
+    if (n_faces > 0) {
+        mr_fill_kernel<<<dim3(fblocks), dim3(kMrThreads), 0, s>>>(P.tiles, w.ftile, w.offset, w.cursor, w.entries, n_faces, (int)bin_capacity);
+        if ((e = check_launch("mesh_render_fill")) != E3DGE_OK) return e;
+    }
     return E3DGE_OK;
 }
 
@@ -500,7 +635,7 @@ extern "C" int e3dge_vertex_normals(float* normals, const float* verts, const in
 }
 
 extern "C" int64_t e3dge_mesh_render_ws_bytes(int64_t n_verts, int64_t n_faces, int image_size, int64_t bin_capacity) {
-    if (mr_check_sizes(n_verts, n_faces, image_size, bin_capacity) != E3DGE_OK) return -1;
+    if (mr_check_sizes("mesh_render", n_verts, n_faces, image_size, bin_capacity, true) != E3DGE_OK) return -1;
     const int64_t t = (image_size + kMrTile - 1) / kMrTile;
     return mr_ws_bytes(n_verts, n_faces, t * t, bin_capacity);
 }
@@ -508,7 +643,7 @@ extern "C" int64_t e3dge_mesh_render_ws_bytes(int64_t n_verts, int64_t n_faces, 
 extern "C" int e3dge_mesh_render(const E3dgeMeshRenderArgs* args, e3dge_stream_t stream) {
     E3DGE_REQUIRE(args, "mesh_render: null args");
     const E3dgeMeshRenderArgs& a = *args;
-    const int rc = mr_check_sizes(a.n_verts, a.n_faces, a.image_size, a.bin_capacity);
+    const int rc = mr_check_sizes("mesh_render", a.n_verts, a.n_faces, a.image_size, a.bin_capacity, true);
     if (rc != E3DGE_OK) return rc;
     E3DGE_REQUIRE(a.faces_per_pixel >= 1 && a.faces_per_pixel <= E3DGE_MESH_MAX_FACES_PER_PIXEL, "mesh_render: faces_per_pixel %d outside 1..%d",
                   a.faces_per_pixel, E3DGE_MESH_MAX_FACES_PER_PIXEL);
@@ -533,24 +668,8 @@ extern "C" int e3dge_mesh_render(const E3dgeMeshRenderArgs* args, e3dge_stream_t
     P.S = a.image_size; P.tiles = (int)t;
     const MrWorkspace w = mr_ws(a.ws, a.n_verts, a.n_faces, n_tiles);
     hipStream_t s = as_stream(stream);
-    // count, offset and cursor are adjacent: one clear
-    if (hipMemsetAsync(w.count, 0, (size_t)(3 * mr_align(n_tiles * 4)), s) != hipSuccess) return check_launch("mesh_render_clear");
-    int e;
-    if (a.n_verts > 0) {
-        mr_vertex_kernel<<<dim3((unsigned)((a.n_verts + kMrThreads - 1) / kMrThreads)), dim3(kMrThreads), 0, s>>>(P, w.vcache, a.verts, a.n_verts);
-        if ((e = check_launch("mesh_render_vertices")) != E3DGE_OK) return e;
-    }
-    const unsigned fblocks = (unsigned)((a.n_faces + kMrThreads - 1) / kMrThreads);
-    if (a.n_faces > 0) {
-        mr_face_kernel<<<dim3(fblocks), dim3(kMrThreads), 0, s>>>(P, w.ftile, w.count, a.faces, w.vcache, a.n_verts, a.n_faces);
-        if ((e = check_launch("mesh_render_faces")) != E3DGE_OK) return e;
-    }
-    mr_scan_kernel<<<dim3(1), dim3(kMrThreads), 0, s>>>(w.count, w.offset, (int)n_tiles, a.status, (int)a.bin_capacity);
-    if ((e = check_launch("mesh_render_scan")) != E3DGE_OK) return e;
-    if (a.n_faces > 0) {
-        mr_fill_kernel<<<dim3(fblocks), dim3(kMrThreads), 0, s>>>(P.tiles, w.ftile, w.offset, w.cursor, w.entries, a.n_faces, (int)a.bin_capacity);
-        if ((e = check_launch("mesh_render_fill")) != E3DGE_OK) return e;
-    }
+    const int e = mr_bin_faces<unsigned>(P, w, a.verts, a.faces, a.n_verts, a.n_faces, n_tiles, a.status, a.bin_capacity, s);
+    if (e != E3DGE_OK) return e;
     switch (a.faces_per_pixel) {
         case 1: return mr_launch_raster<1>(P, a, w, s);
         case 2: return mr_launch_raster<2>(P, a, w, s);
@@ -561,4 +680,53 @@ extern "C" int e3dge_mesh_render(const E3dgeMeshRenderArgs* args, e3dge_stream_t
         case 7: return mr_launch_raster<7>(P, a, w, s);
         default: return mr_launch_raster<8>(P, a, w, s);
     }
+}
+
+extern "C" int64_t e3dge_noise_project_ws_bytes(int64_t n_verts, int64_t n_faces, int image_size, int64_t bin_capacity) {
+    if (mr_check_sizes("noise_project", n_verts, n_faces, image_size, bin_capacity, false) != E3DGE_OK) return -1;
+    const int64_t t = (image_size + kMrTile - 1) / kMrTile;
+    return mr_ws_bytes(n_verts, n_faces, t * t, bin_capacity);
+}
+
+extern "C" int e3dge_noise_project(const E3dgeNoiseProjectArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "noise_project: null args");
+    const E3dgeNoiseProjectArgs& a = *args;
+    const int rc = mr_check_sizes("noise_project", a.n_verts, a.n_faces, a.image_size, a.bin_capacity, false);
+    if (rc != E3DGE_OK) return rc;
+    E3DGE_REQUIRE(a.n_maps >= 1 && a.n_maps <= E3DGE_NOISE_PROJECT_MAX_MAPS, "noise_project: n_maps %d outside 1..%d", a.n_maps,
+                  E3DGE_NOISE_PROJECT_MAX_MAPS);
+    E3DGE_REQUIRE(a.out && a.valid && a.prev && a.status && a.ws, "noise_project: null output, prev, status or workspace");
+    E3DGE_REQUIRE((a.n_verts == 0 || (a.verts && a.vert_noise)) && (a.n_faces == 0 || a.faces), "noise_project: null mesh pointer");
+    E3DGE_REQUIRE(a.tan_half_fov > 0.0f && a.zfar > a.znear && a.znear > 0.0f && a.blur_radius >= 0.0f && a.sigma > 0.0f && a.gamma > 0.0f,
+                  "noise_project: tan_half_fov, znear < zfar, sigma and gamma must be positive, blur_radius non-negative");
+    const int64_t t = (a.image_size + kMrTile - 1) / kMrTile, n_tiles = t * t;
+    const int64_t need = mr_ws_bytes(a.n_verts, a.n_faces, n_tiles, a.bin_capacity);
+    E3DGE_REQUIRE(a.ws_bytes >= need, "noise_project: workspace of %lld bytes, %lld needed", (long long)a.ws_bytes, (long long)need);
+    MrParams P = {};
+    for (int k = 0; k < 12; ++k) P.cam[k] = a.camera[k];
+    P.t = a.tan_half_fov; P.znear = a.znear; P.zfar = a.zfar;
+    P.blur = a.blur_radius; P.sigma = a.sigma; P.gamma = a.gamma;
+    P.S = a.image_size; P.tiles = (int)t;
+    const MrWorkspace w = mr_ws(a.ws, a.n_verts, a.n_faces, n_tiles);
+    hipStream_t s = as_stream(stream);
+    const int e = mr_bin_faces<mr_u64>(P, w, a.verts, a.faces, a.n_verts, a.n_faces, n_tiles, a.status, a.bin_capacity, s);
+    if (e != E3DGE_OK) return e;
+    np_raster_kernel<<<dim3((unsigned)n_tiles), dim3(kMrThreads), 0, s>>>(P, a.status, w.count, w.offset, w.entries, a.faces, w.vcache, a.vert_noise,
+                                                                          a.n_verts, a.n_maps, a.prev, a.out, a.valid);
+    return check_launch("noise_project_raster");
+}
+
+extern "C" int e3dge_mesh_subdivide(float* out_verts, int32_t* out_faces, const float* verts, const int32_t* faces, const int64_t* edge_keys,
+                                    const int32_t* side_rank, int64_t n_verts, int64_t n_faces, int64_t n_edges, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(n_verts >= 0 && n_faces >= 0 && n_edges >= 0 && n_edges <= 3 * n_faces && n_verts + n_edges < ((int64_t)1 << 31) &&
+                      4 * n_faces < ((int64_t)1 << 31),
+                  "mesh_subdivide: %lld vertices, %lld faces, %lld edges", (long long)n_verts, (long long)n_faces, (long long)n_edges);
+    E3DGE_REQUIRE((n_verts == 0 || (out_verts && verts)) && (n_faces == 0 || (out_faces && faces && side_rank)) && (n_edges == 0 || edge_keys),
+                  "mesh_subdivide: null pointer");
+    E3DGE_REQUIRE(n_edges == 0 || n_verts > 0, "mesh_subdivide: edges without vertices");
+    const int64_t n = n_verts + n_edges > n_faces ? n_verts + n_edges : n_faces;
+    if (n == 0) return E3DGE_OK;
+    subdivide_kernel<<<dim3((unsigned)((n + kMrThreads - 1) / kMrThreads)), dim3(kMrThreads), 0, as_stream(stream)>>>(
+        out_verts, out_faces, verts, faces, edge_keys, side_rank, n_verts, n_faces, n_edges);
+    return check_launch("mesh_subdivide");
 }

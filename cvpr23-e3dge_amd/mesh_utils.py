@@ -16,11 +16,19 @@ Surface renderings (mesh_utils.py:107-173 and trainer.py:1482-1534, 2254-2346 of
     create_mesh_renderer / create_depth_mesh_renderer   the pytorch3d Phong renderer as one HIP rasteriser (e3dge_mesh_render)
     render_depth_mesh(xyz, viewpoint) / render_surface_mesh(verts, faces, viewpoint)   the runner's two geometry images
 
+View-consistent decoder noise (NoiseInjection.project_noise, project/models/stylesdf_model.py:365-466 of the reference):
+    pose_to_viewpoint(c2w)                           (azim, elev) of a camera pose: pytorch3d's matrix_to_euler_angles(.., "ZYX") on the host
+    subdivide(verts, faces, levels)                  midpoint subdivision (trimesh.remesh.subdivide) in HIP (e3dge_mesh_subdivide)
+    load_mesh(mesh)                                  an OBJ path, a SurfaceMesh or a (verts, faces) pair -> LoadedMesh, levels cached
+    project_vertex_noise(verts, faces, vert_noise, camera, image_size, prev)   the 17-fragment soft blend of per-vertex noise
+                                                     (e3dge_noise_project): (maps, valid)
+
 The renderer calls align_volume for `return_mesh=True` (volume_renderer.py:1703-1731 of the reference) and returns the aligned
 volume as 'aligned_sdf', and marching_cubes' result as 'mesh_verts' / 'mesh_faces'.  'mesh' comes from marching_cubes_mesh when
 scikit-image and trimesh are installed, otherwise from the HIP result."""
 import ctypes
 import functools
+import os
 
 import numpy as np
 import torch
@@ -399,7 +407,8 @@ def create_mesh_renderer(camera, image_size=256, blur_radius=1e-6, light_locatio
 def create_depth_mesh_renderer(camera, image_size=256, blur_radius=1e-6, light_location=((-0.5, 1., 5.),), faces_per_pixel=5,
                                **light_kwargs):
     """The reference's create_depth_mesh_renderer: the same renderer returning (image, zbuf).  The reference asks for 17 faces per pixel
-    there (it only serves noise projection, which this package does not have): more than 8 is refused."""
+    there; it only serves noise projection, which has its own entry here (project_vertex_noise / e3dge_noise_project, 17 fragments per
+    pixel and no zbuf output): more than 8 is refused by this one."""
     return DepthMeshRenderer(camera, image_size, blur_radius, light_location, faces_per_pixel, **light_kwargs)
 
 
@@ -427,3 +436,189 @@ def render_surface_mesh(verts, faces, viewpoint, fov_ang=6.0, image_size=512, co
     """AERunner.render_trimesh (trainer.py:1482-1534) for a marching-cubes mesh on the device -> (S, S, 3) float32 in 0..255."""
     r = create_mesh_renderer(_viewpoint_camera(viewpoint, fov_ang), image_size=image_size, light_location=((0.0, 3.0, 5.0),), **_RUNNER_LIGHTS)
     return 255 * r(verts, faces, colors=colors)[0, ..., :3]
+
+
+# ---- view-consistent decoder noise -------------------------------------------------------------------------------------------------------
+def pose_to_viewpoint(c2w):
+    """(azim, elev) in radians of a camera pose (3, 4) or (b, 3, 4) -- sample 0 -- as NoiseInjection.project_noise reads it
+    (stylesdf_model.py:427-429 of the reference): angles = matrix_to_euler_angles(R, "ZYX") with R = Rz(a0) Ry(a1) Rx(a2), azim = a1 =
+    asin(-R[2, 0]), elev = -a2 = -atan2(R[2, 1], R[2, 2]).  float64 on the host; for generate_camera_params' poses it returns the
+    viewpoint they were built from."""
+    R = c2w.detach().cpu().double().numpy() if isinstance(c2w, torch.Tensor) else np.asarray(c2w, np.float64)
+    if R.ndim == 3:
+        R = R[0]
+    if R.ndim != 2 or R.shape[0] != 3 or R.shape[1] < 3:
+        raise ValueError(f"pose_to_viewpoint expects a (3, 4) or (b, 3, 4) camera-to-world matrix, got {np.shape(c2w)}")
+    return float(np.arcsin(np.clip(-R[2, 0], -1.0, 1.0))), float(-np.arctan2(R[2, 1], R[2, 2]))
+
+
+def _subdivide_once(verts, faces, lib):
+    nv, nf = verts.shape[0], faces.shape[0]
+    f = faces.to(torch.int64)
+    a, b = f, f.roll(-1, 1)                                                       # sides (a, b), (b, c), (c, a)
+    keys = torch.minimum(a, b) * nv + torch.maximum(a, b)                        # lo V + hi
+    edge_keys, rank = torch.unique(keys.reshape(-1), sorted=True, return_inverse=True)      # ranking the 3 F keys: torch's sort
+    ne = edge_keys.shape[0]
+    if nv + ne >= 2 ** 31 or 4 * nf >= 2 ** 31:
+        raise RuntimeError(f"subdivide: {nv + ne} vertices, {4 * nf} faces exceed the 32-bit indices")
+    rank = rank.to(torch.int32).contiguous()
+    out_v = torch.empty(nv + ne, 3, dtype=torch.float32, device=verts.device)
+    out_f = torch.empty(4 * nf, 3, dtype=torch.int32, device=verts.device)
+    _lib.check(lib.e3dge_mesh_subdivide(_lib.ptr(out_v), _lib.ptr(out_f), _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(edge_keys), _lib.ptr(rank),
+                                        nv, nf, ne, _lib.stream_of(verts)), "e3dge_mesh_subdivide")
+    return out_v, out_f
+
+
+def subdivide(verts, faces, levels=1):
+    """`levels` rounds of midpoint subdivision (trimesh.remesh.subdivide) on the device: every edge gets a vertex at its midpoint, every
+    face becomes four, the winding is kept.  The order of the new vertices and faces is the one include/e3dge_hip.h documents
+    (e3dge_mesh_subdivide): new vertex V + rank of the edge key lo V + hi.  Face indices must lie in [0, V)."""
+    verts, faces = _mesh_args(verts, faces, "subdivide")
+    if int(levels) < 0:
+        raise ValueError(f"subdivide: levels = {levels}")
+    lib = _lib.load()
+    with _lib.on_device(verts.device):
+        for _ in range(int(levels)):
+            verts, faces = _subdivide_once(verts, faces, lib)
+    return verts, faces
+
+
+def subdivision_level(image_size):
+    """The number of subdivisions NoiseInjection.load_mc_mesh applies for a noise map of this size (stylesdf_model.py:394-421 of the
+    reference): 64 and 128 none, 256 one, everything else three.  The reference's return after two subdivisions tests `im_res == 256` a
+    second time and is never reached; no size gets level 2 here either."""
+    return 0 if image_size in (64, 128) else 1 if image_size == 256 else 3
+
+
+def read_obj(path):
+    """(vertices (V, 3) float32, faces (F, 3) int32) of a Wavefront OBJ of `v x y z` / `f i j k` lines, as SurfaceMesh.export writes it
+    (`i/t/n` corners are read by their vertex index; other lines are skipped)."""
+    v, f = [], []
+    with open(path) as fh:
+        for line in fh:
+            p = line.split()
+            if not p:
+                continue
+            if p[0] == "v":
+                v.append([float(x) for x in p[1:4]])
+            elif p[0] == "f":
+                if len(p) != 4:
+                    raise ValueError(f"{path}: only triangles are read, got {line.strip()!r}")
+                f.append([int(x.split("/")[0]) - 1 for x in p[1:4]])
+    return np.asarray(v, np.float64).reshape(-1, 3).astype(np.float32), np.asarray(f, np.int64).reshape(-1, 3).astype(np.int32)
+
+
+class LoadedMesh:
+    """A mesh on the device with its subdivision levels, each computed on first use and kept: level(n) -> (verts, faces)."""
+
+    def __init__(self, verts, faces):
+        self.levels = {0: _mesh_args(verts, faces, "load_mesh")}
+
+    def level(self, n):
+        if n not in self.levels:
+            base = max(k for k in self.levels if k < n)
+            v, f = self.levels[base]
+            for k in range(base + 1, n + 1):
+                v, f = subdivide(v, f, 1)
+                self.levels[k] = (v, f)
+        return self.levels[n]
+
+    def for_image(self, image_size):
+        return self.level(subdivision_level(image_size))
+
+
+_MESHES = {}                        # key -> (what the key was made from, LoadedMesh): the last few meshes
+
+
+def load_mesh(mesh, device="cuda"):
+    """What NoiseInjection's `mesh_path` may be -> LoadedMesh: a path to a Wavefront OBJ as SurfaceMesh.export writes it, a SurfaceMesh
+    (or anything with .vertices / .faces), or a (verts, faces) pair of device tensors.  The result, with the subdivision levels it has
+    computed, is cached per mesh: per (path, modification time), per object, per pair of tensors (identity, pointer and version)."""
+    if isinstance(mesh, (str, bytes)) or hasattr(mesh, "__fspath__"):
+        path = os.path.abspath(os.fsdecode(mesh))
+        st = os.stat(path)
+        key, held = ("path", path, st.st_mtime_ns, st.st_size, str(device)), None
+    elif isinstance(mesh, (tuple, list)) and len(mesh) == 2 and all(isinstance(t, torch.Tensor) for t in mesh):
+        key, held = ("pair",) + tuple((id(t), t.data_ptr(), t._version) for t in mesh), tuple(mesh)
+    elif hasattr(mesh, "vertices") and hasattr(mesh, "faces"):
+        key, held = ("object", id(mesh), str(device)), mesh
+    else:
+        raise TypeError("mesh_path must be an OBJ path, a mesh with .vertices / .faces or a (verts, faces) pair of device tensors, got "
+                        f"{type(mesh).__name__}")
+    hit = _MESHES.get(key)
+    if hit is not None:
+        return hit[1]
+    if key[0] == "pair":
+        loaded = LoadedMesh(mesh[0], mesh[1])
+    else:
+        v, f = read_obj(key[1]) if key[0] == "path" else (np.asarray(mesh.vertices, np.float32), np.asarray(mesh.faces).astype(np.int32))
+        loaded = LoadedMesh(torch.from_numpy(np.ascontiguousarray(v)).to(device), torch.from_numpy(np.ascontiguousarray(f)).to(device))
+    while len(_MESHES) >= 4:                                                     # a video uses one mesh per identity
+        _MESHES.pop(next(iter(_MESHES)))
+    _MESHES[key] = (held, loaded)                                                # `held` keeps the ids of the key alive
+    return loaded
+
+
+def project_vertex_noise(verts, faces, vert_noise, camera, image_size, prev=None, bin_capacity=None):
+    """vert_noise (C, V) or (V,) float32 on the device, 1 <= C <= 4: scalar fields over the vertices -> (maps (C, S, S) float32, valid
+    (S, S) bool).  maps = the soft blend of the 17 nearest fragments' interpolated values as the reference's create_depth_mesh_renderer
+    gives it (blur_radius 1e-6, ambient 1, BlendParams defaults) where valid, `prev` (C, S, S) -- zeros when None -- elsewhere.  One
+    rasterisation for all C maps (e3dge_noise_project).  The bin protocol is MeshRenderer.rasterize's: one retry with the capacity the
+    status word asks for."""
+    verts, faces = _mesh_args(verts, faces, "project_vertex_noise")
+    if not isinstance(camera, MeshCamera):
+        raise TypeError("project_vertex_noise takes a MeshCamera (mesh_utils.MeshCamera(azim, elev, fov))")
+    S = int(image_size)
+    if S < 1:
+        raise ValueError(f"image_size = {image_size}")
+    _lib.require_gpu(vert_noise, "project_vertex_noise: vert_noise")
+    nv, nf, dev = verts.shape[0], faces.shape[0], verts.device
+    vn = vert_noise.detach().reshape(-1, nv).contiguous() if vert_noise.numel() and vert_noise.shape[-1] == nv else None
+    if vn is None or vert_noise.device != dev or vert_noise.dim() > 2 or not 1 <= vn.shape[0] <= _lib.NOISE_PROJECT_MAX_MAPS:
+        raise RuntimeError(f"project_vertex_noise: vert_noise must be (C, {nv}) on the device of verts with 1 <= C <= "
+                           f"{_lib.NOISE_PROJECT_MAX_MAPS}, got {tuple(vert_noise.shape)}")
+    C = vn.shape[0]
+    if prev is None:
+        prev = torch.zeros(C, S, S, dtype=torch.float32, device=dev)
+    else:
+        _lib.require_gpu(prev, "project_vertex_noise: prev")
+        if prev.numel() != C * S * S or prev.device != dev:
+            raise RuntimeError(f"project_vertex_noise: prev must be ({C}, {S}, {S}) on the device of verts, got {tuple(prev.shape)}")
+        prev = prev.detach().contiguous()
+    lib = _lib.load()
+    tiles = ((S + 15) // 16) ** 2
+    fixed = bin_capacity is not None
+    cap = int(bin_capacity) if fixed else 4 * nf + 64 * tiles
+    out = torch.empty(C, S, S, dtype=torch.float32, device=dev)
+    valid = torch.empty(S, S, dtype=torch.uint8, device=dev)
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    a = _lib.NoiseProjectArgs()
+    a.camera[:] = camera.floats().tolist()
+    a.tan_half_fov, a.znear, a.zfar = camera.tan_half_fov, camera.znear, camera.zfar
+    a.blur_radius, a.sigma, a.gamma = 1e-6, MeshRenderer.SIGMA, MeshRenderer.GAMMA
+    a.image_size, a.n_maps, a.n_verts, a.n_faces = S, C, nv, nf
+    a.verts, a.faces, a.vert_noise, a.prev = _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(vn), _lib.ptr(prev)
+    a.out, a.valid, a.status = _lib.ptr(out), _lib.ptr(valid), _lib.ptr(status)
+    with _lib.on_device(dev):
+        for attempt in range(2):
+            cap = min(cap, nf * tiles, 2 ** 31 - 2)
+            nbytes = lib.e3dge_noise_project_ws_bytes(nv, nf, S, cap)
+            if nbytes < 0:
+                raise RuntimeError("project_vertex_noise: " + lib.e3dge_last_error().decode(errors="replace"))
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            a.ws, a.ws_bytes, a.bin_capacity = _lib.ptr(ws), nbytes, cap
+            _lib.check(lib.e3dge_noise_project(ctypes.byref(a), _lib.stream_of(verts)), "e3dge_noise_project")
+            need, _ = status.tolist()
+            if need <= cap:
+                return out, valid.bool()
+            if fixed:
+                break
+            cap = need
+    raise RuntimeError(f"project_vertex_noise: the tile lists need {need} entries, bin_capacity is {cap}")
+
+
+def noise_camera(transform):
+    """The camera NoiseInjection.project_noise draws from (stylesdf_model.py:427-434 of the reference): create_cameras at the pose's
+    (azim, elev), fov 12 degrees, distance 1."""
+    azim, elev = pose_to_viewpoint(transform)
+    return MeshCamera(azim=np.rad2deg(azim), elev=np.rad2deg(elev), fov=12.0, dist=1)

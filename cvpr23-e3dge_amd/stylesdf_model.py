@@ -24,7 +24,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from . import _lib
+from . import _lib, mesh_utils
 from .op import FusedLeakyReLU, fused_leaky_relu, noise_bias_act, upfirdn2d
 from .volume_renderer import VolumeFeatureRenderer, _opt_get
 
@@ -435,19 +435,47 @@ class ModulatedConv2d(nn.Module):
 
 class NoiseInjection(nn.Module):
     """Parameter holder (`weight`, zero-initialised, reference :365-370); StyledConv fuses its arithmetic
-    into the activation kernel.  Mesh-projected noise (`project=True`, :423-457) is out of scope."""
+    into the activation kernel.  `project=True` (reference :375-457): a given noise map is replaced by per-vertex noise of the
+    extracted surface seen from the frame's camera, so that the texture noise stays on the surface when the view changes.  The
+    projection state -- `vert_noise` (V,) on the mesh's device, drawn once per vertex count on the CPU with torch's global generator;
+    `prev_noise`, the first call's map, which fills the pixels the mesh does not cover ever after; `mesh_fn` -- are plain attributes,
+    not buffers: the state dict is the reference's."""
 
     def __init__(self, project=False):
         super().__init__()
-        if project:
-            raise NotImplementedError("project_noise needs pytorch3d mesh rendering (out of scope)")
         self.project = project
         self.weight = nn.Parameter(torch.zeros(1))
+        self.prev_noise = None
+        self.mesh_fn = None
+        self.vert_noise = None
+
+    def projection_inputs(self, noise, mesh_path):
+        """The reference's bookkeeping around the rendering (:383-386, :423-425, :442-452): (verts, faces) of the mesh at the level of
+        the map's size, this module's vertex noise (V,) and the map (1, S, S) that fills what the mesh does not cover."""
+        if noise.dim() != 4 or noise.shape[1] != 1 or noise.shape[2] != noise.shape[3]:
+            raise RuntimeError(f"project_noise expects a (1, 1, S, S) noise map, got {tuple(noise.shape)}")
+        if noise.shape[0] != 1:
+            raise AssertionError(f"project_noise assumes batch size 1 at inference, got a noise map of batch {noise.shape[0]}")
+        self.mesh_fn = mesh_path
+        verts, faces = mesh_utils.load_mesh(mesh_path, device=noise.device).for_image(noise.shape[2])
+        if self.vert_noise is None or self.vert_noise.shape[0] != verts.shape[0]:
+            self.vert_noise = torch.empty(verts.shape[0], 1).normal_()[:, 0].to(verts.device)      # (V, 1) on the CPU, as the reference draws
+        if self.prev_noise is None:
+            self.prev_noise = noise
+        return verts, faces, self.vert_noise, self.prev_noise.reshape(1, noise.shape[2], noise.shape[3])
+
+    def project_noise(self, noise, transform, mesh_path=None):
+        """The reference's project_noise (:423-457): (1, 1, S, S)."""
+        verts, faces, vert_noise, prev = self.projection_inputs(noise, mesh_path)
+        maps, _ = mesh_utils.project_vertex_noise(verts, faces, vert_noise, mesh_utils.noise_camera(transform), noise.shape[2], prev=prev)
+        return maps.unsqueeze(0)
 
     def forward(self, image, noise=None, transform=None, mesh_path=None):
         if noise is None:
             B, _, H, W = image.shape
             noise = image.new_empty(B, 1, H, W).normal_()
+        elif self.project:
+            noise = self.project_noise(noise, transform, mesh_path=mesh_path)
         return noise_bias_act(image, noise, self.weight, None, negative_slope=1.0, scale=1.0)
 
 
@@ -1023,6 +1051,8 @@ class Decoder(nn.Module):
         assert isinstance(styles, list), 'wrap latent code with list'
         latent, noise = self.styles_and_noise_forward(styles, noise, inject_index, truncation, truncation_latent,
                                                       input_is_latent, randomize_noise)
+        if self.conv1.noise.project and any(n is not None for n in noise):
+            noise = self._project_noises(features, noise, transform, mesh_path)
         if self._dec2_ok(features, latent, noise, rgbd_in):
             if not self._needs_graph(features, latent):
                 return self._forward_packed(features, latent, noise), (latent if return_latents else None)
@@ -1036,6 +1066,36 @@ class Decoder(nn.Module):
             img = _PackedDecoderFn.apply(self, nz, features, latent, *self.parameters())
             return img, (latent if return_latents else None)
         return self._forward_layers(features, latent, noise, rgbd_in), (latent if return_latents else None)
+
+    def _project_noises(self, features, noise, transform, mesh_path):
+        """What the reference's NoiseInjection.forward does layer by layer for `project_noise` (:459-466), done first: every given map is
+        replaced by its module's projection (NoiseInjection.project_noise).  The maps of one size share one rasterisation
+        (e3dge_noise_project takes up to four vertex fields): one launch per size, five for the nine maps of a 1024 decoder.  The
+        packed and the layer paths then take the list as any other `noise`."""
+        for value, name in ((transform, "transform"), (mesh_path, "mesh_path")):
+            if value is None:
+                raise ValueError(f"a project_noise decoder called with noise needs `{name}` (the frame's camera poses / the surface mesh); "
+                                 f"got {name}=None")
+        if features.shape[0] != 1:
+            raise AssertionError(f"project_noise assumes batch size 1 at inference, got batch {features.shape[0]}")
+        modules = [self.conv1.noise] + [c.noise for c in self.convs]
+        camera = mesh_utils.noise_camera(transform)
+        groups = {}                                                              # size -> [(index, verts, faces, vert_noise, prev)]
+        for i, (m, n) in enumerate(zip(modules, noise)):                         # in layer order: the order the reference draws in
+            if n is not None:
+                groups.setdefault(n.shape[2], []).append((i,) + m.projection_inputs(n, mesh_path))
+        out = list(noise)
+        for size, members in groups.items():
+            for c0 in range(0, len(members), _lib.NOISE_PROJECT_MAX_MAPS):
+                part = members[c0:c0 + _lib.NOISE_PROJECT_MAX_MAPS]
+                _, verts, faces, _, _ = part[0]
+                if any(p[3].shape != part[0][3].shape for p in part):             # a module that kept the noise of another mesh
+                    raise RuntimeError("project_noise: the modules of one size hold vertex noise of different meshes")
+                maps, _ = mesh_utils.project_vertex_noise(verts, faces, torch.stack([p[3] for p in part]), camera, size,
+                                                          prev=torch.cat([p[4] for p in part]))
+                for k, p in enumerate(part):
+                    out[p[0]] = maps[k].reshape(1, 1, size, size)
+        return out
 
     def _forward_layers(self, features, latent, noise, rgbd_in):
         """The layer-by-layer forward (reference :764-792): fused planar kernels without a graph, weight modulation + library
@@ -1128,8 +1188,6 @@ class Generator(nn.Module):
         """The base class entry (reference :934-1020) -- what the surface-extraction generator `surface_g_ema` is called
         through (train_setup.py:112-126): tuple (rgb or None, thumb [, xyz] [, sdf] [, eikonal_term] [, mask]).
         [`diable_decoder_inference` is the reference's spelling.]"""
-        if project_noise:
-            raise NotImplementedError("project_noise is out of scope")
         # as the reference: no renderer graph when its weights are frozen
         with torch.set_grad_enabled(torch.is_grad_enabled() and self.is_train and self.train_renderer):
             latent = self.styles_and_noise_forward(styles, inject_index, truncation, truncation_latent, input_is_latent)
@@ -1140,7 +1198,7 @@ class Generator(nn.Module):
         rgb = decoder_latent = None
         if self.full_pipeline and not diable_decoder_inference:
             decoder_latent = latent if pred_decoder_latents is None else pred_decoder_latents
-            rgb, decoder_latent = self.decoder(sample_batch['features'], decoder_latent, transform=None,
+            rgb, decoder_latent = self.decoder(sample_batch['features'], decoder_latent, transform=cam_poses if project_noise else None,
                                                return_latents=return_latents, inject_index=inject_index, truncation=truncation,
                                                truncation_latent=truncation_latent, noise=noise,
                                                input_is_latent=input_is_latent, randomize_noise=randomize_noise,
@@ -1169,8 +1227,6 @@ class G_pred_latents(Generator):
                 mesh_with_shading=True, mesh_path=None, conditions=None, sample_mode=False, geometry_sample=None,
                 sample_with_decoder=False, sample_with_renderer=False, return_surface_eikonal=False,
                 renderer_only=False, inference_mode=False, sample_without_grad=False, **kwargs):
-        if project_noise:
-            raise NotImplementedError("project_noise is out of scope")
         if self.full_pipeline:
             assert type(styles) in [list, tuple], 'reformat latent to list/tuple'
             if not input_is_latent:
@@ -1202,7 +1258,7 @@ class G_pred_latents(Generator):
                 elif not isinstance(decoder_latent, list):
                     decoder_latent = [decoder_latent]
                 gen_imgs, decoder_latent = self.decoder(
-                    render_out['features'], decoder_latent, transform=None, return_latents=return_latents,
+                    render_out['features'], decoder_latent, transform=cam_poses if project_noise else None, return_latents=return_latents,
                     inject_index=inject_index, truncation=truncation, truncation_latent=truncation_latent, noise=noise,
                     input_is_latent=input_is_latent, randomize_noise=randomize_noise, mesh_path=mesh_path,
                     conditions=conditions)

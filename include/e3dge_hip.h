@@ -782,6 +782,54 @@ int e3dge_vertex_normals(float* normals, const float* verts, const int32_t* face
 int64_t e3dge_mesh_render_ws_bytes(int64_t n_verts, int64_t n_faces, int image_size, int64_t bin_capacity);
 int e3dge_mesh_render(const E3dgeMeshRenderArgs* args, e3dge_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------------------------
+ * View-consistent decoder noise (csrc/mesh_render.hip): midpoint subdivision of a triangle mesh and the projection of per-vertex noise
+ * into the decoder's noise maps -- what the reference's NoiseInjection.project_noise (project/models/stylesdf_model.py:365-466) gets from
+ * trimesh.remesh.subdivide and from pytorch3d through create_depth_mesh_renderer (mesh_utils.py:130-219: faces_per_pixel = 17, blur_radius
+ * 1e-6, ambient 1, no diffuse or specular term, BlendParams defaults).  Additions to ABI 16.  No allocation, no synchronisation.
+ *
+ * e3dge_mesh_subdivide  one level.  An edge is the unordered pair (lo, hi) of a face side; the E distinct edges are ranked by their key
+ *                       lo V + hi (int64) in ascending order.  edge_keys (E) int64: the distinct keys, ascending; side_rank (F, 3) int32:
+ *                       the rank of the key of side (a, b), (b, c), (c, a) of face (a, b, c) -- ranking 3 F keys is the caller's (a sort).
+ *                       out_verts (V + E, 3): vertex i < V is copied; vertex V + rank is 0.5f * (v_lo + v_hi) in float32 (the float64 mean
+ *                       rounded to float32).  out_faces (4 F, 3) int32: face f = (a, b, c) becomes 4f = (a, m_ab, m_ca), 4f + 1 = (m_ab, b,
+ *                       m_bc), 4f + 2 = (m_ca, m_bc, c), 4f + 3 = (m_ab, m_bc, m_ca), m_xy = V + rank of side (x, y): the winding is kept.
+ *                       No special cases: a face with a repeated index follows the same rule (its side (a, a) is an edge with a "midpoint"
+ *                       at v_a).  Face indices must lie in [0, V) (they are copied, not followed; a key that is no vertex pair gives a
+ *                       vertex at the origin).  V + E and 4 F must stay below 2^31.  Vertex order differs from trimesh's, which numbers the
+ *                       edges in the order numpy's unique of the sorted pairs returns them -- the same ascending (lo, hi) order -- but
+ *                       nothing here depends on it.
+ * e3dge_noise_project   vert_noise (n_maps, V) float32, 1 <= n_maps <= 4: scalar fields over the vertices (the maps of one size share one
+ *                       rasterisation).  Camera, pixel centres, the candidate test, coverage with the blur rule, float64 NDC / barycentrics /
+ *                       depth, the K-list ordered by (z, face index) and the blend with m, w_k, delta are e3dge_mesh_render's, word for word,
+ *                       with K = E3DGE_NOISE_PROJECT_FACES_PER_PIXEL, colour_k = sum b'_k noise_k and background 1:
+ *                         value = (sum w_k colour_k + delta) / (sum w_k + delta).
+ *                       valid (S, S) uint8 = 1 where the largest kept z is > 0 (the reference's zbuf.max(-1) > 0: some fragment was kept);
+ *                       out (n_maps, S, S) = value where valid, prev (n_maps, S, S) elsewhere (out may not alias prev).
+ *                       Binning, status and the overflow protocol are e3dge_mesh_render's (outputs NOT written when status[0] >
+ *                       status[1]); faces x tiles is not bounded here -- the scan carries 64 bits and `entries needed` saturates at
+ *                       2^31 - 1, above every accepted bin_capacity (< 2^31 - 1).  ws: e3dge_noise_project_ws_bytes(V, F, S, bin_capacity)
+ *                       bytes (-1: bad sizes).
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_NOISE_PROJECT_FACES_PER_PIXEL 17
+#define E3DGE_NOISE_PROJECT_MAX_MAPS 4
+typedef struct E3dgeNoiseProjectArgs {
+    const float* verts; const int32_t* faces; const float* vert_noise; const float* prev;
+    int64_t n_verts, n_faces;
+    float camera[12];
+    float tan_half_fov, znear, zfar;
+    float blur_radius, sigma, gamma;
+    int32_t image_size, n_maps;
+    float* out; uint8_t* valid;
+    int32_t* status;
+    void* ws;
+    int64_t ws_bytes, bin_capacity;
+} E3dgeNoiseProjectArgs;
+int e3dge_mesh_subdivide(float* out_verts, int32_t* out_faces, const float* verts, const int32_t* faces, const int64_t* edge_keys,
+                         const int32_t* side_rank, int64_t n_verts, int64_t n_faces, int64_t n_edges, e3dge_stream_t stream);
+int64_t e3dge_noise_project_ws_bytes(int64_t n_verts, int64_t n_faces, int image_size, int64_t bin_capacity);
+int e3dge_noise_project(const E3dgeNoiseProjectArgs* args, e3dge_stream_t stream);
+
 /* Layout self-test: runs a 32x32xK fp32-MFMA product with the fragment conventions the render kernel
  * relies on and writes it to c (32*32 floats, row-major) for the caller to compare with a @ b^T.
  * a: (32, k) row-major, b: (32, k) row-major, k multiple of 8, k <= 256. */
