@@ -20,7 +20,45 @@ _c_float_p = ctypes.c_void_p     # device pointers travel as integers
 _i32, _i64, _f32, _vp = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
 
-class RenderArgs(ctypes.Structure):
+class _Args(ctypes.Structure):
+    """Base of the argument-struct mirrors: a pointer field takes a tensor (its data_ptr() is stored) as well as an address or None, in
+    the constructor and on later assignment.  The struct remembers the distinct devices of the tensors it was given (`devices`; a
+    nested struct such as `plan.up[i]` reports to the outermost one), so that launch() can take the launch device from it and refuse a
+    struct that mixes devices.  The tensors themselves are not kept alive, exactly as with data_ptr()."""
+
+    def __init__(self, *values, **fields):
+        if values:                                  # positional, in field order, as ctypes.Structure takes them
+            fields = dict(zip((f[0] for f in self._fields_), values), **fields)
+        seen = None
+        for name, value in fields.items():          # (one loop here, not one __setattr__ call per field: a launch wrapper's host time)
+            kind = value.__class__
+            if kind is not int and kind is not float and value is not None and hasattr(value, "data_ptr"):
+                if value.device != seen:
+                    seen = self._note(value.device)
+                value = value.data_ptr()
+            _set_field(self, name, value)
+
+    def __setattr__(self, name, value):
+        kind = value.__class__
+        if kind is not int and kind is not float and value is not None and hasattr(value, "data_ptr"):
+            self._note(value.device)
+            value = value.data_ptr()
+        _set_field(self, name, value)
+
+    def _note(self, dev):
+        root = self
+        while root._b_base_ is not None:
+            root = root._b_base_
+        seen = root.__dict__.setdefault("devices", [])
+        if dev not in seen:
+            seen.append(dev)
+        return dev
+
+
+_set_field = ctypes.Structure.__setattr__
+
+
+class RenderArgs(_Args):
     """Mirror of struct E3dgeRenderArgs (include/e3dge_hip.h)."""
     _fields_ = [
         ("packed", _vp), ("film", _vp), ("c2w", _vp), ("focal", _vp), ("near", _vp), ("far", _vp),
@@ -34,7 +72,7 @@ class RenderArgs(ctypes.Structure):
     ]
 
 
-class RenderBwdArgs(ctypes.Structure):
+class RenderBwdArgs(_Args):
     """Mirror of struct E3dgeRenderBwdArgs (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("packed", "film", "args", "sdf", "dists", "points", "weights", "t_vals", "near", "far",
                                    "wg", "wb", "d_rgb_map", "d_feat_map", "d_xyz_map", "d_depth_map", "d_sdf", "tang", "rsave",
@@ -45,28 +83,28 @@ class RenderBwdArgs(ctypes.Structure):
         (n, _vp) for n in ("d_lin", "lin_amax", "d_sigmoid_beta")]
 
 
-class SirenBwdArgs(ctypes.Structure):
+class SirenBwdArgs(_Args):
     """Mirror of struct E3dgeSirenBwdArgs (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("packed", "film", "args", "d_feat", "d_rgb", "d_sdf", "tang", "rsave", "wg", "wb", "tex_alpha")] + [
         ("batch", _i32), ("precision", _i32), ("n_pts", _i64), ("box_scale", _f32)] + [
         (n, _vp) for n in ("partials", "dfilm", "dstyles", "d_pts", "d_tex_alpha", "d_tex_beta", "d_lin", "lin_amax")]
 
 
-class SirenWgradArgs(ctypes.Structure):
+class SirenWgradArgs(_Args):
     """Mirror of struct E3dgeSirenWgradArgs (include/e3dge_hip.h, ABI 16)."""
     _fields_ = [(n, _vp) for n in ("args", "d_lin", "lin_amax", "d_sdf", "d_rgb", "pts", "viewdirs", "d_w", "d_w_view_dirs", "d_w_first",
                                    "d_w_sigma", "d_b_sigma", "d_w_rgb", "d_b_rgb", "ws")] + [
         ("ws_floats", _i64), ("n_pts", _i64), ("batch", _i32), ("samples", _i32), ("precision", _i32), ("box_scale", _f32)]
 
 
-class ModconvArgs(ctypes.Structure):
+class ModconvArgs(_Args):
     """Mirror of struct E3dgeModconvArgs (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("x", "wimg", "style", "demod", "in_amax", "s_amax", "noise", "noise_w", "bias", "y", "out_amax")] + [
         ("negative_slope", _f32), ("act_scale", _f32)] + [(n, _i32) for n in ("act", "upsample", "batch", "ci", "co", "height", "width",
                                                                                 "noise_batch")]
 
 
-class ModLayer(ctypes.Structure):
+class ModLayer(_Args):
     """Mirror of struct E3dgeModLayer (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("mod_weight", "mod_bias", "wsq", "style_out", "demod_out", "s_amax_out")] + [
         (n, _i32) for n in ("ci", "co", "latent_index", "row_start", "co_start")] + [("lin_scale", _f32), ("lr_mul", _f32)]
@@ -75,18 +113,18 @@ class ModLayer(ctypes.Structure):
 DEC2_MAX_UP = 6                 # E3DGE_DEC2_MAX_UP
 
 
-class Dec2Conv(ctypes.Structure):
+class Dec2Conv(_Args):
     """Mirror of struct E3dgeDec2Conv (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("wpre", "style", "demod", "wimg", "noise", "noise_w", "noise_amax", "bias")] + [
         ("bias_amax", _f32), ("ci", _i32), ("co", _i32), ("noise_batch", _i32)]
 
 
-class Dec2Rgb(ctypes.Structure):
+class Dec2Rgb(_Args):
     """Mirror of struct E3dgeDec2Rgb (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("weight", "style", "bias", "wm", "out")] + [("scale", _f32), ("ci", _i32)]
 
 
-class Dec2Plan(ctypes.Structure):
+class Dec2Plan(_Args):
     """Mirror of struct E3dgeDec2Plan (include/e3dge_hip.h)."""
     _fields_ = [("batch", _i32), ("n_up", _i32), ("in_res", _i32), ("in_ch", _i32),
                 ("features", _vp), ("skip_in", _vp), ("mod_table", _vp), ("latent", _vp),
@@ -99,12 +137,12 @@ class Dec2Plan(ctypes.Structure):
                 ("fir_blur_1d", _f32 * 4), ("fir_blur_separable", _i32), ("save_for_backward", _i32)]
 
 
-class Dec2BwdConv(ctypes.Structure):
+class Dec2BwdConv(_Args):
     """Mirror of struct E3dgeDec2BwdConv (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("wpre_t", "wcol", "wimg_t")]
 
 
-class Dec2BwdPlan(ctypes.Structure):
+class Dec2BwdPlan(_Args):
     """Mirror of struct E3dgeDec2BwdPlan (include/e3dge_hip.h)."""
     _fields_ = [("d_img", _vp), ("d_features", _vp), ("conv1", Dec2BwdConv), ("up", Dec2BwdConv * DEC2_MAX_UP),
                 ("conv", Dec2BwdConv * DEC2_MAX_UP), ("gact", _vp * (2 * DEC2_MAX_UP + 2)), ("pbuf", _vp),
@@ -113,7 +151,7 @@ class Dec2BwdPlan(ctypes.Structure):
                 ("d_latent", _vp), ("ds_part", _vp), ("ds_part_floats", _i64)]
 
 
-class WsLinear(ctypes.Structure):
+class WsLinear(_Args):
     """Mirror of struct E3dgeWsLinear (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("wimg", "x", "amax_in", "bias", "colw", "m", "r1", "r2", "y", "amax_out")] + [("n_rows", _i64)] + [
         (n, _i32) for n in ("ld_x", "off_x", "ld_m", "off_m", "ld_r1", "off_r1", "ld_r2", "off_r2", "ld_y", "off_y", "pre_relu", "post")] + [
@@ -121,7 +159,7 @@ class WsLinear(ctypes.Structure):
         ("reserved", _i32)]
 
 
-class Wgrad(ctypes.Structure):
+class Wgrad(_Args):
     """Mirror of struct E3dgeWgrad (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("a", "amax_a", "b", "amax_b", "c", "ws")] + [("ws_floats", _i64), ("n_rows", _i64)] + [
         (n, _i32) for n in ("lda", "off_a", "m", "ldb", "off_b", "n", "ldc", "relu_b")] + [(n, _vp) for n in ("xcol", "colsum", "ccol")] + [
@@ -131,7 +169,7 @@ class Wgrad(ctypes.Structure):
 MESH_MAX_FACES_PER_PIXEL = 8    # E3DGE_MESH_MAX_FACES_PER_PIXEL
 
 
-class MeshRenderArgs(ctypes.Structure):
+class MeshRenderArgs(_Args):
     """Mirror of struct E3dgeMeshRenderArgs (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("verts", "faces", "normals", "colors")] + [("n_verts", _i64), ("n_faces", _i64), ("camera", _f32 * 12),
                ("tan_half_fov", _f32), ("znear", _f32), ("zfar", _f32)] + [
@@ -143,18 +181,16 @@ class MeshRenderArgs(ctypes.Structure):
 NOISE_PROJECT_FACES_PER_PIXEL, NOISE_PROJECT_MAX_MAPS = 17, 4    # E3DGE_NOISE_PROJECT_FACES_PER_PIXEL, E3DGE_NOISE_PROJECT_MAX_MAPS
 
 
-class NoiseProjectArgs(ctypes.Structure):
+class NoiseProjectArgs(_Args):
     """Mirror of struct E3dgeNoiseProjectArgs (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("verts", "faces", "vert_noise", "prev")] + [("n_verts", _i64), ("n_faces", _i64), ("camera", _f32 * 12)] + [
         (n, _f32) for n in ("tan_half_fov", "znear", "zfar", "blur_radius", "sigma", "gamma")] + [("image_size", _i32), ("n_maps", _i32)] + [
         (n, _vp) for n in ("out", "valid", "status", "ws")] + [("ws_bytes", _i64), ("bin_capacity", _i64)]
 
-# include/e3dge_hip_experimental.h: -DE3DGE_EXPERIMENTAL builds (tools/build_variant.sh) carry one more precision mode; no extra symbols
-EXPERIMENTAL_SIGNATURES = {}
-
 
 def has_experimental():
-    """Was the loaded library built with -DE3DGE_EXPERIMENTAL (mode f16x3_v1; f16x3_g2 is in every build)?"""
+    """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
+    precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
     return bool(load().e3dge_build_flags() & 1)
 
 
@@ -287,10 +323,6 @@ def load():
             fn = getattr(lib, name)     # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in EXPERIMENTAL_SIGNATURES.items():      # -DE3DGE_EXPERIMENTAL builds only
-            fn = getattr(lib, name, None)
-            if fn is not None:
-                fn.restype, fn.argtypes = res, args
         got = lib.e3dge_abi_version()
         if got != ABI_VERSION:
             raise RuntimeError(f"libe3dge_hip.so ABI {got} != expected {ABI_VERSION}; rebuild")
@@ -310,9 +342,45 @@ def ptr(t):
 
 
 def stream_of(t):
-    """The current HIP stream of the tensor's device, as the void* the C-ABI wants."""
+    """The current HIP stream of the tensor's device (or of a device), as the void* the C-ABI wants."""
     import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
+    return torch.cuda.current_stream(getattr(t, "device", t)).cuda_stream
+
+
+def launch(name, *args):
+    """Queue the C-ABI entry point `name`: the one way the package launches a kernel.  A tensor argument goes as its data_ptr(), None
+    as NULL, an argument struct (_Args) by reference, numbers as they are (host addresses and `data_ptr() + offset` are plain ints).  The
+    launch device is that of the first tensor -- an argument, or a field of an argument struct --; every other tensor must live there too
+    (a pointer from another GPU would fault inside the kernel, so it raises here, before anything is queued).  The call runs under
+    on_device(dev) with dev's current stream appended as the last argument, and a non-zero return raises with `name` and the library's
+    message.  Entry points that take no stream (size queries, tables, e3dge_last_error) are plain calls on load()."""
+    fn = getattr(load(), name)
+    dev, out = None, []
+    for a in args:
+        kind = a.__class__
+        if kind is int or kind is float or a is None:
+            out.append(a)
+            continue
+        if hasattr(a, "data_ptr"):
+            devices = (a.device,)
+            out.append(a.data_ptr())
+        elif isinstance(a, _Args):
+            devices = a.__dict__.get("devices", ())
+            out.append(ctypes.byref(a))
+        else:                    # bool, numpy scalars, ctypes arrays: ctypes converts them by the declared argtypes
+            out.append(a)
+            continue
+        for d in devices:
+            if dev is None:
+                dev = d
+            elif d != dev:
+                raise RuntimeError(f"{name}: arguments live on {dev} and on {d}; every tensor of a launch must be on the launch device")
+    if dev is None:
+        raise RuntimeError(f"{name}: no tensor argument to take the launch device from")
+    with on_device(dev):
+        rc = fn(*out, stream_of(dev))
+    if rc != 0:
+        check(rc, name)
 
 
 def params_of(module):

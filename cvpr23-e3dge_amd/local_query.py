@@ -14,7 +14,6 @@ texture head is the fused HIP kernel of round 1.  Fuse_sft_MLP (590 k MAC per po
 256x256 linears) runs as nine weight-stationary split-f16 launches (e3dge_ws_linear, round 3) when no autograd graph is
 needed, as torch modules (library GEMMs) otherwise.  The hourglass image filters that PRODUCE the feature maps stay outside the
 path."""
-import ctypes
 import os
 
 import torch
@@ -77,10 +76,7 @@ def query_feature_map(pts, calibs, fmap=None, out=None, col_off=0, mask_out=None
     else:
         mask, m_ptr, m_ld, m_off = mask_out[..., mask_off], mask_out, mask_out.shape[-1], mask_off
     proj = torch.empty((B, N, 3), device=dev, dtype=torch.float32) if want_proj else None
-    with torch.cuda.device(dev):
-        rc = _lib.load().e3dge_local_query(_lib.ptr(out), ld, col_off, _lib.ptr(m_ptr), m_ld, m_off, _lib.ptr(proj), _lib.ptr(p),
-                                           _lib.ptr(c), _lib.ptr(fm), B, N, C, h, w, _lib.stream_of(p))
-    _lib.check(rc, "e3dge_local_query")
+    _lib.launch("e3dge_local_query", out, ld, col_off, m_ptr, m_ld, m_off, proj, p, c, fm, B, N, C, h, w)
     feats = None if fmap is None else out[..., col_off:col_off + C]
     return feats, mask, proj
 
@@ -112,10 +108,7 @@ class _GatherFn(torch.autograd.Function):
         d_p = torch.empty((B, N, 3), device=dev, dtype=torch.float32) if need_p else None
         p = pts.detach().contiguous()
         c = calibs.detach()[:, :3, :4].contiguous()
-        with torch.cuda.device(dev):
-            rc = _lib.load().e3dge_local_query_bwd(_lib.ptr(d_fm), _lib.ptr(d_p), _lib.ptr(g), C, 0, _lib.ptr(p), _lib.ptr(c), _lib.ptr(fm),
-                                                   B, N, C, h, w, _lib.stream_of(g))
-        _lib.check(rc, "e3dge_local_query_bwd")
+        _lib.launch("e3dge_local_query_bwd", d_fm, d_p, g, C, 0, p, c, fm, B, N, C, h, w)
         return d_p, None, (d_fm.permute(0, 3, 1, 2) if need_f else None)
 
 
@@ -155,7 +148,6 @@ class _EncInFn(torch.autograd.Function):
         ld = g.shape[-1]
         p = pts.detach().contiguous()
         out = []
-        lib = _lib.load()
         sort_ref = os.environ.get("E3DGE_GATHER_BWD_SORT", "1") != "0"
         # (the points are samples along the QUERY view's rays: in that view's map a ray is one pixel and the kernel's run accumulation merges
         # its samples; in the reference view's map every sample lands on its own pixel -- those are walked in pixel order instead)
@@ -168,16 +160,12 @@ class _EncInFn(torch.autograd.Function):
             d_fm = torch.zeros((B, h, w, C), device=g.device, dtype=torch.float32)
             fm = d_fm                                            # (fmap_nhwc is only read for d pts, which this node does not produce; any valid pointer)
             c = calibs.detach()[:, :3, :4].contiguous()
-            with torch.cuda.device(g.device):
-                if other_view and sort_ref and B * N < 2 ** 31:
-                    n_ws = lib.e3dge_local_query_sort_ws_ints(B, N, h, w)
-                    ws = torch.empty(n_ws, device=g.device, dtype=torch.int32)
-                    rc = lib.e3dge_local_query_bwd_sorted(_lib.ptr(d_fm), None, _lib.ptr(g), ld, off, _lib.ptr(p), _lib.ptr(c), _lib.ptr(fm),
-                                                          B, N, C, h, w, _lib.ptr(ws), n_ws, _lib.stream_of(g))
-                else:
-                    rc = lib.e3dge_local_query_bwd(_lib.ptr(d_fm), None, _lib.ptr(g), ld, off, _lib.ptr(p), _lib.ptr(c), _lib.ptr(fm),
-                                                   B, N, C, h, w, _lib.stream_of(g))
-            _lib.check(rc, "e3dge_local_query_bwd")
+            if other_view and sort_ref and B * N < 2 ** 31:
+                n_ws = _lib.load().e3dge_local_query_sort_ws_ints(B, N, h, w)
+                ws = torch.empty(n_ws, device=g.device, dtype=torch.int32)
+                _lib.launch("e3dge_local_query_bwd_sorted", d_fm, None, g, ld, off, p, c, fm, B, N, C, h, w, ws, n_ws)
+            else:
+                _lib.launch("e3dge_local_query_bwd", d_fm, None, g, ld, off, p, c, fm, B, N, C, h, w)
             out.append(d_fm.permute(0, 3, 1, 2))
         return None, None, None, None, out[0], out[1]
 
@@ -193,9 +181,7 @@ def pos_encoding(pts, n_freqs=7, out=None, col_off=0):
     if own:
         out = torch.empty((p.shape[0], width), device=p.device, dtype=torch.float32)
         col_off = 0
-    with torch.cuda.device(p.device):
-        rc = _lib.load().e3dge_pos_encoding(_lib.ptr(out), out.shape[-1], col_off, _lib.ptr(p), p.shape[0], n_freqs, _lib.stream_of(p))
-    _lib.check(rc, "e3dge_pos_encoding")
+    _lib.launch("e3dge_pos_encoding", out, out.shape[-1], col_off, p, p.shape[0], n_freqs)
     return out.reshape(*lead, width) if own else out
 
 
@@ -220,6 +206,14 @@ class _ResnetBlockFCLib(nn.Module):
         net = self.fc_0(torch.relu(x))
         dx = self.fc_1(torch.relu(net))
         return (self.shortcut(x) if self.shortcut is not None else x) + dx
+
+
+def _ws_image(w):
+    """The packed image (e3dge_ws_pack) of one 256 x 256 weight block."""
+    w = w.detach().contiguous()
+    t = torch.empty(_lib.load().e3dge_ws_image_bytes(1), dtype=torch.uint8, device=w.device)
+    _lib.launch("e3dge_ws_pack", t, w, 1)
+    return t
 
 
 class Fuse_sft_MLP(nn.Module):
@@ -292,20 +286,13 @@ class Fuse_sft_MLP(nn.Module):
     def _images(self, device):
         """Packed weight images (e3dge_ws_pack) of the nine 256 x 256 blocks, bias / mask-column vectors; rebuilt when a
         parameter changes (_lib.cached)."""
-        return _lib.cached(self, 'images', _lib.params_of(self), lambda: self._build_images(device), (str(device),))
+        return _lib.cached(self, 'images', _lib.params_of(self), self._build_images, (str(device),))
 
-    def _build_images(self, device):
-        lib = _lib.load()
+    def _build_images(self):
         enc, n_in = self.encode_enc, self.encode_enc.fc_0.in_features
         has_col = n_in == 513
         b_off = 257 if has_col else 256                       # first column of the 3D-projected (dec) block
-
-        def img(w):
-            w = w.detach().contiguous()
-            t = torch.empty(lib.e3dge_ws_image_bytes(1), dtype=torch.uint8, device=device)
-            with torch.cuda.device(device):
-                _lib.check(lib.e3dge_ws_pack(_lib.ptr(t), _lib.ptr(w), 1, _lib.stream_of(w)), "e3dge_ws_pack")
-            return t
+        img = _ws_image
         f0, sc = enc.fc_0.weight, enc.shortcut.weight
         return dict(b_off=b_off, has_col=has_col,
                     f0a=img(f0[:, :256]), f0b=img(f0[:, b_off:]), f1=img(enc.fc_1.weight), sa=img(sc[:, :256]), sb=img(sc[:, b_off:]),
@@ -320,15 +307,8 @@ class Fuse_sft_MLP(nn.Module):
         """Packed images of the TRANSPOSED 256 x 256 blocks (d input = d output @ W is the layer of W^T): built on the first backward."""
         I = self._images(device)
         if 'sc2_t' not in I:
-            lib = _lib.load()
             enc, b_off = self.encode_enc, I['b_off']
-
-            def img_t(w):
-                w = w.detach().t().contiguous()
-                t = torch.empty(lib.e3dge_ws_image_bytes(1), dtype=torch.uint8, device=device)
-                with torch.cuda.device(device):
-                    _lib.check(lib.e3dge_ws_pack(_lib.ptr(t), _lib.ptr(w), 1, _lib.stream_of(w)), "e3dge_ws_pack")
-                return t
+            img_t = lambda w: _ws_image(w.t())
             f0, sc = enc.fc_0.weight, enc.shortcut.weight
             I.update(sc2_t=img_t(self.scale[2].weight), sh2_t=img_t(self.shift[2].weight), sc1_t=img_t(self.scale[0].weight),
                      sh1_t=img_t(self.shift[0].weight), f1_t=img_t(enc.fc_1.weight), sa_t=img_t(sc[:, :256]), sb_t=img_t(sc[:, b_off:]),
@@ -344,8 +324,6 @@ class Fuse_sft_MLP(nn.Module):
         dev = g.device
         ld = x.shape[1]
         I = self._images_t(dev)
-        lib = _lib.load()
-        st = _lib.stream_of(g)
         f32 = dict(device=dev, dtype=torch.float32)
         dz1, dz2, de, dnet = (torch.empty((N, 256), **f32) for _ in range(4))
         dx = torch.empty((N, ld), **f32) if need_x else None
@@ -354,36 +332,34 @@ class Fuse_sft_MLP(nn.Module):
         def lin(wimg, xin, am_in, y, ld_x=256, ld_y=256, off_y=0, post=0, sl=0.0, r1=None, r1_ld=256, r1_off=0, r2=None, r2_ld=256, r2_off=0,
                 xmul=None, amax_out=None, x_scale=1.0):
             a = _lib.WsLinear()
-            a.wimg, a.x, a.amax_in, a.y, a.amax_out = _lib.ptr(wimg), _lib.ptr(xin), _lib.ptr(am_in), _lib.ptr(y), _lib.ptr(amax_out)
-            a.r1, a.r2 = _lib.ptr(r1), _lib.ptr(r2)
+            a.wimg, a.x, a.amax_in, a.y, a.amax_out = wimg, xin, am_in, y, amax_out
+            a.r1, a.r2 = r1, r2
             a.n_rows = N
             a.ld_x, a.off_x, a.ld_y, a.off_y = ld_x, 0, ld_y, off_y
             a.ld_r1, a.off_r1, a.ld_r2, a.off_r2, a.ld_m, a.off_m = r1_ld, r1_off, r2_ld, r2_off, 1, 0
             a.post, a.slope, a.w_fuse, a.x_scale = post, sl, w, x_scale
             if xmul is not None:
-                a.xmul, a.amax_xmul, a.ld_xmul, a.off_xmul = _lib.ptr(xmul), _lib.ptr(am_x), ld, b_off
-            _lib.check(lib.e3dge_ws_linear(ctypes.byref(a), st), "e3dge_ws_linear")
-        with torch.cuda.device(dev):
-            if ld_g == 256:
-                _lib.check(lib.e3dge_amax(_lib.ptr(am[0]), _lib.ptr(g), g.numel(), st), "e3dge_amax")
-            else:
-                _lib.check(lib.e3dge_amax_rows(_lib.ptr(am[0]), _lib.ptr(g), N, 256, ld_g, st), "e3dge_amax_rows")
-            lin(I['sc2_t'], g, am[0], dz1, ld_x=ld_g, post=3, sl=slope, r1=s1, xmul=x, x_scale=w, amax_out=am[1])
-            lin(I['sh2_t'], g, am[0], dz2, ld_x=ld_g, post=3, sl=slope, r1=t1, x_scale=w, amax_out=am[2])
-            lin(I['sc1_t'], dz1, am[1], de)
-            lin(I['sh1_t'], dz2, am[2], de, r1=de, amax_out=am[3])
-            lin(I['f1_t'], de, am[3], dnet, post=3, sl=0.0, r1=net, amax_out=am[4])
-            if need_x:
-                lin(I['sa_t'], de, am[3], dx, ld_y=ld, off_y=0)
-                lin(I['f0a_t'], dnet, am[4], dx, ld_y=ld, off_y=0, post=3, sl=0.0, r1=x, r1_ld=ld, r1_off=0, r2=dx, r2_ld=ld, r2_off=0)
-                lin(I['sb_t'], de, am[3], dx, ld_y=ld, off_y=b_off, post=4, r1=g, r1_ld=ld_g, r2=scale)
-                lin(I['f0b_t'], dnet, am[4], dx, ld_y=ld, off_y=b_off, post=3, sl=0.0, r1=x, r1_ld=ld, r1_off=b_off, r2=dx, r2_ld=ld, r2_off=b_off)
-            if need_x and I['has_col'] and not mask_col:
-                dx[:, 256].zero_()
-            if need_x and I['has_col'] and mask_col:
-                # the visibility-mask column (one input column of fc_0 and of the shortcut): two row dot products in one launch
-                _lib.check(lib.e3dge_ws_rowdot2(_lib.ptr(dx), ld, 256, _lib.ptr(de), _lib.ptr(I['scol']), _lib.ptr(dnet), _lib.ptr(I['f0col']),
-                                                _lib.ptr(x), ld, 256, N, st), "e3dge_ws_rowdot2")
+                a.xmul, a.amax_xmul, a.ld_xmul, a.off_xmul = xmul, am_x, ld, b_off
+            _lib.launch("e3dge_ws_linear", a)
+        if ld_g == 256:
+            _lib.launch("e3dge_amax", am[0], g, g.numel())
+        else:
+            _lib.launch("e3dge_amax_rows", am[0], g, N, 256, ld_g)
+        lin(I['sc2_t'], g, am[0], dz1, ld_x=ld_g, post=3, sl=slope, r1=s1, xmul=x, x_scale=w, amax_out=am[1])
+        lin(I['sh2_t'], g, am[0], dz2, ld_x=ld_g, post=3, sl=slope, r1=t1, x_scale=w, amax_out=am[2])
+        lin(I['sc1_t'], dz1, am[1], de)
+        lin(I['sh1_t'], dz2, am[2], de, r1=de, amax_out=am[3])
+        lin(I['f1_t'], de, am[3], dnet, post=3, sl=0.0, r1=net, amax_out=am[4])
+        if need_x:
+            lin(I['sa_t'], de, am[3], dx, ld_y=ld, off_y=0)
+            lin(I['f0a_t'], dnet, am[4], dx, ld_y=ld, off_y=0, post=3, sl=0.0, r1=x, r1_ld=ld, r1_off=0, r2=dx, r2_ld=ld, r2_off=0)
+            lin(I['sb_t'], de, am[3], dx, ld_y=ld, off_y=b_off, post=4, r1=g, r1_ld=ld_g, r2=scale)
+            lin(I['f0b_t'], dnet, am[4], dx, ld_y=ld, off_y=b_off, post=3, sl=0.0, r1=x, r1_ld=ld, r1_off=b_off, r2=dx, r2_ld=ld, r2_off=b_off)
+        if need_x and I['has_col'] and not mask_col:
+            dx[:, 256].zero_()
+        if need_x and I['has_col'] and mask_col:
+            # the visibility-mask column (one input column of fc_0 and of the shortcut): two row dot products in one launch
+            _lib.launch("e3dge_ws_rowdot2", dx, ld, 256, de, I['scol'], dnet, I['f0col'], x, ld, 256, N)
         return dz1, dz2, de, dnet, dx, am
 
     def _fuse_native(self, enc_in, w, out, out_off, keep=None):
@@ -404,40 +380,37 @@ class Fuse_sft_MLP(nn.Module):
             raise RuntimeError("Fuse_sft_MLP.fuse: `out` must be a contiguous (..., ld) buffer")
         if N == 0:
             return out[..., out_off:out_off + 256]
-        lib = _lib.load()
         A, Bf, C = (torch.empty((N, 256), device=dev, dtype=torch.float32) for _ in range(3))
         if keep is not None:
             NET, E, S1, T1 = (torch.empty((N, 256), device=dev, dtype=torch.float32) for _ in range(4))
         else:
             NET, E, S1, T1 = Bf, Bf, A, A
         am = torch.zeros((5, _lib.AMAX_FLOATS), device=dev, dtype=torch.float32)       # x, net, e, h1, h2
-        st = _lib.stream_of(x)
         b_off = I['b_off']
 
         def lin(wimg, xin, ld_x, off_x, amax_in, y, ld_y=256, off_y=0, bias=None, col=None, r1=None, r1_ld=256, r1_off=0, r2=None,
                 pre_relu=False, post=0, amax_out=None):
             a = _lib.WsLinear()
-            a.wimg, a.x, a.amax_in, a.bias = _lib.ptr(wimg), _lib.ptr(xin), _lib.ptr(amax_in), _lib.ptr(bias)
-            a.colw, a.m = (_lib.ptr(col), _lib.ptr(x)) if col is not None else (None, None)
-            a.r1, a.r2, a.y, a.amax_out = _lib.ptr(r1), _lib.ptr(r2), _lib.ptr(y), _lib.ptr(amax_out)
+            a.wimg, a.x, a.amax_in, a.bias = wimg, xin, amax_in, bias
+            a.colw, a.m = (col, x) if col is not None else (None, None)
+            a.r1, a.r2, a.y, a.amax_out = r1, r2, y, amax_out
             a.n_rows = N
             a.ld_x, a.off_x, a.ld_m, a.off_m = ld_x, off_x, ld, 256
             a.ld_r1, a.off_r1, a.ld_r2, a.off_r2, a.ld_y, a.off_y = r1_ld, r1_off, 256, 0, ld_y, off_y
             a.pre_relu, a.post, a.slope, a.w_fuse = int(pre_relu), post, I['slope'], w
-            _lib.check(lib.e3dge_ws_linear(ctypes.byref(a), st), "e3dge_ws_linear")
-        with torch.cuda.device(dev):
-            _lib.check(lib.e3dge_amax(_lib.ptr(am[0]), _lib.ptr(x), x.numel(), st), "e3dge_amax")
-            # ResnetBlockFC: net = fc_0(relu(x)), dx = fc_1(relu(net)), e = shortcut(x) + dx  (K = 513 as two 256-blocks + the mask column)
-            lin(I['f0a'], x, ld, 0, am[0], A, pre_relu=True)
-            lin(I['f0b'], x, ld, b_off, am[0], NET, bias=I['b0'], col=I['f0col'], r1=A, pre_relu=True, amax_out=am[1])
-            lin(I['f1'], NET, 256, 0, am[1], A, bias=I['b1'], pre_relu=True)
-            lin(I['sa'], x, ld, 0, am[0], C)
-            lin(I['sb'], x, ld, b_off, am[0], E, col=I['scol'], r1=C, r2=A, amax_out=am[2])
-            # SFT branches on e, then  dec + w (dec * scale + shift)
-            lin(I['sc1'], E, 256, 0, am[2], S1, bias=I['bsc1'], post=1, amax_out=am[3])
-            lin(I['sc2'], S1, 256, 0, am[3], C, bias=I['bsc2'])
-            lin(I['sh1'], E, 256, 0, am[2], T1, bias=I['bsh1'], post=1, amax_out=am[4])
-            lin(I['sh2'], T1, 256, 0, am[4], o2, ld_y=o2.shape[-1], off_y=out_off, bias=I['bsh2'], r1=x, r1_ld=ld, r1_off=b_off, r2=C, post=2)
+            _lib.launch("e3dge_ws_linear", a)
+        _lib.launch("e3dge_amax", am[0], x, x.numel())
+        # ResnetBlockFC: net = fc_0(relu(x)), dx = fc_1(relu(net)), e = shortcut(x) + dx  (K = 513 as two 256-blocks + the mask column)
+        lin(I['f0a'], x, ld, 0, am[0], A, pre_relu=True)
+        lin(I['f0b'], x, ld, b_off, am[0], NET, bias=I['b0'], col=I['f0col'], r1=A, pre_relu=True, amax_out=am[1])
+        lin(I['f1'], NET, 256, 0, am[1], A, bias=I['b1'], pre_relu=True)
+        lin(I['sa'], x, ld, 0, am[0], C)
+        lin(I['sb'], x, ld, b_off, am[0], E, col=I['scol'], r1=C, r2=A, amax_out=am[2])
+        # SFT branches on e, then  dec + w (dec * scale + shift)
+        lin(I['sc1'], E, 256, 0, am[2], S1, bias=I['bsc1'], post=1, amax_out=am[3])
+        lin(I['sc2'], S1, 256, 0, am[3], C, bias=I['bsc2'])
+        lin(I['sh1'], E, 256, 0, am[2], T1, bias=I['bsh1'], post=1, amax_out=am[4])
+        lin(I['sh2'], T1, 256, 0, am[4], o2, ld_y=o2.shape[-1], off_y=out_off, bias=I['bsh2'], r1=x, r1_ld=ld, r1_off=b_off, r2=C, post=2)
         if keep is not None:
             keep.update(x=x, net=NET, e=E, s1=S1, t1=T1, scale=C, b_off=b_off, slope=I['slope'], am_x=am[0], am=am)
         return out[..., out_off:out_off + 256]

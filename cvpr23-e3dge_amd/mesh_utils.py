@@ -26,7 +26,6 @@ View-consistent decoder noise (NoiseInjection.project_noise, project/models/styl
 The renderer calls align_volume for `return_mesh=True` (volume_renderer.py:1703-1731 of the reference) and returns the aligned
 volume as 'aligned_sdf', and marching_cubes' result as 'mesh_verts' / 'mesh_faces'.  'mesh' comes from marching_cubes_mesh when
 scikit-image and trimesh are installed, otherwise from the HIP result."""
-import ctypes
 import functools
 import os
 
@@ -73,10 +72,7 @@ def align_volume(volume, near=0.88, far=1.12):
         raise RuntimeError(f"align_volume: float32 expected on the GPU, got {volume.dtype}")
     vol = volume.detach().contiguous()
     out = torch.empty_like(vol)
-    with torch.cuda.device(vol.device):
-        rc = _lib.load().e3dge_align_volume(_lib.ptr(out), _lib.ptr(vol), _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(zs),
-                                            _lib.ptr(coef), b, h, w, d, c, _lib.stream_of(vol))
-    _lib.check(rc, "e3dge_align_volume")
+    _lib.launch("e3dge_align_volume", out, vol, xs, ys, zs, coef, b, h, w, d, c)
     return out
 
 
@@ -122,25 +118,20 @@ def marching_cubes(aligned_sdf, scene=True):
     vol = aligned_sdf.detach()[0, ..., 0]                                    # (h, w, d) view: skimage's (x, y, z) = (w, h, d)
     sy, sx, sz = vol.stride()
     dev = vol.device
-    lib = _lib.load()
-    nbytes = lib.e3dge_marching_cubes_ws_bytes(w, h, d)
+    nbytes = _lib.load().e3dge_marching_cubes_ws_bytes(w, h, d)
     if nbytes < 0:
         raise RuntimeError(f"marching_cubes: a {h} x {w} x {d} volume is too large for the 32-bit offsets")
-    with _lib.on_device(dev):
-        stream = _lib.stream_of(vol)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        totals = torch.empty(2, dtype=torch.int32, device=dev)
-        _lib.check(lib.e3dge_marching_cubes_count(_lib.ptr(totals), _lib.ptr(ws), nbytes, _lib.ptr(vol), w, h, d, sx, sy, sz, stream),
-                   "e3dge_marching_cubes_count")
-        nv, nf = totals.tolist()
-        if nv < 0:
-            raise ValueError("Surface level must be within volume data range.")
-        if nv == 0:
-            raise NoSurfaceError('No surface found at the given iso value.')
-        verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-        faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-        _lib.check(lib.e3dge_marching_cubes_emit(_lib.ptr(verts), _lib.ptr(faces), nv, nf, _lib.ptr(ws), nbytes, _lib.ptr(vol), w, h, d,
-                                                 sx, sy, sz, 1 if scene else 0, stream), "e3dge_marching_cubes_emit")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.launch("e3dge_marching_cubes_count", totals, ws, nbytes, vol, w, h, d, sx, sy, sz)
+    nv, nf = totals.tolist()
+    if nv < 0:
+        raise ValueError("Surface level must be within volume data range.")
+    if nv == 0:
+        raise NoSurfaceError('No surface found at the given iso value.')
+    verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    _lib.launch("e3dge_marching_cubes_emit", verts, faces, nv, nf, ws, nbytes, vol, w, h, d, sx, sy, sz, 1 if scene else 0)
     return verts, faces
 
 
@@ -149,7 +140,9 @@ def marching_cubes_tables():
     and edge numbering is in include/e3dge_hip.h."""
     n_tris = np.zeros(256, np.int32)
     tri = np.zeros((256, _lib.MC_MAX_TRIS, 3), np.int32)
-    _lib.check(_lib.load().e3dge_marching_cubes_tables(n_tris.ctypes.data, tri.ctypes.data), "e3dge_marching_cubes_tables")
+    lib = _lib.load()
+    if lib.e3dge_marching_cubes_tables(n_tris.ctypes.data, tri.ctypes.data) != 0:      # (no stream, nothing queued: a plain call)
+        raise RuntimeError("e3dge_marching_cubes_tables: " + lib.e3dge_last_error().decode(errors="replace"))
     return n_tris, tri
 
 
@@ -224,8 +217,7 @@ def depth_mesh(xyz):
     src = xyz.detach().contiguous()
     verts = torch.empty(h * w, 3, dtype=torch.float32, device=src.device)
     faces = torch.empty(2 * (h - 1) * (w - 1), 3, dtype=torch.int32, device=src.device)
-    with _lib.on_device(src.device):
-        _lib.check(_lib.load().e3dge_depth_mesh(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(src), h, w, _lib.stream_of(src)), "e3dge_depth_mesh")
+    _lib.launch("e3dge_depth_mesh", verts, faces, src, h, w)
     return verts, faces
 
 
@@ -254,14 +246,11 @@ def vertex_normals(verts, faces):
     """(V, 3) float32 unit normals: the sum over a vertex's faces of the unit face normal weighted by the face's corner angle at the
     vertex, normalised; (0, 0, 0) for a vertex without faces.  Bit-reproducible (include/e3dge_hip.h, e3dge_vertex_normals)."""
     verts, faces = _mesh_args(verts, faces, "vertex_normals")
-    lib = _lib.load()
     nv, nf = verts.shape[0], faces.shape[0]
-    nbytes = lib.e3dge_vertex_normals_ws_bytes(nv)
+    nbytes = _lib.load().e3dge_vertex_normals_ws_bytes(nv)
     out = torch.empty_like(verts)
-    with _lib.on_device(verts.device):
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=verts.device)
-        _lib.check(lib.e3dge_vertex_normals(_lib.ptr(out), _lib.ptr(verts), _lib.ptr(faces), nv, nf, _lib.ptr(ws), nbytes,
-                                            _lib.stream_of(verts)), "e3dge_vertex_normals")
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=verts.device)
+    _lib.launch("e3dge_vertex_normals", out, verts, faces, nv, nf, ws, nbytes)
     return out
 
 
@@ -365,24 +354,23 @@ class MeshRenderer:
         pix = torch.empty(S, S, K, dtype=torch.int32, device=dev)
         status = torch.zeros(2, dtype=torch.int32, device=dev)
         a = self._args()
-        a.verts, a.faces, a.normals, a.colors = _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(normals), _lib.ptr(colors)
+        a.verts, a.faces, a.normals, a.colors = verts, faces, normals, colors
         a.n_verts, a.n_faces = nv, nf
-        a.image, a.zbuf, a.pix_to_face, a.status = _lib.ptr(image), _lib.ptr(zbuf), _lib.ptr(pix), _lib.ptr(status)
-        with _lib.on_device(dev):
-            for attempt in range(2):
-                cap = min(cap, nf * tiles)
-                nbytes = lib.e3dge_mesh_render_ws_bytes(nv, nf, S, cap)
-                if nbytes < 0:
-                    raise RuntimeError("mesh renderer: " + lib.e3dge_last_error().decode(errors="replace"))
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-                a.ws, a.ws_bytes, a.bin_capacity = _lib.ptr(ws), nbytes, cap
-                _lib.check(lib.e3dge_mesh_render(ctypes.byref(a), _lib.stream_of(verts)), "e3dge_mesh_render")
-                need, _ = status.tolist()
-                if need <= cap:
-                    return image, zbuf, pix
-                if fixed:
-                    break
-                cap = need
+        a.image, a.zbuf, a.pix_to_face, a.status = image, zbuf, pix, status
+        for attempt in range(2):
+            cap = min(cap, nf * tiles)
+            nbytes = lib.e3dge_mesh_render_ws_bytes(nv, nf, S, cap)
+            if nbytes < 0:
+                raise RuntimeError("mesh renderer: " + lib.e3dge_last_error().decode(errors="replace"))
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            a.ws, a.ws_bytes, a.bin_capacity = ws, nbytes, cap
+            _lib.launch("e3dge_mesh_render", a)
+            need, _ = status.tolist()
+            if need <= cap:
+                return image, zbuf, pix
+            if fixed:
+                break
+            cap = need
         raise RuntimeError(f"mesh renderer: the tile lists need {need} entries, bin_capacity is {cap}")
 
     def __call__(self, verts, faces, normals=None, colors=None):
@@ -452,7 +440,7 @@ def pose_to_viewpoint(c2w):
     return float(np.arcsin(np.clip(-R[2, 0], -1.0, 1.0))), float(-np.arctan2(R[2, 1], R[2, 2]))
 
 
-def _subdivide_once(verts, faces, lib):
+def _subdivide_once(verts, faces):
     nv, nf = verts.shape[0], faces.shape[0]
     f = faces.to(torch.int64)
     a, b = f, f.roll(-1, 1)                                                       # sides (a, b), (b, c), (c, a)
@@ -464,8 +452,7 @@ def _subdivide_once(verts, faces, lib):
     rank = rank.to(torch.int32).contiguous()
     out_v = torch.empty(nv + ne, 3, dtype=torch.float32, device=verts.device)
     out_f = torch.empty(4 * nf, 3, dtype=torch.int32, device=verts.device)
-    _lib.check(lib.e3dge_mesh_subdivide(_lib.ptr(out_v), _lib.ptr(out_f), _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(edge_keys), _lib.ptr(rank),
-                                        nv, nf, ne, _lib.stream_of(verts)), "e3dge_mesh_subdivide")
+    _lib.launch("e3dge_mesh_subdivide", out_v, out_f, verts, faces, edge_keys, rank, nv, nf, ne)
     return out_v, out_f
 
 
@@ -476,10 +463,8 @@ def subdivide(verts, faces, levels=1):
     verts, faces = _mesh_args(verts, faces, "subdivide")
     if int(levels) < 0:
         raise ValueError(f"subdivide: levels = {levels}")
-    lib = _lib.load()
-    with _lib.on_device(verts.device):
-        for _ in range(int(levels)):
-            verts, faces = _subdivide_once(verts, faces, lib)
+    for _ in range(int(levels)):
+        verts, faces = _subdivide_once(verts, faces)
     return verts, faces
 
 
@@ -597,23 +582,22 @@ def project_vertex_noise(verts, faces, vert_noise, camera, image_size, prev=None
     a.tan_half_fov, a.znear, a.zfar = camera.tan_half_fov, camera.znear, camera.zfar
     a.blur_radius, a.sigma, a.gamma = 1e-6, MeshRenderer.SIGMA, MeshRenderer.GAMMA
     a.image_size, a.n_maps, a.n_verts, a.n_faces = S, C, nv, nf
-    a.verts, a.faces, a.vert_noise, a.prev = _lib.ptr(verts), _lib.ptr(faces), _lib.ptr(vn), _lib.ptr(prev)
-    a.out, a.valid, a.status = _lib.ptr(out), _lib.ptr(valid), _lib.ptr(status)
-    with _lib.on_device(dev):
-        for attempt in range(2):
-            cap = min(cap, nf * tiles, 2 ** 31 - 2)
-            nbytes = lib.e3dge_noise_project_ws_bytes(nv, nf, S, cap)
-            if nbytes < 0:
-                raise RuntimeError("project_vertex_noise: " + lib.e3dge_last_error().decode(errors="replace"))
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            a.ws, a.ws_bytes, a.bin_capacity = _lib.ptr(ws), nbytes, cap
-            _lib.check(lib.e3dge_noise_project(ctypes.byref(a), _lib.stream_of(verts)), "e3dge_noise_project")
-            need, _ = status.tolist()
-            if need <= cap:
-                return out, valid.bool()
-            if fixed:
-                break
-            cap = need
+    a.verts, a.faces, a.vert_noise, a.prev = verts, faces, vn, prev
+    a.out, a.valid, a.status = out, valid, status
+    for attempt in range(2):
+        cap = min(cap, nf * tiles, 2 ** 31 - 2)
+        nbytes = lib.e3dge_noise_project_ws_bytes(nv, nf, S, cap)
+        if nbytes < 0:
+            raise RuntimeError("project_vertex_noise: " + lib.e3dge_last_error().decode(errors="replace"))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        a.ws, a.ws_bytes, a.bin_capacity = ws, nbytes, cap
+        _lib.launch("e3dge_noise_project", a)
+        need, _ = status.tolist()
+        if need <= cap:
+            return out, valid.bool()
+        if fixed:
+            break
+        cap = need
     raise RuntimeError(f"project_vertex_noise: the tile lists need {need} entries, bin_capacity is {cap}")
 
 

@@ -19,13 +19,14 @@ from torch.autograd import Function
 
 from .. import _lib
 
+_DTYPE_SUFFIX = {torch.float32: "", torch.float16: "_f16", torch.float64: "_f64"}      # e3dge_fused_bias_act / e3dge_upfirdn2d [_f16 | _f64]
+
 
 def fused_bias_act(input, bias, refer, act, grad, alpha, scale):
     """y = act(x + bias[(i / prod(shape[2:])) % len(bias)]) * scale (see include/e3dge_hip.h).
     `bias` / `refer` may be None or empty tensors, as the reference passes `empty`."""
     _lib.require_gpu(input, "input", half_ok=True)
     x = input.contiguous()
-    half = x.dtype == torch.float16          # the reference dispatches on the input's type (fused_bias_act_kernel.cu:79)
     b = bias.contiguous().to(x.dtype) if bias is not None and bias.numel() else None
     r = refer.contiguous().to(x.dtype) if refer is not None and refer.numel() else None
     if b is not None:
@@ -38,12 +39,9 @@ def fused_bias_act(input, bias, refer, act, grad, alpha, scale):
     for d in x.shape[2:]:
         step_b *= d
     y = torch.empty_like(x)
-    lib = _lib.load()
-    fn = lib.e3dge_fused_bias_act_f16 if half else (lib.e3dge_fused_bias_act_f64 if x.dtype == torch.float64 else lib.e3dge_fused_bias_act)
-    with torch.cuda.device(x.device):
-        rc = fn(_lib.ptr(y), _lib.ptr(x), _lib.ptr(b), _lib.ptr(r), int(act), int(grad), float(alpha), float(scale),
-                x.numel(), step_b, 0 if b is None else b.numel(), _lib.stream_of(x))
-    _lib.check(rc, "e3dge_fused_bias_act")
+    # the reference dispatches on the input's type (fused_bias_act_kernel.cu:79)
+    _lib.launch("e3dge_fused_bias_act" + _DTYPE_SUFFIX[x.dtype], y, x, b, r, int(act), int(grad), float(alpha), float(scale),
+                x.numel(), step_b, 0 if b is None else b.numel())
     return y
 
 
@@ -117,12 +115,8 @@ class _NoiseBiasLrelu(Function):
         xc = x.contiguous()
         nz = None if noise is None else noise.contiguous()
         y = torch.empty_like(xc)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().e3dge_noise_bias_act(
-                _lib.ptr(y), _lib.ptr(xc), _lib.ptr(nz), _lib.ptr(noise_weight), _lib.ptr(bias), float(slope),
-                float(scale), B, C, xc.numel() // max(B * C, 1), 0 if nz is None else nz.shape[0],
-                _lib.stream_of(x))
-        _lib.check(rc, "e3dge_noise_bias_act")
+        _lib.launch("e3dge_noise_bias_act", y, xc, nz, noise_weight, bias, float(slope), float(scale), B, C,
+                    xc.numel() // max(B * C, 1), 0 if nz is None else nz.shape[0])
         ctx.save_for_backward(y, nz if nz is not None else y.new_empty(0))
         ctx.slope, ctx.scale = slope, scale
         return y

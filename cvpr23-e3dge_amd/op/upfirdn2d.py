@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from .. import _lib
+from .fused_act import _DTYPE_SUFFIX
 
 
 class Geometry(NamedTuple):
@@ -57,11 +58,8 @@ def _launch(planes, kernel, geo):
         raise RuntimeError(f"upfirdn2d: empty output for input {in_h}x{in_w}, up {geo.up}, down {geo.down}, "
                            f"pad {geo.pad}, kernel {kh}x{kw}")
     y = planes.new_empty((major, out_h, out_w))
-    fn = lib.e3dge_upfirdn2d_f16 if planes.dtype == torch.float16 else (lib.e3dge_upfirdn2d_f64 if planes.dtype == torch.float64 else lib.e3dge_upfirdn2d)
-    with torch.cuda.device(planes.device):
-        rc = fn(_lib.ptr(y), _lib.ptr(planes), _lib.ptr(kernel), major, in_h, in_w, kh, kw,
-                ux, uy, dx, dy, px0, px1, py0, py1, _lib.stream_of(planes))
-    _lib.check(rc, "e3dge_upfirdn2d")
+    _lib.launch("e3dge_upfirdn2d" + _DTYPE_SUFFIX[planes.dtype], y, planes, kernel, major, in_h, in_w, kh, kw,
+                ux, uy, dx, dy, px0, px1, py0, py1)
     return y
 
 

@@ -109,20 +109,15 @@ def image_metrics(pred, gt, l2_lambda=1.0):
     if pred.device.type == "cuda" and pred.dtype == torch.float32 and gt.dtype == torch.float32 and pred.ndim == 4 \
             and pred.shape == gt.shape and not (torch.is_grad_enabled() and (pred.requires_grad or gt.requires_grad)):
         from . import _lib
-        lib = _lib.load()
         B, C, H, W = pred.shape
         p, g = pred.contiguous(), gt.contiguous()
         sums = torch.empty((B, 4), device=p.device, dtype=torch.float32)
-        scratch = torch.empty(lib.e3dge_image_metrics_scratch_floats(B, C, H, W), device=p.device, dtype=torch.float32)
-        with torch.cuda.device(p.device):
-            rc = lib.e3dge_image_metrics(_lib.ptr(sums), _lib.ptr(scratch), _lib.ptr(p), _lib.ptr(g), B, C, H, W, 1.0,
-                                         _lib.stream_of(p))
-            _lib.check(rc, "e3dge_image_metrics")
-            # the reference's losses are means over the whole batch tensor; the eight columns in one more launch (as torch ops
-            # this tail was thirteen 5-us kernels: 3 % of an evaluated image)
-            row = torch.empty(8, device=p.device, dtype=torch.float32)
-            rc = lib.e3dge_image_metric_row(_lib.ptr(row), _lib.ptr(sums), B, float(l2_lambda), _lib.stream_of(p))
-        _lib.check(rc, "e3dge_image_metric_row")
+        scratch = torch.empty(_lib.load().e3dge_image_metrics_scratch_floats(B, C, H, W), device=p.device, dtype=torch.float32)
+        _lib.launch("e3dge_image_metrics", sums, scratch, p, g, B, C, H, W, 1.0)
+        # the reference's losses are means over the whole batch tensor; the eight columns in one more launch (as torch ops
+        # this tail was thirteen 5-us kernels: 3 % of an evaluated image)
+        row = torch.empty(8, device=p.device, dtype=torch.float32)
+        _lib.launch("e3dge_image_metric_row", row, sums, B, float(l2_lambda))
         return row
     return image_metrics_torch(pred, gt, l2_lambda)
 

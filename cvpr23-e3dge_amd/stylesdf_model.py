@@ -290,11 +290,7 @@ class ModulatedConv2d(nn.Module):
         out = torch.empty((B * Ci, Co, k, k) if transpose else (B * Co, Ci, k, k), device=s.device, dtype=torch.float32)
         wt = self.weight.detach().contiguous()
         sc = s.contiguous()
-        with torch.cuda.device(s.device):
-            rc = _lib.load().e3dge_modconv_weights(_lib.ptr(out), _lib.ptr(wt), _lib.ptr(sc), float(self.scale),
-                                                   int(self.demodulate), int(transpose), B, Co, Ci, k * k,
-                                                   _lib.stream_of(sc))
-        _lib.check(rc, "e3dge_modconv_weights")
+        _lib.launch("e3dge_modconv_weights", out, wt, sc, float(self.scale), int(self.demodulate), int(transpose), B, Co, Ci, k * k)
         return out
 
     # ---- fused path --------------------------------------------------------------------------------------------
@@ -328,10 +324,7 @@ class ModulatedConv2d(nn.Module):
             Co, Ci = self.out_channel, self.in_channel
             wpre = torch.empty(Co * Ci * 9, device=w.device, dtype=torch.float32)
             wc = w.detach().reshape(Co, Ci, 9).contiguous()
-            with torch.cuda.device(w.device):
-                rc = _lib.load().e3dge_dec2_prepack_weights_t(_lib.ptr(wpre), _lib.ptr(wc), float(self.scale), Co, Ci,
-                                                              0 if self.upsample else 1, _lib.stream_of(wc))
-            _lib.check(rc, "e3dge_dec2_prepack_weights_t")
+            _lib.launch("e3dge_dec2_prepack_weights_t", wpre, wc, float(self.scale), Co, Ci, 0 if self.upsample else 1)
             return wpre
         return _lib.cached(self, 'wpre_t', (w,), build)
 
@@ -344,9 +337,7 @@ class ModulatedConv2d(nn.Module):
             Co, Ci = self.out_channel, self.in_channel
             wpre = torch.empty(Co * Ci * 9, device=w.device, dtype=torch.float32)
             wc = w.detach().reshape(Co, Ci, 9).contiguous()
-            with torch.cuda.device(w.device):
-                rc = _lib.load().e3dge_dec2_prepack_weights(_lib.ptr(wpre), _lib.ptr(wc), float(self.scale), Co, Ci, _lib.stream_of(wc))
-            _lib.check(rc, "e3dge_dec2_prepack_weights")
+            _lib.launch("e3dge_dec2_prepack_weights", wpre, wc, float(self.scale), Co, Ci)
             return wpre
         return _lib.cached(self, 'wpre', (w,), build)
 
@@ -360,10 +351,7 @@ class ModulatedConv2d(nn.Module):
             img = torch.empty(lib.e3dge_modconv_packed_words(Co, Ci), device=w.device, dtype=torch.int32)
             wsq = torch.empty((Co, Ci), device=w.device, dtype=torch.float32)
             wc = w.detach().reshape(Co, Ci, 9).contiguous()
-            with torch.cuda.device(w.device):
-                rc = lib.e3dge_modconv_pack_weights(_lib.ptr(img), _lib.ptr(wsq), _lib.ptr(wc), float(self.scale), Co, Ci,
-                                                    _lib.stream_of(wc))
-            _lib.check(rc, "e3dge_modconv_pack_weights")
+            _lib.launch("e3dge_modconv_pack_weights", img, wsq, wc, float(self.scale), Co, Ci)
             wmax = float(wc.abs().max().item()) * self.scale
             if wmax >= 400.0:                      # the image stores 128 * scale * w as f16
                 raise RuntimeError(f"modulated-conv weights up to {wmax:g} (after the 1/sqrt(fan_in) scale) do not fit the "
@@ -379,7 +367,6 @@ class ModulatedConv2d(nn.Module):
         B, Ci, H, W = input.shape
         x = input.contiguous()
         img, wsq = self.device_image()
-        lib = _lib.load()
         dev = x.device
         if pre is not None:           # (s, demod, s_amax) from Decoder's e3dge_decoder_styles launch
             s, demod, s_amax = pre
@@ -394,22 +381,17 @@ class ModulatedConv2d(nn.Module):
             nz = noise.contiguous()
             if nz.shape[0] not in (1, B) or nz.numel() != nz.shape[0] * OH * OW:
                 raise RuntimeError(f"noise must be (1|B, 1, {OH}, {OW}); got {tuple(noise.shape)}")
-        with torch.cuda.device(dev):
-            st = _lib.stream_of(x)
-            if pre is None:
-                rc = lib.e3dge_modconv_demod(_lib.ptr(demod), _lib.ptr(s_amax), _lib.ptr(s), _lib.ptr(wsq), B, self.out_channel, Ci,
-                                             int(self.demodulate), st)
-                _lib.check(rc, "e3dge_modconv_demod")
-            if in_amax is None:       # the producer of `input` did not track max|input|: one extra pass over it
-                in_amax = torch.zeros(_lib.AMAX_FLOATS, device=dev, dtype=torch.float32)
-                _lib.check(lib.e3dge_amax(_lib.ptr(in_amax), _lib.ptr(x), x.numel(), st), "e3dge_amax")
-            a = _lib.ModconvArgs(x=_lib.ptr(x), wimg=_lib.ptr(img), style=_lib.ptr(s), demod=_lib.ptr(demod), in_amax=_lib.ptr(in_amax),
-                                 s_amax=_lib.ptr(s_amax), noise=_lib.ptr(nz), noise_w=_lib.ptr(noise_weight) if nz is not None else None,
-                                 bias=_lib.ptr(bias), y=_lib.ptr(y), out_amax=_lib.ptr(out_amax), negative_slope=float(negative_slope),
-                                 act_scale=float(act_scale), act=int(bool(act)), upsample=int(bool(self.upsample)), batch=B, ci=Ci,
-                                 co=self.out_channel, height=H, width=W, noise_batch=0 if nz is None else nz.shape[0])
-            rc = lib.e3dge_modconv3x3(ctypes.byref(a), st)
-        _lib.check(rc, "e3dge_modconv3x3")
+        if pre is None:
+            _lib.launch("e3dge_modconv_demod", demod, s_amax, s, wsq, B, self.out_channel, Ci, int(self.demodulate))
+        if in_amax is None:       # the producer of `input` did not track max|input|: one extra pass over it
+            in_amax = torch.zeros(_lib.AMAX_FLOATS, device=dev, dtype=torch.float32)
+            _lib.launch("e3dge_amax", in_amax, x, x.numel())
+        a = _lib.ModconvArgs(x=x, wimg=img, style=s, demod=demod, in_amax=in_amax, s_amax=s_amax, noise=nz,
+                             noise_w=noise_weight if nz is not None else None, bias=bias, y=y, out_amax=out_amax,
+                             negative_slope=float(negative_slope), act_scale=float(act_scale), act=int(bool(act)),
+                             upsample=int(bool(self.upsample)), batch=B, ci=Ci, co=self.out_channel, height=H, width=W,
+                             noise_batch=0 if nz is None else nz.shape[0])
+        _lib.launch("e3dge_modconv3x3", a)
         return y
 
     def forward(self, input, style):
@@ -512,12 +494,9 @@ class StyledConv(nn.Module):
                 raise RuntimeError(f"noise must be (1|B, 1, {OH}, {OW}); got {tuple(noise.shape)}")
             y = torch.empty((B, conv.out_channel, OH, OW), device=input.device, dtype=torch.float32)
             k = conv.blur.kernel
-            with torch.cuda.device(input.device):
-                rc = _lib.load().e3dge_blur_noise_bias_act(
-                    _lib.ptr(y), _lib.ptr(t), _lib.ptr(k), _lib.ptr(nz), _lib.ptr(self.noise.weight), _lib.ptr(act.bias),
-                    float(act.negative_slope), float(act.scale), B, conv.out_channel, t.shape[2], t.shape[3],
-                    int(conv.blur.pad[0]), int(conv.blur.pad[1]), nz.shape[0], _lib.ptr(out_amax), _lib.stream_of(t))
-            _lib.check(rc, "e3dge_blur_noise_bias_act")
+            _lib.launch("e3dge_blur_noise_bias_act", y, t, k, nz, self.noise.weight, act.bias, float(act.negative_slope),
+                        float(act.scale), B, conv.out_channel, t.shape[2], t.shape[3], int(conv.blur.pad[0]), int(conv.blur.pad[1]),
+                        nz.shape[0], out_amax)
             return y
         out = conv(input, style)
         if noise is None:
@@ -526,9 +505,8 @@ class StyledConv(nn.Module):
         out = noise_bias_act(out, noise, self.noise.weight, self.activate.bias, self.activate.negative_slope,
                              self.activate.scale)
         if out_amax is not None and out.device.type == "cuda":   # a fused consumer follows: it needs max|out|
-            with torch.cuda.device(out.device):
-                oc = out.detach().contiguous()
-                _lib.check(_lib.load().e3dge_amax(_lib.ptr(out_amax), _lib.ptr(oc), oc.numel(), _lib.stream_of(oc)), "e3dge_amax")
+            oc = out.detach().contiguous()
+            _lib.launch("e3dge_amax", out_amax, oc, oc.numel())
         return out
 
 
@@ -566,11 +544,8 @@ class ToRGB(nn.Module):
             w = self.conv.weight.detach().reshape(3, Ci).contiguous()
             y = torch.empty((B, 3, H, W), device=x.device, dtype=torch.float32)
             sk = None if skip is None else skip.contiguous()
-            with torch.cuda.device(x.device):
-                rc = _lib.load().e3dge_torgb(_lib.ptr(y), _lib.ptr(x), _lib.ptr(w), _lib.ptr(s), _lib.ptr(self.bias.detach().reshape(3).contiguous()),
-                                             _lib.ptr(sk), _lib.ptr(self.upsample.kernel) if sk is not None else None,
-                                             float(self.conv.scale), B, Ci, H, W, _lib.stream_of(x))
-            _lib.check(rc, "e3dge_torgb")
+            _lib.launch("e3dge_torgb", y, x, w, s, self.bias.detach().reshape(3).contiguous(), sk,
+                        self.upsample.kernel if sk is not None else None, float(self.conv.scale), B, Ci, H, W)
             return y
         out = self.conv(input, style) + self.bias
         if skip is not None:
@@ -654,9 +629,9 @@ class Decoder(nn.Module):
                     a_v = buf[off:off + B]; off += pad4(B)
                 views.append((s_v, d_v, a_v))
                 mod = m.modulation
-                rows[j] = _lib.ModLayer(mod_weight=_lib.ptr(mod.weight), mod_bias=_lib.ptr(mod.bias), wsq=_lib.ptr(w),
-                                        style_out=_lib.ptr(s_v), demod_out=_lib.ptr(d_v) if (w is not None and m.demodulate) else None,
-                                        s_amax_out=_lib.ptr(a_v), ci=m.in_channel, co=m.out_channel if w is not None else 0,
+                rows[j] = _lib.ModLayer(mod_weight=mod.weight, mod_bias=mod.bias, wsq=w, style_out=s_v,
+                                        demod_out=d_v if (w is not None and m.demodulate) else None,
+                                        s_amax_out=a_v, ci=m.in_channel, co=m.out_channel if w is not None else 0,
                                         latent_index=li, row_start=row_start, co_start=co_start, lin_scale=float(mod.scale),
                                         lr_mul=float(mod.lr_mul))
                 row_start += m.in_channel
@@ -677,10 +652,7 @@ class Decoder(nn.Module):
         raw, buf, views, n, rows, cos = self._style_table(B, latent.device)
         self.__dict__['_dec2_gen'] = self.__dict__.get('_dec2_gen', 0) + 1      # (the packed backward reads these buffers)
         lat = latent.contiguous()
-        with torch.cuda.device(latent.device):
-            rc = _lib.load().e3dge_decoder_styles(_lib.ptr(raw), n, rows, cos, _lib.ptr(lat), lat.shape[1], lat.shape[2], B,
-                                                  _lib.stream_of(lat))
-        _lib.check(rc, "e3dge_decoder_styles")
+        _lib.launch("e3dge_decoder_styles", raw, n, rows, cos, lat, lat.shape[1], lat.shape[2], B)
         return views
 
     # ---- packed pipeline: the whole forward as one native call (e3dge_dec2_forward, csrc/decoder2.hip) -----------------
@@ -754,8 +726,7 @@ class Decoder(nn.Module):
             if hit is not None and hit[0] is nz and hit[1] == nz._version:
                 return hit[2]
         am = torch.zeros(_lib.AMAX_FLOATS, device=nz.device, dtype=torch.float32)
-        with torch.cuda.device(nz.device):
-            _lib.check(_lib.load().e3dge_amax(_lib.ptr(am), _lib.ptr(nz), nz.numel(), _lib.stream_of(nz)), "e3dge_amax")
+        _lib.launch("e3dge_amax", am, nz, nz.numel())
         if own:
             if len(cache) >= 64:
                 cache.pop(next(iter(cache)))
@@ -782,7 +753,7 @@ class Decoder(nn.Module):
         keep = [raw, buf, *wpres.values()]                 # every tensor whose pointer the plan stores
         plan = _lib.Dec2Plan()
         plan.batch, plan.n_up, plan.in_res, plan.in_ch = B, n_up, res, self.conv1.conv.in_channel
-        plan.mod_table = _lib.ptr(raw)
+        plan.mod_table = raw
         plan.n_mod, plan.mod_rows, plan.mod_co = n_mod, rows, cos
         plan.n_latent, plan.style_dim = self.n_latent, self.style_dim
         plan.negative_slope, plan.act_scale = float(self.conv1.activate.negative_slope), float(self.conv1.activate.scale)
@@ -792,8 +763,8 @@ class Decoder(nn.Module):
             wimg = torch.empty(B * lib.e3dge_modconv_packed_words(m.out_channel, m.in_channel), device=device, dtype=torch.int32)
             bias = sc.activate.bias.detach()
             keep.extend([wimg, bias])
-            dst.wpre, dst.style, dst.demod, dst.wimg = _lib.ptr(wpres[sc]), _lib.ptr(view[0]), _lib.ptr(view[1]), _lib.ptr(wimg)
-            dst.noise_w, dst.bias = _lib.ptr(sc.noise.weight), _lib.ptr(bias)
+            dst.wpre, dst.style, dst.demod, dst.wimg = wpres[sc], view[0], view[1], wimg
+            dst.noise_w, dst.bias = sc.noise.weight, bias
             dst.bias_amax = float(bias.abs().max().item())
             dst.ci, dst.co = m.in_channel, m.out_channel
 
@@ -804,7 +775,7 @@ class Decoder(nn.Module):
             out = torch.empty((B, 3, r, r), **f32)
             bias = tr.bias.detach().reshape(3)
             keep.extend([w, wm, out, bias])
-            dst.weight, dst.style, dst.bias, dst.wm, dst.out = _lib.ptr(w), _lib.ptr(view[0]), _lib.ptr(bias), _lib.ptr(wm), _lib.ptr(out)
+            dst.weight, dst.style, dst.bias, dst.wm, dst.out = w, view[0], bias, wm, out
             dst.scale, dst.ci = float(m.scale), m.in_channel
             return out
 
@@ -824,13 +795,13 @@ class Decoder(nn.Module):
             acts += [packed(up_c.conv.out_channel, r), packed(cv.conv.out_channel, r)]
             outs.append(fill_rgb(plan.rgb[u], tr, views[4 + 3 * u], r))
         for i, t in enumerate(acts):
-            plan.act[i] = _lib.ptr(t)
+            plan.act[i] = t.data_ptr()
         amax = torch.zeros((3 * n_up + 2, _lib.AMAX_FLOATS), **f32)
         meta = torch.zeros(2 * n_up + 2, device=device, dtype=torch.int32)
         fir_blur = (self.convs[0].conv.blur.kernel if n_up else self.conv1.conv.weight.new_zeros(4, 4)).detach().contiguous()
         fir_up = (self.to_rgbs[0].upsample.kernel if n_up else fir_blur).detach().contiguous()
         keep += [amax, meta, fir_blur, fir_up]
-        plan.amax, plan.meta, plan.fir_blur, plan.fir_up = _lib.ptr(amax), _lib.ptr(meta), _lib.ptr(fir_blur), _lib.ptr(fir_up)
+        plan.amax, plan.meta, plan.fir_blur, plan.fir_up = amax, meta, fir_blur, fir_up
         g = self._blur_factor() if n_up else None        # (None: e3dge_dec2_forward refuses the plan; _dec2_ok keeps such decoders off it)
         if g is not None:
             for i in range(4):
@@ -861,12 +832,12 @@ class Decoder(nn.Module):
                 raise RuntimeError(f"noise[{i}] must be (1|B, 1, {r}, {r}); got {tuple(nz.shape)}")
             dst = plan.conv1 if i == 0 else (plan.up[(i - 1) // 2] if i % 2 == 1 else plan.conv[(i - 1) // 2])
             am = self._noise_amax(nz)
-            dst.noise, dst.noise_amax, dst.noise_batch = _lib.ptr(nz), _lib.ptr(am), nz.shape[0]
+            dst.noise, dst.noise_amax, dst.noise_batch = nz, am, nz.shape[0]
             hold += [nz, am]
         out = torch.empty_like(st['outs'][-1])
         last = plan.rgb[len(self.to_rgbs) - 1] if len(self.to_rgbs) else plan.rgb1
-        last.out = _lib.ptr(out)
-        plan.features, plan.latent = _lib.ptr(x), _lib.ptr(lat)
+        last.out = out
+        plan.features, plan.latent = x, lat
         plan.save_for_backward = int(bool(save))         # keep the top activation too: the backward reads every activation's signs
         self.__dict__['_dec2_gen'] = self.__dict__.get('_dec2_gen', 0) + 1      # (a backward checks that its forward was the last one)
         ms = None
@@ -875,9 +846,7 @@ class Decoder(nn.Module):
             plan.kernel_ms, plan.n_kernel_ms = ctypes.cast(ms, ctypes.POINTER(ctypes.c_float)), st['n_launch']
         else:
             plan.kernel_ms, plan.n_kernel_ms = None, 0
-        with torch.cuda.device(dev):
-            rc = _lib.load().e3dge_dec2_forward(ctypes.byref(plan), _lib.stream_of(x))
-        _lib.check(rc, "e3dge_dec2_forward")
+        _lib.launch("e3dge_dec2_forward", plan)
         if ms is not None:
             kernel_ms[:] = list(ms)
         st['hold'] = hold            # inputs of the launches just queued stay alive until the next call on this stream
@@ -902,7 +871,7 @@ class Decoder(nn.Module):
             wcol = m.device_image()[1].sum(0).contiguous()     # (ci): column sums of the squared-norm table, for the operator-norm bound
             wpt = m.device_wpre_t()
             keep.extend([wimg, wcol, wpt])
-            dst.wpre_t, dst.wcol, dst.wimg_t = _lib.ptr(wpt), _lib.ptr(wcol), _lib.ptr(wimg)
+            dst.wpre_t, dst.wcol, dst.wimg_t = wpt, wcol, wimg
         fill(q.conv1, self.conv1)
         gacts = [None, torch.zeros_like(st['acts'][1])]
         r, pwords = res, 0
@@ -911,19 +880,19 @@ class Decoder(nn.Module):
             fill(q.conv[u], self.convs[2 * u + 1])
             d = torch.empty((B, 3, r, r), **f32)
             keep.append(d)
-            q.drgb[u] = _lib.ptr(d)
+            q.drgb[u] = d.data_ptr()
             r *= 2
             gacts += [torch.zeros_like(st['acts'][2 + 2 * u]), torch.zeros_like(st['acts'][3 + 2 * u])]
             pwords = max(pwords, lib.e3dge_dec2_pbuf_words(B, self.convs[2 * u].conv.out_channel, r))
         for i, t in enumerate(gacts):
             if t is not None:
-                q.gact[i] = _lib.ptr(t)
+                q.gact[i] = t.data_ptr()
         pbuf = torch.empty(max(pwords, 4), device=device, dtype=torch.int32)
         amax = torch.zeros((4 * n_up + 2, _lib.AMAX_FLOATS), **f32)
         meta = torch.zeros(3 * n_up + 1, device=device, dtype=torch.int32)
         bounds = torch.zeros(3 * n_up + 2, **f32)
         keep += [gacts, pbuf, amax, meta, bounds]
-        q.pbuf, q.amax, q.meta, q.bounds = _lib.ptr(pbuf), _lib.ptr(amax), _lib.ptr(meta), _lib.ptr(bounds)
+        q.pbuf, q.amax, q.meta, q.bounds = pbuf, amax, meta, bounds
         bw = dict(plan=q, keep=keep, gacts=gacts, meta=meta, amax=amax, bounds=bounds, n_launch=lib.e3dge_dec2_bwd_num_launches(n_up))
         st['bwd'] = bw
         return bw
@@ -942,14 +911,14 @@ class Decoder(nn.Module):
         if g.dtype != torch.float32 or g.shape != st['outs'][-1].shape:
             raise RuntimeError(f"d image must be float32 {tuple(st['outs'][-1].shape)}; got {g.dtype} {tuple(g.shape)}")
         d_feat = torch.empty((B, self.conv1.conv.in_channel, res, res), device=dev, dtype=torch.float32)
-        q.d_img, q.d_features = _lib.ptr(g), _lib.ptr(d_feat)
+        q.d_img, q.d_features = g, d_feat
         d_lat = None
         if want_latent:
             if 'ds_part' not in bw:
-                n = _lib.load().e3dge_dec2_dlatent_ws_floats(ctypes.byref(st['plan']))
+                n = _lib.load().e3dge_dec2_dlatent_ws_floats(st['plan'])      # (ctypes passes the struct by reference: POINTER argtype)
                 bw['ds_part'] = torch.empty(max(int(n), 1), device=dev, dtype=torch.float32)
             d_lat = torch.empty((B, self.n_latent, self.style_dim), device=dev, dtype=torch.float32)
-            q.d_latent, q.ds_part, q.ds_part_floats = _lib.ptr(d_lat), _lib.ptr(bw['ds_part']), bw['ds_part'].numel()
+            q.d_latent, q.ds_part, q.ds_part_floats = d_lat, bw['ds_part'], bw['ds_part'].numel()
         else:
             q.d_latent, q.ds_part, q.ds_part_floats = None, None, 0
         ms = None
@@ -958,9 +927,7 @@ class Decoder(nn.Module):
             q.kernel_ms, q.n_kernel_ms = ctypes.cast(ms, ctypes.POINTER(ctypes.c_float)), bw['n_launch']
         else:
             q.kernel_ms, q.n_kernel_ms = None, 0
-        with torch.cuda.device(dev):
-            rc = _lib.load().e3dge_dec2_backward(ctypes.byref(st['plan']), ctypes.byref(q), _lib.stream_of(g))
-        _lib.check(rc, "e3dge_dec2_backward")
+        _lib.launch("e3dge_dec2_backward", st['plan'], q)
         if ms is not None:
             kernel_ms[:] = list(ms)
         bw['hold'] = [g]
@@ -990,10 +957,7 @@ class Decoder(nn.Module):
         # meta: G2 of level u at [u + 1] (activation index 3 + 2u; conv1's output: u = -1), G1 of level u at [n_up + 1 + u] (index 2 + 2u)
         mi = (index - 3) // 2 + 1 if index % 2 == 1 else n_up + 1 + (index - 2) // 2
         out = torch.empty((B, chans[index], ress[index], ress[index]), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            rc = _lib.load().e3dge_dec2_unpack(_lib.ptr(out), _lib.ptr(bw['gacts'][index]), bw['meta'][mi:].data_ptr(), B, chans[index],
-                                               ress[index], torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "e3dge_dec2_unpack")
+        _lib.launch("e3dge_dec2_unpack", out, bw['gacts'][index], bw['meta'][mi:], B, chans[index], ress[index])
         return out
 
     def dec2_launch_names(self):
@@ -1017,10 +981,7 @@ class Decoder(nn.Module):
             chans += [self.convs[2 * u].conv.out_channel, self.convs[2 * u + 1].conv.out_channel]
             ress += [r, r]
         out = torch.empty((B, chans[index], ress[index], ress[index]), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            rc = _lib.load().e3dge_dec2_unpack(_lib.ptr(out), _lib.ptr(st['acts'][index]), st['meta'][index:].data_ptr(), B, chans[index],
-                                               ress[index], torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "e3dge_dec2_unpack")
+        _lib.launch("e3dge_dec2_unpack", out, st['acts'][index], st['meta'][index:], B, chans[index], ress[index])
         return out
 
     def get_latent(self, input):

@@ -23,7 +23,6 @@ contraction e3dge_siren_wgrad turns it into the weight gradients, the FiLM biase
 side.  Precision f16x3_g2 only; the eikonal term and the texture-FiLM pass with trainable weights are refused.  Off (the default),
 trainable SIREN parameters under a backward raise NotImplementedError, as before.
 """
-import ctypes
 import os
 import weakref
 import warnings
@@ -338,12 +337,8 @@ class SirenGenerator(nn.Module):
                     self.sigma_linear.std_init != 1 or self.sigma_linear.bias_init != 0:
                 raise NotImplementedError("head LinearLayers with std_init != 1 / bias_init != 0")
             packed = torch.empty(lib.e3dge_siren_packed_floats(), **f32)
-            with _lib.on_device(dev):
-                rc = lib.e3dge_siren_pack_weights(
-                    _lib.ptr(packed), _lib.ptr(w_first), _lib.ptr(b_first), _lib.ptr(w_hidden), _lib.ptr(b_hidden),
-                    _lib.ptr(w_view), _lib.ptr(b_view), _lib.ptr(w_rgb), _lib.ptr(b_rgb), _lib.ptr(w_sig),
-                    _lib.ptr(b_sig), _lib.stream_of(packed))
-            _lib.check(rc, "e3dge_siren_pack_weights")
+            _lib.launch("e3dge_siren_pack_weights", packed, w_first, b_first, w_hidden, b_hidden, w_view, b_view, w_rgb, b_rgb,
+                        w_sig, b_sig)
             # The f16x3 images carry the weights times 128 as f16 (max 65504): a checkpoint with |w| >= 256 in the
             # 256-wide layers (trained ones are ~0.01) cannot use them; check_mode() then selects the fp32 MFMA kernels.
             wmax = float(torch.maximum(w_hidden.abs().max(), w_view.abs().max()).item())
@@ -405,10 +400,7 @@ class SirenGenerator(nn.Module):
         _, wg, bg, wb, bb = self.device_image()
         B = styles.shape[0]
         film = torch.empty((B, 9, 2, self.W), device=styles.device, dtype=torch.float32)
-        with _lib.on_device(styles.device):
-            rc = _lib.load().e3dge_film_params(_lib.ptr(film), _lib.ptr(styles), _lib.ptr(wg), _lib.ptr(bg),
-                                               _lib.ptr(wb), _lib.ptr(bb), B, _lib.stream_of(styles))
-        _lib.check(rc, "e3dge_film_params")
+        _lib.launch("e3dge_film_params", film, styles, wg, bg, wb, bb, B)
         return film
 
     def query_points(self, pts, viewdirs, styles, box_scale, want_raw=True, mfma_mode=None, save_args=None,
@@ -446,12 +438,8 @@ class SirenGenerator(nn.Module):
         raw = torch.empty((B, N, 260), device=pts.device, dtype=torch.float32) if want_raw else None
         if B == 0 or N == 0:
             return sdf, raw
-        with _lib.on_device(pts.device):
-            rc = _lib.load().e3dge_siren_points_fwd(_lib.ptr(packed), _lib.ptr(film), _lib.ptr(pts), _lib.ptr(vd),
-                                                    float(box_scale), B, N, _lib.ptr(sdf), _lib.ptr(raw), _lib.ptr(save_args),
-                                                    self.save_precision(mfma_mode) if save_args is not None else self.check_mode(mfma_mode or self.mfma_mode),
-                                                    _lib.stream_of(pts))
-        _lib.check(rc, "e3dge_siren_points_fwd")
+        prec = self.save_precision(mfma_mode) if save_args is not None else self.check_mode(mfma_mode or self.mfma_mode)
+        _lib.launch("e3dge_siren_points_fwd", packed, film, pts, vd, float(box_scale), B, N, sdf, raw, save_args, prec)
         return sdf, raw
 
     def forward(self, net_inputs, styles, residuals=None):
@@ -471,11 +459,7 @@ def sdf_gradient(siren, film, args, box_scale):
     B, N = args.shape[0], args.shape[1]
     rsave = saved_state_buffer(B, N, 8, args.device, siren.W)
     eik = torch.empty((B, N, 3), device=args.device, dtype=torch.float32)
-    with _lib.on_device(args.device):
-        rc = _lib.load().e3dge_siren_sdf_grad(_lib.ptr(packed), _lib.ptr(film), _lib.ptr(args), None, float(box_scale),
-                                              B, N, _lib.ptr(rsave), _lib.ptr(eik), siren.check_mode(siren.bwd_mode),
-                                              _lib.stream_of(args))
-    _lib.check(rc, "e3dge_siren_sdf_grad")
+    _lib.launch("e3dge_siren_sdf_grad", packed, film, args, None, float(box_scale), B, N, rsave, eik, siren.check_mode(siren.bwd_mode))
     return eik, rsave
 
 
@@ -492,15 +476,11 @@ def tangent_arguments(siren, film, args, v, box_scale, images=None, rsave=None, 
     v = v.reshape(B, N, 3).contiguous().float()
     tang = out if out is not None else saved_state_buffer(B, N, 8, args.device, siren.W)
     prec = siren.check_mode(siren.bwd_mode)
-    with _lib.on_device(args.device):
-        if prec == _lib.PREC_F16X3_G2 and rsave is not None:
-            rc = _lib.load().e3dge_siren_tangent_tr(_lib.ptr(packed), _lib.ptr(film), _lib.ptr(args), _lib.ptr(v), _lib.ptr(rsave),
-                                                    float(box_scale), B, N, _lib.ptr(tang), prec, _lib.stream_of(args))
-            rsave = None
-        else:
-            rc = _lib.load().e3dge_siren_tangent(_lib.ptr(packed), _lib.ptr(film), _lib.ptr(args), _lib.ptr(v), float(box_scale),
-                                                 B, N, _lib.ptr(tang), prec, _lib.stream_of(args))
-    _lib.check(rc, "e3dge_siren_tangent")
+    if prec == _lib.PREC_F16X3_G2 and rsave is not None:
+        _lib.launch("e3dge_siren_tangent_tr", packed, film, args, v, rsave, float(box_scale), B, N, tang, prec)
+        rsave = None
+    else:
+        _lib.launch("e3dge_siren_tangent", packed, film, args, v, float(box_scale), B, N, tang, prec)
     return tang, rsave
 
 
@@ -525,16 +505,12 @@ def siren_backward(siren, film, args, d_feat, d_rgb, d_sdf, tang=None, rsave=Non
         d_ta = torch.empty((B, N, siren.W), device=dev, dtype=torch.float32)
         d_tb = torch.empty((B, N, siren.W), device=dev, dtype=torch.float32)
     a = _lib.SirenBwdArgs(
-        packed=_lib.ptr(packed), film=_lib.ptr(film), args=_lib.ptr(args), d_feat=_lib.ptr(d_feat), d_rgb=_lib.ptr(d_rgb),
-        d_sdf=_lib.ptr(d_sdf), tang=_lib.ptr(tang), rsave=_lib.ptr(rsave), wg=_lib.ptr(wg), wb=_lib.ptr(wb),
-        tex_alpha=_lib.ptr(tex_alpha), batch=B, precision=siren.check_mode(siren.bwd_mode), n_pts=N, box_scale=float(box_scale),
-        partials=_lib.ptr(partials), dfilm=_lib.ptr(dfilm), dstyles=_lib.ptr(dstyles), d_pts=_lib.ptr(d_pts),
-        d_tex_alpha=_lib.ptr(d_ta), d_tex_beta=_lib.ptr(d_tb))
+        packed=packed, film=film, args=args, d_feat=d_feat, d_rgb=d_rgb, d_sdf=d_sdf, tang=tang, rsave=rsave, wg=wg, wb=wb,
+        tex_alpha=tex_alpha, batch=B, precision=siren.check_mode(siren.bwd_mode), n_pts=N, box_scale=float(box_scale),
+        partials=partials, dfilm=dfilm, dstyles=dstyles, d_pts=d_pts, d_tex_alpha=d_ta, d_tex_beta=d_tb)
     if lin is not None:                            # (d_lin, lin_amax) of lin_buffers(): the renderer's parameter gradients follow
-        a.d_lin, a.lin_amax = _lib.ptr(lin[0]), _lib.ptr(lin[1])
-    with _lib.on_device(dev):
-        rc = lib.e3dge_siren_bwd(ctypes.byref(a), _lib.stream_of(args))
-    _lib.check(rc, "e3dge_siren_bwd")
+        a.d_lin, a.lin_amax = lin
+    _lib.launch("e3dge_siren_bwd", a)
     return dstyles, dfilm, d_pts, (None if d_ta is None else (d_ta, d_tb))
 
 
@@ -578,13 +554,10 @@ def siren_param_grads(siren, film, styles, dfilm, args, d_lin, lin_amax, d_sdf, 
     c = lambda t: None if t is None else t.contiguous().float()
     d_sdf, d_rgb, pts, viewdirs = c(d_sdf), c(d_rgb), c(pts), c(viewdirs)
     a = _lib.SirenWgradArgs(
-        args=_lib.ptr(args), d_lin=_lib.ptr(d_lin), lin_amax=_lib.ptr(lin_amax), d_sdf=_lib.ptr(d_sdf), d_rgb=_lib.ptr(d_rgb),
-        pts=_lib.ptr(pts), viewdirs=_lib.ptr(viewdirs), d_w=_lib.ptr(d_w), d_w_view_dirs=_lib.ptr(d_wv), d_w_first=_lib.ptr(d_w0),
-        d_w_sigma=_lib.ptr(d_ws), d_b_sigma=_lib.ptr(d_bs), d_w_rgb=_lib.ptr(d_wr), d_b_rgb=_lib.ptr(d_br), ws=_lib.ptr(ws),
+        args=args, d_lin=d_lin, lin_amax=lin_amax, d_sdf=d_sdf, d_rgb=d_rgb, pts=pts, viewdirs=viewdirs, d_w=d_w, d_w_view_dirs=d_wv,
+        d_w_first=d_w0, d_w_sigma=d_ws, d_b_sigma=d_bs, d_w_rgb=d_wr, d_b_rgb=d_br, ws=ws,
         ws_floats=n_ws, n_pts=N, batch=B, samples=int(samples), precision=siren.check_mode(siren.bwd_mode), box_scale=float(box_scale))
-    with _lib.on_device(dev):
-        rc = lib.e3dge_siren_wgrad(ctypes.byref(a), _lib.stream_of(args))
-    _lib.check(rc, "e3dge_siren_wgrad")
+    _lib.launch("e3dge_siren_wgrad", a)
     st = styles.detach().float()
     st = st.unsqueeze(1).expand(-1, 9, -1) if st.ndim == 2 else st            # (B, 9, 256)
     dg, db = dfilm[:, :, 0], dfilm[:, :, 1]                                    # (B, 9, 256)
@@ -813,33 +786,27 @@ class _RenderQuery(torch.autograd.Function):
             d_ta = torch.empty((B, H, H, S, siren.W), device=dev, dtype=torch.float32)
             d_tb = torch.empty((B, H, H, S, siren.W), device=dev, dtype=torch.float32)
         a = _lib.RenderBwdArgs(
-            packed=_lib.ptr(packed), film=_lib.ptr(film), args=_lib.ptr(args), sdf=_lib.ptr(sdf), dists=_lib.ptr(dists),
-            points=_lib.ptr(points), weights=_lib.ptr(weights), t_vals=_lib.ptr(r.t_vals), near=_lib.ptr(near),
-            far=_lib.ptr(far), wg=_lib.ptr(wg), wb=_lib.ptr(wb), d_rgb_map=_lib.ptr(d_rgb_map),
-            d_feat_map=_lib.ptr(d_feat_map), d_xyz_map=_lib.ptr(d_xyz_map), d_depth_map=_lib.ptr(d_depth_map),
-            d_sdf=_lib.ptr(d_sdf_in), tang=_lib.ptr(tang), rsave=_lib.ptr(rs), d_weights=_lib.ptr(d_w_in),
-            tex_alpha=_lib.ptr(tex_a), sigmoid_beta=ctx.sigmoid_beta, batch=B, height=H, width=H, n_samples=S,
-            force_background=int(bool(r.force_background)), precision=siren.check_mode(siren.bwd_mode), d_rgb_pts=_lib.ptr(d_rgb_pts), d_sdf_pts=_lib.ptr(d_sdf_pts),
-            partials=_lib.ptr(partials), dfilm=_lib.ptr(dfilm), dstyles=_lib.ptr(dstyles), d_tex_alpha=_lib.ptr(d_ta),
-            d_tex_beta=_lib.ptr(d_tb))
+            packed=packed, film=film, args=args, sdf=sdf, dists=dists, points=points, weights=weights, t_vals=r.t_vals, near=near,
+            far=far, wg=wg, wb=wb, d_rgb_map=d_rgb_map, d_feat_map=d_feat_map, d_xyz_map=d_xyz_map, d_depth_map=d_depth_map,
+            d_sdf=d_sdf_in, tang=tang, rsave=rs, d_weights=d_w_in, tex_alpha=tex_a, sigmoid_beta=ctx.sigmoid_beta, batch=B,
+            height=H, width=H, n_samples=S, force_background=int(bool(r.force_background)),
+            precision=siren.check_mode(siren.bwd_mode), d_rgb_pts=d_rgb_pts, d_sdf_pts=d_sdf_pts, partials=partials, dfilm=dfilm,
+            dstyles=dstyles, d_tex_alpha=d_ta, d_tex_beta=d_tb)
         lin = d_beta = None
         if ctx.n_params:                                                     # trainable renderer (eikonal / tex passes were refused)
             d_beta = torch.empty(B * H * H, device=dev, dtype=torch.float32)
-            a.d_sigmoid_beta = _lib.ptr(d_beta)
+            a.d_sigmoid_beta = d_beta
         if ctx.n_params > 1:                                                 # (1 = sigmoid_beta alone: no d_lin, no contraction)
             lin = lin_buffers(B, n_pts, dev)
-            a.d_lin, a.lin_amax = _lib.ptr(lin[0]), _lib.ptr(lin[1])
-        with _lib.on_device(dev):
-            if wait_for is None:
-                rc = lib.e3dge_siren_render_bwd(ctypes.byref(a), _lib.stream_of(film))
-            else:
-                a.phase = 1                                                  # the backward of the compositing does not read the tangent
-                rc = lib.e3dge_siren_render_bwd(ctypes.byref(a), _lib.stream_of(film))
-                torch.cuda.current_stream(dev).wait_stream(wait_for)
-                if rc == 0:
-                    a.phase = 2
-                    rc = lib.e3dge_siren_render_bwd(ctypes.byref(a), _lib.stream_of(film))
-        _lib.check(rc, "e3dge_siren_render_bwd")
+            a.d_lin, a.lin_amax = lin
+        if wait_for is None:
+            _lib.launch("e3dge_siren_render_bwd", a)
+        else:
+            a.phase = 1                                                      # the backward of the compositing does not read the tangent
+            _lib.launch("e3dge_siren_render_bwd", a)
+            torch.cuda.current_stream(dev).wait_stream(wait_for)
+            a.phase = 2
+            _lib.launch("e3dge_siren_render_bwd", a)
         pgrads = ()
         if ctx.n_params > 1:
             styles, viewdirs = ctx.saved_tensors[10:]
@@ -965,10 +932,7 @@ class ResnetBlockFC(nn.Module):
             lib = _lib.load()
             packed = torch.empty(lib.e3dge_resblock_packed_floats(), device=dev, dtype=torch.float32)
             c = [p.detach().contiguous().float() for p in ps]
-            with _lib.on_device(dev):
-                rc = lib.e3dge_resblock_pack_weights(_lib.ptr(packed), *[_lib.ptr(t) for t in c], self.size_in,
-                                                     torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(rc, "e3dge_resblock_pack_weights")
+            _lib.launch("e3dge_resblock_pack_weights", packed, *c, self.size_in)
             wmax = max(float(t.abs().max().item()) for t in (c[0], c[2], c[4]))
             if wmax >= 500.0:              # the image stores 128 * w as f16
                 raise RuntimeError(f"texture-head weights up to {wmax:g} do not fit the f16x3 weight image (|w| < 500)")
@@ -985,10 +949,7 @@ class ResnetBlockFC(nn.Module):
             lib = _lib.load()
             packed = torch.empty(lib.e3dge_resblock_bwd_packed_floats(), device=dev, dtype=torch.float32)
             c = [p.detach().contiguous().float() for p in ps]
-            with _lib.on_device(dev):
-                rc = lib.e3dge_resblock_bwd_pack_weights(_lib.ptr(packed), *[_lib.ptr(t) for t in c], self.size_in,
-                                                         torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(rc, "e3dge_resblock_bwd_pack_weights")
+            _lib.launch("e3dge_resblock_bwd_pack_weights", packed, *c, self.size_in)
             # Range check of the f16x3 image (|w| < 500) without stalling the launch queue: a training head rebuilds this image every
             # step, and three blocking .item() reads per rebuild sat in front of every backward (round-5 advisor finding).  The first
             # image is checked synchronously; after that the maximum is reduced on the device, copied to pinned host memory without
@@ -1029,10 +990,7 @@ class ResnetBlockFC(nn.Module):
         ws = torch.empty(lib.e3dge_tex_modulations_bwd_ws_floats(n), device=x.device, dtype=torch.float32)
         net = torch.empty((n, 320), device=x.device, dtype=torch.float32) if want_net else None
         am = torch.zeros((4, _lib.AMAX_FLOATS), device=x.device, dtype=torch.float32) if want_amax else None
-        with _lib.on_device(x.device):
-            rc = lib.e3dge_tex_modulations_bwd(_lib.ptr(packed), _lib.ptr(x), self.size_in, n, _lib.ptr(d_alpha), _lib.ptr(d_beta),
-                                               _lib.ptr(dx), _lib.ptr(ws), _lib.ptr(net) if want_net else None, _lib.ptr(am), _lib.stream_of(x))
-        _lib.check(rc, "e3dge_tex_modulations_bwd")
+        _lib.launch("e3dge_tex_modulations_bwd", packed, x, self.size_in, n, d_alpha, d_beta, dx, ws, net, am)
         if want_amax:
             return dx, ws[:n * 320].view(n, 320), net, am
         return dx, ws[:n * 320].view(n, 320), net
@@ -1048,10 +1006,7 @@ class ResnetBlockFC(nn.Module):
         alpha = torch.empty((n, 256), device=f.device, dtype=torch.float32)
         beta = torch.empty((n, 256), device=f.device, dtype=torch.float32)
         packed = self.device_image()
-        with _lib.on_device(f.device):
-            rc = _lib.load().e3dge_tex_modulations_fwd(_lib.ptr(packed), _lib.ptr(f), self.size_in, n, _lib.ptr(alpha),
-                                                       _lib.ptr(beta), _lib.stream_of(f))
-        _lib.check(rc, "e3dge_tex_modulations_fwd")
+        _lib.launch("e3dge_tex_modulations_fwd", packed, f, self.size_in, n, alpha, beta)
         return alpha, beta
 
     def tex_film(self, feats, record_in, record_out, B, H, W, S):
@@ -1062,10 +1017,7 @@ class ResnetBlockFC(nn.Module):
         if f.shape[0] != B * H * W * S:
             raise RuntimeError(f"local features {tuple(feats.shape)} do not match the render ({B},{H},{W},{S},{self.size_in})")
         packed = self.device_image()
-        with _lib.on_device(f.device):
-            rc = _lib.load().e3dge_tex_film_fwd(_lib.ptr(packed), _lib.ptr(f), self.size_in, B, H, W, S, _lib.ptr(record_in),
-                                                _lib.ptr(record_out), _lib.stream_of(f))
-        _lib.check(rc, "e3dge_tex_film_fwd")
+        _lib.launch("e3dge_tex_film_fwd", packed, f, self.size_in, B, H, W, S, record_in, record_out)
         return record_out
 
     def tex_modulations(self, feats):
@@ -1330,14 +1282,8 @@ class VolumeFeatureRenderer(nn.Module):
         focal_c = focal.reshape(B).contiguous()
         near_c = near.reshape(B).contiguous()
         far_c = far.reshape(B).contiguous()
-        ta = tb = None
         lazy = tex_conditions if isinstance(tex_conditions, _LazyTex) else None
-        if tex_conditions is not None and lazy is None:
-            ta, tb = tex_conditions
-            _lib.require_gpu(ta, "tex alpha"); _lib.require_gpu(tb, "tex beta")
-            if tuple(ta.shape) != (B, H, Wd, S, 256) or tuple(tb.shape) != (B, H, Wd, S, 256):
-                raise RuntimeError(f"tex conditions must be (B,H,W,S,256) = {(B, H, Wd, S, 256)}; got {tuple(ta.shape)}")
-            ta, tb = ta.contiguous(), tb.contiguous()
+        ab = tex_conditions if lazy is None else None       # (alpha, beta) given, or materialised below when the record path is closed
         f32 = dict(device=dev, dtype=torch.float32)
         use = bb_out = None
         if reuse_key is not None and B > 0 and self._reuse_enabled(save_args):
@@ -1367,11 +1313,14 @@ class VolumeFeatureRenderer(nn.Module):
                 use['tex_buf'] = tb_
                 bb_in = lazy.head.tex_film(lazy.feats, use['buf'], tb_, B, H, Wd, S)
             else:
-                ta, tb = lazy.materialize()
-                _lib.require_gpu(ta, "tex alpha"); _lib.require_gpu(tb, "tex beta")
-                if tuple(ta.shape) != (B, H, Wd, S, 256) or tuple(tb.shape) != (B, H, Wd, S, 256):
-                    raise RuntimeError(f"tex conditions must be (B,H,W,S,256) = {(B, H, Wd, S, 256)}; got {tuple(ta.shape)}")
-                ta, tb = ta.contiguous(), tb.contiguous()
+                ab = lazy.materialize()
+        ta = tb = None
+        if ab is not None:
+            ta, tb = ab
+            _lib.require_gpu(ta, "tex alpha"); _lib.require_gpu(tb, "tex beta")
+            if tuple(ta.shape) != (B, H, Wd, S, 256) or tuple(tb.shape) != (B, H, Wd, S, 256):
+                raise RuntimeError(f"tex conditions must be (B,H,W,S,256) = {(B, H, Wd, S, 256)}; got {tuple(ta.shape)}")
+            ta, tb = ta.contiguous(), tb.contiguous()
         if use is not None:
             o1 = use['out']
             out = dict(o1, rgb=torch.empty((B, 3, H, Wd), **f32), features=torch.empty((B, 256, H, Wd), **f32))
@@ -1385,11 +1334,10 @@ class VolumeFeatureRenderer(nn.Module):
                 rays_d=torch.empty((B, H, Wd, 3), **f32), viewdirs=torch.empty((B, H, Wd, 3), **f32),
                 dists=torch.empty((B, H, Wd, S), **f32))
             own = tuple(out)
-        op = {k: (_lib.ptr(out[k]) if k in own else None) for k in out}
+        op = {k: (out[k] if k in own else None) for k in out}
         args = _lib.RenderArgs(
-            packed=_lib.ptr(packed), film=_lib.ptr(film), c2w=_lib.ptr(c2w_c), focal=_lib.ptr(focal_c),
-            near=_lib.ptr(near_c), far=_lib.ptr(far_c), t_vals=_lib.ptr(self.t_vals),
-            tex_alpha=_lib.ptr(ta), tex_beta=_lib.ptr(tb),
+            packed=packed, film=film, c2w=c2w_c, focal=focal_c, near=near_c, far=far_c, t_vals=self.t_vals,
+            tex_alpha=ta, tex_beta=tb,
             sigmoid_beta=self._sigmoid_beta_value(),
             box_scale=float(self.box_scale), mask_depth_thresh=float(self.mask_depth_thresh),
             batch=B, height=H, width=Wd, n_samples=S, res=int(self.out_im_res),
@@ -1397,12 +1345,9 @@ class VolumeFeatureRenderer(nn.Module):
             precision=self.siren.save_precision() if save_args is not None else self.siren.check_mode(self.siren.mfma_mode),
             rgb=op['rgb'], features=op['features'], xyz=op['xyz'], depth=op['depth'], mask=op['mask'], sdf=op['sdf'],
             weights=op['weights'], points=op['points'], rays_d=op['rays_d'], viewdirs=op['viewdirs'], dists=op['dists'],
-            save_args=_lib.ptr(save_args), backbone_out=_lib.ptr(bb_out),
-            backbone_in=_lib.ptr(bb_in) if use is not None else None,
-            weights_in=_lib.ptr(use['out']['weights']) if use is not None else None)
-        with _lib.on_device(dev):
-            rc = _lib.load().e3dge_siren_render_fwd(ctypes.byref(args), _lib.stream_of(c2w))
-        _lib.check(rc, "e3dge_siren_render_fwd")
+            save_args=save_args, backbone_out=bb_out, backbone_in=bb_in if use is not None else None,
+            weights_in=use['out']['weights'] if use is not None else None)
+        _lib.launch("e3dge_siren_render_fwd", args)
         if bb_out is not None:
             # the record keeps the geometry tensors a second pass returns (a few MB), not the first pass's rgb / features
             geo = {k: v for k, v in out.items() if k not in ('rgb', 'features')}
@@ -1619,7 +1564,6 @@ class VolumeFeatureRenderer(nn.Module):
                 raise RuntimeError(f"query_hitting_probability_fixed_interval: {name} must be a tensor on {dev} "
                                    f"(got {getattr(t, 'device', type(t))})")
         with torch.no_grad():
-            lib = _lib.load()
             N = H * W
             near = ro['near'].reshape(B, N).contiguous().float()
             far = ro['far'].reshape(B, N).contiguous().float()
@@ -1628,17 +1572,13 @@ class VolumeFeatureRenderer(nn.Module):
             q = torch.empty((B, N * S * Sn, 3), device=dev, dtype=torch.float32)
             aux = torch.empty((B, N, S, 4), device=dev, dtype=torch.float32)
             out = torch.empty((B, N, S), device=dev, dtype=torch.float32)
-            with _lib.on_device(dev):
-                st = _lib.stream_of(pts)
-                # launch 1: the Sn samples of the reference camera's ray through every point + where the point sits between them
-                _lib.check(lib.e3dge_hitprob_points(_lib.ptr(q), _lib.ptr(aux), _lib.ptr(pts), _lib.ptr(pc), _lib.ptr(ec), _lib.ptr(near),
-                                                    _lib.ptr(far), _lib.ptr(tv), B, N, S, Sn, st), "e3dge_hitprob_points")
-                # launch 2: sdf of all B*HW*S*Sn samples (view directions do not enter the sdf head)
-                sdf = self.siren.query_points(q, None, styles, self.box_scale, want_raw=False)[0]
-                # launch 3: alpha, transmittance scan without the far-plane stop, interpolation
-                _lib.check(lib.e3dge_hitprob_composite(_lib.ptr(out), _lib.ptr(sdf.contiguous()), _lib.ptr(aux), _lib.ptr(near), _lib.ptr(far),
-                                                       _lib.ptr(tv), float(self._sigmoid_beta_value()), int(return_type == 'visibility'),
-                                                       B, N, S, Sn, st), "e3dge_hitprob_composite")
+            # launch 1: the Sn samples of the reference camera's ray through every point + where the point sits between them
+            _lib.launch("e3dge_hitprob_points", q, aux, pts, pc, ec, near, far, tv, B, N, S, Sn)
+            # launch 2: sdf of all B*HW*S*Sn samples (view directions do not enter the sdf head)
+            sdf = self.siren.query_points(q, None, styles, self.box_scale, want_raw=False)[0]
+            # launch 3: alpha, transmittance scan without the far-plane stop, interpolation
+            _lib.launch("e3dge_hitprob_composite", out, sdf.contiguous(), aux, near, far, tv, float(self._sigmoid_beta_value()),
+                        int(return_type == 'visibility'), B, N, S, Sn)
         return out.reshape(B, H, W, S, 1)
 
     # -------------------------------------------------------------------------------------------------

@@ -2,7 +2,6 @@
 relu, contracted over the points in split-f16 x 3 MFMAs with a fixed-order split-K fold -- what autograd runs for ResnetBlockFC
 (helper_modules/resnetfc.py:49-58) and Fuse_sft_MLP (helper_modules/sft.py:84-110) in the reference's stage-2 step (e3dge_full_runner.py:185-317).
 E3DGE_WGRAD = hip (default) | library (torch matmul, rounds 2-4)."""
-import ctypes
 import os
 
 import torch
@@ -23,8 +22,7 @@ def amax_of(t):
     if t.numel() == 0:
         return am
     if t.is_contiguous() and t.data_ptr() % 16 == 0:
-        with _lib.on_device(t.device):
-            _lib.check(_lib.load().e3dge_amax(_lib.ptr(am), _lib.ptr(t), t.numel(), _lib.stream_of(t)), "e3dge_amax")
+        _lib.launch("e3dge_amax", am, t, t.numel())
     else:
         am[0] = t.abs().amax()
     return am
@@ -68,15 +66,13 @@ def wgrad(a, b, relu_b=False, amax_a=None, amax_b=None, out=None, colsum=False, 
     n_ws = lib.e3dge_wgrad_ws_floats(m, n_eff, P)
     ws = torch.empty(max(n_ws, 1), device=a.device, dtype=torch.float32)
     g = _lib.Wgrad()
-    g.a, g.amax_a, g.b, g.amax_b, g.c, g.ws = _lib.ptr(a), _lib.ptr(amax_a), _lib.ptr(b), _lib.ptr(amax_b), _lib.ptr(out), _lib.ptr(ws)
+    g.a, g.amax_a, g.b, g.amax_b, g.c, g.ws = a, amax_a, b, amax_b, out, ws
     g.ws_floats, g.n_rows = n_ws, P
     g.lda, g.off_a, g.m, g.ldb, g.off_b, g.n, g.ldc, g.relu_b = lda, 0, m, ldb, 0, n_eff, ldc, int(bool(relu_b))
-    g.colsum = _lib.ptr(cs)
+    g.colsum = cs
     if gap_col is not None:
         g.b_gap_at, g.b_gap = gap_col, 1
         g.xcol, g.ld_xcol = b.data_ptr() + 4 * gap_col, ldb
         g.ccol, g.ld_ccol = out.data_ptr() + 4 * gap_col, ldc
-    with _lib.on_device(a.device):
-        rc = lib.e3dge_wgrad(ctypes.byref(g), _lib.stream_of(a))
-    _lib.check(rc, "e3dge_wgrad")
+    _lib.launch("e3dge_wgrad", g)
     return (out, cs) if colsum else out

@@ -321,3 +321,49 @@ def test_modconv_weights_kernel():
         e = maxerr(out, want)
         record("modconv_weights", Co=Co, Ci=Ci, err=e)
         assert e <= 2e-6
+
+
+# ---- the launch path (_lib.launch) ---------------------------------------------------------------------------------------------------------
+def test_launch_error_names_the_symbol_that_ran(lib):
+    """An argument the entry point refuses before any kernel is queued comes back as a RuntimeError with the symbol's own name and the
+    library's message -- also for the ops that pick their symbol by dtype."""
+    a, b, c = torch.zeros(32, 24, device=DEV), torch.zeros(32, 24, device=DEV), torch.zeros(32, 32, device=DEV)
+    with pytest.raises(RuntimeError) as e:                      # k = 24 is no multiple of 16 (siren.hip: the entry point's first check)
+        _lib.launch("e3dge_selftest_mfma16", c, a, b, 24)
+    assert "e3dge_selftest_mfma16 " in str(e.value) and "selftest_mfma16: bad arguments" in str(e.value)
+    # e3dge_fused_bias_act_f16 indexes a bias of any length modulo its size, so five bias values on four channels are NOT refused
+    # (checked here); what its argument checks refuse is an element count outside int32.  The tensors are allocated, never touched.
+    x = torch.zeros(1, 4, 8, 8, device=DEV, dtype=torch.float16)
+    assert op.fused_leaky_relu(x, torch.zeros(5, device=DEV)).shape == x.shape
+    big = torch.empty(2, 2 ** 30, device=DEV, dtype=torch.float16)
+    with pytest.raises(RuntimeError) as e:
+        op.fused_leaky_relu(big)
+    assert "e3dge_fused_bias_act_f16 " in str(e.value) and "outside int32 range" in str(e.value)
+    del big
+    with pytest.raises(RuntimeError) as e:                      # a 33 x 33 FIR: upfirdn2d.hip refuses kernels outside 1..32
+        op.upfirdn2d(torch.zeros(1, 1, 40, 40, device=DEV, dtype=torch.float16), torch.ones(33, 33, device=DEV))
+    assert "e3dge_upfirdn2d_f16 " in str(e.value) and "33x33 outside 1..32" in str(e.value)
+    with pytest.raises(RuntimeError) as e:
+        op.upfirdn2d(torch.zeros(1, 1, 40, 40, device=DEV, dtype=torch.float64), torch.ones(33, 33, device=DEV))
+    assert "e3dge_upfirdn2d_f64 " in str(e.value)
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_launch_on_a_device_that_is_not_current(lib):
+    """Inputs on cuda:1 while cuda:0 is current: the launch goes to cuda:1 (same bits as on cuda:0; neither kernel uses atomics) and
+    the current device is left alone.  A tensor of the other device beside them raises instead of reaching the kernel."""
+    from e3dge_amd.local_query import pos_encoding
+    g = torch.Generator().manual_seed(5)
+    pts = torch.rand(1000, 3, generator=g) * 0.24 - 0.12
+    x, bias = torch.randn(2, 8, 16, 16, generator=g), torch.randn(8, generator=g)
+    torch.cuda.set_device(0)
+    ref_pe = pos_encoding(pts.to("cuda:0"), 7)
+    ref_act = op.fused_leaky_relu(x.to("cuda:0"), bias.to("cuda:0"))
+    pe = pos_encoding(pts.to("cuda:1"), 7)
+    act = op.fused_leaky_relu(x.to("cuda:1"), bias.to("cuda:1"))
+    assert torch.cuda.current_device() == 0
+    assert pe.device == torch.device("cuda:1") and act.device == torch.device("cuda:1")
+    assert torch.equal(pe.cpu(), ref_pe.cpu()) and torch.equal(act.cpu(), ref_act.cpu())
+    with pytest.raises(RuntimeError, match="e3dge_fused_bias_act"):
+        op.fused_bias_act(x.to("cuda:1"), bias.to("cuda:0"), None, 3, 0, 0.2, 1.0)
+    assert torch.cuda.current_device() == 0
