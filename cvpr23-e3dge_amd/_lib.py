@@ -188,6 +188,16 @@ class NoiseProjectArgs(_Args):
         (n, _vp) for n in ("out", "valid", "status", "ws")] + [("ws_bytes", _i64), ("bin_capacity", _i64)]
 
 
+LPIPS_LAYERS = 5
+
+
+class LpipsArgs(_Args):
+    """Mirror of struct E3dgeLpipsArgs (include/e3dge_hip.h)."""
+    _fields_ = [(n, _vp) for n in ("packed", "x", "y")] + [(n, _i32) for n in ("batch", "height", "width", "reserved")] + [
+        ("mean", _f32 * 3), ("std", _f32 * 3)] + [(n, _vp) for n in ("per_image", "per_layer", "mean_out")] + [
+        ("taps", _vp * LPIPS_LAYERS), ("ws", _vp), ("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -261,6 +271,11 @@ SIGNATURES = {
     "e3dge_image_metrics_scratch_floats": (_i64, [_i32, _i32, _i32, _i32]),
     "e3dge_image_metrics": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
     "e3dge_image_metric_row": (_i32, [_vp, _vp, _i32, _f32, _vp]),
+    "e3dge_lpips_packed_floats": (_i64, []),
+    "e3dge_lpips_pack_weights": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "e3dge_lpips_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "e3dge_lpips_forward": (_i32, [ctypes.POINTER(LpipsArgs), _vp]),
+    "e3dge_image_metric_row_lpips": (_i32, [_vp, _vp, _vp, _i32, _f32, _f32, _vp]),
     "e3dge_hitprob_points": (_i32, [_vp] * 8 + [_i32, _i64, _i32, _i32, _vp]),
     "e3dge_hitprob_composite": (_i32, [_vp] * 6 + [_f32, _i32, _i32, _i64, _i32, _i32, _vp]),
     "e3dge_align_volume": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

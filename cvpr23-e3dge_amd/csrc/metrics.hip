@@ -3,8 +3,8 @@
 //
 // Reference: Loss.calc_2d_rec_loss (project/losses/builder.py:130-184): loss_l2 = MSE, mae = L1, PSNR on the [0,1]-scaled
 // images, SSIM = 1 - kornia.losses.ssim_loss(pred, gt, window 5) (Gaussian window sigma 1.5, reflect padding,
-// C1 = 0.01^2, C2 = 0.03^2, loss = mean(clamp((1 - ssim) / 2, 0, 1))).  The identity / LPIPS terms need pretrained
-// networks and are outside the path (reported as 0 by the host code).
+// C1 = 0.01^2, C2 = 0.03^2, loss = mean(clamp((1 - ssim) / 2, 0, 1))).  The identity term needs a pretrained network and is
+// outside the path (reported as 0); the LPIPS term is csrc/lpips.hip, whose row kernel fills the loss_lpips column.
 //
 // One 32x32-pixel tile of one channel per workgroup: both images (+2-pixel reflected halo) staged in LDS once, the five
 // windowed moments of every pixel from 25 taps, per-workgroup partial sums (squared error, absolute error, SSIM loss) to a

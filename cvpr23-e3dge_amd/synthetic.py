@@ -123,6 +123,27 @@ def load_synthetic(module, seed=0, prefix=''):
     return module
 
 
+def load_synthetic_lpips(module, seed=0):
+    """Deterministic stand-ins for the pretrained weights of an `e3dge_amd.lpips.LPIPS` module (no checkpoint is reachable offline):
+    conv weights N(0, 2 / fan_in) (He: about half of every tap's ReLUs stay active), biases of std 0.1, lin weights |N(0,1)| * 4 / C
+    (trained lin weights are non-negative).  net.mean / net.std keep the reference's constants."""
+    sd = {}
+    for k, v in module.state_dict().items():
+        if k in ('net.mean', 'net.std'):
+            continue
+        t = synthetic_tensor('lpips.' + k, v.shape, seed)
+        if k.startswith('lin.'):
+            t = t.abs() * (4.0 / v.shape[1])
+        elif k.endswith('.weight'):
+            t = t * math.sqrt(2.0 / (v.shape[1] * v.shape[2] * v.shape[3]))
+        else:
+            t = t * 2.0                                               # synthetic_tensor's biases have std 0.05
+        sd[k] = t
+    missing, unexpected = module.load_state_dict(sd, strict=False)
+    assert not unexpected and sorted(missing) == ['net.mean', 'net.std'], (missing, unexpected)
+    return module
+
+
 STRESS_VARIANTS = {            # name: (SIREN hidden-weight factor, gamma-mapping weight factor, std of the W+ codes)
     "wide": (1.0, 1.0, 1.0),    # unit-variance styles: FiLM frequencies 13.5 .. 48 instead of 27.7 .. 32.3
     "s2": (2.0, 3.0, 0.3),      # per-layer gain 2: fp32 rounding amplified ~300x over the init-range fixtures, still well defined

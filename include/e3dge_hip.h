@@ -671,9 +671,53 @@ int e3dge_image_metrics(float* sums, float* scratch, const float* pred, const fl
                         int height, int width, float max_val, e3dge_stream_t stream);
 /* The eight columns builder.py:174-184 reports, from those sums (means over the whole batch tensor, as the reference's
  * losses are): row (8) = [loss_l2 = MSE, loss_id = 0, loss_lpips = 0, loss = l2_lambda * MSE, mae, PSNR of the images
- * rescaled to [0,1], SSIM = 1 - ssim_loss, ID_SIM = 1] -- the identity / LPIPS networks are outside the path and their
- * columns are what the reference reports with those lambdas at 0 (:145, :158-163). */
+ * rescaled to [0,1], SSIM = 1 - ssim_loss, ID_SIM = 1] -- the identity network is outside the path; this entry reports the
+ * identity and LPIPS columns as the reference does with those lambdas at 0 (:145, :158-163).  The LPIPS column is filled by
+ * e3dge_image_metric_row_lpips below. */
 int e3dge_image_metric_row(float* row, const float* sums, int batch, float l2_lambda, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * LPIPS-alex perceptual distance (csrc/lpips.hip).  Additions to ABI 16.  No allocation, no synchronisation.  Replaces
+ * LPIPS.forward (project/losses/lpips/lpips.py:33-39) with BaseNet.z_score / forward and AlexNet (networks.py:52-65, 80-89)
+ * and normalize_activation (utils.py:6-9), as calc_2d_rec_loss calls it (project/losses/builder.py:143, 168, 176):
+ *   z = (x - mean) / std per channel (zero padding applies to z);
+ *   conv 3->64 k11 s4 p2, relu [tap 1], maxpool 3 s2 (floor), conv 64->192 k5 p2, relu [tap 2], maxpool 3 s2, conv 192->384 k3 p1,
+ *   relu [tap 3], conv 384->256 k3 p1, relu [tap 4], conv 256->256 k3 p1, relu [tap 5];
+ *   f^ = f / (sqrt(sum_c f^2 + 1e-8) + 1e-10);  d_l[b] = mean_{h,w} sum_c lin_l[c] (x^_c - y^_c)^2;  per_image[b] = sum_l d_l[b].
+ * fp32 throughout (v_mfma_f32_16x16x4_f32); every sum is folded in a fixed order: bit-reproducible, and an image pair's value does
+ * not depend on the batch it is in.
+ *
+ * e3dge_lpips_packed_floats  floats of the packed weight image: the five conv weights in MFMA A-fragment order (K padded to a
+ *                            multiple of 32 with zeros), the five biases, the five lin rows.
+ * e3dge_lpips_pack_weights   w, b, lin: HOST arrays of five device pointers -- w[l] (C_out, C_in, k, k) contiguous as torchvision's
+ *                            features.{0,3,6,8,10}.weight, b[l] (C_out), lin[l] (C_out of layer l) the 1x1 weight of lin layer l
+ *                            (the renamed keys of utils.py:31-37).  One launch; call once per weight update.
+ * e3dge_lpips_ws_bytes       workspace bytes of a forward (-1: batch < 1 or height / width < 31, the smallest image for which every
+ *                            layer has an output).
+ * e3dge_lpips_forward        x, y (batch, 3, height, width) fp32 contiguous.  per_image (batch); per_layer NULL or (batch, 5) = d_l[b];
+ *                            mean_out NULL or (1) = (sum_b per_image[b]) / batch, summed in ascending b in fp32 -- the scalar
+ *                            lpips.py:39 returns; taps[l] NULL or (2 batch, C_l, H_l, W_l): the normalised features of x (images
+ *                            0..batch-1) and y (batch..2 batch-1).  Nine launches.  Fails before any launch on a null required pointer,
+ *                            batch < 1, height or width < 31, ws_bytes below e3dge_lpips_ws_bytes().
+ * e3dge_image_metric_row_lpips  e3dge_image_metric_row with the LPIPS column filled, in one launch: row[2] = (sum_b
+ *                            lpips_per_image[b]) / batch (the same fp32 sum as mean_out), row[3] = l2_lambda MSE + vgg_lambda row[2]
+ *                            (builder.py:168 with id_lambda = 0); the other six columns are e3dge_image_metric_row's, bit for bit.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct E3dgeLpipsArgs {
+    const float* packed; const float* x; const float* y;
+    int32_t batch, height, width, reserved;
+    float mean[3], std[3];            /* net.mean, net.std of the reference module (networks.py:41-46) */
+    float* per_image; float* per_layer; float* mean_out;
+    float* taps[5];
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeLpipsArgs;
+int64_t e3dge_lpips_packed_floats(void);
+int e3dge_lpips_pack_weights(float* packed, const float* const* w, const float* const* b, const float* const* lin, e3dge_stream_t stream);
+int64_t e3dge_lpips_ws_bytes(int batch, int height, int width);
+int e3dge_lpips_forward(const E3dgeLpipsArgs* args, e3dge_stream_t stream);
+int e3dge_image_metric_row_lpips(float* row, const float* sums, const float* lpips_per_image, int batch, float l2_lambda,
+                                 float vgg_lambda, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Surface extraction, device half: replaces align_volume (project/utils/mesh_utils.py:17-44; called on the rendered
