@@ -23,6 +23,11 @@ constexpr int kWsSets = 4;
 constexpr int kWsSetBytes = 32 * 1024, kWsHalfBytes = 16 * 1024;
 constexpr int kWsXBytes = kWsSets * kWsSetBytes;
 constexpr int kWsSteps = 8;          // k-steps of 32
+// The lo half of the weight image is stored 2^10 times too large and meets activations 2^10 times too small (exact powers of two).
+// 128 W splits into hi + lo with |lo| < 2^-10 |hi|: for |W| < 2^-10 a plain lo is below 2^-14, an f16 SUBNORMAL of spacing 2^-24, and the
+// weight kept 2^-31 absolute instead of 2^-21 relative (tests/test_gpu_ws_linear.py::test_pack_one_product_per_output: 2^-14 of a weight
+// of 1e-6).  Scaled, lo stays normal down to |W| = 2^-20 and below 2^15 for the largest hi.
+constexpr float kWsLoUp = 1024.0f, kWsLoDown = 1.0f / 1024.0f;
 
 struct WsRegs {
     u32x4 wh[2][kWsSteps], wl[2][kWsSteps];      // this wave's 32 output features (two 16-row tiles) x K = 256, hi and lo
@@ -214,15 +219,18 @@ __global__ void __launch_bounds__(kWsThreads) ws_linear_kernel(const WsLinK a) {
                     xl[g & 1][pt] = rescaled(xl[g & 1][pt], ratio);
                 }
 #pragma unroll
-                for (int pass = 0; pass < 3; ++pass)
+                for (int pass = 0; pass < 3; ++pass) {
+                    u32x4 xs[2];                                             // the partner of the scaled lo weights (kWsLoUp): xh / 2^10
+                    if (pass == 1) { xs[0] = rescaled(xh[g & 1][0], kWsLoDown); xs[1] = rescaled(xh[g & 1][1], kWsLoDown); }
 #pragma unroll
                     for (int ft = 0; ft < 2; ++ft)
 #pragma unroll
                         for (int pt = 0; pt < 2; ++pt) {
                             const u32x4 wa = (pass == 1) ? R.wl[ft][g] : R.wh[ft][g];
-                            const u32x4 xb = (pass == 2) ? xl[g & 1][pt] : xh[g & 1][pt];
+                            const u32x4 xb = (pass == 2) ? xl[g & 1][pt] : (pass == 1) ? xs[pt] : xh[g & 1][pt];
                             acc.t[ft][pt] = mfma16x16(wa, xb, (g == 0 && pass == 0) ? zero4() : acc.t[ft][pt]);
                         }
+                }
             }
             // ---- post: this lane's features 32 wave + 16 ft + 4 q .. + 3 of the rows 16 pt + n of the set ----
             // (all residual loads of the set first, unconditional lanes on clamped rows -- see stage_load)
@@ -300,7 +308,7 @@ __global__ void __launch_bounds__(kWsThreads) ws_linear_kernel(const WsLinK a) {
 namespace e3dge {
 // weight image of ws_linear_kernel from fp32 weights (n_layers, 256 out, 256 in): word `wd` (two f16) of lane l (n = l & 15,
 // q = l >> 4) of [layer][wave][g][ft][hi | lo] holds 128 W[32 wave + 16 ft + n][32 g + 8 q + 2 wd], + 1 -- hi = round-toward-zero
-// f16 of the scaled value, lo = f16 of the remainder (as split2)
+// f16 of the scaled value, lo = f16 (round toward zero) of kWsLoUp x the remainder
 __global__ void __launch_bounds__(256) ws_pack_kernel(unsigned* __restrict__ img, const float* __restrict__ w, int64_t n_words) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_words; e += (int64_t)gridDim.x * 256) {
         int64_t r = e;
@@ -313,8 +321,10 @@ __global__ void __launch_bounds__(256) ws_pack_kernel(unsigned* __restrict__ img
         const int layer = (int)r;
         const int f = 32 * wave + 16 * ft + (lane & 15), k = 32 * g + 8 * (lane >> 4) + 2 * wd;
         const float* src = w + ((int64_t)layer * kWidth + f) * kWidth + k;
-        const HiLo p = split2(src[0] * kW16Scale, src[1] * kW16Scale);
-        img[e] = hl ? p.l : p.h;
+        const float s0 = src[0] * kW16Scale, s1 = src[1] * kW16Scale;
+        const unsigned h = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(s0, s1));
+        const unsigned l = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz((s0 - f16lo(h)) * kWsLoUp, (s1 - f16hi(h)) * kWsLoUp));   // (the remainders are exact)
+        img[e] = hl ? l : h;
     }
 }
 }  // namespace e3dge
