@@ -37,14 +37,17 @@ constexpr int k16Slots = 2;                      // rays a 16-point slab can tou
 constexpr int k16Ring = 2;
 
 // ---- LDS carve (floats) ----
-constexpr int k16LdsW = 0;
-constexpr int k16LdsFilm = k16LdsW + k16NBuf * k16ChunkFloats;        // [9][2][256]
+// The small tables come first: everything the tile streams read from them lies below 64 KiB, inside the 16-bit offset field of a
+// ds_read, so a FiLM row or a view record is one base register + an immediate (behind the weight buffers, at 0x14000 and up, every
+// tile rebuilt two addresses in the VALU).
+constexpr int k16LdsFilm = 0;                                         // [9][2][256]
 constexpr int k16LdsHead = k16LdsFilm + 9 * 2 * kWidth;               // w_sigma[256], w_rgb[3][256], b_sigma, b_rgb[3]
 constexpr int k16LdsW0 = k16LdsHead + kHeadFloats;                    // [3][256] first-layer weights, column-major
 // [2][256][4] per-feature record of the view layer, one ds_read_b128 per half: (gamma, beta, w_r, w_g), (w_b, view-direction
 // columns x, y, z x128) -- gamma / beta as in the FiLM block (bias folded in, 1/128 divided out), w_rgb a copy of the head's
 constexpr int k16LdsVrec = k16LdsW0 + 3 * kWidth;
-constexpr int k16LdsFeat = k16LdsVrec + 2 * 4 * kWidth;               // [kRMax][kFPitch]
+constexpr int k16LdsW = k16LdsVrec + 2 * 4 * kWidth;                  // [k16NBuf] weight chunks
+constexpr int k16LdsFeat = k16LdsW + k16NBuf * k16ChunkFloats;        // [kRMax][kFPitch]
 constexpr int k16LdsPart = k16LdsFeat + kRMax * kFPitch;              // [8 waves][2 slots][256]
 constexpr int k16LdsAlpha = ((k16LdsPart + 8 * k16Slots * kWidth + 3) / 4) * 4;
 constexpr int k16LdsWgt = k16LdsAlpha + kTilePts;
@@ -57,7 +60,8 @@ constexpr int k16LdsVd = k16LdsWq + 8 * k16Slots * 16;                // [8 wave
 constexpr int k16LdsFloats = k16LdsVd + 8 * 16 * 4;
 constexpr int k16LdsBytes = k16LdsFloats * 4;
 static_assert(k16LdsBytes <= 160 * 1024, "LDS budget");
-static_assert((k16LdsFilm % 4) == 0 && (k16LdsHead % 4) == 0 && (k16LdsW0 % 4) == 0 && (k16LdsVrec % 4) == 0, "alignment");
+static_assert((k16LdsFilm % 4) == 0 && (k16LdsHead % 4) == 0 && (k16LdsW0 % 4) == 0 && (k16LdsVrec % 4) == 0 && (k16LdsW % 4) == 0, "alignment");
+static_assert(k16LdsW * 4 <= 64 * 1024, "the tables stay inside the ds_read offset field");
 
 // one 16-byte store of saved state: non-temporal (against plain stores an A/B of round 6)
 __device__ __forceinline__ void save_st4(float* p, const f32x4v& v) {
@@ -416,6 +420,14 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
     };
     // packed f16 (hi, lo) activations of this wave's 16 points: word 2e + (r >> 1), half r & 1 of in?[g] = feature 32g + 16e + 4q + r
     u32x4 inH[k16Steps], inL[k16Steps], outH[k16Steps], outL[k16Steps];
+    // Inference renders run the hidden layers without a seam: the layers alternate between the two arrays (no `in := out` copies) and
+    // the last tile's epilogue of a layer runs inside the first tile of the next one, so the backbone output ends up in `out` when the
+    // number of hidden layers is odd.  The saving forward and the point query keep the seam (epilogue behind the layer, copy back):
+    // their counted waits depend on where the argument stores sit, and they are at the register limit when unrolled further.
+    constexpr bool kSeamless = MODE == 0 && !SAVE;
+    constexpr bool kFinalOut = kSeamless && ((E3DGE_SIREN_DEPTH - 1) & 1) != 0;
+    u32x4 (&hH)[k16Steps] = kFinalOut ? outH : inH;       // layer 7's output: sdf head, layer-7 record, texture FiLM, view layer
+    u32x4 (&hL)[k16Steps] = kFinalOut ? outL : inL;
 #ifdef E3DGE_PHASE_TIMING
     unsigned long long tstamp[18];
     for (int i = 0; i < 18; ++i) tstamp[i] = 0;
@@ -498,6 +510,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
         // =====================================================================================
         // 2. layer 0 (3 -> 256) in the VALU: every lane its 4 features of each tile
         // =====================================================================================
+        f32x4v prev = zero4();        // a tile's four accumulator sums, until its epilogue has run (seamless: also over a layer boundary)
         if (CACHE != 2) {
             const float xs = __fmul_rn(px, a.box_scale), ys = __fmul_rn(py, a.box_scale), zs = __fmul_rn(pz, a.box_scale);
 #pragma unroll
@@ -505,17 +518,23 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
                 const int o = 16 * t + 4 * q;
                 const f32x4v wx = *reinterpret_cast<const f32x4v*>(w0_s + o), wy = *reinterpret_cast<const f32x4v*>(w0_s + kWidth + o),
                              wz = *reinterpret_cast<const f32x4v*>(w0_s + 2 * kWidth + o);
-                const f32x4v g4 = *reinterpret_cast<const f32x4v*>(film + o), b4 = *reinterpret_cast<const f32x4v*>(film + kWidth + o);
-                f32x4v arg, v;
+                f32x4v lin;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float lin = fmaf(wz[r], zs, fmaf(wy[r], ys, wx[r] * xs));
-                    arg[r] = fmaf(g4[r], lin, b4[r]);
-                    v[r] = sin_f32(arg[r]);
+                for (int r = 0; r < 4; ++r) lin[r] = fmaf(wz[r], zs, fmaf(wy[r], ys, wx[r] * xs));
+                if (kSeamless && t == k16Tiles - 1) {      // the last tile's FiLM + sine run inside layer 1's first tile, like every layer's
+                    prev = lin;
+                } else {
+                    const f32x4v g4 = *reinterpret_cast<const f32x4v*>(film + o), b4 = *reinterpret_cast<const f32x4v*>(film + kWidth + o);
+                    f32x4v arg, v;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        arg[r] = fmaf(g4[r], lin[r], b4[r]);
+                        v[r] = sin_f32(arg[r]);
+                    }
+                    if (SAVE) save_st4(sv + t * sv_ts, arg);
+                    SPLIT2_TO(v[0], v[1], inH[t >> 1][2 * (t & 1)], inL[t >> 1][2 * (t & 1)]);
+                    SPLIT2_TO(v[2], v[3], inH[t >> 1][2 * (t & 1) + 1], inL[t >> 1][2 * (t & 1) + 1]);
                 }
-                if (SAVE) save_st4(sv + t * sv_ts, arg);
-                SPLIT2_TO(v[0], v[1], inH[t >> 1][2 * (t & 1)], inL[t >> 1][2 * (t & 1)]);
-                SPLIT2_TO(v[2], v[3], inH[t >> 1][2 * (t & 1) + 1], inL[t >> 1][2 * (t & 1) + 1]);
             }
         }
 
@@ -525,35 +544,40 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
         // =====================================================================================
         // (A role split of the two waves of a SIMD -- GEMM segment / epilogue segment in opposite phases, two barriers per tile -- was
         // built and measured 5 % slower; the code is in the history at da20f64.)
-#pragma unroll 1
-        for (int L = 1; L < ((CACHE == 2) ? 0 : E3DGE_SIREN_DEPTH); ++L) {
-            const float* __restrict__ film_l = film + L * 2 * kWidth;
-            f32x4v prev = zero4();
-            auto finish = [&](int tp, const f32x4v& pv) {      // whole epilogue of tile tp (used for the layer's last tile)
-                const int o = 16 * tp + 4 * q;
-                const f32x4v g4 = *reinterpret_cast<const f32x4v*>(film_l + o), b4 = *reinterpret_cast<const f32x4v*>(film_l + kWidth + o);
-                f32x4v arg, v;
+        // whole epilogue of tile tp of layer L at once, FiLM row `fl` (where no following tile is there to carry it)
+        auto finish = [&](const float* __restrict__ fl, int L, int tp, const f32x4v& pv, auto& dH, auto& dL) {
+            const int o = 16 * tp + 4 * q;
+            const f32x4v g4 = *reinterpret_cast<const f32x4v*>(fl + o), b4 = *reinterpret_cast<const f32x4v*>(fl + kWidth + o);
+            f32x4v arg, v;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { arg[r] = fmaf(g4[r], pv[r], b4[r]); v[r] = sin_f32(arg[r]); }
-                if (SAVE) save_st4(sv + L * sv_ls + tp * sv_ts, arg);
-                SPLIT2_TO(v[0], v[1], outH[tp >> 1][2 * (tp & 1)], outL[tp >> 1][2 * (tp & 1)]);
-                SPLIT2_TO(v[2], v[3], outH[tp >> 1][2 * (tp & 1) + 1], outL[tp >> 1][2 * (tp & 1) + 1]);
-            };
+            for (int r = 0; r < 4; ++r) { arg[r] = fmaf(g4[r], pv[r], b4[r]); v[r] = sin_f32(arg[r]); }
+            if (SAVE) save_st4(sv + L * sv_ls + tp * sv_ts, arg);
+            SPLIT2_TO(v[0], v[1], dH[tp >> 1][2 * (tp & 1)], dL[tp >> 1][2 * (tp & 1)]);
+            SPLIT2_TO(v[2], v[3], dH[tp >> 1][2 * (tp & 1) + 1], dL[tp >> 1][2 * (tp & 1) + 1]);
+        };
+        // Layer L from (sH, sL) into (dH, dL).  Seamless: tile 0 carries the epilogue of the PREVIOUS layer's last tile -- `prev` and the
+        // FiLM row of layer L-1, into words 2, 3 of s?[7], which only k-step 7 reads and stage 4 has written by then -- and the layer
+        // leaves its own last tile in `prev`.  One base register for both FiLM rows: the reads are ds_read_b128 base offset:imm.
+        auto hidden_layer = [&](int L, auto& sH, auto& sL, auto& dH, auto& dL) {
+            const float* __restrict__ film_p = film + (L - 1) * 2 * kWidth;
 #pragma unroll
             for (int t = 0; t < k16Tiles; ++t) {
                 f32x4v acc = zero4(), accb = zero4();
-                if (t == 0) {
-                    tile16<false>(pipe, lane, inH, inL, acc, accb, ringH, ringL, [](int) {}, [&]() { fwd_hook(2); }, t % k16NBuf);
+                if (t == 0 && !kSeamless) {
+                    tile16<false>(pipe, lane, sH, sL, acc, accb, ringH, ringL, [](int) {}, [&]() { fwd_hook(2); }, t % k16NBuf);
                 } else {
-                    const int o = 16 * (t - 1) + 4 * q;
+                    const int tp = (t == 0) ? k16Tiles - 1 : t - 1;
+                    const int o = ((t == 0) ? 0 : 2 * kWidth) + 16 * tp + 4 * q;
+                    auto& eH = (t == 0) ? sH : dH;
+                    auto& eL = (t == 0) ? sL : dL;
                     f32x4v g4 = zero4(), b4 = zero4(), arg4 = zero4(), kf4 = zero4(), x4 = zero4();
-                    tile16<false>(pipe, lane, inH, inL, acc, accb, ringH, ringL, [&](int g) {
-                        // the FiLM + sine + split of tile t-1's four values, staged over the k-steps with the four values side by
+                    tile16<false>(pipe, lane, sH, sL, acc, accb, ringH, ringL, [&](int g) {
+                        // the FiLM + sine + split of tile tp's four values, staged over the k-steps with the four values side by
                         // side: every slice is four independent instructions deep instead of one dependent chain (a lone chain
                         // leaves the wave -- in order -- waiting on VALU latency with nothing else to issue)
                         if (g == 0) {
-                            g4 = *reinterpret_cast<const f32x4v*>(film_l + o);
-                            b4 = *reinterpret_cast<const f32x4v*>(film_l + kWidth + o);
+                            g4 = *reinterpret_cast<const f32x4v*>(film_p + o);
+                            b4 = *reinterpret_cast<const f32x4v*>(film_p + kWidth + o);
                         } else if (g == 1) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) arg4[r] = fmaf(g4[r], prev[r], b4[r]);
@@ -571,10 +595,10 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
 #else
                             for (int r = 0; r < 4; ++r) x4[r] = sin_poly_f32(arg4[r]);
 #endif
-                            if (SAVE) save_st4(sv + L * sv_ls + (t - 1) * sv_ts, arg4);
+                            if (SAVE) save_st4(sv + L * sv_ls + tp * sv_ts, arg4);
                         } else if (g == 4) {
-                            SPLIT2_TO(x4[0], x4[1], outH[(t - 1) >> 1][2 * ((t - 1) & 1)], outL[(t - 1) >> 1][2 * ((t - 1) & 1)]);
-                            SPLIT2_TO(x4[2], x4[3], outH[(t - 1) >> 1][2 * ((t - 1) & 1) + 1], outL[(t - 1) >> 1][2 * ((t - 1) & 1) + 1]);
+                            SPLIT2_TO(x4[0], x4[1], eH[tp >> 1][2 * (tp & 1)], eL[tp >> 1][2 * (tp & 1)]);
+                            SPLIT2_TO(x4[2], x4[3], eH[tp >> 1][2 * (tp & 1) + 1], eL[tp >> 1][2 * (tp & 1) + 1]);
                         }
                     // (guaranteed operations younger than chunk t+1: the two pieces of hook t-1 and the stores of tiles t-3, t-2 -- none
                     // guaranteed in front of a layer's first tiles: the view layer's stores are predicated)
@@ -583,9 +607,28 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
                 pipe.advance();
                 prev = acc + accb;
             }
-            finish(k16Tiles - 1, prev);
+        };
+        if constexpr (kSeamless) {
+            if (CACHE != 2) {
+                // two layer bodies, in -> out and out -> in, in one loop (not one body per layer: the pair is the hot set of the
+                // instruction cache)
+#pragma unroll 1
+                for (int L = 1; L < E3DGE_SIREN_DEPTH; L += 2) {
+                    hidden_layer(L, inH, inL, outH, outL);
+                    if (L + 1 >= E3DGE_SIREN_DEPTH) break;
+                    hidden_layer(L + 1, outH, outL, inH, inL);
+                }
+                // the sdf head needs all of layer 7: its last tile's epilogue stays exposed, once per sub-tile
+                finish(film + (E3DGE_SIREN_DEPTH - 1) * 2 * kWidth, E3DGE_SIREN_DEPTH - 1, k16Tiles - 1, prev, hH, hL);
+            }
+        } else {
+#pragma unroll 1
+            for (int L = 1; L < E3DGE_SIREN_DEPTH; ++L) {
+                hidden_layer(L, inH, inL, outH, outL);
+                finish(film + L * 2 * kWidth, L, k16Tiles - 1, prev, outH, outL);
 #pragma unroll
-            for (int g = 0; g < k16Steps; ++g) { inH[g] = outH[g]; inL[g] = outL[g]; }
+                for (int g = 0; g < k16Steps; ++g) { inH[g] = outH[g]; inL[g] = outL[g]; }
+            }
         }
 
         if (CACHE != 0) {
@@ -593,11 +636,11 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
             if (CACHE == 1) {
                 u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(a.bb_out) + rec;
 #pragma unroll
-                for (int g = 0; g < k16Steps; ++g) { dst[(g * 2 + 0) * 64] = inH[g]; dst[(g * 2 + 1) * 64] = inL[g]; }
+                for (int g = 0; g < k16Steps; ++g) { dst[(g * 2 + 0) * 64] = hH[g]; dst[(g * 2 + 1) * 64] = hL[g]; }
             } else {
                 const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(a.bb_in) + rec;
 #pragma unroll
-                for (int g = 0; g < k16Steps; ++g) { inH[g] = src[(g * 2 + 0) * 64]; inL[g] = src[(g * 2 + 1) * 64]; }
+                for (int g = 0; g < k16Steps; ++g) { hH[g] = src[(g * 2 + 0) * 64]; hL[g] = src[(g * 2 + 1) * 64]; }
             }
         }
 
@@ -614,10 +657,10 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
             for (int t = 0; t < k16Tiles; ++t) {
                 const f32x4v w4 = *reinterpret_cast<const f32x4v*>(head_s + 16 * t + 4 * q);
                 const int g = t >> 1, w0i = 2 * (t & 1);
-                acc = fma_mix_h<0>(inH[g][w0i], w4[0], acc); acc = fma_mix_h<0>(inL[g][w0i], w4[0], acc);
-                acc = fma_mix_h<1>(inH[g][w0i], w4[1], acc); acc = fma_mix_h<1>(inL[g][w0i], w4[1], acc);
-                acc = fma_mix_h<0>(inH[g][w0i + 1], w4[2], acc); acc = fma_mix_h<0>(inL[g][w0i + 1], w4[2], acc);
-                acc = fma_mix_h<1>(inH[g][w0i + 1], w4[3], acc); acc = fma_mix_h<1>(inL[g][w0i + 1], w4[3], acc);
+                acc = fma_mix_h<0>(hH[g][w0i], w4[0], acc); acc = fma_mix_h<0>(hL[g][w0i], w4[0], acc);
+                acc = fma_mix_h<1>(hH[g][w0i], w4[1], acc); acc = fma_mix_h<1>(hL[g][w0i], w4[1], acc);
+                acc = fma_mix_h<0>(hH[g][w0i + 1], w4[2], acc); acc = fma_mix_h<0>(hL[g][w0i + 1], w4[2], acc);
+                acc = fma_mix_h<1>(hH[g][w0i + 1], w4[3], acc); acc = fma_mix_h<1>(hL[g][w0i + 1], w4[3], acc);
             }
             sdf = sum_over_q(acc) + head_s[4 * kWidth];
         }
@@ -685,9 +728,9 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
                 const f32x4v b4 = *reinterpret_cast<const f32x4v*>(tb + 16 * t + 4 * q);
                 float y[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) y[r] = __fadd_rn(__fmul_rn(__fadd_rn(a4[r], 1.0f), act16_get(inH, inL, t, r)), b4[r]);
-                SPLIT2_TO(y[0], y[1], inH[t >> 1][2 * (t & 1)], inL[t >> 1][2 * (t & 1)]);
-                SPLIT2_TO(y[2], y[3], inH[t >> 1][2 * (t & 1) + 1], inL[t >> 1][2 * (t & 1) + 1]);
+                for (int r = 0; r < 4; ++r) y[r] = __fadd_rn(__fmul_rn(__fadd_rn(a4[r], 1.0f), act16_get(hH, hL, t, r)), b4[r]);
+                SPLIT2_TO(y[0], y[1], hH[t >> 1][2 * (t & 1)], hL[t >> 1][2 * (t & 1)]);
+                SPLIT2_TO(y[2], y[3], hH[t >> 1][2 * (t & 1) + 1], hL[t >> 1][2 * (t & 1) + 1]);
             }
         }
 
@@ -787,7 +830,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
             auto load_rec = [&](int t) { ra = vra[16 * t]; rb = vrb[16 * t]; };     // after stage 3: the last use of the previous record
             auto view_tile = [&](int t, int sbuf) {
                 f32x4v acc = zero4(), accb = zero4();
-                tile16<true>(pipe, lane, inH, inL, acc, accb, ringH, ringL, [&](int g) {
+                tile16<true>(pipe, lane, hH, hL, acc, accb, ringH, ringL, [&](int g) {
                     if (t > 0 && g <= 5) epi(t - 1, g);
                     if (g == 4) load_rec(t);
                 }, [&]() { fwd_hook(2); }, sbuf);
