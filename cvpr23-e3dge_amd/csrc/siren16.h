@@ -136,6 +136,9 @@ __device__ __forceinline__ float wave_sum_last(float x) {      // the sum over t
 // 16-KiB weight chunks through k16NBuf LDS buffers; every wave moves a 2-KiB slice (two LDS-DMA pieces) of each chunk.
 //   tile g: sync() -> wait for everything but the chunk issued one tile ago, barrier (publishes chunk g+2, proves tile g-1 is
 //   finished) -> issue chunk g+3 into the buffer tile g-1 used: two tile times to arrive.
+// The chunk may be issued anywhere in tile g behind that barrier, as long as its two pieces stay in this order and in this tile
+// (the counted wait is about the youngest two operations): the inference renders issue them two and three k-steps behind the
+// barrier, one piece per k-step (issue_piece), everything else right behind it (issue_chunk).
 struct ChunkPipe16 {
     const char* img;
     uint32_t voff, lds_base;
@@ -161,6 +164,17 @@ struct ChunkPipe16 {
         glds16_saddr<1024>(s, voff, d);
         idx = (idx + 1 == count) ? 0 : idx + 1;
         buf = (buf + 1 == k16NBuf) ? 0 : buf + 1;
+    }
+    template <int PIECE> __device__ __forceinline__ void issue_piece() {      // issue_chunk() as two calls: PIECE 0, then PIECE 1
+        const char* s = img + (size_t)idx * (k16ChunkFloats * 4);
+        const uint32_t d = lds_base + (uint32_t)buf * (k16ChunkFloats * 4);
+        if (PIECE == 0) {
+            glds16_saddr<0>(s, voff, d);
+        } else {
+            glds16_saddr<1024>(s, voff, d);
+            idx = (idx + 1 == count) ? 0 : idx + 1;
+            buf = (buf + 1 == k16NBuf) ? 0 : buf + 1;
+        }
     }
     __device__ __forceinline__ void prime() {
         issue_chunk(); issue_chunk(); issue_chunk();
@@ -201,7 +215,8 @@ __device__ unsigned long long g_trace16[2][24];
 
 // K = 256 contraction of one 16-feature tile: 8 k-steps x (hi*hi, lo*hi, hi*lo) on two alternating accumulators.
 // On entry the ring holds k-steps 0..2 of this chunk; on exit k-steps 0..2 of the next one.
-// `hook()` runs once, after k-step 1: the chunk wait + workgroup barrier + next DMA issue (and whatever else has to sit there).
+// `hook()` runs once, after k-step 1: the chunk wait + workgroup barrier + next DMA issue (and whatever else has to sit there;
+// the inference renders issue the DMA from `epi`, in k-steps kDmaStep and kDmaStep + 1 -- see siren16_kernel).
 template <bool TRANSPOSED, int RING = k16Ring, class Epi, class Hook>
 __device__ __forceinline__ void tile16(ChunkPipe16& pipe, int lane, const u32x4 (&aH)[k16Steps], const u32x4 (&aL)[k16Steps],
                                        f32x4v& acc, f32x4v& accb, u32x4 (&ringH)[RING], u32x4 (&ringL)[RING], Epi&& epi,
@@ -405,6 +420,20 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
     // (s_waitcnt vmcnt(0), and __syncthreads() adds the same for the compiler's own stores): every tile of the saving forward waited for
     // its previous tile's stores to reach L2 -- +40 % over the plain forward.  Now a counted wait (the chunk of tile t+1 was issued at
     // hook t-2; younger than it: `younger` guaranteed operations) and a barrier in asm, as in siren16_bwd.h.
+    // Inference renders (MODE 0, no SAVE, every CACHE): the hook only waits; the two DMA pieces of the next chunk go out in k-steps
+    // kDmaStep and kDmaStep + 1 of the same tile, one each.  Right behind the barrier all eight waves issued theirs at the same moment,
+    // each in front of its own k-step-1 epilogue slice and with its partner's MFMAs waiting for the pipe.  Same chunks, same order, same
+    // counted wait (the youngest two operations at a hook are still the previous tile's pieces).  Kernel time -2.6 % against the parent
+    // (medians 0.28992 -> 0.28240 ms, profiles/r9_ab.txt visit 4); the other placements measured are in DESIGN.md 4.1c, round 9.  The
+    // saving forward and the point query keep issue_chunk() in the hook: their hand-counted waits depend on where the pieces sit
+    // between the argument stores.
+    constexpr bool kSeamless = MODE == 0 && !SAVE;      // (also: the hidden layers run without a seam, below)
+    constexpr bool kDmaInTile = kSeamless;              // every tile of these renders has an epilogue lambda, which calls dma_step()
+    constexpr int kDmaStep = 3;
+    auto dma_step = [&](int g) {
+        if (kDmaInTile && g == kDmaStep) pipe.template issue_piece<0>();
+        if (kDmaInTile && g == kDmaStep + 1) pipe.template issue_piece<1>();
+    };
     auto fwd_hook = [&](int younger) {          // younger: compile-time constant at every call site; ignored without SAVE
         if (SAVE) {
             switch (younger) {
@@ -416,15 +445,14 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
         } else {
             pipe.template sync<false>();
         }
-        pipe.issue_chunk();
+        if (!kDmaInTile) pipe.issue_chunk();
     };
     // packed f16 (hi, lo) activations of this wave's 16 points: word 2e + (r >> 1), half r & 1 of in?[g] = feature 32g + 16e + 4q + r
     u32x4 inH[k16Steps], inL[k16Steps], outH[k16Steps], outL[k16Steps];
-    // Inference renders run the hidden layers without a seam: the layers alternate between the two arrays (no `in := out` copies) and
+    // Inference renders (kSeamless, above) run the hidden layers without a seam: the layers alternate between the two arrays (no `in := out` copies) and
     // the last tile's epilogue of a layer runs inside the first tile of the next one, so the backbone output ends up in `out` when the
     // number of hidden layers is odd.  The saving forward and the point query keep the seam (epilogue behind the layer, copy back):
     // their counted waits depend on where the argument stores sit, and they are at the register limit when unrolled further.
-    constexpr bool kSeamless = MODE == 0 && !SAVE;
     constexpr bool kFinalOut = kSeamless && ((E3DGE_SIREN_DEPTH - 1) & 1) != 0;
     u32x4 (&hH)[k16Steps] = kFinalOut ? outH : inH;       // layer 7's output: sdf head, layer-7 record, texture FiLM, view layer
     u32x4 (&hL)[k16Steps] = kFinalOut ? outL : inL;
@@ -563,6 +591,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
 #pragma unroll
             for (int t = 0; t < k16Tiles; ++t) {
                 f32x4v acc = zero4(), accb = zero4();
+                static_assert(!kDmaInTile || kSeamless, "a tile without an epilogue lambda issues its chunk in the hook only");
                 if (t == 0 && !kSeamless) {
                     tile16<false>(pipe, lane, sH, sL, acc, accb, ringH, ringL, [](int) {}, [&]() { fwd_hook(2); }, t % k16NBuf);
                 } else {
@@ -575,6 +604,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
                         // the FiLM + sine + split of tile tp's four values, staged over the k-steps with the four values side by
                         // side: every slice is four independent instructions deep instead of one dependent chain (a lone chain
                         // leaves the wave -- in order -- waiting on VALU latency with nothing else to issue)
+                        dma_step(g);
                         if (g == 0) {
                             g4 = *reinterpret_cast<const f32x4v*>(film_p + o);
                             b4 = *reinterpret_cast<const f32x4v*>(film_p + kWidth + o);
@@ -833,6 +863,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
                 tile16<true>(pipe, lane, hH, hL, acc, accb, ringH, ringL, [&](int g) {
                     if (t > 0 && g <= 5) epi(t - 1, g);
                     if (g == 4) load_rec(t);
+                    dma_step(g);
                 }, [&]() { fwd_hook(2); }, sbuf);
                 pipe.advance();
                 pacc = acc; paccb = accb;
