@@ -351,6 +351,31 @@ def check(rc, what):
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
 
 
+STAMP_UNITS = ("siren", "siren_bwd", "resblock", "modconv", "decoder2")      # kStampUnit* (csrc/stamps.h), in order
+STAMP_SLOTS, STAMP_WORDS = 320, 24                                           # kStampSlots, kStampWords
+
+
+def _stamps_call(unit, out, n_words):
+    lib = load()
+    fn = lib.e3dge_debug_stamps          # (not in include/e3dge_hip.h: bound here, on first use)
+    fn.restype, fn.argtypes = _i32, [_i32, ctypes.POINTER(ctypes.c_ulonglong), _i64]
+    check(fn(STAMP_UNITS.index(unit), out, n_words), f"stamps({unit})")
+
+
+def read_stamps(unit):
+    """The cycle stamps the kernels of translation unit `unit` (STAMP_UNITS) left in their side buffer, as STAMP_SLOTS lists of
+    STAMP_WORDS ints (csrc/stamps.h says which word is what; tools/kernel_stamps.py prints them).  Synchronises with the device.
+    Raises RuntimeError naming the -D the unit needs when the loaded library (E3DGE_LIB_PATH) is not instrumented for it."""
+    buf = (ctypes.c_ulonglong * (STAMP_SLOTS * STAMP_WORDS))()
+    _stamps_call(unit, buf, len(buf))
+    return [list(buf[s * STAMP_WORDS:(s + 1) * STAMP_WORDS]) for s in range(STAMP_SLOTS)]
+
+
+def clear_stamps(unit):
+    """Zero the unit's stamp buffer (same errors as read_stamps)."""
+    _stamps_call(unit, None, 0)
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

@@ -11,6 +11,7 @@
 // per forward.  The operand scale of a packed tensor comes from an a-priori bound (demodulated filters have unit norm,
 // the FIR taps of a phase sum to one), so a producer can scale before it has seen its own maximum.
 #include "decoder_common.h"
+#include "stamps.h"
 #include <stdlib.h>
 #include <math.h>
 #include <type_traits>
@@ -21,26 +22,16 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kPkSlab = 9 * 2 * 1024;            // bytes of one weight slab: (32 co) x (16 ci) x 9 taps x (hi, lo)
 
-// -DE3DGE_PK_TIMING: waves 0 and NW-1 of workgroup 0 accumulate shader-cycle deltas per phase of a step (0: vmcnt + barrier,
-// 1: DMA issue, 2: fragment reads + MFMAs, 3: epilogue) and leave them in the unused floats of the output amax buffer's first
-// line (tools/dec2_check.py --timing).
+// -DE3DGE_PK_TIMING: waves 0 and NW-1 of workgroup 0 sum the cycles of each phase of a step (0: vmcnt + barrier, 1: DMA issue,
+// 2: fragment reads + MFMAs, 3: epilogue; 4..7: taps, see stamps.h: decoder2).
 // the LDS-DMA pieces of the next step go out behind the MFMAs of this many taps (stride-1 and fused up-sampling kernels); behind 1 / 3 / 9
 // taps measured within 1 % (the wait at the step's top is barrier skew, not DMA latency)
 constexpr int kPkIssueTaps = 6;
 constexpr int kPkEpiValu = 8;    // VALU instructions of a finished tile's epilogue scheduled behind each MFMA of the next tile
-#ifdef E3DGE_PK_TIMING
-#define PK_T(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; } while (0)
-#define PK_T_INIT unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter(); const unsigned long long tbegin = tlast
-#define PK_T_DONE(NW_) do { if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == (NW_) - 1) && a.out_amax) { \
-        float* o_ = a.out_amax + 1 + (wave == 0 ? 0 : 8); \
-        for (int i_ = 0; i_ < 4; ++i_) o_[i_] = (float)tacc[i_]; \
-        o_[4] = (float)(__builtin_readcyclecounter() - tbegin); o_[5] = (float)nsteps; \
-        if (wave == 0) for (int i_ = 0; i_ < 4; ++i_) a.out_amax[17 + i_] = (float)tacc[4 + i_]; } } while (0)
-#else
-#define PK_T(i) do { } while (0)
-#define PK_T_INIT do { } while (0)
-#define PK_T_DONE(NW_) do { } while (0)
-#endif
+#define PK_T(i) IF_PK_TIMING(stamp_add(tacc, i, tlast);)
+#define PK_T_INIT IF_PK_TIMING(stamp_t tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = stamp_now(); const stamp_t tbegin = tlast;)
+#define PK_T_DONE(NW_) IF_PK_TIMING(tacc[8] = stamp_now() - tbegin; tacc[9] = nsteps; \
+                                    stamps_flush(blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == (NW_) - 1), 2 * a.stamp_row + (wave != 0), tacc, 10);)
 
 __device__ __forceinline__ uint32_t lds_u32(const void* p) {
     return (uint32_t)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
@@ -226,6 +217,7 @@ struct PkConvK {
     const float* rgbt_l1;          // device scalar: max_{b, ci} sum_c |rgb_wm[b][c][ci]|
     const float* bwd_wl1;          // device scalar: bound on max_{b, row} sum |w''| of the transposed image (operator norm, max-abs)
     float* out_f32;                // BWD = 2: fp32 (B, Co, H, W) output (the gradient of the feature map), no mask
+    IF_PK_TIMING(int stamp_row;)   // forward launches: the index of their output amax buffer; 0 otherwise (stamps.h: decoder2)
 };
 
 // ---- epilogue of one 32-channel x 32-pixel accumulator tile of a data-gradient convolution ------------------------------------------
@@ -690,9 +682,7 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
             constexpr bool EPI = decltype(epi_tag)::value;
             const unsigned char* xb = smem_pk + cur * STAGE + (size_t)(half * 2) * XPLANE;
             const unsigned char* wb = smem_pk + cur * STAGE + XST + (size_t)(wco * NCT) * kPkSlab + lane * 16;
-#ifdef E3DGE_PK_TIMING
-            unsigned long long tl2 = __builtin_readcyclecounter();
-#endif
+            IF_PK_TIMING(stamp_t tl2 = stamp_now();)
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int ky = tap / 3, kx = tap % 3;
@@ -744,10 +734,7 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
                 }
                 if (has_next && tap * PPT < NSLOT) issue(src_nx, xl_nx, tap * PPT, min((tap + 1) * PPT, NSLOT));
                 if (tap % 3 == 2 || EPI) __builtin_amdgcn_sched_barrier(0);      // keep the fragment reads of later taps from piling up
-#ifdef E3DGE_PK_TIMING
-                if (tap == 0 || tap == 8) { const unsigned long long n2_ = __builtin_readcyclecounter();
-                    tacc[(EPI ? 4 : 6) + (tap == 8)] += n2_ - tl2; tl2 = n2_; }
-#endif
+                IF_PK_TIMING(if (tap == 0 || tap == 8) stamp_add(tacc, (EPI ? 4 : 6) + (tap == 8), tl2);)
             }
         };
         if (OVL && do_epi) taps(std::true_type{}); else taps(std::false_type{});
@@ -1343,6 +1330,8 @@ static int check_conv(const E3dgeDec2Conv& c, const char* what) {
     return E3DGE_OK;
 }
 
+E3DGE_STAMPS_UNIT(decoder2, 0 IF_PK_TIMING(+ 1), "-DE3DGE_PK_TIMING")
+
 }  // namespace e3dge
 
 using namespace e3dge;
@@ -1477,6 +1466,7 @@ extern "C" int e3dge_dec2_forward(const E3dgeDec2Plan* P, e3dge_stream_t stream)
         PkConvK k = conv_args(P->conv1, res);
         k.x = reinterpret_cast<const unsigned char*>(P->act[0]); k.in_meta = P->meta; k.in_amax = P->amax;
         k.y = reinterpret_cast<unsigned char*>(P->act[1]); k.out_meta = P->meta + 1; k.out_amax = P->amax + E3DGE_AMAX_FLOATS;
+        IF_PK_TIMING(k.stamp_row = 1;)
         DEC2_STEP(conv_s1(k, st));
         DEC2_STEP(launch_torgb(P->rgb1.out, reinterpret_cast<const unsigned char*>(P->act[1]), P->meta + 1, P->rgb1.wm, P->rgb1.bias,
                                nullptr, nullptr, B, P->rgb1.ci, res, st));
@@ -1494,6 +1484,7 @@ extern "C" int e3dge_dec2_forward(const E3dgeDec2Plan* P, e3dge_stream_t stream)
             k.x = reinterpret_cast<const unsigned char*>(P->act[prev_act]); k.in_meta = P->meta + prev_act;
             k.in_amax = P->amax + (int64_t)E3DGE_AMAX_FLOATS * (prev_act == 1 ? 1 : 4 + 3 * (u - 1));
             k.y = reinterpret_cast<unsigned char*>(P->act[2 + 2 * u]); k.out_meta = P->meta + 2 + 2 * u; k.out_amax = am_u;
+            IF_PK_TIMING(k.stamp_row = 3 + 3 * u;)
             DEC2_STEP(launch_upblur(k, P->fir_blur_1d, st));
             mark(true);                   // (keeps the kernel_ms slots aligned: this level's blur entry reads 0)
             res *= 2;
@@ -1506,6 +1497,7 @@ extern "C" int e3dge_dec2_forward(const E3dgeDec2Plan* P, e3dge_stream_t stream)
             PkConvK k = conv_args(cc, res);
             k.x = reinterpret_cast<const unsigned char*>(P->act[2 + 2 * u]); k.in_meta = P->meta + 2 + 2 * u; k.in_amax = am_u;
             k.y = reinterpret_cast<unsigned char*>(P->act[3 + 2 * u]); k.out_meta = P->meta + 3 + 2 * u; k.out_amax = am_v;
+            IF_PK_TIMING(k.stamp_row = 4 + 3 * u;)
             if (fuse_rgb) {
                 k.rgb_wm = P->rgb[u].wm; k.rgb_bias = P->rgb[u].bias; k.rgb_skip = skip; k.rgb_fir = P->fir_up; k.rgb_out = P->rgb[u].out;
                 k.rgb_store = (last_level && !P->save_for_backward) ? 0 : 1;      // (a backward needs the top activation's signs)

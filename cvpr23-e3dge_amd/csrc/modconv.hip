@@ -34,11 +34,8 @@ constexpr int kMcThreads = 512;                       // 8 waves: two per SIMD
 constexpr int kMcMaxCi = 1024;                        // style vector staged in LDS
 // The input patches are loaded ONE step ahead in every tile shape.  Two steps ahead (NIT*8 more registers) let the two wave groups
 // run their issue / convert / compute phases in opposite order: built and measured in round 2, no gain beyond noise.
-#ifdef E3DGE_MC_TIMING
-#define MC_T(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define MC_T(i) do { } while (0)
-#endif
+// -DE3DGE_MC_TIMING: thread 0 of workgroup 0 sums the cycles of each phase of a step (stamps.h: modconv)
+#define MC_T(i) IF_MC_TIMING(stamp_add(tacc, i, tlast);)
 
 struct ModconvK {
     const float* x;          // (B, Ci, H, W)
@@ -228,10 +225,7 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
     store_input(p_cur, true, 0, preg[0]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#ifdef E3DGE_MC_TIMING
-    unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-    const unsigned long long tbegin = tlast;
-#endif
+    IF_MC_TIMING(stamp_t tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = stamp_now(); const stamp_t tbegin = tlast;)
 
     f32x16 acc[NPH][NCT][NPT];
     float amax_wg = 0.0f;
@@ -353,13 +347,8 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
         p_nxa = p_nx1;
     };
     for (int step = 0; step < nsteps; ++step) run_step(step, preg[0], preg[0]);   // the patch of step+1: loaded at the top, stored at the end
-#ifdef E3DGE_MC_TIMING
-    if (blockIdx.x == 0 && tid == 0 && a.out_amax) {   // profiling build: cycle sums in the unused floats of slot 0's line
-        for (int i = 0; i < 6; ++i) a.out_amax[1 + i] = (float)tacc[i];
-        a.out_amax[7] = (float)(__builtin_readcyclecounter() - tbegin);
-        a.out_amax[8] = (float)nsteps;
-    }
-#endif
+    IF_MC_TIMING(tacc[6] = stamp_now() - tbegin; tacc[7] = nsteps;
+                 stamps_flush(blockIdx.x == 0 && tid == 0, 0, tacc, 8);)
     if (a.out_amax) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) amax_wg = fmaxf(amax_wg, __shfl_xor(amax_wg, off, kWave));
@@ -536,6 +525,8 @@ static int launch_modconv(ModconvK k, hipStream_t st, const char* what) {
     fn<<<dim3((unsigned)grid), dim3(kMcThreads), lds, st>>>(k);
     return check_launch(what);
 }
+
+E3DGE_STAMPS_UNIT(modconv, 0 IF_MC_TIMING(+ 1), "-DE3DGE_MC_TIMING")
 
 }  // namespace e3dge
 

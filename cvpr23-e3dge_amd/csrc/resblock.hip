@@ -13,7 +13,7 @@
 // barrier waits with a COUNTED vmcnt that leaves the younger chunks in flight.  x and r = relu(net) are kept as packed
 // (hi, lo) words (160 registers each); relu(x) is formed from x's words on the fly per k-step (packed integer ops).  Neither
 // the (P, 301) hidden activations nor r ever touch memory; the output goes straight to (alpha, beta).  DESIGN.md 4.7 has the
-// measurements behind every choice here (tools/rb_trace.py, profiles/r2_pmc_issue_texhead.txt).
+// measurements behind every choice here (tools/kernel_stamps.py rb, profiles/r2_pmc_issue_texhead.txt).
 #include "siren_common.h"
 #include <type_traits>
 
@@ -247,27 +247,21 @@ __device__ __forceinline__ void relu_hilo(unsigned h, unsigned l, unsigned& rh, 
     rl = l & ~neg;
 }
 
-#ifdef E3DGE_RB_TRACE
-// (tag, s_memtime) pairs of one wave (tools/rb_trace.py): tag = 1000 * phase + 100 * what + index
-__device__ unsigned long long g_rb_trace[640];
-#if E3DGE_RB_TRACE > 1
-#define RB_STAMP(tag) do { if (tr_on) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)); \
-                                        if ((tid_k & 63) == 0 && tr_i < 320) { g_rb_trace[2 * tr_i] = (tag); g_rb_trace[2 * tr_i + 1] = t_; } \
-                                        ++tr_i; } } while (0)
-#else       // coarse: the four phase boundaries only, held in SGPRs until the sub-tile ends (leaves the register allocation alone)
-#define RB_STAMP(tag) do { if ((tag) >= 1000) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tr_ts[(tag) / 1000 - 1])); \
-                             if ((tag) == 4000 && tr_sub && (tid_k & 63) == 0) {                                                    \
-                                 for (int i_ = 0; i_ < 4; ++i_) { g_rb_trace[2 * i_] = 1000 * (i_ + 1); g_rb_trace[2 * i_ + 1] = tr_ts[i_]; } \
-                                 g_rb_trace[9] = 0; } } } while (0)
-#endif
+// -DE3DGE_RB_TRACE: (tag, s_memtime) pairs of one wave (stamps.h: resblock): tag = 1000 * phase + 100 * what + index.
+// =2: every stamp is stored where it is taken.  =1: the four phase boundaries only, held in SGPRs until the sub-tile ends
+// (leaves the register allocation alone).
+#define RB_STAMP(tag)                                                                                                            \
+    IF_RB_TRACE2(if (tr_on) { stamp_t t_[2] = {(stamp_t)(tag), 0}; STAMP_MEMTIME_WAIT(t_[1]);                                    \
+                              stamps_flush((tid_k & 63) == 0, tr_i, t_, 2); ++tr_i; })                                          \
+    IF_RB_TRACE1(if ((tag) >= 1000) { STAMP_MEMTIME_WAIT(tr_ts[(tag) / 1000 - 1]);                                               \
+                                      if ((tag) == 4000 && tr_sub)                                                               \
+                                          for (int i_ = 0; i_ < 4; ++i_) { const stamp_t t_[2] = {1000ull * (i_ + 1), tr_ts[i_]}; \
+                                                                           stamps_flush((tid_k & 63) == 0, i_, t_, 2); } })
 #ifndef E3DGE_RB_TRACE_T2
-#define E3DGE_RB_TRACE_T2 1
+#define E3DGE_RB_TRACE_T2 1      // the tiles of phases 2 and 3 that level 2 records
 #endif
 #ifndef E3DGE_RB_TRACE_T3
 #define E3DGE_RB_TRACE_T3 5
-#endif
-#else
-#define RB_STAMP(tag) do { } while (0)
 #endif
 
 struct __attribute__((packed, aligned(4))) F4u { float v[4]; };        // 16-byte load at 4-byte alignment
@@ -302,22 +296,17 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
     pipe.init(wbuf, packed, tid_k >> 6, tid_k & 63, kRbChunks);
     pipe.prime();
     auto issue_piece = [&](int i) { pipe.issue_piece(i); };
-#ifdef E3DGE_RB_TRACE
-    bool tr_on = false, tr_sub = false;
-    int tr_i = 0;
-    unsigned long long tr_ts[4] = {0, 0, 0, 0};
-    auto chunk_sync = [&]() {
+    IF_RB_TRACE([[maybe_unused]] bool tr_on = false; bool tr_sub = false;
+                [[maybe_unused]] int tr_i = 0;
+                [[maybe_unused]] stamp_t tr_ts[4] = {0, 0, 0, 0};)
+    auto chunk_sync = [&]() {                 // pipe.sync(), with a stamp around each of its halves
         RB_STAMP(100);
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRbPieces * (kRbNBuf - 3)) : "memory");
         RB_STAMP(200);
         __syncthreads();
         RB_STAMP(300);
     };
-    auto kstep = [&](int g) { RB_STAMP(g); };
-#else
-    auto chunk_sync = [&]() { pipe.sync(); };
-    auto kstep = [](int) {};
-#endif
+    auto kstep = [&]([[maybe_unused]] int g) { RB_STAMP(g); };
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     u32x4 ringH[kRbRing], ringL[kRbRing];
@@ -354,12 +343,10 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
             stash = reinterpret_cast<f32x4*>(smem + kRbLdsStash + wave * 1024) + lane;
         }
 
-#ifdef E3DGE_RB_TRACE
-        tr_sub = blockIdx.x == 7 && (tid_k >> 6) == 0 && sub == 1;
-        tr_on = tr_sub;
-        if (tr_on) tr_i = 0;
+        IF_RB_TRACE(tr_sub = blockIdx.x == 7 && (tid_k >> 6) == 0 && sub == 1;
+                    tr_on = tr_sub;
+                    if (tr_on) tr_i = 0;)
         RB_STAMP(1000);
-#endif
         // ---- 1. x: each lane keeps its point's values; then (hi, lo) ----
         u32x4 xH[kRbStepsIn], xL[kRbStepsIn];
         float inv_x, xnorm;
@@ -449,9 +436,7 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
         }
 
         RB_STAMP(2000);
-#if defined(E3DGE_RB_TRACE) && E3DGE_RB_TRACE > 1
-        tr_on = false;
-#endif
+        IF_RB_TRACE2(tr_on = false;)
         // ---- 2. net = W_0 relu(x) + b_0 ; r = relu(net) as (hi, lo) words ----
         // r has to be split tile by tile (keeping it in fp32 until its column maximum is known costs 160 more registers
         // than there are), so its scale comes from the bound max|net| <= max_n ||W_0[n,:]|| * ||x|| + max|b_0| instead of the
@@ -478,9 +463,7 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
             f32x16 P0, P1, Q0, Q1;
 #pragma unroll
             for (int t = 0; t < kRbTilesIn; ++t) {
-#if defined(E3DGE_RB_TRACE) && E3DGE_RB_TRACE > 1
-                tr_on = tr_sub && t == E3DGE_RB_TRACE_T2;
-#endif
+                IF_RB_TRACE2(tr_on = tr_sub && t == E3DGE_RB_TRACE_T2;)
                 f32x16& A0 = (t & 1) ? Q0 : P0;
                 f32x16& A1 = (t & 1) ? Q1 : P1;
                 const f32x16& B0 = (t & 1) ? P0 : Q0;                       // the pair tile t-1 left behind
@@ -513,9 +496,7 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
             asm volatile("" : "+a"(rH[18]), "+a"(rH[19]), "+a"(rL[18]), "+a"(rL[19]));
             RB_STAMP(500);
 
-#ifdef E3DGE_RB_TRACE
-            tr_on = tr_sub;
-#endif
+            IF_RB_TRACE(tr_on = tr_sub;)
             RB_STAMP(3000);
             // ---- 3. out = W_s x + W_1 r + b_1 -> alpha (tiles 0..7), beta (tiles 8..15) ----
             // W_s x accumulates in P, W_1 r in Q.  P is folded into `px` in front of k-steps 20..23 (while Q runs); Q is folded,
@@ -592,18 +573,14 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
             // an epilogue.  The tile loop runs over feature blocks (alpha tile, beta tile) so that a slice's kind is a compile-time fact.
 #pragma unroll 1
             for (int blk = 0; blk < kRbTilesOut / 2; ++blk) {
-#if defined(E3DGE_RB_TRACE) && E3DGE_RB_TRACE > 1
-                tr_on = tr_sub && 2 * blk == E3DGE_RB_TRACE_T3;
-#endif
+                IF_RB_TRACE2(tr_on = tr_sub && 2 * blk == E3DGE_RB_TRACE_T3;)
                 run_tile([&](int g) {                   // alpha tile of block blk; finishes the beta tile of block blk - 1
                     kstep(g);
                     if (g >= 1 && g <= 4 && blk > 0) out_slice(ParB{}, 2 * blk - 1, g - 1);
                     if (FILM && g >= 11 && g <= 14) h8_piece(blk, g - 11);
                     fold_px(g);
                 });
-#if defined(E3DGE_RB_TRACE) && E3DGE_RB_TRACE > 1
-                tr_on = tr_sub && 2 * blk + 1 == E3DGE_RB_TRACE_T3;
-#endif
+                IF_RB_TRACE2(tr_on = tr_sub && 2 * blk + 1 == E3DGE_RB_TRACE_T3;)
                 run_tile([&](int g) {                   // beta tile of block blk; finishes its alpha tile
                     kstep(g);
                     if (g >= 1 && g <= 4) out_slice(ParA{}, 2 * blk, g - 1);
@@ -614,9 +591,7 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
             for (int q = 0; q < 4; ++q) out_slice(ParB{}, kRbTilesOut - 1, q);
             RB_STAMP(800);
         }
-#ifdef E3DGE_RB_TRACE
-        tr_on = tr_sub;
-#endif
+        IF_RB_TRACE(tr_on = tr_sub;)
         RB_STAMP(4000);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -624,15 +599,11 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
 
 #include "resblock_bwd.h"
 
+E3DGE_STAMPS_UNIT(resblock, 0 IF_RB_TRACE(+ 1), "-DE3DGE_RB_TRACE=1 or =2")
+
 }  // namespace e3dge
 
 using namespace e3dge;
-
-#ifdef E3DGE_RB_TRACE
-extern "C" int e3dge_debug_rb_trace(unsigned long long* out640) {
-    return hipMemcpyFromSymbol(out640, HIP_SYMBOL(e3dge::g_rb_trace), sizeof(unsigned long long) * 640) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int64_t e3dge_resblock_packed_floats(void) { return kRbPackedFloats; }
 

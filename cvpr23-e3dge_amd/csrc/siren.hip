@@ -30,14 +30,8 @@ namespace e3dge {
 // ---------------------------------------------------------------------------------------------
 // the kernel.  MODE 0 = render (rays x samples + compositing), MODE 1 = arbitrary point set (raw outputs)
 // ---------------------------------------------------------------------------------------------
-// Phase timing (variant builds only, -DE3DGE_PHASE_TIMING): wave 0 of workgroup 0 records s_memtime at the phase
-// boundaries of each sub-tile and, at the very end, overwrites the first floats of the `dists` output with the
-// per-phase cycle counts (tools/phase_timing.py reads them back).
-#ifdef E3DGE_PHASE_TIMING
-#define PHASE_MARK(i) do { if (MODE == 0 && blockIdx.x == 0 && tid == 0 && sub < 4) tstamp[sub * 6 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define PHASE_MARK(i) do { } while (0)
-#endif
+// -DE3DGE_PHASE_TIMING: thread 0 of workgroup 0 marks the phase boundaries of its first four sub-tiles (stamps.h)
+#define PHASE_MARK(i) IF_PHASE_TIMING(if (MODE == 0 && blockIdx.x == 0 && tid == 0 && sub < 4) stamp_mark(tstamp, sub * 6 + (i));)
 
 // PREC 0: fp32 MFMA (v_mfma_f32_32x32x2_f32).  PREC 1: "f16x3" -- split-f16 contraction on v_mfma_f32_32x32x16_f16.
 // SAVE: additionally store the pre-sine argument of every FiLM layer (what the backward kernels consume).
@@ -140,10 +134,7 @@ __global__ void __launch_bounds__(kThreads) siren_kernel(const SirenK a) {
     //   f16x3: inH/inL[2t + (r>>3)] word (r&7)>>1, half-word r&1  (packed f16 hi / lo of the same value)
     f32x16 in[kNT], out[kNT];
     u32x4 inH[2 * kNT], inL[2 * kNT], outH[2 * kNT], outL[2 * kNT];
-#ifdef E3DGE_PHASE_TIMING
-    unsigned long long tstamp[24];
-    for (int i = 0; i < 24; ++i) tstamp[i] = 0;
-#endif
+    IF_PHASE_TIMING(stamp_t tstamp[24]; for (int i = 0; i < 24; ++i) tstamp[i] = 0;)
 
     const int tid_k = tid;
     for (int sub = 0; sub < n_sub; ++sub) {
@@ -706,15 +697,8 @@ __global__ void __launch_bounds__(kThreads) siren_kernel(const SirenK a) {
             if (a.depth) a.depth[(int64_t)b * HW + pix] = st[2];
             if (a.mask) a.mask[(int64_t)b * HW + pix] = (st[2] < a.mask_thresh) ? 1.0f : 0.0f;
         }
-#ifdef E3DGE_PHASE_TIMING
-        __syncthreads();
-        if (blockIdx.x == 0 && tid == 0 && a.dists)
-            for (int i = 0; i < 18; ++i)
-                a.dists[i] = (i % 6 == 0) ? (float)(i / 6 ? tstamp[i] - tstamp[i - 1] : 0) : (float)(tstamp[i] - tstamp[i - 1]);
-        if (blockIdx.x == 0 && (tid & 63) == 0 && a.dists) {
-            a.dists[18 + wave * 3 + 0] = (float)pipe.t_vm; a.dists[18 + wave * 3 + 1] = (float)pipe.t_bar; a.dists[18 + wave * 3 + 2] = 0.0f;
-        }
-#endif
+        IF_PHASE_TIMING(stamps_flush<kStampBarrier>(blockIdx.x == 0 && tid == 0, 0, tstamp, 24);
+                        stamps_flush(blockIdx.x == 0 && (tid & 63) == 0, 1 + wave, pipe.t_wait, 2);)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the pipeline fetches two chunks past the end of the work
 }
@@ -999,6 +983,8 @@ static int pick_rays_per_wg(int S, int64_t total_rays) {
     return best;
 }
 
+E3DGE_STAMPS_UNIT(siren, 0 IF_PHASE_TIMING(+ 1) IF_16_TRACE(+ 1), "-DE3DGE_PHASE_TIMING or -DE3DGE_16_TRACE")
+
 }  // namespace e3dge
 
 using namespace e3dge;
@@ -1137,12 +1123,6 @@ extern "C" int e3dge_selftest_mfma16(float* c, const float* a, const float* b, i
     selftest_mfma16_kernel<<<dim3(1), dim3(64), 0, as_stream(stream)>>>(c, a, b, k);
     return check_launch("selftest_mfma16");
 }
-
-#ifdef E3DGE_16_TRACE
-extern "C" int e3dge_debug_trace16(unsigned long long* out48) {
-    return hipMemcpyFromSymbol(out48, HIP_SYMBOL(e3dge::g_trace16), sizeof(unsigned long long) * 48) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int e3dge_selftest_mfma16x16(float* c, const float* a, const float* b, int k, e3dge_stream_t stream) {
     E3DGE_REQUIRE(c && a && b && k > 0 && k <= 256 && (k % 32) == 0, "selftest_mfma16x16: bad arguments");

@@ -179,23 +179,15 @@ struct ChunkPipe16 {
     __device__ __forceinline__ void prime() {
         issue_chunk(); issue_chunk(); issue_chunk();
     }
-#ifdef E3DGE_PHASE_TIMING
-    unsigned long long t_vm = 0, t_bar = 0;
-#endif
+    IF_PHASE_TIMING(stamp_t t_wait[2] = {0, 0};)              // cycles in sync(): [0] the vmcnt wait, [1] the barrier
     template <bool STRICT> __device__ __forceinline__ void sync() {
-#ifdef E3DGE_PHASE_TIMING
-        const unsigned long long c0 = __builtin_readcyclecounter();
-#endif
+        IF_PHASE_TIMING(stamp_t tc[2]; stamp_mark(tc, 0);)
         // STRICT (training: the epilogue's argument stores share vmcnt): wait for everything
         if (STRICT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#ifdef E3DGE_PHASE_TIMING
-        const unsigned long long c1 = __builtin_readcyclecounter();
-#endif
+        IF_PHASE_TIMING(stamp_mark(tc, 1);)
         __syncthreads();
-#ifdef E3DGE_PHASE_TIMING
-        t_vm += c1 - c0; t_bar += __builtin_readcyclecounter() - c1;
-#endif
+        IF_PHASE_TIMING(t_wait[0] += tc[1] - tc[0]; stamp_add(t_wait, 1, tc[1]);)
     }
     __device__ __forceinline__ void advance() {
         use_buf = (use_buf + 1 == k16NBuf) ? 0 : use_buf + 1;
@@ -204,14 +196,9 @@ struct ChunkPipe16 {
     }
 };
 
-#ifdef E3DGE_16_TRACE
-// profiling build: s_memtime at the start of every k-step and after its MFMAs, for one tile of two partner waves
-// (tools/trace16.py).  Inline asm, so no s_waitcnt is placed behind the stamps; they are collected after the tile.
-__device__ unsigned long long g_trace16[2][24];
-#define TRACE16_STAMP(i) do { if (trace) asm volatile("s_memtime %0" : "=s"(tstamp[i])); } while (0)
-#else
-#define TRACE16_STAMP(i) do { } while (0)
-#endif
+// -DE3DGE_16_TRACE: s_memtime at the start of every k-step, after its MFMAs and after its epilogue slice, for one tile of two
+// partner waves (stamps.h).  Inline asm, so no s_waitcnt is placed behind the stamps; they are collected after the tile.
+#define TRACE16_STAMP(i) IF_16_TRACE(if (trace) STAMP_MEMTIME(tstamp[i]);)
 
 // K = 256 contraction of one 16-feature tile: 8 k-steps x (hi*hi, lo*hi, hi*lo) on two alternating accumulators.
 // On entry the ring holds k-steps 0..2 of this chunk; on exit k-steps 0..2 of the next one.
@@ -221,9 +208,7 @@ template <bool TRANSPOSED, int RING = k16Ring, class Epi, class Hook>
 __device__ __forceinline__ void tile16(ChunkPipe16& pipe, int lane, const u32x4 (&aH)[k16Steps], const u32x4 (&aL)[k16Steps],
                                        f32x4v& acc, f32x4v& accb, u32x4 (&ringH)[RING], u32x4 (&ringL)[RING], Epi&& epi,
                                        Hook&& hook, int sbuf = -1, [[maybe_unused]] int trace = 0) {
-#ifdef E3DGE_16_TRACE
-    unsigned long long tstamp[24];
-#endif
+    IF_16_TRACE(stamp_t tstamp[24];)
     // sbuf >= 0: the caller knows the buffer index statically (tile index mod k16NBuf in a fully unrolled layer): the fragment
     // reads then are one base register + immediates instead of per-buffer address registers
     const u32x4* __restrict__ wp = reinterpret_cast<const u32x4*>(sbuf >= 0 ? pipe.wbuf + sbuf * k16ChunkFloats : pipe.wcur) + lane;
@@ -252,21 +237,12 @@ __device__ __forceinline__ void tile16(ChunkPipe16& pipe, int lane, const u32x4 
         epi(g);
         TRACE16_STAMP(3 * g + 2);
     }
-#ifdef E3DGE_16_TRACE
-    if (trace) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if ((threadIdx.x & 63) == 0)
-            for (int i = 0; i < 24; ++i) g_trace16[trace - 1][i] = tstamp[i];
-    }
-#endif
+    IF_16_TRACE(if (trace) stamps_flush<kStampWaitLgkm>((threadIdx.x & 63) == 0, 8 + trace - 1, tstamp, 24);)
 }
 
 #ifndef E3DGE_16_HELPERS_ONLY
-#ifdef E3DGE_PHASE_TIMING
-#define PHASE16(i) do { if (MODE == 0 && blockIdx.x == 0 && tid == 0 && sub < 3) tstamp[sub * 6 + (i)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define PHASE16(i) do { } while (0)
-#endif
+// -DE3DGE_PHASE_TIMING: thread 0 of workgroup 0 marks the phase boundaries of its first three sub-tiles (stamps.h)
+#define PHASE16(i) IF_PHASE_TIMING(if (MODE == 0 && blockIdx.x == 0 && tid == 0 && sub < 3) stamp_mark(tstamp, sub * 6 + (i));)
 
 // CACHE (render mode without SAVE only): 1 = also write the backbone output (layer 7, packed hi / lo) to a.bb_out, one 16-KiB
 // record per wave slab in register order; 2 = read it (and the composite weights a.weights_in) back instead of running layers
@@ -294,10 +270,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
     float* const state = smem + k16LdsState;
 
     const int tid_k = threadIdx.x;
-#ifdef E3DGE_PHASE_TIMING
-    const unsigned long long t_entry = __builtin_readcyclecounter();
-    unsigned long long t_loop0 = 0, t_loop1 = 0;
-#endif
+    IF_PHASE_TIMING(stamp_t tstamp[24]; stamp_mark(tstamp, 20);)
     // ---- work assignment (as siren_kernel) ----
     int b, npts, n_sub;
     int pix0 = 0, nrays = 0;
@@ -408,14 +381,11 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
         }
     }
 
-#ifdef E3DGE_16_TRACE
-    auto trace_sel = [&](int L, int t) {
-        const int w = __builtin_amdgcn_readfirstlane(tid_k >> 6);
-        return (MODE == 0 && blockIdx.x == 7 && L == 3 && t == 6 && (w == 0 || w == 4)) ? 1 + (w >> 2) : 0;
+    auto trace_sel = [&]([[maybe_unused]] int L, [[maybe_unused]] int t) {      // 1 / 2: tile16 records this tile for wave 0 / 4
+        IF_16_TRACE(const int w = __builtin_amdgcn_readfirstlane(tid_k >> 6);
+                    if (MODE == 0 && blockIdx.x == 7 && L == 3 && t == 6 && (w == 0 || w == 4)) return 1 + (w >> 2);)
+        return 0;
     };
-#else
-    auto trace_sel = [](int, int) { return 0; };
-#endif
     // SAVE: the argument stores share the in-order memory queue with the weight DMA.  Until round 6 this hook drained the queue
     // (s_waitcnt vmcnt(0), and __syncthreads() adds the same for the compiler's own stores): every tile of the saving forward waited for
     // its previous tile's stores to reach L2 -- +40 % over the plain forward.  Now a counted wait (the chunk of tile t+1 was issued at
@@ -456,14 +426,8 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
     constexpr bool kFinalOut = kSeamless && ((E3DGE_SIREN_DEPTH - 1) & 1) != 0;
     u32x4 (&hH)[k16Steps] = kFinalOut ? outH : inH;       // layer 7's output: sdf head, layer-7 record, texture FiLM, view layer
     u32x4 (&hL)[k16Steps] = kFinalOut ? outL : inL;
-#ifdef E3DGE_PHASE_TIMING
-    unsigned long long tstamp[18];
-    for (int i = 0; i < 18; ++i) tstamp[i] = 0;
-#endif
-
-#ifdef E3DGE_PHASE_TIMING
-    t_loop0 = __builtin_readcyclecounter();
-#endif
+    IF_PHASE_TIMING(for (int i = 0; i < 18; ++i) tstamp[i] = 0;
+                    stamp_mark(tstamp, 21);)
     for (int sub = 0; sub < n_sub; ++sub) {
         int tid_o = tid_k;
         asm volatile("" : "+v"(tid_o));                    // opaque: address math stays inside the sub-tile (no hoisted registers)
@@ -967,9 +931,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
         PHASE16(5);
     }  // sub-tiles
 
-#ifdef E3DGE_PHASE_TIMING
-    t_loop1 = __builtin_readcyclecounter();
-#endif
+    IF_PHASE_TIMING(stamp_mark(tstamp, 22);)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no LDS-DMA in flight when the workgroup retires
     if (MODE == 0) {
         // 7. per-ray outputs, channel-first like VolumeFeatureRenderer.forward returns them (:1957-1968)
@@ -998,19 +960,10 @@ __global__ void __launch_bounds__(k16Threads) siren16_kernel(const SirenK a) {
             if (a.depth) a.depth[(int64_t)b * HW + pix] = st[2];
             if (a.mask) a.mask[(int64_t)b * HW + pix] = (st[2] < a.mask_thresh) ? 1.0f : 0.0f;
         }
-#ifdef E3DGE_PHASE_TIMING
-        // profiling build: the first floats of `dists` carry thread 0's per-phase cycle counts (tools/phase_timing.py)
-        __syncthreads();
-        float* const td = a.dists ? a.dists : a.rgb;       // (the launch on the layer-7 record has no `dists`: its counts overwrite rgb[0..22])
-        if (blockIdx.x == 0 && tid == 0 && td) {
-            for (int i = 0; i < 18; ++i)
-                td[i] = (i % 6 == 0) ? (float)(i / 6 ? tstamp[i] - tstamp[i - 1] : 0) : (float)(tstamp[i] - tstamp[i - 1]);
-            td[18] = (float)pipe.t_vm; td[19] = (float)pipe.t_bar;
-            td[20] = (float)(t_loop0 - t_entry);                            // prologue: LDS tables, first weight chunks
-            td[21] = (float)(t_loop1 - t_loop0);                            // all sub-tiles
-            td[22] = (float)(__builtin_readcyclecounter() - t_loop1);       // per-ray outputs (up to this thread's last store)
-        }
-#endif
+        IF_PHASE_TIMING(tstamp[18] = pipe.t_wait[0]; tstamp[19] = pipe.t_wait[1];
+                        __syncthreads();
+                        stamp_mark(tstamp, 23);                 // per-ray outputs: up to this thread's last store
+                        stamps_flush(blockIdx.x == 0 && tid == 0, 0, tstamp, 24);)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }

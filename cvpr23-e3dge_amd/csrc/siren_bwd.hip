@@ -212,17 +212,12 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
             }
         }
     };
-#ifdef E3DGE_BWD_TIMING
-    unsigned long long t_tile = 0, t_epi = 0, t_pro = 0, t_tail = 0;
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#define BT_NOW() __builtin_readcyclecounter()
-#else
-#define BT_NOW() 0ull
-#endif
+    // -DE3DGE_BWD_TIMING: cycle sums of this thread per part of a sub-tile (stamps.h: siren_bwd)
+    IF_BWD_TIMING(stamp_t bt[7] = {0, 0, 0, 0, 0, 0, 0}, bt_last; const stamp_t bt_begin = stamp_now();)
 
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     for (int sub = 0; sub < n_sub; ++sub) {
-        [[maybe_unused]] const unsigned long long tp0 = BT_NOW();
+        IF_BWD_TIMING(bt_last = stamp_now();)
         const int lane = lane_id_fresh(), half = lane >> 5, col = lane & 31;      // (per sub-tile: see lane_id_fresh)
         const int wave = wave_s;
         const int p = sub * kTilePts + 32 * wave + col;
@@ -340,9 +335,7 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
             }
         }
 
-#ifdef E3DGE_BWD_TIMING
-        t_pro += BT_NOW() - tp0;
-#endif
+        IF_BWD_TIMING(stamp_add(bt, 1, bt_last);)
         // =====================================================================================
         // 2. the chain: GEMM Gb (layer L = 8 - Gb) turns g_L into dh_{L-1}; its epilogue makes g_{L-1}
         // =====================================================================================
@@ -493,7 +486,7 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                     }
                 };
                 f32x16 acc = zero16();
-                [[maybe_unused]] const unsigned long long c0 = BT_NOW();
+                IF_BWD_TIMING(stamp_t tc[2]; stamp_mark(tc, 0);)
                 if (!F16) {
                     acc = big_tile<false>(pipe.wcur, pipe.wnxt, lane, in, acc, ring, NoEpilogue(), sync_and_fetch, issue_piece);
                 } else {
@@ -507,7 +500,7 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                     }
                     acc = (acc + accb) * inv_scale;
                 }
-                [[maybe_unused]] const unsigned long long c1 = BT_NOW();
+                IF_BWD_TIMING(stamp_mark(tc, 1);)
                 pipe.advance();
                 if (!F16 && t > 0) {
                     epilogue(t - 1, prev, argb, out[t - 1]);
@@ -515,11 +508,9 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
                 }
                 prev = acc;
                 if (F16) asm volatile("" : "+v"(prev));
-#ifdef E3DGE_BWD_TIMING
-                t_tile += c1 - c0; t_epi += BT_NOW() - c1;
-#endif
+                IF_BWD_TIMING(bt[2] += tc[1] - tc[0]; stamp_add(bt, 3, tc[1]);)
             }
-            [[maybe_unused]] const unsigned long long ct0 = BT_NOW();
+            IF_BWD_TIMING(bt_last = stamp_now();)
             if (F16) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -536,9 +527,7 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
             __syncthreads();       // the last two epilogues of a layer have no weight-chunk barrier between them
             epilogue(kNT - 1, prev, argt, out[kNT - 1]);
             next_operand();
-#ifdef E3DGE_BWD_TIMING
-            t_tail += BT_NOW() - ct0;
-#endif
+            IF_BWD_TIMING(stamp_add(bt, 4, bt_last);)
         }
         // ---- optional: dL/dx = s W_0^T g_0 (g_0 = gamma_0 * adj(a_0) is in out[]), like the sdf chain's last step ----
         if (DPTS) {
@@ -572,14 +561,9 @@ __global__ void __launch_bounds__(kThreads) siren_bwd_kernel(const SirenBwdK a) 
     __syncthreads();
     float* const my_partial = a.partials + (int64_t)blockIdx.x * (9 * 2 * kWidth);
     for (int i = tid; i < 9 * 2 * kWidth; i += kThreads) my_partial[i] = acc_s[i];
-#ifdef E3DGE_BWD_TIMING
-    // profiling build: the first floats of this workgroup's slice carry wave 0's cycle counts (tools/bwd_timing.py)
-    __syncthreads();
-    if (tid == 0) {
-        my_partial[0] = (float)(BT_NOW() - t_begin); my_partial[1] = (float)t_pro; my_partial[2] = (float)t_tile;
-        my_partial[3] = (float)t_epi; my_partial[4] = (float)t_tail; my_partial[5] = (float)pipe.t_vm; my_partial[6] = (float)pipe.t_bar;
-    }
-#endif
+    IF_BWD_TIMING(__syncthreads();
+                  bt[0] = stamp_now() - bt_begin; bt[5] = pipe.t_wait[0]; bt[6] = pipe.t_wait[1];
+                  stamps_flush(tid == 0, blockIdx.x, bt, 7);)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1138,6 +1122,8 @@ film_bwd_kernel(float* __restrict__ dstyles, const float* __restrict__ dfilm, co
     __syncthreads();
     if (ng == 0) dstyles[((int64_t)b * 9 + l) * kWidth + k] = ((part[0][kk] + part[1][kk]) + part[2][kk]) + part[3][kk];
 }
+
+E3DGE_STAMPS_UNIT(siren_bwd, 0 IF_BWD_TIMING(+ 1), "-DE3DGE_BWD_TIMING")
 
 }  // namespace e3dge
 

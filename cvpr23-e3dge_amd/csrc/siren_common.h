@@ -1,7 +1,7 @@
 // Shared device-side definitions of the SIREN kernels (forward: siren.hip, backward: siren_bwd.hip): vector types,
 // the packed weight image layout, LDS carve of the forward kernel, MFMA / LDS-DMA / sine helpers and the tile routines.
 #pragma once
-#include "common.h"
+#include "stamps.h"
 
 namespace e3dge {
 
@@ -211,9 +211,7 @@ struct ChunkPipe {
     float* wbuf;
     const float* wcur;
     const float* wnxt;
-#if defined(E3DGE_PHASE_TIMING) || defined(E3DGE_BWD_TIMING)
-    unsigned long long t_vm, t_bar;
-#endif
+    IF_PIPE_TIMING(stamp_t t_wait[2];)             // cycles in sync(): [0] the vmcnt wait, [1] the barrier
     __device__ __forceinline__ void init(float* wbuf_, const float* image, int wave, int lane, int first_, int count_) {
         const int wave_u = __builtin_amdgcn_readfirstlane(wave);
         wbuf = wbuf_;
@@ -225,9 +223,7 @@ struct ChunkPipe {
         src = img + (size_t)idx * (kChunkFloats * 4);
         lds_dst = lds_base;
         wcur = wbuf_; wnxt = wbuf_ + kChunkFloats;
-#if defined(E3DGE_PHASE_TIMING) || defined(E3DGE_BWD_TIMING)
-        t_vm = 0; t_bar = 0;
-#endif
+        IF_PIPE_TIMING(t_wait[0] = 0; t_wait[1] = 0;)
     }
     __device__ __forceinline__ void issue_piece(int i) {     // i is a compile-time constant at every call site
         const char* s = src + (i >> 2) * 4096;
@@ -251,16 +247,11 @@ struct ChunkPipe {
             for (int i = 0; i < 8; ++i) issue_piece(i);
     }
     __device__ __forceinline__ void sync() {
-#if defined(E3DGE_PHASE_TIMING) || defined(E3DGE_BWD_TIMING)
-        const unsigned long long c0 = __builtin_readcyclecounter();
+        IF_PIPE_TIMING(stamp_t tc[2]; stamp_mark(tc, 0);)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long c1 = __builtin_readcyclecounter();
+        IF_PIPE_TIMING(stamp_mark(tc, 1);)
         __syncthreads();
-        t_vm += c1 - c0; t_bar += __builtin_readcyclecounter() - c1;
-#else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#endif
+        IF_PIPE_TIMING(t_wait[0] += tc[1] - tc[0]; stamp_add(t_wait, 1, tc[1]);)
     }
     __device__ __forceinline__ void advance() {
         use_buf = (use_buf + 1 == kNBuf) ? 0 : use_buf + 1;

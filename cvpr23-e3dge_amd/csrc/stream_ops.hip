@@ -3,7 +3,7 @@
 //
 // Roofline: all three are pure streams (8 B/element fwd for the activations), so the only goals are
 // 16 B/lane coalesced accesses, no per-element integer division, and >= 2k workgroups in flight.
-#include "common.h"
+#include "stamps.h"
 
 namespace e3dge {
 
@@ -285,6 +285,20 @@ extern "C" int e3dge_build_flags(void) {
     return 0;
 #endif
 }
+
+// cycle stamps of instrumented builds (stamps.h): out == NULL zeroes the unit's buffer
+extern "C" int e3dge_debug_stamps(int unit, unsigned long long* out, int64_t n_words) {
+    E3DGE_REQUIRE(!out || (n_words >= 0 && n_words <= kStampSlots * kStampWords), "debug_stamps: n_words=%lld", (long long)n_words);
+    switch (unit) {
+        case kStampUnitSiren: return stamps_siren(out, n_words);
+        case kStampUnitSirenBwd: return stamps_siren_bwd(out, n_words);
+        case kStampUnitResblock: return stamps_resblock(out, n_words);
+        case kStampUnitModconv: return stamps_modconv(out, n_words);
+        case kStampUnitDecoder2: return stamps_decoder2(out, n_words);
+    }
+    return fail(E3DGE_ERR_INVALID_ARG, "debug_stamps: unit=%d", unit);
+}
+extern "C" int e3dge_debug_stamps_clear(int unit) { return e3dge_debug_stamps(unit, nullptr, 0); }
 
 extern "C" int64_t e3dge_stream_capture_id(e3dge_stream_t stream) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
