@@ -198,6 +198,13 @@ class LpipsArgs(_Args):
         ("taps", _vp * LPIPS_LAYERS), ("ws", _vp), ("ws_bytes", _i64)]
 
 
+class LpipsBwdArgs(_Args):
+    """Mirror of struct E3dgeLpipsBwdArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("packed_t", _vp), ("fwd_ws", _vp), ("fwd_ws_bytes", _i64)] + [
+        (n, _i32) for n in ("batch", "height", "width")] + [("std", _f32 * 3)] + [(n, _vp) for n in ("upstream", "grad_x", "grad_y")] + [
+        ("gpre", _vp * LPIPS_LAYERS), ("ws", _vp), ("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -276,6 +283,10 @@ SIGNATURES = {
     "e3dge_lpips_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "e3dge_lpips_forward": (_i32, [ctypes.POINTER(LpipsArgs), _vp]),
     "e3dge_image_metric_row_lpips": (_i32, [_vp, _vp, _vp, _i32, _f32, _f32, _vp]),
+    "e3dge_lpips_packed_t_floats": (_i64, []),
+    "e3dge_lpips_pack_weights_t": (_i32, [_vp, _vp, _vp]),
+    "e3dge_lpips_bwd_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "e3dge_lpips_backward": (_i32, [ctypes.POINTER(LpipsBwdArgs), _vp]),
     "e3dge_hitprob_points": (_i32, [_vp] * 8 + [_i32, _i64, _i32, _i32, _vp]),
     "e3dge_hitprob_composite": (_i32, [_vp] * 6 + [_f32, _i32, _i32, _i64, _i32, _i32, _vp]),
     "e3dge_align_volume": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -10,6 +10,8 @@
 //   conv 192->384 k3 p1, relu [tap 3], conv 384->256 k3 p1, relu [tap 4], conv 256->256 k3 p1, relu [tap 5]
 //   f^ = f / (sqrt(sum_c f^2 + 1e-8) + 1e-10);   d_l[b] = mean_{h,w} sum_c lin_l[c] (x^_c - y^_c)^2;   per_image[b] = sum_l d_l[b]
 //
+// The backward (the gradient with respect to x and y, eight launches) is lpips_bwd.h.
+//
 // Kernels (nine launches for one forward, whatever the batch):
 //   conv_kernel      implicit GEMM on v_mfma_f32_16x16x4_f32, fp32 throughout.  M = output channels, N = the output pixels of all 2B
 //                    images (x then y) flattened, K = (ci, r, s).  A workgroup is 4 waves = 64 channels x 16 NT pixels (NT = 1, 2, 4
@@ -90,11 +92,17 @@ __global__ void __launch_bounds__(256) lpips_pack_kernel(float* __restrict__ pac
 
 struct LpNorm { float mean[3], std[3]; };
 
-template <int KS_, int STRIDE, int PAD, int NT, bool FIRST>
+// The epilogue of conv_kernel.  kLpEpiRelu: the forward's, relu(acc + bias).  The other two make the same kernel a stride-1 data-gradient
+// convolution on the transposed weight image (lpips_bwd.h): kLpEpiStore writes the sum (the gradient of a pooled map), kLpEpiMask
+// writes (acc + out) * [f > 0] in place over the masked tap gradient that out already holds (`bias` is then f, the forward's
+// post-ReLU activation of this layer, image `f_first` onwards).
+enum { kLpEpiRelu = 0, kLpEpiStore = 1, kLpEpiMask = 2 };
+
+template <int KS_, int STRIDE, int PAD, int NT, bool FIRST, int EPI = kLpEpiRelu>
 __global__ void __launch_bounds__(256)
 lpips_conv_kernel(float* __restrict__ out, const float* __restrict__ in0, const float* __restrict__ in1, int n_first,
                   const float* __restrict__ wfrag, const float* __restrict__ bias, int Cin, int IH, int IW, int Cout, int OH, int OW,
-                  int64_t N, int K, int KS4, LpNorm nrm) {
+                  int64_t N, int K, int KS4, LpNorm nrm, int f_first = 0) {
     constexpr int BN = 16 * NT, BNP = NT == 1 ? 16 : BN + 16;      // row pitch: the four k rows of one read land in four bank groups
     constexpr int ROWS = 256 / BN, PER = kLpKC / ROWS;               // staged elements per thread and tile
     constexpr int KK = KS_ * KS_;
@@ -168,8 +176,16 @@ lpips_conv_kernel(float* __restrict__ out, const float* __restrict__ in0, const 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = mt * 16 + 4 * (lane >> 4) + r;
-            const float v = __fadd_rn(__fadd_rn(acc[t][0][r], acc[t][1][r]), bias[row]);
-            out[((int64_t)img * Cout + row) * OHW + pix] = fmaxf(v, 0.0f);
+            const int64_t at = ((int64_t)img * Cout + row) * OHW + pix;
+            if (EPI == kLpEpiRelu) {
+                const float v = __fadd_rn(__fadd_rn(acc[t][0][r], acc[t][1][r]), bias[row]);
+                out[at] = fmaxf(v, 0.0f);
+            } else if (EPI == kLpEpiStore) {
+                out[at] = __fadd_rn(acc[t][0][r], acc[t][1][r]);
+            } else {
+                const float f = bias[((int64_t)(img + f_first) * Cout + row) * OHW + pix];
+                out[at] = f > 0.0f ? __fadd_rn(__fadd_rn(acc[t][0][r], acc[t][1][r]), out[at]) : 0.0f;
+            }
         }
     }
 }
@@ -346,6 +362,12 @@ static bool lp_dims(int batch, int height, int width, LpDims* d) {
     return true;
 }
 
+// the widest pixel tile (16 NT pixels) that still gives every CU a workgroup
+static int lp_tile_width(int64_t N, int gy) {
+    auto blocks = [&](int bn) { return (N + bn - 1) / bn; };
+    return blocks(64) * gy >= kLpCUs ? 4 : blocks(32) * gy >= kLpCUs ? 2 : 1;
+}
+
 template <int KS_, int STRIDE, int PAD, bool FIRST>
 static int lp_conv(float* out, const float* in0, const float* in1, int n_first, const float* packed, int l, int IH, int IW, int OH, int OW,
                    int n_img, const LpNorm& nrm, hipStream_t st) {
@@ -356,8 +378,7 @@ static int lp_conv(float* out, const float* in0, const float* in1, int n_first, 
     const int K = lp_k(l), KS4 = lp_kpad(l) / 4;
     auto blocks = [&](int bn) { return (N + bn - 1) / bn; };
     E3DGE_REQUIRE(blocks(16) < ((int64_t)1 << 31), "lpips_forward: grid too large");
-    // the widest pixel tile that still gives every CU a workgroup
-    const int nt = blocks(64) * gy >= kLpCUs ? 4 : blocks(32) * gy >= kLpCUs ? 2 : 1;
+    const int nt = lp_tile_width(N, gy);
 #define E3DGE_LP_LAUNCH(NT)                                                                                                     \
     lpips_conv_kernel<KS_, STRIDE, PAD, NT, FIRST><<<dim3((unsigned)blocks(16 * NT), gy), dim3(256), 0, st>>>(                 \
         out, in0, in1, n_first, wf, bias, lp_cin(l), IH, IW, Cout, OH, OW, N, K, KS4, nrm)
@@ -371,6 +392,8 @@ static int lp_pool(float* out, const float* in, int64_t planes, int IH, int IW, 
     lpips_pool_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(out, in, planes, IH, IW, OH, OW);
     return check_launch("lpips_forward(pool)");
 }
+
+#include "lpips_bwd.h"
 
 }  // namespace e3dge
 
@@ -439,6 +462,35 @@ extern "C" int e3dge_lpips_forward(const E3dgeLpipsArgs* args, e3dge_stream_t st
     f.partial = t.partial; f.per_image = a.per_image; f.per_layer = a.per_layer; f.mean = a.mean_out; f.batch = B;
     lpips_fold_kernel<<<dim3(1), dim3(64 * kLpLayers), 0, st>>>(f);
     return check_launch("lpips_forward(fold)");
+}
+
+extern "C" int64_t e3dge_lpips_packed_t_floats(void) { return kLpPackedTFloats; }
+
+extern "C" int e3dge_lpips_pack_weights_t(float* packed_t, const float* const* w, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(packed_t && w, "lpips_pack_weights_t: null pointer");
+    LpPackTSrc src;
+    for (int l = 0; l < kLpLayers; ++l) {
+        E3DGE_REQUIRE(w[l], "lpips_pack_weights_t: null pointer (layer %d)", l);
+        src.w[l] = w[l];
+    }
+    lpips_pack_t_kernel<<<dim3((unsigned)((kLpPackedTFloats + 255) / 256)), dim3(256), 0, as_stream(stream)>>>(packed_t, src);
+    return check_launch("lpips_pack_weights_t");
+}
+
+extern "C" int64_t e3dge_lpips_bwd_ws_bytes(int batch, int height, int width, int both) {
+    LpDims d;
+    if (!lp_dims(batch, height, width, &d) || batch >= 32768) {
+        fail(E3DGE_ERR_INVALID_ARG, "lpips_bwd_ws_bytes: batch=%d height=%d width=%d (batch >= 1, height and width >= 31)", batch, height, width);
+        return -1;
+    }
+    LpBwdDims bd;
+    lp_bwd_dims(d, both ? 2 * batch : batch, &bd);
+    return bd.total_bytes;
+}
+
+extern "C" int e3dge_lpips_backward(const E3dgeLpipsBwdArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "lpips_backward: null argument struct");
+    return lp_backward(*args, as_stream(stream));
 }
 
 extern "C" int e3dge_image_metric_row_lpips(float* row, const float* sums, const float* lpips_per_image, int batch, float l2_lambda,

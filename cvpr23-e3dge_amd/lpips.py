@@ -6,7 +6,13 @@ state dict saved from the reference's `LPIPS` loads with strict=True:
     net.mean, net.std, net.layers.{0,3,6,8,10}.{weight,bias}, lin.{0..4}.1.weight
 
 Unlike the reference it never downloads anything: a fresh module holds zeros, and `load_pretrained(alexnet_file, lin_file)` reads two
-LOCAL files (a torchvision AlexNet state dict and richzhang's alex.pth).  Only the forward exists; inputs that require grad raise."""
+LOCAL files (a torchvision AlexNet state dict and richzhang's alex.pth).
+
+The gradient with respect to the two images (csrc/lpips_bwd.h; the weights stay frozen, as the reference freezes them) is opt-in:
+`LPIPS(..., differentiable=True)` or `module.differentiable = True`.  Then, with grad enabled and an input that requires grad, the
+call goes through one autograd Function whose forward is the same launch (bit-identical values) and keeps its workspace -- the five
+activations and two pooled maps -- for the backward; the backward is once-differentiable.  With the switch off (the default) inputs
+that require grad raise NotImplementedError, as before."""
 import ctypes
 
 import torch
@@ -68,7 +74,7 @@ class LPIPS(nn.Module):
     """`LPIPS(device)(x, y)`: the scalar of lpips.py:39 for x, y (B, 3, H, W) float32 on the GPU, H, W >= 31.
     `forward(x, y, per_image=True)` returns the (B,) distances whose mean that scalar is."""
 
-    def __init__(self, device=None, net_type='alex', version='0.1'):
+    def __init__(self, device=None, net_type='alex', version='0.1', differentiable=False):
         assert version in ['0.1'], 'v0.1 is only supported now'
         if net_type in ('vgg', 'squeeze'):
             raise NotImplementedError(f"LPIPS net_type '{net_type}': only the AlexNet backbone has HIP kernels")
@@ -77,6 +83,7 @@ class LPIPS(nn.Module):
         super().__init__()
         self.net = _AlexFeatures()
         self.lin = _LinLayers(self.net.n_channels_list)
+        self.differentiable = bool(differentiable)
         if device is not None:
             self.to(device)
 
@@ -117,15 +124,29 @@ class LPIPS(nn.Module):
 
         return _lib.cached(self, "lpips_packed", src, build)
 
+    def _packed_t(self, device):
+        """The transposed weight image of the backward, on the same sources as the forward image."""
+        src = self._sources()
+        for t in src:
+            if t.device != device or t.dtype != torch.float32:
+                raise RuntimeError(f"LPIPS weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
+
+        def build():
+            with torch.no_grad():
+                keep = [t.detach().contiguous() for t in src[:5]]
+                packed_t = torch.empty(_lib.load().e3dge_lpips_packed_t_floats(), device=device, dtype=torch.float32)
+                _lib.launch("e3dge_lpips_pack_weights_t", packed_t, (ctypes.c_void_p * 5)(*[t.data_ptr() for t in keep]))
+                return packed_t
+
+        return _lib.cached(self, "lpips_packed_t", src, build)
+
     def _norm(self):
         """net.mean / net.std as host floats (read back once per buffer update, not per call)."""
         src = [self.net.mean, self.net.std]
         return _lib.cached(self, "lpips_norm", src, lambda: ([float(v) for v in src[0].reshape(-1).tolist()],
                                                              [float(v) for v in src[1].reshape(-1).tolist()]))
 
-    def run(self, x, y, per_layer=False, taps=False):
-        """The forward with its side outputs: dict(per_image (B,), mean (), per_layer (B, 5) or None, taps: five (2B, C, H, W) tensors
-        of the normalised features (x's images first) or None)."""
+    def _check(self, x, y):
         if not (torch.is_tensor(x) and torch.is_tensor(y)):
             raise TypeError("LPIPS takes two tensors")
         if x.ndim != 4 or x.shape[1] != 3 or x.shape != y.shape:
@@ -133,13 +154,15 @@ class LPIPS(nn.Module):
         B, _, H, W = x.shape
         if B < 1 or H < MIN_SIZE or W < MIN_SIZE:
             raise ValueError(f"LPIPS needs B >= 1 and H, W >= {MIN_SIZE} (got {tuple(x.shape)})")
-        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
-            raise NotImplementedError("LPIPS backward is not implemented: call under torch.no_grad() or detach the inputs")
+
+    def _launch_forward(self, x, y, per_layer=False, taps=False):
+        """(result dict of run(), workspace tensor): the one forward launch sequence, for detached GPU inputs."""
         _lib.require_gpu(x, "LPIPS x")
         _lib.require_gpu(y, "LPIPS y")
         dev = x.device
         if y.device != dev:
             raise RuntimeError(f"LPIPS x is on {dev}, y on {y.device}")
+        B, _, H, W = x.shape
         packed = self._packed(dev)
         mean, std = self._norm()
         x, y = x.detach().contiguous(), y.detach().contiguous()
@@ -161,8 +184,92 @@ class LPIPS(nn.Module):
             for i, t in enumerate(res['taps']):
                 a.taps[i] = t.data_ptr()
         _lib.launch("e3dge_lpips_forward", a)
-        return res
+        return res, ws
+
+    def _launch_backward(self, ws, shape, upstream, want_x, want_y, gpre=False):
+        """(grad_x or None, grad_y or None, the five G_l or None) from the workspace `ws` a forward of inputs of `shape` left behind;
+        upstream (B,) = dL / d per_image."""
+        B, _, H, W = shape
+        dev = ws.device
+        lib = _lib.load()
+        both = bool(want_x and want_y)
+        ws_bytes = lib.e3dge_lpips_bwd_ws_bytes(B, H, W, int(both))
+        if ws_bytes < 0:
+            raise RuntimeError(f"e3dge_lpips_bwd_ws_bytes: {lib.e3dge_last_error().decode(errors='replace')}")
+        bws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        gx = torch.empty(shape, device=dev, dtype=torch.float32) if want_x else None
+        gy = torch.empty(shape, device=dev, dtype=torch.float32) if want_y else None
+        a = _lib.LpipsBwdArgs(packed=self._packed(dev), packed_t=self._packed_t(dev), fwd_ws=ws, fwd_ws_bytes=ws.numel(), batch=B, height=H,
+                              width=W, upstream=upstream, grad_x=gx, grad_y=gy, ws=bws, ws_bytes=ws_bytes)
+        a.std[:] = self._norm()[1]
+        g = None
+        if gpre:
+            g = [torch.empty(((2 if both else 1) * B, c, h, w), device=dev, dtype=torch.float32) for c, h, w in tap_shapes(H, W)]
+            for i, t in enumerate(g):
+                a.gpre[i] = t.data_ptr()
+        _lib.launch("e3dge_lpips_backward", a)
+        return gx, gy, g
+
+    def run(self, x, y, per_layer=False, taps=False):
+        """The forward with its side outputs: dict(per_image (B,), mean (), per_layer (B, 5) or None, taps: five (2B, C, H, W) tensors
+        of the normalised features (x's images first) or None).  With `differentiable` set, grad enabled and an input that requires
+        grad, per_image and mean carry the graph (per_layer and taps never do)."""
+        self._check(x, y)
+        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+            if not self.differentiable:
+                raise NotImplementedError("LPIPS backward is off for this module: set `differentiable = True` (or construct it with "
+                                          "differentiable=True), call under torch.no_grad(), or detach the inputs")
+            _lib.require_gpu(x, "LPIPS x")
+            _lib.require_gpu(y, "LPIPS y")
+            side = {}
+            per_image, mean = _LpipsFunction.apply(self, side, bool(per_layer), bool(taps), x, y)
+            return dict(per_image=per_image, mean=mean, per_layer=side['per_layer'], taps=side['taps'])
+        return self._launch_forward(x, y, per_layer, taps)[0]
+
+    def run_backward(self, x, y, upstream, want_x=True, want_y=False, gpre=False):
+        """Debug entry: the forward, then the backward for upstream (B,) = dL / d per_image.  Returns (grad_x or None, grad_y or None,
+        the five gradients G_l at the conv pre-activations -- (n, C_l, H_l, W_l) of the images that get a gradient, x's first -- or
+        None).  Needs no autograd and records none."""
+        self._check(x, y)
+        if not (want_x or want_y):
+            raise ValueError("LPIPS.run_backward: neither gradient is wanted")
+        _lib.require_gpu(upstream, "LPIPS upstream")
+        if upstream.shape != (x.shape[0],):
+            raise ValueError(f"LPIPS upstream must be ({x.shape[0]},) (got {tuple(upstream.shape)})")
+        with torch.no_grad():
+            _, ws = self._launch_forward(x, y)
+            return self._launch_backward(ws, tuple(x.shape), upstream.detach().contiguous(), want_x, want_y, gpre)
 
     def forward(self, x, y, per_image=False):
         res = self.run(x, y)
         return res['per_image'] if per_image else res['mean']
+
+
+class _LpipsFunction(torch.autograd.Function):
+    """(per_image, mean) of one forward launch; the backward reads the workspace that launch left behind."""
+
+    @staticmethod
+    def forward(ctx, module, side, per_layer, taps, x, y):
+        res, ws = module._launch_forward(x, y, per_layer, taps)
+        side['per_layer'], side['taps'] = res['per_layer'], res['taps']
+        ctx.module, ctx.ws, ctx.shape = module, ws, tuple(x.shape)
+        ctx.set_materialize_grads(False)
+        # two tensors of their own storage would cost a copy: the two views of one buffer are returned as they are
+        return res['per_image'], res['mean']
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_per_image, g_mean):
+        want_x, want_y = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        if (g_per_image is None and g_mean is None) or not (want_x or want_y):
+            return None, None, None, None, None, None
+        B = ctx.shape[0]
+        if g_mean is None:
+            u = g_per_image
+        else:
+            u = (g_mean / B).expand(B)
+            if g_per_image is not None:
+                u = g_per_image + u
+        u = u.to(torch.float32).contiguous()
+        gx, gy, _ = ctx.module._launch_backward(ctx.ws, ctx.shape, u, want_x, want_y)
+        return None, None, None, None, gx, gy

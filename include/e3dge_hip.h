@@ -720,6 +720,47 @@ int e3dge_image_metric_row_lpips(float* row, const float* sums, const float* lpi
                                  float vgg_lambda, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * LPIPS backward (csrc/lpips_bwd.h): the gradient of per_image[b] with respect to x, y or both; the AlexNet and lin weights
+ * are frozen, as the reference freezes them.  Additions to ABI 16.  No allocation, no synchronisation, no atomics: eight
+ * launches whatever the batch, bit-reproducible, and an image's gradient does not depend on the batch it is in.
+ *
+ * The workspace of e3dge_lpips_forward is therefore also an OUTPUT of the forward: after the call it holds the five post-ReLU
+ * conv outputs and the two pooled maps of the 2 batch images, and a caller that wants the gradient keeps it untouched until
+ * e3dge_lpips_backward has run (fwd_ws, fwd_ws_bytes; same batch, height and width).  Nothing of the forward is recomputed
+ * but the channel norms.
+ *
+ * e3dge_lpips_packed_t_floats floats of the transposed weight image: W_l^T with flipped taps for conv 2..5 (M = C_in, K = (co, r, s)
+ *                            padded to a multiple of 32) in MFMA A-fragment order, then conv 1 as (3, 64, 11, 11).  A buffer of
+ *                            its own; the forward image is unchanged.
+ * e3dge_lpips_pack_weights_t w: HOST array of the five device pointers e3dge_lpips_pack_weights takes.  One launch per weight update.
+ * e3dge_lpips_bwd_ws_bytes   workspace bytes of a backward for `batch` gradient images (both = 0) or 2 batch (both != 0); -1 as
+ *                            e3dge_lpips_ws_bytes.
+ * e3dge_lpips_backward       upstream (batch) = dL / d per_image[b] (for the scalar mean: dL / d mean / batch).  grad_x, grad_y: NULL
+ *                            or (batch, 3, height, width), at least one; every element is written.  gpre[l]: NULL or (n, C_l, H_l,
+ *                            W_l), the gradient at conv l + 1's pre-activation of the images that get a gradient, x's first
+ *                            (n = batch or 2 batch).  std as in the forward.  Fails before any launch on a null required pointer
+ *                            ("null"), both gradients NULL, batch < 1 ("batch"), height or width < 31, a zero std, or either
+ *                            workspace too small ("workspace").
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct E3dgeLpipsBwdArgs {
+    const float* packed;              /* the forward image (its lin rows are read) */
+    const float* packed_t;            /* e3dge_lpips_pack_weights_t */
+    const void* fwd_ws;               /* what a completed e3dge_lpips_forward of the same batch / height / width left behind */
+    int64_t fwd_ws_bytes;
+    int32_t batch, height, width;
+    float std[3];
+    const float* upstream;
+    float* grad_x; float* grad_y;
+    float* gpre[5];
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeLpipsBwdArgs;
+int64_t e3dge_lpips_packed_t_floats(void);
+int e3dge_lpips_pack_weights_t(float* packed_t, const float* const* w, e3dge_stream_t stream);
+int64_t e3dge_lpips_bwd_ws_bytes(int batch, int height, int width, int both);
+int e3dge_lpips_backward(const E3dgeLpipsBwdArgs* args, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Surface extraction, device half: replaces align_volume (project/utils/mesh_utils.py:17-44; called on the rendered
  * 128^3 SDF volume at volume_renderer.py:1706, before the CPU marching cubes).  volume, out (batch, height, width, depth,
  * channels), not aliased; xs (width), ys (height), zs (depth) = linspace(-1, 1, n) and coef (depth) = linspace(far / near,

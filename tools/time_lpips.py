@@ -2,12 +2,16 @@
 """Time of one LPIPS forward (e3dge_amd.lpips.LPIPS, csrc/lpips.hip) against the library formulation a user runs today: the same
 forward as torch ops on GPU tensors (conv2d / max_pool2d through MIOpen), in the same process on the same GPU.
 
-    python tools/time_lpips.py [--out FILE.json] [--steps 20] [--no-launches]
+    python tools/time_lpips.py [--out FILE.json] [--steps 20] [--no-launches] [--backward]
 
 Cases: 256^2 with B = 1 and B = 8, 1024^2 with B = 1 (what the C3 leg of bench.py hands to image_metrics).  Estimator: warm-up, then
 five blocks of `steps` forwards between two HIP events; the median block, per forward.  `achieved` is the fraction of the fp32
 matrix peak (157.3 TFLOP/s) the HIP path reaches on the convolutions' 2 x MAC count.  The device kernels of one forward of each path are
-counted with torch.profiler (--no-launches skips that, e.g. under another profiler).  Prints one JSON line per case."""
+counted with torch.profiler (--no-launches skips that, e.g. under another profiler).  Prints one JSON line per case.
+
+--backward times the training direction instead: forward + backward with the gradient to x only (LPIPS(differentiable=True), csrc/
+lpips_bwd.h) against autograd through the same torch ops, at 256^2 with B = 1 and B = 4 (the samples per GPU of a training step) and
+1024^2 with B = 1; same estimator; `grad_rel_diff` is max|hip - torch| / max|torch| of the two gradients."""
 import argparse
 import json
 import os
@@ -77,14 +81,38 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--no-launches", action="store_true")
+    ap.add_argument("--backward", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = "cuda:0"
     m = syn.load_synthetic_lpips(LPIPS()).to(dev)
     sd = {k: v for k, v in m.state_dict().items()}
     lines = []
+    if args.backward:
+        m.differentiable = True
+        for batch, size in ((1, 256), (4, 256), (1, 1024)):
+            g = torch.Generator(device=dev).manual_seed(size + batch)
+            x = (torch.rand(batch, 3, size, size, device=dev, generator=g) * 2 - 1).requires_grad_(True)
+            y = (x.detach() + 0.3 * torch.randn(batch, 3, size, size, device=dev, generator=g)).clamp(-1, 1)
+
+            def step(fn):
+                x.grad = None
+                fn(x, y).backward()
+                return x.grad
+
+            hip, lib = lambda: step(m), lambda: step(lambda a, b: torch_lpips(sd, a, b))
+            ga, gb = hip().clone(), lib().clone()
+            t_hip, t_lib = block_ms(hip, args.steps), block_ms(lib, args.steps)
+            line = dict(case=f"B{batch}_{size}", what="forward + backward, gradient to x", hip_ms=t_hip[0], hip_ms_min=t_hip[1],
+                        hip_ms_max=t_hip[2], torch_ms=t_lib[0], torch_ms_min=t_lib[1], torch_ms_max=t_lib[2], speedup=t_lib[0] / t_hip[0],
+                        grad_rel_diff=float((ga - gb).abs().max() / gb.abs().max()),
+                        estimator=f"median of 5 blocks of {args.steps} steps, HIP events")
+            if not args.no_launches:
+                line["hip_launches"], line["torch_launches"] = count_kernels(hip), count_kernels(lib)
+            print(json.dumps(line), flush=True)
+            lines.append(line)
     with torch.no_grad():
-        for batch, size in ((1, 256), (8, 256), (1, 1024)):
+        for batch, size in () if args.backward else ((1, 256), (8, 256), (1, 1024)):
             g = torch.Generator(device=dev).manual_seed(size + batch)
             x = torch.rand(batch, 3, size, size, device=dev, generator=g) * 2 - 1
             y = (x + 0.3 * torch.randn(batch, 3, size, size, device=dev, generator=g)).clamp(-1, 1)
