@@ -10,8 +10,8 @@
 // w'' = ((scale W) s) demod per sample, rounded as the reference rounds it (:319-326), rebuilt by one streaming launch
 // per forward.  The operand scale of a packed tensor comes from an a-priori bound (demodulated filters have unit norm,
 // the FIR taps of a phase sum to one), so a producer can scale before it has seen its own maximum.
+#include "siren_common.h"      // vector types, split2, mfma16, kW16Scale
 #include "decoder_common.h"
-#include "stamps.h"
 #include <stdlib.h>
 #include <math.h>
 #include <type_traits>
@@ -33,14 +33,6 @@ constexpr int kPkEpiValu = 8;    // VALU instructions of a finished tile's epilo
 #define PK_T_DONE(NW_) IF_PK_TIMING(tacc[8] = stamp_now() - tbegin; tacc[9] = nsteps; \
                                     stamps_flush(blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == (NW_) - 1), 2 * a.stamp_row + (wave != 0), tacc, 10);)
 
-__device__ __forceinline__ uint32_t lds_u32(const void* p) {
-    return (uint32_t)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
-}
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {       // make wave-uniformity explicit for an SGPR operand
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    return reinterpret_cast<const void*>(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-                                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
-}
 // q / d for 0 <= q < 2^24, d > 0 (float reciprocal + fix-up)
 __device__ __forceinline__ int div_small(int q, int d, float rcp) {
     int i = (int)((float)q * rcp);
@@ -49,13 +41,6 @@ __device__ __forceinline__ int div_small(int q, int d, float rcp) {
     return i;
 }
 __device__ __forceinline__ float pow2_bits(unsigned biased) { return __uint_as_float(biased << 23); }
-// value of the lane one below / one above in the wavefront (DPP wave_shr:1 / wave_shl:1; the end lanes read 0)
-__device__ __forceinline__ float dpp_wave_shr1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float dpp_wave_shl1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // fp32 (B, C, R, R) <-> packed
@@ -299,18 +284,8 @@ __device__ __forceinline__ void bwd_tile_epilogue(const PkConvK& a, const f32x16
     if (ok) amax_l = fmaxf(amax_l, m);
 }
 
-// one LDS-DMA piece (64 lanes x 16 B -> 1 KiB of LDS at lds_dst), global address = wave-uniform base + per-lane byte offset
-__device__ __forceinline__ void dma_piece(const void* sbase, uint32_t voff, uint32_t lds_dst) {
-    glds16_saddr<0>(uniform_ptr(sbase), voff, (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_dst));
-}
-
-// XCD-aware tile order (MI355X_MICROARCH: block b runs on XCD b % 8, each XCD has its own L2): workgroup-tile t -> logical
-// tile id such that every XCD walks one CONTIGUOUS range of logical ids; logical ids put the co-blocks of one pixel tile
-// next to each other (they read the same input patch) and neighbouring pixel tiles after that (they share halos).
-__device__ __forceinline__ int xcd_logical(int t, int n_tiles) {
-    const int nq = n_tiles >> 3, nr = n_tiles & 7, xcd = t & 7, slot = t >> 3;
-    return (xcd < nr ? xcd * (nq + 1) : nr * (nq + 1) + (xcd - nr) * nq) + slot;
-}
+// Tile order: xcd_logical (gfx950_prims.h); logical ids put the co-blocks of one pixel tile next to each other (they read the same
+// input patch) and neighbouring pixel tiles after that (they share halos).
 
 // ---- stride-1 3x3, pad 1 ---------------------------------------------------------------------------------------------
 // Workgroup tile: (32 NCT WCO) output channels x (NPY WY) rows x (32 NPX WX) columns; a wave owns NCT co-tiles x NPY x NPX
@@ -455,7 +430,7 @@ __global__ void __launch_bounds__(64 * WCO * WY * WX) pkconv_s1_kernel(const PkC
         }
     };
     auto stage_lds = [&](int stage) {
-        uint32_t xl = lds_u32(smem_pk) + (uint32_t)(stage * STAGE);
+        uint32_t xl = lds_addr(smem_pk) + (uint32_t)(stage * STAGE);
         asm volatile("" : "+s"(xl));
         return xl;
     };
@@ -895,7 +870,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) pkconv_upblur2_kerne
         return sc;
     };
     auto issue = [&](const Src& sc, int stage, int s_lo, int s_hi) {
-        uint32_t xl = lds_u32(smem_pk) + (uint32_t)(stage * STAGE);
+        uint32_t xl = lds_addr(smem_pk) + (uint32_t)(stage * STAGE);
         asm volatile("" : "+s"(xl));
         const void* wsrc = reinterpret_cast<const void*>((uint64_t)sc.whi << 32 | sc.wlo);
         const void* xsrc = reinterpret_cast<const void*>((uint64_t)sc.xhi << 32 | sc.xlo);

@@ -87,8 +87,7 @@ pk_drgb_down_kernel(float* __restrict__ y, float* __restrict__ y_amax, const flo
         y[(int64_t)pl * hw + p] = v;
     }
     float m = fabsf(v);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0)
@@ -149,8 +148,7 @@ __global__ void __launch_bounds__(256) pk_rgbt_mask_kernel(const PkRgbtK a) {
         reinterpret_cast<u32x4*>(a.y)[e[u]] = hi;
         reinterpret_cast<u32x4*>(a.y)[e[u] + plane] = lo;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    m = wave_max(m);
     if (lane == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0)
@@ -271,8 +269,7 @@ __global__ void __launch_bounds__(256) pk_dblur_kernel(const PkDblurK a) {
             pp[(int64_t)(4 + ph) * planep] = lo;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    m = wave_max(m);
     if (lane == 0) red[tid >> 6] = m;
     __syncthreads();
     if (tid == 0)
@@ -370,7 +367,7 @@ __global__ void __launch_bounds__(256) pkconv_down_kernel(const PkConvK a) {
         }
     };
     auto stage_lds = [&](int stage) {
-        uint32_t xl = lds_u32(smem_pk) + (uint32_t)(stage * STAGE);
+        uint32_t xl = lds_addr(smem_pk) + (uint32_t)(stage * STAGE);
         asm volatile("" : "+s"(xl));
         return xl;
     };

@@ -120,13 +120,8 @@ __global__ void __launch_bounds__(kMcThreads) modconv_kernel(const ModconvK a) {
             const int ct = piece / 18, pc = piece - ct * 18;
             const unsigned char* src = reinterpret_cast<const unsigned char*>(a.wimg) +
                                        ((size_t)(cb * NCTB + ct) * a.n_chunks + c) * kMcSlabBytes + (size_t)pc * 1024;
-            const uint32_t dst = (uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)(wbuf + buf * WBUF) +
-                                 (uint32_t)(ct * kMcSlabBytes + pc * 1024);
-            // (the address is wave-uniform by construction; readfirstlane makes that explicit for the SGPR operand)
-            const uint64_t sa = reinterpret_cast<uint64_t>(src);
-            const uint64_t su = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sa >> 32)) << 32) |
-                                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sa);
-            glds16_saddr<0>(reinterpret_cast<const void*>(su), (uint32_t)lane * 16u, (uint32_t)__builtin_amdgcn_readfirstlane((int)dst));
+            // (both addresses are wave-uniform by construction; dma_piece makes that explicit for the SGPR operands)
+            dma_piece(src, (uint32_t)lane * 16u, lds_addr(wbuf + buf * WBUF) + (uint32_t)(ct * kMcSlabBytes + pc * 1024));
         }
     };
     // The geometry of a patch item (which pixel of the patch, which global element, inside the image or not) depends on the tile
@@ -410,8 +405,7 @@ modconv_demod_kernel(float* __restrict__ demod, float* __restrict__ s_amax, cons
     if (blockIdx.x == 0 && wave == 0) {
         float m = 0.0f;
         for (int ci = lane; ci < Ci; ci += 64) m = fmaxf(m, fabsf(s[ci]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+        m = wave_max(m);
         if (lane == 0) s_amax[b] = m;
     }
 }
@@ -436,8 +430,7 @@ __global__ void __launch_bounds__(256) amax_kernel(float* __restrict__ out, cons
         m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0)
@@ -496,8 +489,7 @@ decoder_demod_kernel(const E3dgeModLayer* __restrict__ tab, int n_layers, int to
         const float* __restrict__ s = L.style_out + (size_t)b * L.ci;
         float m = 0.0f;
         for (int ci = lane; ci < L.ci; ci += 64) m = fmaxf(m, fabsf(s[ci]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+        m = wave_max(m);
         if (lane == 0) L.s_amax_out[b] = m;
     }
 }
@@ -597,8 +589,7 @@ __global__ void __launch_bounds__(256) amax_rows_kernel(float* __restrict__ out,
         const int64_t r = i / width;
         m = fmaxf(m, fabsf(x[r * ld + (i - r * width)]));
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0)

@@ -126,66 +126,10 @@ resblock_norm_kernel(float* __restrict__ aux, const float* __restrict__ w0, cons
     if (threadIdx.x == 0) { aux[0] = red[0][0]; aux[1] = red[1][0]; aux[2] = 0.0f; aux[3] = 0.0f; }
 }
 
-// The weight-chunk pipeline of this kernel (cf. ChunkPipe in siren_common.h, which the 8-wave SIREN kernels use with three
-// 32-KiB buffers and a plain vmcnt(0)).  Chunk c lives in buffer c % kRbNBuf; wave w copies bytes [5 w, 5 w + 5) KiB of a
-// chunk in five 1-KiB LDS-DMA pieces.  sync(), early in chunk c: every wave waits until ITS pieces of chunk c+1 have landed
-// -- in-order completion: at most the 5 (kRbNBuf - 3) pieces of the chunks after it may still be outstanding; output stores
-// and x loads in the queue only make the wait stricter, never laxer --, the barrier publishes chunk c+1 and proves that
-// everybody has left chunk c-1, whose buffer the DMA of chunk c + kRbNBuf - 1 may now overwrite.  Chunk indices wrap
-// after `count`; chunks fetched past the end of the work land in buffers nobody reads (the kernel ends with vmcnt(0)).
-struct RbPipe {
-    const char* img;          // image + this wave's 5-KiB slice (wave-uniform)
-    const char* src;          // chunk being issued
-    uint32_t voff;            // lane * 16
-    uint32_t lds_base;        // LDS byte address of wbuf + this wave's slice
-    uint32_t lds_dst;         // ... of the buffer being filled
-    int idx, count, buf, use_buf;
-    float* wbuf;
-    const float* wcur;
-    const float* wnxt;
-    static constexpr int kSliceBytes = kRbPieces * 1024;
-    __device__ __forceinline__ void init(float* wbuf_, const float* image, int wave, int lane, int count_) {
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        wbuf = wbuf_;
-        img = reinterpret_cast<const char*>(image) + wave_u * kSliceBytes;
-        voff = (uint32_t)lane * 16u;
-        lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) float*)wbuf_ + (uint32_t)wave_u * kSliceBytes;
-        count = count_;
-        idx = 0; buf = 0; use_buf = 0;
-        src = img;
-        lds_dst = lds_base;
-        wcur = wbuf_; wnxt = wbuf_ + kRbChunkFloats;
-    }
-    __device__ __forceinline__ void issue_piece(int i) {     // i is a compile-time constant at every call site
-        switch (i) {
-            case 0: glds16_saddr<0>(src, voff, lds_dst); break;
-            case 1: glds16_saddr<1024>(src, voff, lds_dst); break;
-            case 2: glds16_saddr<2048>(src, voff, lds_dst); break;
-            case 3: glds16_saddr<3072>(src, voff, lds_dst); break;
-            default: glds16_saddr<0>(src + 4096, voff, lds_dst + 4096u); break;     // the immediate is 13-bit signed
-        }
-        if (i == kRbPieces - 1) {
-            idx = (idx + 1 == count) ? 0 : idx + 1;
-            src = img + (size_t)idx * (kRbChunkFloats * 4);
-            buf = (buf + 1 == kRbNBuf) ? 0 : buf + 1;
-            lds_dst = lds_base + (uint32_t)buf * (kRbChunkFloats * 4);
-        }
-    }
-    __device__ __forceinline__ void prime() {
-        for (int c = 0; c < kRbNBuf - 1; ++c)
-#pragma unroll
-            for (int i = 0; i < kRbPieces; ++i) issue_piece(i);
-    }
-    __device__ __forceinline__ void sync() {
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRbPieces * (kRbNBuf - 3)) : "memory");
-        __syncthreads();
-    }
-    __device__ __forceinline__ void advance() {
-        use_buf = (use_buf + 1 == kRbNBuf) ? 0 : use_buf + 1;
-        wcur = wnxt;
-        wnxt = wbuf + ((use_buf + 1 == kRbNBuf) ? 0 : use_buf + 1) * kRbChunkFloats;
-    }
-};
+// The weight-chunk pipeline of this kernel: ChunkPipeT (gfx950_prims.h, which states the wait rule) with five 20-KiB buffers, five
+// pieces per wave and chunk and the counted vmcnt that leaves the kRbNBuf - 3 youngest chunks in flight; the x loads and output
+// stores of this kernel sit in the same queue and only make that wait stricter.
+using RbPipe = ChunkPipeT<kRbChunkFloats, kRbPieces, kRbNBuf, kRbPieces * (kRbNBuf - 3)>;
 
 // one weight chunk against its KSTEPS k-steps of a B operand produced by `opnd(g, H, L)`; the same operand ring as
 // big_tile_f16 (siren_common.h), with the chunk barrier after k-step SYNC and the DMA pieces of the chunk kRbNBuf - 1
@@ -293,7 +237,7 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
     for (int i = tid_k; i < kRbKin + kRbOut; i += kThreads) b0_s[i] = packed[kRbOffBias0 + i];
 
     RbPipe pipe;
-    pipe.init(wbuf, packed, tid_k >> 6, tid_k & 63, kRbChunks);
+    pipe.init(wbuf, packed, tid_k >> 6, tid_k & 63, 0, kRbChunks);
     pipe.prime();
     auto issue_piece = [&](int i) { pipe.issue_piece(i); };
     IF_RB_TRACE([[maybe_unused]] bool tr_on = false; bool tr_sub = false;
@@ -301,7 +245,7 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
                 [[maybe_unused]] stamp_t tr_ts[4] = {0, 0, 0, 0};)
     auto chunk_sync = [&]() {                 // pipe.sync(), with a stamp around each of its halves
         RB_STAMP(100);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRbPieces * (kRbNBuf - 3)) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RbPipe::kWait) : "memory");
         RB_STAMP(200);
         __syncthreads();
         RB_STAMP(300);
@@ -339,7 +283,7 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
             const unsigned pin = in_img - tile * (unsigned)a.R * (unsigned)a.S;
             const unsigned slab = ((b * (unsigned)a.tiles_per_img + tile) * (unsigned)a.bb_subs + (pin >> 7)) * 8u + ((pin >> 4) & 7u);
             rec_b = (slab * 1024u + (pin & 15u) + 16u * (unsigned)half) * 16u;
-            h8_lds = (uint32_t)(size_t)(__attribute__((address_space(3))) float*)(smem + kRbLdsH8) + (uint32_t)wave * 8192u;
+            h8_lds = lds_addr(smem + kRbLdsH8) + (uint32_t)wave * 8192u;
             stash = reinterpret_cast<f32x4*>(smem + kRbLdsStash + wave * 1024) + lane;
         }
 
@@ -421,9 +365,8 @@ __global__ void __launch_bounds__(kThreads) resblock_kernel(const ResblockK a) {
             m = fmaxf(m, xhalf(m));
             ss += xhalf(ss);
             xnorm = sqrtf(ss);
-            const unsigned e = min((__float_as_uint(m) >> 23) & 255u, 254u);
-            const float sc = __uint_as_float((254u - e) << 23);
-            inv_x = __uint_as_float((e > 8u ? e - 7u : 1u) << 23);
+            float sc;
+            block_scale(m, sc, inv_x);
 #pragma unroll
             for (int t = 0; t < kRbTilesIn; ++t) {
 #pragma unroll

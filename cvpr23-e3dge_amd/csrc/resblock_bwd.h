@@ -5,7 +5,7 @@
 // hand-written backward here; `_resblock_backward_torch` (volume_renderer.py of this package) was the library form of the same lines.
 //
 // Same machine as the forward kernel (4 waves x 32 points, a point in a lane pair, split-f16 MFMA with per-point power-of-two block
-// scales, weights streamed L2 -> LDS in 20-KiB chunks through RbPipe), four contractions per 128-point sub-tile:
+// scales, weights streamed L2 -> LDS in 20-KiB chunks through RbPipe = ChunkPipeT of gfx950_prims.h), four contractions per 128-point sub-tile:
 //   G1  net = W_0 relu(x) + b_0     K 320 -> 320   x resident (160 operand registers); only the SIGNS of net are kept (sign words in LDS),
 //                                                  x's own signs likewise; then x is dropped
 //   G2  d net = (W_1^T d out) [net > 0]   K 512 -> 320   d out resident (256 operand registers); d net -> workspace rows (fp32, 320 wide)
@@ -122,17 +122,8 @@ struct ResblockBwdK {
 // the wave's largest value into an amax buffer (round 6: the kernel holds every operand of the head's parameter gradients anyway; four
 // e3dge_amax passes over 100-MB tensors -- 120 us per stage-2 step -- are not needed)
 __device__ __forceinline__ void rb_amax_publish(float* buf, float m, int lane, int slot) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    m = wave_max(m);
     if (lane == 0) atomic_max_nonneg(buf + (slot & (kAmaxSlots - 1)) * kAmaxStride, m);
-}
-
-// power-of-two block scale of a point whose largest magnitude is m: operand = value * sc in [1, 2), accumulator * inv = true sum (the
-// weight image carries kW16Scale = 128); the forward's rule (resblock_kernel, "x")
-__device__ __forceinline__ void rb_block_scale(float m, float& sc, float& inv) {
-    const unsigned e = min((__float_as_uint(m) >> 23) & 255u, 254u);
-    sc = __uint_as_float((254u - e) << 23);
-    inv = __uint_as_float((e > 8u ? e - 7u : 1u) << 23);
 }
 
 // sign words: 32 decisions [v > 0] per word, pushed in from the right (decision i of a word ends at bit 31 - i); integer ops only
@@ -162,7 +153,7 @@ __global__ void __launch_bounds__(kThreads) resblock_bwd_kernel(const ResblockBw
     for (int i = tid_k; i < kRbKin; i += kThreads) b0_s[i] = packed[kRbBOffBias0 + i];
 
     RbPipe pipe;
-    pipe.init(wbuf, packed, tid_k >> 6, tid_k & 63, kRbBChunks);
+    pipe.init(wbuf, packed, tid_k >> 6, tid_k & 63, 0, kRbBChunks);
     pipe.prime();
     auto issue_piece = [&](int i) { pipe.issue_piece(i); };
     auto chunk_sync = [&]() { pipe.sync(); };
@@ -260,7 +251,7 @@ __global__ void __launch_bounds__(kThreads) resblock_bwd_kernel(const ResblockBw
                 m = fmaxf(m, xhalf(m));
                 if (a.amax4) rb_amax_publish(a.amax4, m, lane, (int)blockIdx.x * 4 + wave);
                 float sc;
-                rb_block_scale(m, sc, inv_x);
+                block_scale(m, sc, inv_x);
 #pragma unroll
                 for (int t = 0; t < kRbTilesIn; ++t) {
 #pragma unroll
@@ -322,7 +313,7 @@ __global__ void __launch_bounds__(kThreads) resblock_bwd_kernel(const ResblockBw
             m = fmaxf(m, xhalf(m));
             if (a.amax4) rb_amax_publish(a.amax4 + E3DGE_AMAX_FLOATS, m, lane, (int)blockIdx.x * 4 + wave);
             float sc_y;
-            rb_block_scale(m, sc_y, inv_y);
+            block_scale(m, sc_y, inv_y);
 #pragma unroll
             for (int T = 0; T < kRbTilesOut; ++T) {
                 const float* __restrict__ s = (T < 8) ? ya + 32 * T : yb + 32 * (T - 8);
@@ -387,7 +378,7 @@ __global__ void __launch_bounds__(kThreads) resblock_bwd_kernel(const ResblockBw
         // ---- 6. G3: d x = (W_0^T d net) [x > 0] + short ----
         {
             // `short` of tile t by LDS-DMA into buffer t % 3 of this wave, two tiles ahead of its use: piece q = this lane's quad q
-            const uint32_t sh_lds = (uint32_t)(size_t)(__attribute__((address_space(3))) float*)(smem + kRbBLdsShort) + (uint32_t)wave * (3u * 4096u);
+            const uint32_t sh_lds = lds_addr(smem + kRbBLdsShort) + (uint32_t)wave * (3u * 4096u);
             const unsigned sh_voff = row_off * 4u;
             auto short_piece = [&](int t, int q) {
                 const uint32_t dst = sh_lds + (uint32_t)((t % 3) * 4096 + q * 1024);
@@ -399,7 +390,7 @@ __global__ void __launch_bounds__(kThreads) resblock_bwd_kernel(const ResblockBw
             for (int q = 0; q < 4; ++q) short_piece(1, q);
             m_d = fmaxf(m_d, xhalf(m_d));
             float sc_d, inv_d;
-            rb_block_scale(m_d, sc_d, inv_d);
+            block_scale(m_d, sc_d, inv_d);
             u32x4 dH[kRbStepsIn], dL[kRbStepsIn];
             {
                 const float* __restrict__ src = ws_net + row_off;

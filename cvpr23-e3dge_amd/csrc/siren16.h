@@ -83,15 +83,12 @@ __device__ __forceinline__ float act16_get(const u32x4 (&aH)[k16Steps], const u3
     const int g = t >> 1, w = 2 * (t & 1) + (r >> 1);
     return (r & 1) ? f16hi(aH[g][w]) + f16hi(aL[g][w]) : f16lo(aH[g][w]) + f16lo(aL[g][w]);
 }
-template <int CTRL> __device__ __forceinline__ float dpp16(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-}
 // sum over the 16 lanes of a row (every lane of the row gets the total)
 __device__ __forceinline__ float row_sum16(float x) {
-    x += dpp16<0x128>(x);    // row_ror:8
-    x += dpp16<0x124>(x);    // row_ror:4
-    x += dpp16<0x122>(x);    // row_ror:2
-    x += dpp16<0x121>(x);    // row_ror:1
+    x += dpp_f32<0x128>(x);    // row_ror:8
+    x += dpp_f32<0x124>(x);    // row_ror:4
+    x += dpp_f32<0x122>(x);    // row_ror:2
+    x += dpp_f32<0x121>(x);    // row_ror:1
     return x;
 }
 
@@ -108,12 +105,9 @@ __device__ __forceinline__ float sum_over_q(float x) {
     return __builtin_bit_cast(float, (unsigned)t[0]) + __builtin_bit_cast(float, (unsigned)t[1]);
 }
 
-// Wave-wide inclusive scans in the VALU (DPP; gfx9 controls row_shr:n = 0x110 + n, row_bcast:15 = 0x142, row_bcast:31 = 0x143,
-// wave_shr:1 = 0x138): four shifted steps inside every 16-lane row, then lane 15 of rows 0 / 2 into rows 1 / 3 and lane 31 into
-// rows 2 and 3.  Lanes a step does not reach combine with the identity.  Lane 63 ends up with the reduction over the wave.
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_or(float ident, float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ident), __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xf, false));
-}
+// Wave-wide inclusive scans in the VALU (dpp_or, gfx950_prims.h): four shifted steps inside every 16-lane row, then lane 15 of rows
+// 0 / 2 into rows 1 / 3 and lane 31 into rows 2 and 3.  Lanes a step does not reach combine with the identity.  Lane 63 ends up
+// with the reduction over the wave.
 __device__ __forceinline__ float wave_incl_prod(float x) {
     x = __fmul_rn(x, dpp_or<0x111, 0xf>(1.0f, x));
     x = __fmul_rn(x, dpp_or<0x112, 0xf>(1.0f, x));
@@ -153,7 +147,7 @@ struct ChunkPipe16 {
         count = count_;
         img = reinterpret_cast<const char*>(image) + wave_u * 2048;
         voff = (uint32_t)lane * 16u;
-        lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) float*)wbuf_ + (uint32_t)wave_u * 2048u;
+        lds_base = lds_addr(wbuf_) + (uint32_t)wave_u * 2048u;
         idx = 0; buf = 0; use_buf = 0;
         wcur = wbuf_; wnxt = wbuf_ + k16ChunkFloats;
     }

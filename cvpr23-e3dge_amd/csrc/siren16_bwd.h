@@ -128,13 +128,11 @@ __device__ __forceinline__ void t3_issue_tile(const void* gbase, uint32_t voff, 
 template <int NS, int NO> __device__ __forceinline__ void t3_hook_wait(int t) {
     if (t == 2) t3_wait<2 + 2 * NS + NO>(); else t3_wait<2 + 2 * NS + 2 * NO>();
 }
-__device__ __forceinline__ uint32_t lds_addr_of(const float* p) {
-    return (uint32_t)(size_t)(__attribute__((address_space(3))) const float*)p;
-}
 
-// Split-f16 operand of a backward-type GEMM (see scale_split in siren_bwd.hip): the 256 values of a point are spread over the
-// four lanes n, n+16, n+32, n+48; one power-of-two scale per point brings the largest into [1, 2).  `m` = max |value| over
-// this lane's 64 values.  Returns 1 / (kW16Scale * scale) for the epilogue of the GEMM that consumes the operand.
+// Split-f16 operand of a backward-type GEMM (scale_split of siren_bwd.hip on this kernel's lane layout): the 256 values of a point are
+// spread over the four lanes n, n+16, n+32, n+48; one power-of-two scale per point (block_scale, gfx950_prims.h) brings the largest into
+// [1, 2).  `m` = max |value| over this lane's 64 values.  Returns 1 / (kW16Scale * scale) for the epilogue of the GEMM that consumes
+// the operand.
 __device__ __forceinline__ float scale_split16(const f32x4v (&src)[k16Tiles], u32x4 (&dH)[k16Steps], u32x4 (&dL)[k16Steps], float m) {
     {   // max over the four 16-lane groups in the VALU (the same exchanges as sum_over_q)
         const unsigned u = __builtin_bit_cast(unsigned, m);
@@ -144,21 +142,14 @@ __device__ __forceinline__ float scale_split16(const f32x4v (&src)[k16Tiles], u3
         const auto t = __builtin_amdgcn_permlane32_swap(v, v, false, false);
         m = fmaxf(__builtin_bit_cast(float, (unsigned)t[0]), __builtin_bit_cast(float, (unsigned)t[1]));
     }
-    const unsigned e = min((__float_as_uint(m) >> 23) & 255u, 254u);    // m in [2^(e-127), 2^(e-126)); inf/nan: scale 0 -> NaN out
-    const float sc = __uint_as_float((254u - e) << 23);                 // m * sc in [1, 2)   (m == 0: sc = 2^127, harmless)
-    const float inv = __uint_as_float((e > 8u ? e - 7u : 1u) << 23);    // 1 / (128 * sc) = 2^(e-134)
+    float sc, inv;
+    block_scale(m, sc, inv);
 #pragma unroll
     for (int t = 0; t < k16Tiles; ++t) {
         SPLIT2_TO(src[t][0] * sc, src[t][1] * sc, dH[t >> 1][2 * (t & 1)], dL[t >> 1][2 * (t & 1)]);
         SPLIT2_TO(src[t][2] * sc, src[t][3] * sc, dH[t >> 1][2 * (t & 1) + 1], dL[t >> 1][2 * (t & 1) + 1]);
     }
     return inv;
-}
-
-__device__ __forceinline__ void sincos_hw16(float x, float& sn, float& cs) {
-    const float r = revolutions_f32(x);
-    sn = __builtin_amdgcn_sinf(r);
-    cs = __builtin_amdgcn_cosf(r);
 }
 
 // EIK / TEX / DPTS as in siren_bwd_kernel.  EIK: a.tang holds the PRODUCTS ta_l r_l (e3dge_siren_tangent_tr), a.rsave is unused.
@@ -203,7 +194,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
     const char* const g_args = reinterpret_cast<const char*>(a.args + base_row * (9 * kWidth));
     const char* const g_tr = EIK ? reinterpret_cast<const char*>(a.tang + base_row * (8 * kWidth)) : nullptr;
     // ring base (LDS byte address of slot 0) of this wave
-    const uint32_t ring_b = lds_addr_of(smem + kB16LdsRing) + (uint32_t)wave_u * (kSlots * 1024u);
+    const uint32_t ring_b = lds_addr(smem + kB16LdsRing) + (uint32_t)wave_u * (kSlots * 1024u);
     constexpr uint32_t kStream1 = (uint32_t)kRingF * 4u;                      // byte distance of the second stream's ring
     // row (relative to the workgroup's first) of this lane's column in wave `w` of sub-tile `sub`; rows beyond the tensor read the last valid row
     auto row_of = [&](int sub, int w, int tid_x) {
@@ -302,8 +293,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
         auto publish_amax = [&](int layer_s) {
             if constexpr (LIN) {
                 float m = gmax;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+                m = wave_max(m);
                 if ((tid_k & 63) == 0)
                     atomic_max_nonneg(a.lin_amax + layer_s * E3DGE_AMAX_FLOATS + (((int)blockIdx.x * 8 + (tid_k >> 6)) & (kAmaxSlots - 1)) * kAmaxStride, m);
             }
@@ -386,7 +376,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_bwd_kernel(const SirenBwdK
                 const float ar = a4[r];
                 float xin = prev[r];
                 float sn = 0.f, cs;
-                if (EIK || tex_here) sincos_hw16(ar, sn, cs);
+                if (EIK || tex_here) sincos_hw_f32(ar, sn, cs);
                 else cs = cos_hw_f32(ar);
                 if (tex_here) { e_da[r] = xin * sn; e_db[r] = xin; xin = __fadd_rn(al2[tp & 1][r], 1.0f) * xin; }
                 const float dh = fmaf(e_w[r], sdf_term, xin);            // padded lanes: operand 0 and dsdf = 0, so dh = 0
@@ -519,7 +509,7 @@ __global__ void __launch_bounds__(k16Threads) siren16_chain_kernel(const SirenCh
     const int64_t base_row = (int64_t)b * saved_rows_per_image(true, a.n_pts) + pt0;
     const char* const g_args = reinterpret_cast<const char*>(a.args + base_row * (9 * kWidth));
     const char* const g_r = TR ? reinterpret_cast<const char*>(a.rmul + base_row * (8 * kWidth)) : nullptr;
-    const uint32_t ring_b = lds_addr_of(smem + kC16LdsRing) + (uint32_t)wave_u * (kSlots * 1024u);
+    const uint32_t ring_b = lds_addr(smem + kC16LdsRing) + (uint32_t)wave_u * (kSlots * 1024u);
     constexpr uint32_t kStream1 = (uint32_t)kRingF * 4u;
     auto row_of = [&](int sub, int w, int tid_x) {
         const int p = sub * kTilePts + 16 * w + (tid_x & 15);

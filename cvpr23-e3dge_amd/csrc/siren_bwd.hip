@@ -61,9 +61,6 @@ constexpr int kBwdLdsBytes = kBwdLdsFloats * 4;
 // with the even rows of another, so x[i] + x[4+i] after the swap is the two-row sum of value i in even rows and of
 // value 4+i in odd rows; four DPP row rotations finish the 16 lanes.  Result: q[i] (i < 4) on every lane = total of
 // value i (lanes 0-15 of the half) or value 4+i (lanes 16-31).
-template <int CTRL> __device__ __forceinline__ float dpp_f32(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-}
 __device__ __forceinline__ void reduce8_over_lanes(const float (&v)[8], float (&q)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -78,13 +75,6 @@ __device__ __forceinline__ void reduce8_over_lanes(const float (&v)[8], float (&
     }
 }
 
-// sin and cos of a saved argument with one shared range reduction
-__device__ __forceinline__ void sincos_hw_f32(float x, float& sn, float& cs) {
-    const float r = revolutions_f32(x);
-    sn = __builtin_amdgcn_sinf(r);
-    cs = __builtin_amdgcn_cosf(r);
-}
-
 // Split-f16 operand of a backward-type GEMM.  The B operand here is a gradient: no bounded range, so each point (a
 // column of B, one lane pair) gets its own power-of-two scale that brings the largest of its 256 values into [1, 2)
 // before the (hi, lo) split; the GEMM is linear per column, so D / (128 * scale) is the unscaled result exactly.
@@ -93,10 +83,8 @@ __device__ __forceinline__ void sincos_hw_f32(float x, float& sn, float& cs) {
 // layout); returns 1 / (kW16Scale * scale) for the epilogue.
 // `m` = max |value| over this lane's 128 values (the producers keep it as a running max).
 __device__ __forceinline__ float scale_split(const f32x16 (&src)[kNT], u32x4 (&dH)[2 * kNT], u32x4 (&dL)[2 * kNT], float m) {
-    m = fmaxf(m, xhalf(m));
-    const unsigned e = min((__float_as_uint(m) >> 23) & 255u, 254u);    // m in [2^(e-127), 2^(e-126)); inf/nan: scale 0 -> NaN out
-    const float sc = __uint_as_float((254u - e) << 23);                 // m * sc in [1, 2)   (m == 0: sc = 2^127, harmless)
-    const float inv = __uint_as_float((e > 8u ? e - 7u : 1u) << 23);    // 1 / (128 * sc) = 2^(e-134)
+    float sc, inv;
+    block_scale(fmaxf(m, xhalf(m)), sc, inv);
 #pragma unroll
     for (int t = 0; t < kNT; ++t)
 #pragma unroll

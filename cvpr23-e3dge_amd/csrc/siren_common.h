@@ -1,7 +1,8 @@
 // Shared device-side definitions of the SIREN kernels (forward: siren.hip, backward: siren_bwd.hip): vector types,
-// the packed weight image layout, LDS carve of the forward kernel, MFMA / LDS-DMA / sine helpers and the tile routines.
+// the packed weight image layout, LDS carve of the forward kernel, MFMA / sine helpers and the tile routines.  The primitives that
+// are not SIREN-specific (LDS-DMA, the chunk pipeline template, block scale, lane moves) live in gfx950_prims.h.
 #pragma once
-#include "stamps.h"
+#include "gfx950_prims.h"
 
 namespace e3dge {
 
@@ -182,83 +183,9 @@ __device__ __forceinline__ float acts16_get(const u32x4 (&aH)[2 * kNT], const u3
     return (r & 1) ? f16hi(aH[g][k]) + f16hi(aL[g][k]) : f16lo(aH[g][k]) + f16lo(aL[g][k]);
 }
 
-// LDS-DMA (global_load_lds_dwordx4: 16 B per lane straight into LDS, wave-uniform LDS base in M0).  The instruction's
-// immediate offset is added to BOTH the global and the LDS address (validated on gfx950), so with the chunk image laid
-// out identically on both sides the pieces of a chunk differ only in that immediate.
-// Addressing: scalar 64-bit base + per-lane 32-bit byte offset + immediate.  hipcc never selects this mode for
-// __builtin_amdgcn_global_load_lds (it builds a 64-bit VGPR address per piece: ~10 instructions and two VGPRs each
-// time); written out, a piece is s_mov m0 / s_nop / global_load_lds.  No other code in these kernels uses M0.  The
-// compiler does not count these in vmcnt; every consumer waits with an explicit vmcnt(0).
-template <int OFF_BYTES>
-__device__ __forceinline__ void glds16_saddr(const void* sbase, uint32_t voff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3"
-                 :: "v"(voff), "s"(sbase), "s"(lds_addr), "n"(OFF_BYTES) : "memory");
-}
-
-// The weight-chunk pipeline shared by every kernel: 32 KiB chunks (one 32-row output tile x K=256) of a fragment image
-// stream L2 -> LDS through kNBuf buffers, eight 16-B LDS-DMA pieces per lane and chunk, handed out one per MFMA group
-// pair inside the tile two chunks earlier.  sync() runs early in every tile g: each wave drains its own DMA (chunk g+1,
-// issued one whole tile earlier), the barrier publishes it and proves that everybody has left tile g-1, whose buffer
-// the DMA of chunk g+2 may now overwrite.  Chunk indices wrap inside [first, first+count): the two chunks fetched past
-// the end of the work land in buffers nobody reads (kernels end with vmcnt(0)).
-struct ChunkPipe {
-    const char* img;          // image + this wave's 8 KiB slice (wave-uniform)
-    const char* src;          // chunk being issued
-    uint32_t voff;            // lane * 16
-    uint32_t lds_base;        // LDS byte address of wbuf + this wave's slice
-    uint32_t lds_dst;         // ... of the buffer being filled
-    int idx, first, count, buf, use_buf;
-    float* wbuf;
-    const float* wcur;
-    const float* wnxt;
-    IF_PIPE_TIMING(stamp_t t_wait[2];)             // cycles in sync(): [0] the vmcnt wait, [1] the barrier
-    __device__ __forceinline__ void init(float* wbuf_, const float* image, int wave, int lane, int first_, int count_) {
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        wbuf = wbuf_;
-        img = reinterpret_cast<const char*>(image) + wave_u * 8192;
-        voff = (uint32_t)lane * 16u;
-        lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) float*)wbuf_ + (uint32_t)wave_u * 8192u;
-        first = first_; count = count_;
-        idx = first_; buf = 0; use_buf = 0;
-        src = img + (size_t)idx * (kChunkFloats * 4);
-        lds_dst = lds_base;
-        wcur = wbuf_; wnxt = wbuf_ + kChunkFloats;
-        IF_PIPE_TIMING(t_wait[0] = 0; t_wait[1] = 0;)
-    }
-    __device__ __forceinline__ void issue_piece(int i) {     // i is a compile-time constant at every call site
-        const char* s = src + (i >> 2) * 4096;
-        const uint32_t d = lds_dst + (uint32_t)(i >> 2) * 4096u;
-        switch (i & 3) {
-            case 0: glds16_saddr<0>(s, voff, d); break;
-            case 1: glds16_saddr<1024>(s, voff, d); break;
-            case 2: glds16_saddr<2048>(s, voff, d); break;
-            default: glds16_saddr<3072>(s, voff, d); break;
-        }
-        if (i == 7) {
-            idx = (idx + 1 == first + count) ? first : idx + 1;
-            src = img + (size_t)idx * (kChunkFloats * 4);
-            buf = (buf + 1 == kNBuf) ? 0 : buf + 1;
-            lds_dst = lds_base + (uint32_t)buf * (kChunkFloats * 4);
-        }
-    }
-    __device__ __forceinline__ void prime() {
-        for (int c = 0; c < kNBuf - 1; ++c)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) issue_piece(i);
-    }
-    __device__ __forceinline__ void sync() {
-        IF_PIPE_TIMING(stamp_t tc[2]; stamp_mark(tc, 0);)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        IF_PIPE_TIMING(stamp_mark(tc, 1);)
-        __syncthreads();
-        IF_PIPE_TIMING(t_wait[0] += tc[1] - tc[0]; stamp_add(t_wait, 1, tc[1]);)
-    }
-    __device__ __forceinline__ void advance() {
-        use_buf = (use_buf + 1 == kNBuf) ? 0 : use_buf + 1;
-        wcur = wnxt;
-        wnxt = wbuf + ((use_buf + 1 == kNBuf) ? 0 : use_buf + 1) * kChunkFloats;
-    }
-};
+// The weight-chunk pipeline of siren.hip and siren_bwd.hip (gfx950_prims.h): eight pieces per lane and chunk, handed out one per MFMA
+// group pair inside the tile two chunks earlier; three buffers, so nothing younger than the awaited chunk is in flight: vmcnt(0).
+using ChunkPipe = ChunkPipeT<kChunkFloats, 8, kNBuf, 0>;
 
 // Two sines, both with an exact FMA Cody-Waite range reduction (|x| < ~1e5):
 //  * sin_hw_f32 (default, 5 VALU ops): x/2pi reduced to [-0.5, 0.5] revolutions, hardware v_sin_f32.  Max abs error 3e-7.
@@ -278,6 +205,12 @@ __device__ __forceinline__ float revolutions_f32(float x) {
 __device__ __forceinline__ float sin_hw_f32(float x) { return __builtin_amdgcn_sinf(revolutions_f32(x)); }
 // cos of the SAVED argument (backward kernels: d/dx sin)
 __device__ __forceinline__ float cos_hw_f32(float x) { return __builtin_amdgcn_cosf(revolutions_f32(x)); }
+// sin and cos of a saved argument with one shared range reduction
+__device__ __forceinline__ void sincos_hw_f32(float x, float& sn, float& cs) {
+    const float r = revolutions_f32(x);
+    sn = __builtin_amdgcn_sinf(r);
+    cs = __builtin_amdgcn_cosf(r);
+}
 __device__ __forceinline__ float sin_poly_f32(float x) {
     const float kf = rintf(x * 0.318309886183790672f);
     float r = fmaf(-kf, 3.1415927410125732f, x);

@@ -31,7 +31,7 @@
 #else
 #define IF_PHASE_TIMING(...)
 #endif
-#if defined(E3DGE_PHASE_TIMING) || defined(E3DGE_BWD_TIMING)      // ChunkPipe (siren_common.h) serves both kernels
+#if defined(E3DGE_PHASE_TIMING) || defined(E3DGE_BWD_TIMING)      // ChunkPipeT (gfx950_prims.h) as ChunkPipe serves both kernels
 #define IF_PIPE_TIMING(...) __VA_ARGS__
 #else
 #define IF_PIPE_TIMING(...)

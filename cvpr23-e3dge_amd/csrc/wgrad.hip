@@ -21,6 +21,7 @@
 //     513-wide Fuse_sft_MLP input: the block grid then skips that column of B -- `b_gap`) come from the values the conversion already
 //     holds: per-slab partials, folded in the same fixed order.
 #include <type_traits>
+#include "siren_common.h"      // vector types, split2, mfma16
 #include "decoder_common.h"
 
 namespace e3dge {
@@ -84,12 +85,6 @@ __device__ __forceinline__ void wg_store(const f32x4 (&v)[2], unsigned char* __r
     }
 }
 
-// consecutive logical ids on one XCD (hardware deals workgroup t to XCD t & 7)
-__device__ __forceinline__ int wg_xcd_logical(int t, int n) {
-    const int nq = n >> 3, nr = n & 7, xcd = t & 7, slot = t >> 3;
-    return (xcd < nr ? xcd * (nq + 1) : nr * (nq + 1) + (xcd - nr) * nq) + slot;
-}
-
 template <int MI, int NJ>
 constexpr int wg_lds_bytes() { return 2 * 2 * (64 * MI + 128 * NJ) * kWgPitch; }
 
@@ -104,7 +99,7 @@ __global__ void __launch_bounds__(kWgThreads, MINB) wgrad_kernel(const WgradK a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
     const int pp = tid & 7, fq = tid >> 3;                    // (a wave: 8 point pairs x 8 quads)
     const int nblk = a.mb * a.nb;
-    const int L = wg_xcd_logical((int)blockIdx.x, (int)gridDim.x);
+    const int L = xcd_logical((int)blockIdx.x, (int)gridDim.x);
     const int blk = L % nblk, slab = L / nblk;
     const int bm = blk / a.nb, bn = blk % a.nb;
     const long long p_begin = (long long)slab * a.slab, p_end = min(a.n_rows, p_begin + a.slab);
