@@ -205,6 +205,26 @@ class LpipsBwdArgs(_Args):
         ("gpre", _vp * LPIPS_LAYERS), ("ws", _vp), ("ws_bytes", _i64)]
 
 
+IDNET_CONVS, IDNET_BNS, IDNET_UNITS, IDNET_TAPS = 52, 54, 24, 8     # E3DGE_IDNET_* (include/e3dge_hip.h)
+
+
+class IdnetPackSrc(_Args):
+    """Mirror of struct E3dgeIdnetPackSrc (include/e3dge_hip.h)."""
+    _fields_ = [("conv_w", _vp * IDNET_CONVS)] + [(n, _vp * IDNET_BNS) for n in ("bn_weight", "bn_bias", "bn_mean", "bn_var")] + [
+        ("prelu", _vp * (IDNET_UNITS + 1)), ("se_fc1", _vp * IDNET_UNITS), ("se_fc2", _vp * IDNET_UNITS), ("head_w", _vp), ("head_b", _vp)]
+
+
+class IdnetArgs(_Args):
+    """Mirror of struct E3dgeIdnetArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("images", _vp * 3)] + [(n, _i32) for n in ("n_per_set", "n_sets", "height", "width")] + [
+        ("embeddings", _vp), ("taps", _vp * IDNET_TAPS), ("ws", _vp), ("ws_bytes", _i64)]
+
+
+class IdLossArgs(_Args):
+    """Mirror of struct E3dgeIdLossArgs (include/e3dge_hip.h)."""
+    _fields_ = [(n, _vp) for n in ("y_hat", "y", "x")] + [("batch", _i32), ("reserved", _i32)] + [(n, _vp) for n in ("dots", "loss", "sim_improvement")]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -287,6 +307,14 @@ SIGNATURES = {
     "e3dge_lpips_pack_weights_t": (_i32, [_vp, _vp, _vp]),
     "e3dge_lpips_bwd_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "e3dge_lpips_backward": (_i32, [ctypes.POINTER(LpipsBwdArgs), _vp]),
+    "e3dge_idnet_packed_floats": (_i64, []),
+    "e3dge_idnet_pack_weights": (_i32, [_vp, _vp, _vp]),
+    "e3dge_idnet_ws_bytes": (_i64, [_i32]),
+    "e3dge_idnet_embed": (_i32, [ctypes.POINTER(IdnetArgs), _vp]),
+    "e3dge_id_loss": (_i32, [ctypes.POINTER(IdLossArgs), _vp]),
+    "e3dge_idnet_conv_tiles": (_i32, [_i32] * 5),
+    "e3dge_idnet_conv": (_i32, [_vp] * 8 + [_i32] * 7 + [_vp]),
+    "e3dge_image_metric_row_full": (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp]),
     "e3dge_hitprob_points": (_i32, [_vp] * 8 + [_i32, _i64, _i32, _i32, _vp]),
     "e3dge_hitprob_composite": (_i32, [_vp] * 6 + [_f32, _i32, _i32, _i64, _i32, _i32, _vp]),
     "e3dge_align_volume": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -103,11 +103,13 @@ def ssim_index(x, y, window=5, max_val=1.0):
     return 1 - torch.clamp((1 - ssim) / 2, 0, 1).mean()
 
 
-def image_metrics(pred, gt, l2_lambda=1.0, lpips=None, vgg_lambda=0.0):
+def image_metrics(pred, gt, l2_lambda=1.0, lpips=None, vgg_lambda=0.0, id_loss=None, id_lambda=0.0):
     """The 8 metric columns of one image pair (see image_metrics_torch).  GPU fp32 tensors take the fused HIP kernel
     e3dge_image_metrics (one pass over both images); anything else the plain-torch formulation.  `lpips`: None (the loss_lpips
     column is 0 and `loss` is l2_lambda * MSE, as the reference reports with vgg_lambda = 0) or an `e3dge_amd.lpips.LPIPS` module on
-    the images' device: its forward fills column 2 and `loss` becomes l2_lambda * MSE + vgg_lambda * LPIPS (builder.py:168)."""
+    the images' device: its forward fills column 2 and `loss` becomes l2_lambda * MSE + vgg_lambda * LPIPS (builder.py:168).
+    `id_loss`: None (loss_id = 0, ID_SIM = 1; every output is what it was without the argument) or an `e3dge_amd.id_loss.IDLoss` module
+    on the images' device: loss_id = criterionID(pred, gt, gt)[0] fills columns 1 and 7 and adds id_lambda * loss_id to `loss`."""
     if pred.device.type == "cuda" and pred.dtype == torch.float32 and gt.dtype == torch.float32 and pred.ndim == 4 \
             and pred.shape == gt.shape and not (torch.is_grad_enabled() and (pred.requires_grad or gt.requires_grad)):
         from . import _lib
@@ -119,24 +121,34 @@ def image_metrics(pred, gt, l2_lambda=1.0, lpips=None, vgg_lambda=0.0):
         # the reference's losses are means over the whole batch tensor; the eight columns in one more launch (as torch ops
         # this tail was thirteen 5-us kernels: 3 % of an evaluated image)
         row = torch.empty(8, device=p.device, dtype=torch.float32)
-        if lpips is None:
+        if id_loss is not None:
+            per_image = None if lpips is None else lpips(p, g, per_image=True)
+            lid = id_loss.run(p, g)['loss']
+            _lib.launch("e3dge_image_metric_row_full", row, sums, per_image, lid, B, float(l2_lambda), float(vgg_lambda), float(id_lambda))
+        elif lpips is None:
             _lib.launch("e3dge_image_metric_row", row, sums, B, float(l2_lambda))
         else:
             per_image = lpips(p, g, per_image=True)
             _lib.launch("e3dge_image_metric_row_lpips", row, sums, per_image, B, float(l2_lambda), float(vgg_lambda))
         return row
-    return image_metrics_torch(pred, gt, l2_lambda, lpips, vgg_lambda)
+    return image_metrics_torch(pred, gt, l2_lambda, lpips, vgg_lambda, id_loss, id_lambda)
 
 
-def image_metrics_torch(pred, gt, l2_lambda=1.0, lpips=None, vgg_lambda=0.0):
+def image_metrics_torch(pred, gt, l2_lambda=1.0, lpips=None, vgg_lambda=0.0, id_loss=None, id_lambda=0.0):
     """(8,) = [loss_l2, loss_id, loss_lpips, loss, mae, PSNR, SSIM, ID_SIM] for one predicted image against its target,
-    both (1,3,H,W) in [-1,1] (calc_2d_rec_loss, builder.py:130-184).  The ArcFace identity term needs a pretrained network the
-    image does not have and is reported as 0 (ID_SIM = 1 - 0), exactly as the reference does when its lambda is 0 (:145,
-    :158-163).  `lpips`: None (column 2 is 0) or any callable (pred, gt) -> scalar; then loss = l2_lambda * MSE + vgg_lambda * lpips."""
+    both (1,3,H,W) in [-1,1] (calc_2d_rec_loss, builder.py:130-184).  `lpips`: None (column 2 is 0) or any callable (pred, gt) ->
+    scalar; `id_loss`: None (loss_id = 0 and ID_SIM = 1, as the reference reports with id_lambda = 0, :146, :156) or any callable
+    (pred, gt, gt) -> scalar or the reference's triple (an `e3dge_amd.id_loss.IDLoss` on CPU tensors, say).  Then
+    loss = (l2_lambda * MSE + vgg_lambda * lpips) + id_lambda * loss_id (:168), ID_SIM = 1 - loss_id (:182)."""
     mse = torch.mean((pred - gt) ** 2)
     zero = torch.zeros((), device=pred.device, dtype=pred.dtype)
     p01, g01 = pred / 2 + 0.5, gt / 2 + 0.5
     psnr = 10.0 * torch.log10(1.0 / torch.mean((p01 - g01) ** 2))
     lp = zero if lpips is None else torch.as_tensor(lpips(pred, gt), device=pred.device, dtype=pred.dtype).reshape(())
     loss = mse * l2_lambda if lpips is None else mse * l2_lambda + lp * vgg_lambda
-    return torch.stack([mse, zero, lp, loss, torch.mean((pred - gt).abs()), psnr, ssim_index(pred, gt), 1 - zero])
+    lid = zero
+    if id_loss is not None:
+        lid = id_loss(pred, gt, gt)
+        lid = torch.as_tensor(lid[0] if isinstance(lid, tuple) else lid, device=pred.device, dtype=pred.dtype).reshape(())
+        loss = loss + lid * id_lambda
+    return torch.stack([mse, lid, lp, loss, torch.mean((pred - gt).abs()), psnr, ssim_index(pred, gt), 1 - lid])

@@ -144,7 +144,49 @@ def load_synthetic_lpips(module, seed=0):
     return module
 
 
-STRESS_VARIANTS = {            # name: (SIREN hidden-weight factor, gamma-mapping weight factor, std of the W+ codes)
+ID_CONV2_GAIN, ID_SHORTCUT_GAIN, ID_SE_GAIN = 0.5, 1.0, 0.7
+
+
+def load_synthetic_idloss(module, seed=0):
+    """Deterministic stand-ins for the ir_se50 checkpoint of an `e3dge_amd.id_loss.IDLoss` module (no checkpoint is reachable offline).
+    Conv weights are He-scaled, N(0, 2 / fan_in), times a per-role gain: 1 for the input layer and a unit's first 3x3, ID_CONV2_GAIN
+    for its second 3x3 (the trailing BatchNorm does not normalise with synthetic statistics, so the residual branch's gain is what
+    keeps 24 units from compounding), ID_SHORTCUT_GAIN / sqrt(2) for the 1x1 shortcuts (variance-preserving), ID_SE_GAIN for the two
+    SE matrices.  PReLU slopes 0.25 + 0.05 N; BatchNorm gamma 1 + 0.1 N, beta 0.1 N, running_mean 0.1 N, running_var 1 + 0.2 N (> 0);
+    the head's Linear N(0, 1 / fan_in) with bias 0.05 N.  The constants were chosen on the float64 CPU forward so that the "network is
+    alive" conditions of tests/test_idloss_host.py hold (values found: DESIGN.md 4.11d)."""
+    sd = {}
+    kinds = dict(module.named_modules())
+    for k, v in module.state_dict().items():
+        owner, leaf = k.rsplit('.', 1)
+        m = kinds[owner]
+        if leaf == 'num_batches_tracked':
+            sd[k] = torch.zeros_like(v)
+            continue
+        t = synthetic_tensor('idloss.' + k, v.shape, seed)            # 'weight': N(0, 1); everything else: 0.05 N(0, 1)
+        if isinstance(m, torch.nn.Conv2d):
+            fan_in = v.shape[1] * v.shape[2] * v.shape[3]
+            if '.fc1' in k or '.fc2' in k:
+                gain = ID_SE_GAIN
+            elif '.shortcut_layer.' in k:
+                gain = ID_SHORTCUT_GAIN / math.sqrt(2.0)
+            elif k.endswith('res_layer.3.weight'):
+                gain = ID_CONV2_GAIN
+            else:
+                gain = 1.0
+            t = t * (gain * math.sqrt(2.0 / fan_in))
+        elif isinstance(m, torch.nn.PReLU):
+            t = 0.25 + 0.05 * t
+        elif isinstance(m, (torch.nn.BatchNorm2d, torch.nn.BatchNorm1d)):
+            t = {'weight': 1.0 + 0.1 * t, 'bias': 2.0 * t, 'running_mean': 2.0 * t, 'running_var': 1.0 + 4.0 * t}[leaf]
+        elif isinstance(m, torch.nn.Linear):
+            t = t * math.sqrt(1.0 / v.shape[1]) if leaf == 'weight' else t
+        sd[k] = t.to(v.dtype)
+    module.load_state_dict(sd, strict=True)
+    return module
+
+
+STRESS_VARIANTS = {          # name: (SIREN hidden-weight factor, gamma-mapping weight factor, std of the W+ codes)
     "wide": (1.0, 1.0, 1.0),    # unit-variance styles: FiLM frequencies 13.5 .. 48 instead of 27.7 .. 32.3
     "s2": (2.0, 3.0, 0.3),      # per-layer gain 2: fp32 rounding amplified ~300x over the init-range fixtures, still well defined
     "x4": (4.0, 3.0, 1.0),      # per-layer gain 4 and above: the network is chaotic -- the reference's own fp32 output is O(1) away

@@ -761,6 +761,83 @@ int64_t e3dge_lpips_bwd_ws_bytes(int batch, int height, int width, int both);
 int e3dge_lpips_backward(const E3dgeLpipsBwdArgs* args, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * ArcFace identity term, forward (csrc/idnet.hip).  Additions to ABI 16.  No allocation, no synchronisation, no atomics;
+ * bit-reproducible, and an image's embedding does not depend on its position in the batch or on the batch size.  Replaces
+ * IDLoss.forward (project/losses/id_loss.py:23-55) with Backbone(112, 50, 'ir_se') in eval form (models/encoders/
+ * model_irse.py:8-51, models/helper_modules/helpers.py:83-224) and the pooling of builder.py:157-160.
+ *
+ * Order of the pointer arrays of E3dgeIdnetPackSrc (unit = one of the 24 bottleneck_IR_SE, in body order):
+ *   conv_w    [0] input_layer.0; [1 + 2u], [2 + 2u] unit u's res_layer.1 and res_layer.3; [49..51] shortcut_layer.0 of units 3, 7, 21 (unit 0 is
+ *             64 -> 64: its shortcut is the strided pick)
+ *   bn_*      [0] input_layer.1; [1 + 2u], [2 + 2u] unit u's res_layer.0 and res_layer.4; [49..51] shortcut_layer.1 of those units;
+ *             [52] output_layer.0 (BatchNorm2d); [53] output_layer.4 (BatchNorm1d).  weight = gamma, bias = beta, running mean / var
+ *   prelu     [0] input_layer.2; [1 + u] unit u's res_layer.2
+ *   se_fc1/2  unit u's res_layer.5.fc1 (C / 16, C) and fc2 (C, C / 16);  head_w (512, 25088), head_b (512): output_layer.3
+ *
+ * e3dge_idnet_packed_floats  floats of the packed image: the 52 conv weights in MFMA A-fragment order (K = (ci, r, s) padded to a
+ *                            multiple of 32), every BatchNorm as per-channel pairs (a, b) with a = gamma / sqrt(var + 1e-5),
+ *                            b = beta - mean a, PReLU slopes, SE matrices, the head's matrix and bias.
+ * e3dge_idnet_pack_weights   src: HOST struct of device pointers.  Re-run after a weight update.
+ * e3dge_idnet_ws_bytes       workspace bytes of an embed of n_images (-1: n_images < 1 or too large).
+ * e3dge_idnet_embed          images[s] (n_per_set, 3, height, width) fp32 contiguous, s < n_sets (1..3); image s * n_per_set + i of
+ *                            the batch is images[s][i].  height = width = 256: crop [35:223, 32:220], adaptive average to 112 x 112;
+ *                            any other size: the 256 x 256 adaptive average first, each value rounded to fp32.  embeddings
+ *                            (n, 512), unit L2 norm.  taps[t] NULL or: the network input (n, 3, 112, 112), the input layer's output,
+ *                            the outputs of units 0, 3, 7, 21, 23, the head's output before the normalisation (n, 512).  103
+ *                            launches without taps.  Fails before any launch on a null required pointer ("null"),
+ *                            n_per_set < 1 or n_sets outside 1..3 ("n_"), height or width < 1, ws_bytes too small ("workspace").
+ * e3dge_id_loss              y_hat, y, x (batch, 512) embeddings.  dots (batch, 3) = [y_hat.y, y_hat.x, y.x] per sample; loss =
+ *                            (sum_b 1 - dots[b][0]) / batch in fp32, sim_improvement = (sum_b dots[b][0] - dots[b][2]) / batch in
+ *                            double, both in sample order (NULL: not written).  One launch.
+ * e3dge_idnet_conv_tiles     pixel tiles per (image, channel) plane of e3dge_idnet_conv's plane sums (-1: bad sizes).
+ * e3dge_idnet_conv           debug entry: one convolution of the family.  in (n, cin, height, width), w (cout, cin, ksize, ksize)
+ *                            with ksize 1 (pad 0) or 3 (pad 1), stride 1 or 2, cout a multiple of 64.  wfrag: scratch of
+ *                            cout * roundup(cin ksize^2, 32) floats for the A-fragment image.  in_ab NULL or (cin, 2): x <- a x + b
+ *                            on in-image elements (padding stays 0); epi_ab NULL or (cout, 2); slope NULL or (cout): PReLU after
+ *                            the affine; plane NULL or (n, cout, tiles) partial sums of the stored plane.  Two launches.
+ * e3dge_image_metric_row_full  e3dge_image_metric_row_lpips with the identity columns: lpips_per_image NULL: LPIPS = 0; id_loss
+ *                            NULL (a device scalar otherwise): loss_id = 0.  row[1] = loss_id, row[7] = 1 - loss_id, row[3] =
+ *                            ((l2_lambda MSE) + (vgg_lambda LPIPS)) + (id_lambda loss_id) in that fp32 order (builder.py:168).
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_IDNET_CONVS 52
+#define E3DGE_IDNET_BNS 54
+#define E3DGE_IDNET_UNITS 24
+#define E3DGE_IDNET_TAPS 8
+typedef struct E3dgeIdnetPackSrc {
+    const float* conv_w[E3DGE_IDNET_CONVS];
+    const float* bn_weight[E3DGE_IDNET_BNS]; const float* bn_bias[E3DGE_IDNET_BNS];
+    const float* bn_mean[E3DGE_IDNET_BNS]; const float* bn_var[E3DGE_IDNET_BNS];
+    const float* prelu[E3DGE_IDNET_UNITS + 1];
+    const float* se_fc1[E3DGE_IDNET_UNITS]; const float* se_fc2[E3DGE_IDNET_UNITS];
+    const float* head_w; const float* head_b;
+} E3dgeIdnetPackSrc;
+typedef struct E3dgeIdnetArgs {
+    const float* packed;
+    const float* images[3];
+    int32_t n_per_set, n_sets, height, width;
+    float* embeddings;
+    float* taps[E3DGE_IDNET_TAPS];
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeIdnetArgs;
+typedef struct E3dgeIdLossArgs {
+    const float* y_hat; const float* y; const float* x;
+    int32_t batch, reserved;
+    float* dots; float* loss; float* sim_improvement;
+} E3dgeIdLossArgs;
+int64_t e3dge_idnet_packed_floats(void);
+int e3dge_idnet_pack_weights(float* packed, const E3dgeIdnetPackSrc* src, e3dge_stream_t stream);
+int64_t e3dge_idnet_ws_bytes(int n_images);
+int e3dge_idnet_embed(const E3dgeIdnetArgs* args, e3dge_stream_t stream);
+int e3dge_id_loss(const E3dgeIdLossArgs* args, e3dge_stream_t stream);
+int e3dge_idnet_conv_tiles(int cout, int height, int width, int ksize, int stride);
+int e3dge_idnet_conv(float* out, const float* in, const float* w, float* wfrag, const float* in_ab, const float* epi_ab,
+                     const float* slope, float* plane, int n, int cin, int cout, int height, int width, int ksize, int stride,
+                     e3dge_stream_t stream);
+int e3dge_image_metric_row_full(float* row, const float* sums, const float* lpips_per_image, const float* id_loss, int batch,
+                                float l2_lambda, float vgg_lambda, float id_lambda, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Surface extraction, device half: replaces align_volume (project/utils/mesh_utils.py:17-44; called on the rendered
  * 128^3 SDF volume at volume_renderer.py:1706, before the CPU marching cubes).  volume, out (batch, height, width, depth,
  * channels), not aliased; xs (width), ys (height), zs (depth) = linspace(-1, 1, n) and coef (depth) = linspace(far / near,
