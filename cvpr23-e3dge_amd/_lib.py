@@ -220,6 +220,21 @@ class IdnetArgs(_Args):
         ("embeddings", _vp), ("taps", _vp * IDNET_TAPS), ("ws", _vp), ("ws_bytes", _i64)]
 
 
+IDNET_PRELUS = IDNET_UNITS + 1                                      # E3DGE_IDNET_PRELUS
+
+
+class IdnetSaveArgs(_Args):
+    """Mirror of struct E3dgeIdnetSaveArgs (include/e3dge_hip.h)."""
+    _fields_ = [("net", IdnetArgs), ("saved", _vp), ("saved_bytes", _i64), ("n_saved", _i32), ("reserved", _i32)]
+
+
+class IdnetBwdArgs(_Args):
+    """Mirror of struct E3dgeIdnetBwdArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("packed_t", _vp), ("saved", _vp), ("saved_bytes", _i64)] + [
+        (n, _i32) for n in ("n", "height", "width", "reserved")] + [("grad_embeddings", _vp), ("grad_images", _vp), ("gstage", _vp * IDNET_TAPS),
+                                                                    ("masks", _vp * IDNET_PRELUS), ("ws", _vp), ("ws_bytes", _i64)]
+
+
 class IdLossArgs(_Args):
     """Mirror of struct E3dgeIdLossArgs (include/e3dge_hip.h)."""
     _fields_ = [(n, _vp) for n in ("y_hat", "y", "x")] + [("batch", _i32), ("reserved", _i32)] + [(n, _vp) for n in ("dots", "loss", "sim_improvement")]
@@ -314,6 +329,14 @@ SIGNATURES = {
     "e3dge_id_loss": (_i32, [ctypes.POINTER(IdLossArgs), _vp]),
     "e3dge_idnet_conv_tiles": (_i32, [_i32] * 5),
     "e3dge_idnet_conv": (_i32, [_vp] * 8 + [_i32] * 7 + [_vp]),
+    "e3dge_idnet_packed_t_floats": (_i64, []),
+    "e3dge_idnet_pack_weights_t": (_i32, [_vp, _vp, _vp]),
+    "e3dge_idnet_saved_bytes": (_i64, [_i32]),
+    "e3dge_idnet_embed_save": (_i32, [ctypes.POINTER(IdnetSaveArgs), _vp]),
+    "e3dge_idnet_bwd_ws_bytes": (_i64, [_i32, _i32, _i32]),
+    "e3dge_idnet_backward": (_i32, [ctypes.POINTER(IdnetBwdArgs), _vp]),
+    "e3dge_idnet_conv_bwd": (_i32, [_vp] * 9 + [_i32] * 7 + [_vp]),
+    "e3dge_idnet_prep_bwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "e3dge_image_metric_row_full": (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp]),
     "e3dge_hitprob_points": (_i32, [_vp] * 8 + [_i32, _i64, _i32, _i32, _vp]),
     "e3dge_hitprob_composite": (_i32, [_vp] * 6 + [_f32, _i32, _i32, _i64, _i32, _i32, _vp]),

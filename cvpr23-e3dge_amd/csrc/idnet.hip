@@ -25,6 +25,8 @@
 //   head_kernel   BN2d while loading, then 4 output rows x 1/7 of K per workgroup for up to 8 images at once (the 51 MB matrix is
 //                 read once per 8 images); head_fold_kernel adds the seven slices in order, bias, BN1d, L2 normalisation.
 //   dot_kernel    the three dot products per sample and the two batch means in sample order.
+// The backward (the gradient to the y_hat images, 104 launches) is idnet_bwd.h; the conv, se, merge and head fold kernels have a SAVE
+// instantiation that keeps what it needs.
 // Measured times, the per-kernel split and what bounds each kernel: DESIGN.md 4.11d.
 #include "common.h"
 
@@ -151,9 +153,12 @@ struct IdConvArgs {
     float* out; const float* in; const float* wfrag;
     const float2* in_ab; const float2* epi_ab; const float* slope; float* plane;
     int Cin, IH, IW, Cout, OH, OW, K, KS4, tiles;
+    unsigned char* mask; int n_mask;                // SAVE only: the PReLU branch of the leading n_mask images
 };
 
-template <int KS_, int STRIDE, int NT>
+// SAVE (here and in the se, merge and head fold kernels): the state-saving form for the backward (idnet_bwd.h).  It is a template
+// parameter and not a null check so that the plain forward runs the instructions it ran before the backward existed.
+template <int KS_, int STRIDE, int NT, bool SAVE = false>
 __global__ void __launch_bounds__(256) idnet_conv_kernel(IdConvArgs a) {
     constexpr int BN = 16 * NT, BNP = NT == 1 ? 16 : BN + 16;      // row pitch: the four k rows of one read land in four bank groups
     constexpr int ROWS = 256 / BN, PER = kIdKC / ROWS;
@@ -223,7 +228,10 @@ __global__ void __launch_bounds__(256) idnet_conv_kernel(IdConvArgs a) {
             const int row = row0 + r;
             float v = __fadd_rn(acc[t][0][r], acc[t][1][r]);
             if (a.epi_ab) { const float2 e = a.epi_ab[row]; v = __fmaf_rn(e.x, v, e.y); }
-            if (a.slope) v = v > 0.0f ? v : __fmul_rn(a.slope[row], v);
+            if (a.slope) {
+                if (SAVE && ok && img < a.n_mask) a.mask[((int64_t)img * a.Cout + row) * OHW + pix] = v > 0.0f;
+                v = v > 0.0f ? v : __fmul_rn(a.slope[row], v);
+            }
             if (ok) {
                 a.out[((int64_t)img * a.Cout + row) * OHW + pix] = v;
                 psum[r] = __fadd_rn(psum[r], v);
@@ -242,8 +250,10 @@ __global__ void __launch_bounds__(256) idnet_conv_kernel(IdConvArgs a) {
 }
 
 // ---- SE gate ------------------------------------------------------------------------------------------------------------------
+template <bool SAVE>
 __global__ void __launch_bounds__(256) idnet_se_kernel(float* __restrict__ gate, const float* __restrict__ plane, const float* __restrict__ fc1,
-                                                       const float* __restrict__ fc2, int C, int tiles, int HW) {
+                                                       const float* __restrict__ fc2, int C, int tiles, int HW, float* __restrict__ gate_save,
+                                                       float* __restrict__ hid_save, int n_saved) {
     __shared__ float mean[512];
     __shared__ float hid[32];
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, Ch = C / 16;
@@ -259,27 +269,36 @@ __global__ void __launch_bounds__(256) idnet_se_kernel(float* __restrict__ gate,
         for (int c = lane; c < C; c += 64) s = __fmaf_rn(fc1[j * C + c], mean[c], s);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) s = __fadd_rn(s, __shfl_xor(s, off, kWave));
-        if (lane == 0) hid[j] = fmaxf(s, 0.0f);
+        if (lane == 0) {
+            hid[j] = fmaxf(s, 0.0f);
+            if (SAVE && img < n_saved) hid_save[(int64_t)img * Ch + j] = hid[j];
+        }
     }
     __syncthreads();
     for (int c = tid; c < C; c += 256) {
         float s = 0.0f;
         for (int j = 0; j < Ch; ++j) s = __fmaf_rn(fc2[c * Ch + j], hid[j], s);
-        gate[(int64_t)img * C + c] = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-s)));
+        const float g = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-s)));
+        gate[(int64_t)img * C + c] = g;
+        if (SAVE && img < n_saved) gate_save[(int64_t)img * C + c] = g;
     }
 }
 
 // ---- unit merge ---------------------------------------------------------------------------------------------------------------
+template <bool SAVE>
 __global__ void __launch_bounds__(256) idnet_merge_kernel(float* __restrict__ out, const float* __restrict__ res, const float* __restrict__ gate,
                                                           const float* __restrict__ sc, const float* __restrict__ xin, int OH, int OW, int IH,
-                                                          int IW, int stride, int64_t total) {
+                                                          int IW, int stride, int64_t total, float* __restrict__ res_save,
+                                                          int64_t saved_total) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int OHW = OH * OW;
     const int64_t plane = i / OHW;                                   // img * C + c
     const int pix = (int)(i - plane * OHW), oy = pix / OW, ox = pix - oy * OW;
     const float s = sc ? sc[i] : xin[(plane * IH + (int64_t)oy * stride) * IW + ox * stride];
-    out[i] = __fadd_rn(__fmul_rn(res[i], gate[plane]), s);           // helpers.py:158, :223
+    const float r = res[i];
+    if (SAVE && i < saved_total) res_save[i] = r;                    // the leading images are the ones that get a gradient
+    out[i] = __fadd_rn(__fmul_rn(r, gate[plane]), s);                // helpers.py:158, :223
 }
 
 // ---- head ---------------------------------------------------------------------------------------------------------------------
@@ -337,8 +356,11 @@ __global__ void __launch_bounds__(256) idnet_head_kernel(float* __restrict__ par
     }
 }
 
+template <bool SAVE>
 __global__ void __launch_bounds__(kIdEmbed) idnet_head_fold_kernel(float* __restrict__ emb, float* __restrict__ tap, const float* __restrict__ part,
-                                                                   const float* __restrict__ bias, const float2* __restrict__ ab, int n) {
+                                                                   const float* __restrict__ bias, const float2* __restrict__ ab, int n,
+                                                                   float* __restrict__ save_v, float* __restrict__ save_f,
+                                                                   float* __restrict__ save_norm, int n_saved) {
     __shared__ float sq[kIdEmbed];
     const int img = blockIdx.x, o = threadIdx.x;
     float v = 0.0f;
@@ -354,7 +376,13 @@ __global__ void __launch_bounds__(kIdEmbed) idnet_head_fold_kernel(float* __rest
         if (o < off) sq[o] = __fadd_rn(sq[o], sq[o + off]);
         __syncthreads();
     }
-    emb[(int64_t)img * kIdEmbed + o] = __fdiv_rn(v, __fsqrt_rn(sq[0]));        // helpers.py:89-92
+    const float norm = __fsqrt_rn(sq[0]), f = __fdiv_rn(v, norm);
+    emb[(int64_t)img * kIdEmbed + o] = f;                                       // helpers.py:89-92
+    if (SAVE && img < n_saved) {
+        save_v[(int64_t)img * kIdEmbed + o] = v;
+        save_f[(int64_t)img * kIdEmbed + o] = f;
+        if (o == 0) save_norm[img] = norm;
+    }
 }
 
 // ---- dot products -------------------------------------------------------------------------------------------------------------
@@ -413,8 +441,9 @@ static int id_tile_width(int OHW, int Cout) {
 static int id_tiles(int OHW, int Cout) { const int bn = 16 * id_tile_width(OHW, Cout); return (OHW + bn - 1) / bn; }
 
 static int id_conv(float* out, const float* in, const float* wfrag, const float* in_ab, const float* epi_ab, const float* slope, float* plane,
-                   int n, int Cin, int Cout, int IH, int IW, int ks, int stride, hipStream_t st) {
+                   int n, int Cin, int Cout, int IH, int IW, int ks, int stride, hipStream_t st, unsigned char* mask = nullptr, int n_mask = 0) {
     IdConvArgs a;
+    a.mask = mask; a.n_mask = n_mask;
     a.out = out; a.in = in; a.wfrag = wfrag;
     a.in_ab = reinterpret_cast<const float2*>(in_ab); a.epi_ab = reinterpret_cast<const float2*>(epi_ab); a.slope = slope; a.plane = plane;
     a.Cin = Cin; a.IH = IH; a.IW = IW; a.Cout = Cout; a.OH = id_out_size(IH, stride); a.OW = id_out_size(IW, stride);
@@ -428,7 +457,12 @@ static int id_conv(float* out, const float* in, const float* wfrag, const float*
         else if (nt == 2) idnet_conv_kernel<KS_, S_, 2><<<grid, dim3(256), 0, st>>>(a);             \
         else idnet_conv_kernel<KS_, S_, 1><<<grid, dim3(256), 0, st>>>(a);                          \
     } while (0)
-    if (ks == 3 && stride == 1) E3DGE_ID_LAUNCH(3, 1);
+    if (mask && ks == 3 && stride == 1) {                            // every PReLU follows a 3x3 of stride 1
+        if (nt == 4) idnet_conv_kernel<3, 1, 4, true><<<grid, dim3(256), 0, st>>>(a);
+        else if (nt == 2) idnet_conv_kernel<3, 1, 2, true><<<grid, dim3(256), 0, st>>>(a);
+        else idnet_conv_kernel<3, 1, 1, true><<<grid, dim3(256), 0, st>>>(a);
+    }
+    else if (ks == 3 && stride == 1) E3DGE_ID_LAUNCH(3, 1);
     else if (ks == 3) E3DGE_ID_LAUNCH(3, 2);
     else if (stride == 1) E3DGE_ID_LAUNCH(1, 1);
     else E3DGE_ID_LAUNCH(1, 2);
@@ -459,6 +493,34 @@ static bool id_ws(int64_t n, IdWs* d) {
     d->gate = take(n * 512);
     d->part = take((int64_t)kIdHeadSlices * n * kIdEmbed);
     d->total_bytes = off * (int64_t)sizeof(float);
+    return true;
+}
+
+// what the saving forward keeps for the backward (idnet_bwd.h), tensor after tensor, each for all n_saved images: offsets in bytes
+struct IdSaved {
+    int64_t res[kIdUnits], gate[kIdUnits], hid[kIdUnits], v, f, norm, mask[kIdUnits + 1], total_bytes;
+    int mask_c[kIdUnits + 1], mask_size[kIdUnits + 1];
+};
+
+static bool id_saved(int64_t n, IdSaved* d) {
+    if (n < 1 || n > 4096) return false;
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) { const int64_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    int size = kIdNet;
+    d->mask_c[0] = 64; d->mask_size[0] = kIdNet;
+    for (int u = 0; u < kIdUnits; ++u) {
+        const IdUnit q = id_unit(u);
+        d->mask_c[1 + u] = q.depth; d->mask_size[1 + u] = size;       // the first 3x3 has stride 1
+        size = id_out_size(size, q.stride);
+        d->res[u] = take(n * q.depth * size * size * (int64_t)sizeof(float));
+        d->gate[u] = take(n * q.depth * (int64_t)sizeof(float));
+        d->hid[u] = take(n * (q.depth / 16) * (int64_t)sizeof(float));
+    }
+    d->v = take(n * kIdEmbed * (int64_t)sizeof(float));
+    d->f = take(n * kIdEmbed * (int64_t)sizeof(float));
+    d->norm = take(n * (int64_t)sizeof(float));
+    for (int i = 0; i <= kIdUnits; ++i) d->mask[i] = take(n * d->mask_c[i] * d->mask_size[i] * d->mask_size[i]);
+    d->total_bytes = off;
     return true;
 }
 
@@ -509,9 +571,8 @@ extern "C" int64_t e3dge_idnet_ws_bytes(int n_images) {
     return d.total_bytes;
 }
 
-extern "C" int e3dge_idnet_embed(const E3dgeIdnetArgs* args, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(args, "idnet_embed: null argument struct");
-    const E3dgeIdnetArgs& a = *args;
+// e3dge_idnet_embed, and with `saved` the saving forward: the same launches, which also fill `saved` for the leading n_saved images
+static int id_embed(const E3dgeIdnetArgs& a, void* saved, int64_t saved_bytes, int n_saved, bool saving, e3dge_stream_t stream) {
     E3DGE_REQUIRE(a.n_sets >= 1 && a.n_sets <= 3, "idnet_embed: n_sets=%d (1..3)", a.n_sets);
     E3DGE_REQUIRE(a.n_per_set >= 1 && a.n_per_set <= 4096 / a.n_sets, "idnet_embed: n_per_set=%d (n_sets * n_per_set in 1..4096)", a.n_per_set);
     E3DGE_REQUIRE(a.packed && a.embeddings && a.ws, "idnet_embed: null pointer");
@@ -522,6 +583,18 @@ extern "C" int e3dge_idnet_embed(const E3dgeIdnetArgs* args, e3dge_stream_t stre
     IdWs d;
     E3DGE_REQUIRE(id_ws(n, &d), "idnet_embed: n_images=%d", n);
     E3DGE_REQUIRE(a.ws_bytes >= d.total_bytes, "idnet_embed: workspace of %lld bytes, %lld needed", (long long)a.ws_bytes, (long long)d.total_bytes);
+    IdSaved sv{};
+    if (saving) {
+        E3DGE_REQUIRE(n_saved >= 1 && n_saved <= n, "idnet_embed_save: n_saved=%d (1..%d)", n_saved, n);
+        E3DGE_REQUIRE(saved, "idnet_embed_save: null pointer (saved)");
+        E3DGE_REQUIRE(id_saved(n_saved, &sv) && saved_bytes >= sv.total_bytes, "idnet_embed_save: saved state of %lld bytes, %lld needed",
+                      (long long)saved_bytes, (long long)sv.total_bytes);
+    } else {
+        n_saved = 0;
+    }
+    char* const S = static_cast<char*>(saved);
+    auto sv_f = [&](int64_t off) { return saving ? reinterpret_cast<float*>(S + off) : nullptr; };
+    auto sv_m = [&](int i) { return saving ? reinterpret_cast<unsigned char*>(S + sv.mask[i]) : nullptr; };
     const IdLayout& l = id_layout();
     hipStream_t st = as_stream(stream);
     float* ws = static_cast<float*>(a.ws);
@@ -545,13 +618,16 @@ extern "C" int e3dge_idnet_embed(const E3dgeIdnetArgs* args, e3dge_stream_t stre
     float* sc = ws + d.sc;
     float* plane = ws + d.plane;
     float* gate = ws + d.gate;
-    if ((rc = id_conv(x, net_in, P + l.w_off[0], nullptr, P + l.bn_off[0], P + l.prelu_off[0], nullptr, n, 3, 64, kIdNet, kIdNet, 3, 1, st))) return rc;
+    if ((rc = id_conv(x, net_in, P + l.w_off[0], nullptr, P + l.bn_off[0], P + l.prelu_off[0], nullptr, n, 3, 64, kIdNet, kIdNet, 3, 1, st, sv_m(0),
+                      n_saved)))
+        return rc;
     tap(1, x, (int64_t)n * 64 * kIdNet * kIdNet);
     int size = kIdNet;
     for (int u = 0; u < kIdUnits; ++u) {
         const IdUnit q = id_unit(u);
         const int osize = id_out_size(size, q.stride), c1 = 1 + 2 * u, c2 = 2 + 2 * u;
-        if ((rc = id_conv(t1, x, P + l.w_off[c1], P + l.bn_off[c1], nullptr, P + l.prelu_off[1 + u], nullptr, n, q.cin, q.depth, size, size, 3, 1, st)))
+        if ((rc = id_conv(t1, x, P + l.w_off[c1], P + l.bn_off[c1], nullptr, P + l.prelu_off[1 + u], nullptr, n, q.cin, q.depth, size, size, 3, 1, st,
+                          sv_m(1 + u), n_saved)))
             return rc;
         if ((rc = id_conv(res, t1, P + l.w_off[c2], nullptr, P + l.bn_off[c2], nullptr, plane, n, q.depth, q.depth, size, size, 3, q.stride, st)))
             return rc;
@@ -560,12 +636,22 @@ extern "C" int e3dge_idnet_embed(const E3dgeIdnetArgs* args, e3dge_stream_t stre
             if ((rc = id_conv(sc, x, P + l.w_off[cs], nullptr, P + l.bn_off[cs], nullptr, nullptr, n, q.cin, q.depth, size, size, 1, q.stride, st)))
                 return rc;
         }
-        idnet_se_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(gate, plane, P + l.fc1_off[u], P + l.fc2_off[u], q.depth,
-                                                                 id_tiles(osize * osize, q.depth), osize * osize);
+        if (saving)
+            idnet_se_kernel<true><<<dim3((unsigned)n), dim3(256), 0, st>>>(gate, plane, P + l.fc1_off[u], P + l.fc2_off[u], q.depth,
+                                                                           id_tiles(osize * osize, q.depth), osize * osize, sv_f(sv.gate[u]),
+                                                                           sv_f(sv.hid[u]), n_saved);
+        else
+            idnet_se_kernel<false><<<dim3((unsigned)n), dim3(256), 0, st>>>(gate, plane, P + l.fc1_off[u], P + l.fc2_off[u], q.depth,
+                                                                            id_tiles(osize * osize, q.depth), osize * osize, nullptr, nullptr, 0);
         if ((rc = check_launch("idnet_embed(se)"))) return rc;
         const int64_t total = (int64_t)n * q.depth * osize * osize;
-        idnet_merge_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(y, res, gate, q.shortcut >= 0 ? sc : nullptr, x, osize, osize,
-                                                                                        size, size, q.stride, total);
+        if (saving)
+            idnet_merge_kernel<true><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(y, res, gate, q.shortcut >= 0 ? sc : nullptr, x, osize,
+                                                                                                 osize, size, size, q.stride, total, sv_f(sv.res[u]),
+                                                                                                 (int64_t)n_saved * q.depth * osize * osize);
+        else
+            idnet_merge_kernel<false><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(y, res, gate, q.shortcut >= 0 ? sc : nullptr, x,
+                                                                                                   osize, osize, size, size, q.stride, total, nullptr, 0);
         if ((rc = check_launch("idnet_embed(merge)"))) return rc;
         const int t = id_tap_of_unit(u);
         if (t >= 0) tap(t, y, total);
@@ -576,9 +662,20 @@ extern "C" int e3dge_idnet_embed(const E3dgeIdnetArgs* args, e3dge_stream_t stre
     idnet_head_kernel<<<dim3(kIdEmbed / kIdHeadRows, kIdHeadSlices), dim3(256), 0, st>>>(part, x, P + l.head_w_off,
                                                                                          reinterpret_cast<const float2*>(P + l.bn_off[52]), n);
     if ((rc = check_launch("idnet_embed(head)"))) return rc;
-    idnet_head_fold_kernel<<<dim3((unsigned)n), dim3(kIdEmbed), 0, st>>>(a.embeddings, a.taps[7], part, P + l.head_b_off,
-                                                                         reinterpret_cast<const float2*>(P + l.bn_off[53]), n);
+    if (saving)
+        idnet_head_fold_kernel<true><<<dim3((unsigned)n), dim3(kIdEmbed), 0, st>>>(a.embeddings, a.taps[7], part, P + l.head_b_off,
+                                                                                  reinterpret_cast<const float2*>(P + l.bn_off[53]), n, sv_f(sv.v),
+                                                                                  sv_f(sv.f), sv_f(sv.norm), n_saved);
+    else
+        idnet_head_fold_kernel<false><<<dim3((unsigned)n), dim3(kIdEmbed), 0, st>>>(a.embeddings, a.taps[7], part, P + l.head_b_off,
+                                                                                    reinterpret_cast<const float2*>(P + l.bn_off[53]), n, nullptr,
+                                                                                    nullptr, nullptr, 0);
     return check_launch("idnet_embed(head fold)");
+}
+
+extern "C" int e3dge_idnet_embed(const E3dgeIdnetArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "idnet_embed: null argument struct");
+    return id_embed(*args, nullptr, 0, 0, false, stream);
 }
 
 extern "C" int e3dge_id_loss(const E3dgeIdLossArgs* args, e3dge_stream_t stream) {
@@ -629,3 +726,5 @@ extern "C" int e3dge_image_metric_row_full(float* row, const float* sums, const 
                                                                                id_lambda);
     return check_launch("image_metric_row_full");
 }
+
+#include "idnet_bwd.h"

@@ -1,5 +1,11 @@
 """ArcFace identity term (IR-SE50 backbone) on the HIP kernels of csrc/idnet.hip: the loss_id / ID_SIM columns of the evaluated image
-and the `id_lambda` term of the reference's 2-D reconstruction loss (forward only; the backward is not in this build).
+and the `id_lambda` term of the reference's 2-D reconstruction loss.
+
+The gradient with respect to y_hat (csrc/idnet_bwd.h; the network stays frozen, as the reference freezes it, and y and x never get
+one: id_loss.py:36 detaches y's features and x's enter only the logs) is opt-in: `IDLoss(..., differentiable=True)` or
+`module.differentiable = True`.  Then, with grad enabled and a y_hat that requires grad, the call goes through one autograd Function
+whose forward is the state-saving form of the same launches (bit-identical values) and whose backward is once-differentiable.  With the
+switch off (the default) inputs that require grad raise NotImplementedError, as before.
 
 The module has the reference's call surface and state-dict keys (project/losses/id_loss.py, models/encoders/model_irse.py,
 models/helper_modules/helpers.py:83-224), so a state dict saved from the reference's `IDLoss` loads with strict=True:
@@ -23,6 +29,15 @@ TAP_UNITS = (0, 3, 7, 21, 23)
 TAP_NAMES = ("net_input", "input_layer") + tuple(f"unit{u}" for u in TAP_UNITS) + ("head",)
 EMBED = 512
 CROP = (35, 223, 32, 220)                                            # id_loss.py:24
+
+
+def mask_shapes(n):
+    """Shapes of the 25 PReLU inputs for n images: the input layer's, then each unit's (its first 3x3 has stride 1)."""
+    out, size = [(n, 64, 112, 112)], 112
+    for _, depth, stride in UNITS:
+        out.append((n, depth, size, size))
+        size //= stride
+    return out
 
 
 def tap_shapes(n):
@@ -92,10 +107,11 @@ class _Backbone(nn.Module):
 
 class IDLoss(nn.Module):
     """`IDLoss(device)(y_hat, y, x)`: (loss, sim_improvement, id_logs) of id_loss.py:29-55 for three (B, 3, S, S) tensors in [-1, 1].
-    GPU float32 tensors run the HIP kernels, CPU tensors the torch layers of `facenet`."""
+    GPU float32 tensors run the HIP kernels, CPU tensors the torch layers of `facenet` (under autograd when `differentiable`)."""
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, differentiable=False):
         super().__init__()
+        self.differentiable = bool(differentiable)
         self.facenet = _Backbone()
         self.face_pool = nn.AdaptiveAvgPool2d((112, 112))
         self.id_loss_pool = nn.AdaptiveAvgPool2d((256, 256))          # builder.py:27
@@ -153,8 +169,33 @@ class IDLoss(nn.Module):
 
         return _lib.cached(self, "idnet_packed", src, build)
 
+    def _packed_t(self, device):
+        """The transposed weight image of the backward, on the same sources as the forward image."""
+        groups = self._sources()
+        src = [t for g in groups.values() for t in g]
+        for t in src:
+            if t.device != device or t.dtype != torch.float32:
+                raise RuntimeError(f"IDLoss weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
+
+        def build():
+            with torch.no_grad():
+                keep = [t.detach().contiguous() for t in groups["conv_w"]]
+                s = _lib.IdnetPackSrc()
+                s.conv_w[:] = [t.data_ptr() for t in keep]
+                packed_t = torch.empty(_lib.load().e3dge_idnet_packed_t_floats(), device=device, dtype=torch.float32)
+                _lib.launch("e3dge_idnet_pack_weights_t", packed_t, ctypes.addressof(s))
+                return packed_t
+
+        return _lib.cached(self, "idnet_packed_t", src, build)
+
+    def _check(self, sets):
+        self._check_shapes(sets)
+        for t in sets:
+            if torch.is_grad_enabled() and t.requires_grad and not self.differentiable:
+                raise NotImplementedError("IDLoss backward is not in this build: call under torch.no_grad() or detach the inputs")
+
     @staticmethod
-    def _check(sets):
+    def _check_shapes(sets):
         first = sets[0]
         for t in sets:
             if not torch.is_tensor(t):
@@ -163,25 +204,28 @@ class IDLoss(nn.Module):
                 raise ValueError(f"IDLoss takes (B, 3, S, S) tensors of one shape, B >= 1 (got {[tuple(q.shape) for q in sets]})")
             if t.device != first.device or t.dtype != first.dtype:
                 raise RuntimeError("IDLoss inputs must share one device and dtype")
-            if torch.is_grad_enabled() and t.requires_grad:
-                raise NotImplementedError("IDLoss backward is not in this build: call under torch.no_grad() or detach the inputs")
 
-    def _embed_sets(self, sets, taps=False):
-        """(embeddings (len(sets) * B, 512), taps or None) of up to three image sets of one shape, set after set."""
+    def _wants_grad(self, y_hat):
+        return self.differentiable and torch.is_grad_enabled() and y_hat.requires_grad
+
+    def _embed_sets(self, sets, taps=False, n_saved=0, grad_first=False):
+        """(embeddings (len(sets) * B, 512), taps or None) of up to three image sets of one shape, set after set.  GPU, n_saved > 0: the
+        state-saving forward; the saved state of the leading n_saved images is returned as a third value.  CPU, grad_first: the first
+        set's embeddings carry the graph (the reference's own path); taps never do."""
         dev, B, S = sets[0].device, sets[0].shape[0], sets[0].shape[2]
         n = B * len(sets)
         if dev.type != "cuda":
-            with torch.no_grad():
-                embs, per_set = [], []
-                for z in sets:                                        # set by set, as id_loss.py:33-35 calls extract_feats
+            embs, per_set = [], []
+            for i, z in enumerate(sets):                              # set by set, as id_loss.py:33-35 calls extract_feats
+                with torch.enable_grad() if grad_first and i == 0 else torch.no_grad():
                     z = z.to(self.facenet.input_layer[0].weight.dtype)
                     if S != 256:
                         z = self.id_loss_pool(z)                      # builder.py:157-160
                     z = self.face_pool(z[:, :, CROP[0]:CROP[1], CROP[2]:CROP[3]])
                     tl = [z] if taps else None
                     embs.append(self.facenet(z, tl))
-                    per_set.append(tl)
-                return torch.cat(embs), ([torch.cat(t) for t in zip(*per_set)] if taps else None)
+                    per_set.append([t.detach() for t in tl] if taps else None)
+            return torch.cat(embs), ([torch.cat(t) for t in zip(*per_set)] if taps else None)
         for i, t in enumerate(sets):
             _lib.require_gpu(t, f"IDLoss input {i}")
         lib = _lib.load()
@@ -201,12 +245,62 @@ class IDLoss(nn.Module):
             for i, t in enumerate(tl):
                 a.taps[i] = t.data_ptr()
         a._note(dev)
+        if n_saved:
+            saved_bytes = lib.e3dge_idnet_saved_bytes(n_saved)
+            if saved_bytes < 0:
+                raise RuntimeError(f"e3dge_idnet_saved_bytes: {lib.e3dge_last_error().decode(errors='replace')}")
+            saved = torch.empty(saved_bytes, device=dev, dtype=torch.uint8)
+            sa = _lib.IdnetSaveArgs(net=a, saved=saved, saved_bytes=saved_bytes, n_saved=n_saved)
+            _lib.launch("e3dge_idnet_embed_save", sa)
+            return emb, tl, saved
         _lib.launch("e3dge_idnet_embed", a)
         return emb, tl
+
+    def _launch_backward(self, saved, shape, grad_emb, stages=False, masks=False):
+        """(grad_y_hat, the eight stage gradients or None, the 25 masks or None) from the state `saved` a saving forward of inputs of
+        `shape` left behind; grad_emb (B, 512) = dL / d f_hat."""
+        B, _, S, _ = shape
+        dev = saved.device
+        lib = _lib.load()
+        ws_bytes = lib.e3dge_idnet_bwd_ws_bytes(B, S, S)
+        if ws_bytes < 0:
+            raise RuntimeError(f"e3dge_idnet_bwd_ws_bytes: {lib.e3dge_last_error().decode(errors='replace')}")
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        grad = torch.empty(shape, device=dev, dtype=torch.float32)
+        a = _lib.IdnetBwdArgs(packed=self._packed(dev), packed_t=self._packed_t(dev), saved=saved, saved_bytes=saved.numel(), n=B, height=S,
+                              width=S, grad_embeddings=grad_emb, grad_images=grad, ws=ws, ws_bytes=ws_bytes)
+        gs = ms = None
+        if stages:
+            gs = [torch.empty(s, device=dev, dtype=torch.float32) for s in tap_shapes(B)]
+            for i, t in enumerate(gs):
+                a.gstage[i] = t.data_ptr()
+        if masks:
+            ms = [torch.empty(s, device=dev, dtype=torch.uint8) for s in mask_shapes(B)]
+            for i, t in enumerate(ms):
+                a.masks[i] = t.data_ptr()
+        _lib.launch("e3dge_idnet_backward", a)
+        return grad, gs, ms
+
+    def run_backward(self, y_hat, y, upstream, stages=False, masks=False):
+        """Debug entry, no synchronisation: the saving forward of (y_hat, y), then the backward for upstream (B,) = dL / d(1 - dot_b)
+        (1 / B for the loss).  Returns (grad_y_hat, the gradients at the eight tensors of TAP_NAMES or None -- the head's is the
+        gradient at v, before the normalisation --, the 25 PReLU branch masks (uint8, shaped like the PReLU inputs of y_hat's images, 1 =
+        positive branch) or None).  Needs no autograd and records none."""
+        self._check_shapes([y_hat, y])
+        _lib.require_gpu(upstream, "IDLoss upstream")
+        B = y_hat.shape[0]
+        if upstream.shape != (B,):
+            raise ValueError(f"IDLoss upstream must be ({B},) (got {tuple(upstream.shape)})")
+        with torch.no_grad():
+            emb, _, saved = self._embed_sets([y_hat, y], n_saved=B)
+            g_f = -upstream.detach().to(torch.float32)[:, None] * emb[B:2 * B]       # dL / d f_hat[b] = -u_b f_y[b]
+            return self._launch_backward(saved, tuple(y_hat.shape), g_f, stages, masks)
 
     def embed(self, images):
         """(n, 512) unit-norm embeddings of (n, 3, S, S) images."""
         self._check([images])
+        if torch.is_grad_enabled() and images.requires_grad:
+            raise NotImplementedError("IDLoss backward is not in this build for embed(): the gradient exists for the loss of run() / forward()")
         return self._embed_sets([images])[0]
 
     def run(self, y_hat, y, x=None, taps=False):
@@ -216,8 +310,17 @@ class IDLoss(nn.Module):
         two = x is None or x is y
         sets = [y_hat, y] if two else [y_hat, y, x]
         self._check(sets)
-        emb, tl = self._embed_sets(sets, taps)
         B = y_hat.shape[0]
+        want = self._wants_grad(y_hat)
+        if want and y_hat.device.type == "cuda":
+            side = {}
+            loss = _IdLossFunction.apply(self, side, bool(taps), y_hat, y.detach(), None if two else x.detach())
+            return dict(side, loss=loss)
+        emb, tl = self._embed_sets(sets, taps, grad_first=want)
+        return self._finish(emb, tl, B, two)
+
+    def _finish(self, emb, tl, B, two):
+        """The dot products, the loss and the result dict of run() from the embeddings."""
         fh, fy = emb[:B], emb[B:2 * B]
         fx = fy if two else emb[2 * B:]
         if emb.device.type != "cuda":
@@ -227,15 +330,15 @@ class IDLoss(nn.Module):
             loss, sim = 0, 0
             for b in range(B):
                 loss = loss + (1 - dots[b, 0])
-                sim += float(dots[b, 0]) - float(dots[b, 2])
+                sim += float(dots[b, 0].detach()) - float(dots[b, 2].detach())
             loss, sim = loss / B, torch.tensor(sim / B, dtype=dots.dtype)
         else:
             out = torch.empty(3 * B + 2, device=emb.device, dtype=torch.float32)
             a = _lib.IdLossArgs(y_hat=fh, y=fy, x=fx, batch=B, dots=out, loss=out.data_ptr() + 12 * B, sim_improvement=out.data_ptr() + 12 * B + 4)
             _lib.launch("e3dge_id_loss", a)
             dots, loss, sim = out[:3 * B].view(B, 3), out[3 * B], out[3 * B + 1]
-        return dict(embeddings=emb, dots=dots, diff_target=dots[:, 0], diff_input=dots[:, 1], diff_views=dots[:, 2], loss=loss,
-                    sim_improvement=sim, taps=tl)
+        return dict(embeddings=emb.detach(), dots=dots.detach(), diff_target=dots[:, 0].detach(), diff_input=dots[:, 1].detach(),
+                    diff_views=dots[:, 2].detach(), loss=loss, sim_improvement=sim, taps=tl)
 
     def forward(self, y_hat, y, x):
         res = self.run(y_hat, y, x)
@@ -244,3 +347,28 @@ class IDLoss(nn.Module):
         B = len(rows)
         sim = sum(r[0] - r[2] for r in rows) / B                      # Python floats, as id_loss.py:51-55
         return res['loss'], sim, logs
+
+
+class _IdLossFunction(torch.autograd.Function):
+    """The loss of one saving forward (its side outputs go to `side`); the graph leads to y_hat only."""
+
+    @staticmethod
+    def forward(ctx, module, side, taps, y_hat, y, x=None):
+        sets = [y_hat, y] if x is None else [y_hat, y, x]
+        B = y_hat.shape[0]
+        emb, tl, saved = module._embed_sets(sets, taps, n_saved=B)
+        res = module._finish(emb, tl, B, x is None)
+        side.update(res)
+        ctx.module, ctx.saved, ctx.shape, ctx.f_y = module, saved, tuple(y_hat.shape), emb[B:2 * B]
+        ctx.set_materialize_grads(False)
+        return res['loss']
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        if g_loss is None or not ctx.needs_input_grad[3]:
+            return (None,) * 6
+        B = ctx.shape[0]
+        u = (g_loss.to(torch.float32) / B).expand(B)
+        g_f = -u[:, None] * ctx.f_y                                    # dL / d f_hat[b] = -u_b f_y[b]
+        return None, None, None, ctx.module._launch_backward(ctx.saved, ctx.shape, g_f)[0], None, None

@@ -838,6 +838,72 @@ int e3dge_image_metric_row_full(float* row, const float* sums, const float* lpip
                                 float l2_lambda, float vgg_lambda, float id_lambda, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * ArcFace identity term, backward (csrc/idnet_bwd.h): the gradient of the loss with respect to the y_hat images; the network is
+ * frozen, as the reference freezes it.  Additions to ABI 16.  No allocation, no synchronisation, no atomics; bit-reproducible,
+ * and an image's gradient does not depend on the batch it is in or on its position in it.
+ *
+ * e3dge_idnet_packed_t_floats floats of the transposed weight image: for each of the 52 convolutions W^T with flipped taps
+ *                            (M = C_in padded to 16, K = (co, r, s) padded to a multiple of 32) in MFMA A-fragment order.  A
+ *                            buffer of its own; the forward image is unchanged.
+ * e3dge_idnet_pack_weights_t src: the struct e3dge_idnet_pack_weights takes (only conv_w is read).  Re-run after a weight update.
+ * e3dge_idnet_saved_bytes    bytes of the state the saving forward keeps for n_saved images (-1: n_saved outside 1..4096): per
+ *                            image the 25 PReLU branches as bytes (3,713,024), the 24 `res` tensors (BN2 output before the
+ *                            gate; 1,781,248 floats), the gates, the SE hidden activations, and the head's v, f and |v|.
+ * e3dge_idnet_embed_save     e3dge_idnet_embed (net: same fields, same launches, bit-identical embeddings and taps) that also
+ *                            fills `saved` for the leading n_saved images of the batch (set 0 first).  1 <= n_saved <=
+ *                            n_per_set * n_sets.  Fails like e3dge_idnet_embed, and on a null or too small `saved` ("saved").
+ * e3dge_idnet_bwd_ws_bytes   workspace bytes of a backward of n images of height x width (-1: bad n or size).
+ * e3dge_idnet_backward       saved: what e3dge_idnet_embed_save left for n_saved = n images of the same height and width.
+ *                            grad_embeddings (n, 512) = dL / d f (for the loss term: -u_b f_y[b], u_b = dL / d(1 - dot_b)).
+ *                            grad_images (n, 3, height, width): every element is written (exact zeros outside the crop's
+ *                            pre-image).  gstage[t]: NULL or the gradient at tap t of E3dgeIdnetArgs (the head's is the
+ *                            gradient at v, before the normalisation).  masks[i]: NULL or bytes shaped like PReLU i's input
+ *                            ([0] input layer, [1 + u] unit u) that receive 1 where the saved branch is the positive one.
+ *                            104 launches without gstage and masks.  Fails before any launch on a null required pointer
+ *                            ("null"), n < 1 ("n="), height or width < 1, saved_bytes too small ("saved") or ws_bytes too
+ *                            small ("workspace").
+ * e3dge_idnet_conv_bwd       debug entry: one data gradient of the family.  g (n, cout, OH, OW) with OH = (height - 1) / stride
+ *                            + 1, w (cout, cin, ksize, ksize), ksize 1 (pad 0) or 3 (pad 1), stride 1 or 2; out (n, cin,
+ *                            height, width) = (conv^T g) * factor + addend.  wfrag_t: scratch of roundup(cin, 16) * roundup(cout
+ *                            ksize^2, 32) floats.  in_ab NULL or (n, cout, 2): g <- a g + b per (image, channel) on in-image
+ *                            elements.  factor: mask (n, cin, height, width bytes) with slope (cin): 1 where the byte is set,
+ *                            slope[c] elsewhere; or scale (cin): scale[c]; both NULL: 1.  addend NULL or (n, cin, height,
+ *                            width).  Two launches.
+ * e3dge_idnet_prep_bwd       debug entry: the adjoint of the crop and the adaptive averages.  grad_net_in (n, 3, 112, 112) ->
+ *                            grad_images (n, 3, height, width), every element written.  One launch.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_IDNET_PRELUS 25
+typedef struct E3dgeIdnetSaveArgs {
+    E3dgeIdnetArgs net;
+    void* saved;
+    int64_t saved_bytes;
+    int32_t n_saved, reserved;
+} E3dgeIdnetSaveArgs;
+typedef struct E3dgeIdnetBwdArgs {
+    const float* packed;              /* the forward image (BN pairs, slopes and SE matrices are read) */
+    const float* packed_t;            /* e3dge_idnet_pack_weights_t */
+    const void* saved;                /* e3dge_idnet_embed_save with n_saved = n */
+    int64_t saved_bytes;
+    int32_t n, height, width, reserved;
+    const float* grad_embeddings;
+    float* grad_images;
+    float* gstage[E3DGE_IDNET_TAPS];
+    unsigned char* masks[E3DGE_IDNET_PRELUS];
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeIdnetBwdArgs;
+int64_t e3dge_idnet_packed_t_floats(void);
+int e3dge_idnet_pack_weights_t(float* packed_t, const E3dgeIdnetPackSrc* src, e3dge_stream_t stream);
+int64_t e3dge_idnet_saved_bytes(int n_saved);
+int e3dge_idnet_embed_save(const E3dgeIdnetSaveArgs* args, e3dge_stream_t stream);
+int64_t e3dge_idnet_bwd_ws_bytes(int n, int height, int width);
+int e3dge_idnet_backward(const E3dgeIdnetBwdArgs* args, e3dge_stream_t stream);
+int e3dge_idnet_conv_bwd(float* out, const float* g, const float* w, float* wfrag_t, const float* in_ab, const unsigned char* mask,
+                         const float* slope, const float* scale, const float* addend, int n, int cin, int cout, int height, int width,
+                         int ksize, int stride, e3dge_stream_t stream);
+int e3dge_idnet_prep_bwd(float* grad_images, const float* grad_net_in, int n, int height, int width, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Surface extraction, device half: replaces align_volume (project/utils/mesh_utils.py:17-44; called on the rendered
  * 128^3 SDF volume at volume_renderer.py:1706, before the CPU marching cubes).  volume, out (batch, height, width, depth,
  * channels), not aliased; xs (width), ys (height), zs (depth) = linspace(-1, 1, n) and coef (depth) = linspace(far / near,

@@ -4,11 +4,16 @@ torch layers on the GPU (conv2d / batch_norm / prelu through MIOpen, the pooling
 the same GPU.
 
     python tools/time_idloss.py [--out FILE.json] [--steps 10] [--no-launches] [--no-graph] [--only B1_256]
+    python tools/time_idloss.py --backward [--out profiles/idloss_bwd_times.json] [--steps 10] [--no-launches] [--only B1_256]
 
 Cases: one 256^2 pair (the evaluation shape), B = 4 pairs, one 1024^2 pair (through the 256^2 pooling).  Estimator: warm-up, then
 five blocks of `steps` forwards between two HIP events; the median block, per forward.  `graph_ms` is the same forward captured once
 with e3dge_amd.graphs.GraphedCall and replayed.  `achieved` is the fraction of the fp32 matrix peak (157.3 TFLOP/s) the HIP path
-reaches on the convolutions' and the head's 2 x MAC count.  Prints one JSON line per case."""
+reaches on the convolutions' and the head's 2 x MAC count.  Prints one JSON line per case.
+
+--backward: forward + backward of the loss with respect to y_hat (one 256^2 pair, B = 4 pairs), IDLoss(differentiable=True) -- the
+saving forward (csrc/idnet.hip) and the backward (csrc/idnet_bwd.h) -- against the same torch layers under autograd (y's features
+under no_grad, as id_loss.py:36 detaches them), with the plain forward's time and the saved-state and workspace bytes beside it."""
 import argparse
 import json
 import os
@@ -33,6 +38,53 @@ def torch_chain(m, y_hat, y):
     e = m.facenet(m.face_pool(z[:, :, CROP[0]:CROP[1], CROP[2]:CROP[3]]))
     B = y.shape[0]
     return (1 - (e[:B] * e[B:]).sum(1)).sum() / B
+
+
+def torch_chain_grad(m, y_hat, y):
+    """The loss with a graph to y_hat only, through the torch layers."""
+    prep = lambda z: m.face_pool((z if z.shape[-1] == 256 else m.id_loss_pool(z))[:, :, CROP[0]:CROP[1], CROP[2]:CROP[3]])
+    with torch.no_grad():
+        fy = m.facenet(prep(y))
+    fh = m.facenet(prep(y_hat))
+    return (1 - (fh * fy).sum(1)).sum() / y.shape[0]
+
+
+def backward_cases(args, dev):
+    from e3dge_amd import _lib
+    m = syn.load_synthetic_idloss(IDLoss(differentiable=True)).to(dev)
+    lib, lines = _lib.load(), []
+    for batch, size in ((1, 256), (4, 256)):
+        if args.only and args.only != f"B{batch}_{size}":
+            continue
+        g = torch.Generator(device=dev).manual_seed(size + batch)
+        y = torch.rand(batch, 3, size, size, device=dev, generator=g) * 2 - 1
+        y_hat = (y + 0.3 * torch.randn(batch, 3, size, size, device=dev, generator=g)).clamp(-1, 1).requires_grad_(True)
+
+        def step(loss_of):
+            y_hat.grad = None
+            loss_of().backward()
+            return y_hat.grad
+
+        hip, ref = lambda: step(lambda: m.run(y_hat, y)['loss']), lambda: step(lambda: torch_chain_grad(m, y_hat, y))
+        with torch.no_grad():
+            fwd = lambda: m.run(y_hat, y)['loss']
+            t_fwd = block_ms(fwd, args.steps)
+        a, b = hip().clone(), ref().clone()
+        t_hip, t_ref = block_ms(hip, args.steps), block_ms(ref, args.steps)
+        line = dict(case=f"B{batch}_{size}", hip_fwd_bwd_ms=t_hip[0], hip_fwd_bwd_ms_min=t_hip[1], hip_fwd_bwd_ms_max=t_hip[2],
+                    torch_fwd_bwd_ms=t_ref[0], torch_fwd_bwd_ms_min=t_ref[1], torch_fwd_bwd_ms_max=t_ref[2],
+                    ratio_torch_over_hip=t_ref[0] / t_hip[0], hip_plain_fwd_ms=t_fwd[0], hip_plain_fwd_ms_min=t_fwd[1],
+                    hip_plain_fwd_ms_max=t_fwd[2], grad_rel_diff=float((a - b).abs().max() / b.abs().max()),
+                    saved_bytes_per_image=lib.e3dge_idnet_saved_bytes(batch) / batch,
+                    bwd_ws_bytes_per_image=lib.e3dge_idnet_bwd_ws_bytes(batch, size, size) / batch,
+                    estimator=f"median of 5 blocks of {args.steps} forward + backward steps, HIP events")
+        if not args.no_launches:
+            line["hip_launches"], line["torch_launches"] = count_kernels(hip), count_kernels(ref)
+            with torch.no_grad():
+                line["hip_plain_fwd_launches"] = count_kernels(fwd)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
 
 
 def flops(n_images):
@@ -77,13 +129,14 @@ def main():
     ap.add_argument("--no-launches", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--only", help="one case, e.g. B1_256")
+    ap.add_argument("--backward", action="store_true", help="forward + backward of the loss with respect to y_hat")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = "cuda:0"
+    lines = backward_cases(args, dev) if args.backward else []
     m = syn.load_synthetic_idloss(IDLoss()).to(dev)
-    lines = []
     with torch.no_grad():
-        for batch, size in ((1, 256), (4, 256), (1, 1024)):
+        for batch, size in () if args.backward else ((1, 256), (4, 256), (1, 1024)):
             if args.only and args.only != f"B{batch}_{size}":
                 continue
             g = torch.Generator(device=dev).manual_seed(size + batch)
