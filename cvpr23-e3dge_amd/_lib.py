@@ -240,6 +240,20 @@ class IdLossArgs(_Args):
     _fields_ = [(n, _vp) for n in ("y_hat", "y", "x")] + [("batch", _i32), ("reserved", _i32)] + [(n, _vp) for n in ("dots", "loss", "sim_improvement")]
 
 
+SHAPE_LOSS_SEGMENTS, SHAPE_SMOOTH_L1, SHAPE_EIKONAL = 4, 0, 1      # E3DGE_SHAPE_LOSS_SEGMENTS, E3DGE_SHAPE_* (include/e3dge_hip.h)
+
+
+class ShapeLossSegment(_Args):
+    """Mirror of struct E3dgeShapeLossSegment (include/e3dge_hip.h)."""
+    _fields_ = [("pred", _vp), ("gt", _vp), ("d_pred", _vp), ("n", _i64), ("lambda_", _f32), ("kind", _i32)]
+
+
+class ShapeLossArgs(_Args):
+    """Mirror of struct E3dgeShapeLossArgs (include/e3dge_hip.h)."""
+    _fields_ = [("seg", ShapeLossSegment * SHAPE_LOSS_SEGMENTS), ("terms", _vp), ("total", _vp), ("partial", _vp), ("partial_floats", _i64),
+                ("upstream", _vp)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -362,6 +376,12 @@ SIGNATURES = {
     "e3dge_ws_rowdot2": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp]),
     "e3dge_selftest_sin": (_i32, [_vp, _vp, _i32, _vp]),
     "e3dge_selftest_sin_poly": (_i32, [_vp, _vp, _i32, _vp]),
+    "e3dge_avgpool_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "e3dge_avgpool_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "e3dge_sqerr_bwd": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "e3dge_shape_loss_partial_floats": (_i64, [ctypes.POINTER(ShapeLossArgs)]),
+    "e3dge_shape_loss_fwd": (_i32, [ctypes.POINTER(ShapeLossArgs), _vp]),
+    "e3dge_shape_loss_bwd": (_i32, [ctypes.POINTER(ShapeLossArgs), _vp]),
 }
 
 _lib = None

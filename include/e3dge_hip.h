@@ -1128,6 +1128,52 @@ int e3dge_selftest_sin(float* y, const float* x, int n, e3dge_stream_t stream);
 /* The alternative 13-op polynomial sine (kernels built with -DE3DGE_POLY_SINE use it). */
 int e3dge_selftest_sin_poly(float* y, const float* x, int n, e3dge_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The training loss's own kernels (csrc/losses.hip).  Additions to ABI 16.  No allocation, no synchronisation, no atomics:
+ * results are bit-identical from run to run.  Replaces what LossClass (project/losses/builder.py) and its callers run as
+ * framework kernels: the trainers' pool_256 / pool_64 (trainer.py:1023-1025), the backward of criterionImg (builder.py:142)
+ * and the four terms of calc_shape_rec_loss (builder.py:76-104) with eikonal_loss (gan_loss.py:14-25).
+ *
+ * e3dge_avgpool_fwd   out (planes, in_h / f, in_w / f) = mean over the f x f blocks of in (planes, in_h, in_w); f in {1, 2, 4, 8, 16}
+ *                     dividing in_h and in_w -- AdaptiveAvgPool2d at an integer ratio.  Summed row-major inside the block, then one
+ *                     division by f^2.
+ * e3dge_avgpool_bwd   d_in[p, y, x] = d_out[p, y / f, x / f] / f^2 (every element of d_in is written).
+ * e3dge_sqerr_bwd     d_pred[i] = (*scale_ptr) * (pred[i] - gt[i]), i < n: the backward of mean((pred - gt)^2) with the caller's
+ *                     (upstream * 2 * l2_lambda / n) read from device memory.  The forward is e3dge_image_metrics' sums.
+ * planes == 0 / n == 0: nothing is launched, E3DGE_OK.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int e3dge_avgpool_fwd(float* out, const float* in, int64_t planes, int in_h, int in_w, int f, e3dge_stream_t stream);
+int e3dge_avgpool_bwd(float* d_in, const float* d_out, int64_t planes, int in_h, int in_w, int f, e3dge_stream_t stream);
+int e3dge_sqerr_bwd(float* d_pred, const float* pred, const float* gt, int64_t n, const float* scale_ptr, e3dge_stream_t stream);
+/* The shape terms.  seg[0..3] are, in the reference's order of summation, sdf_rec_loss, surf_rec_loss, surface_norm_rec_loss and
+ * eikonal_term; a segment with n == 0 is off (its term is 0 and is not added).  kind:
+ *   E3DGE_SHAPE_SMOOTH_L1  mean over n elements of smooth_l1(pred - gt), beta 1: 0.5 d^2 if |d| < 1, else |d| - 0.5; gt NULL = zeros
+ *   E3DGE_SHAPE_EIKONAL    mean over n 3-vectors of (|pred| - 1)^2; gt must be NULL
+ * forward:  terms[s] = lambda_s * mean_s, *total = the enabled terms added in slot order; one tile launch over all segments and
+ *           one single-workgroup fold in double.  partial: e3dge_shape_loss_partial_floats(args) floats of workspace.
+ * backward: one launch; d_pred_s = (*upstream) * lambda_s / n_s * clamp(pred - gt, -1, 1)  (Smooth-L1)
+ *                                  (*upstream) * lambda_s / n_s * 2 (|e| - 1) e / |e|, exactly 0 where e = 0  (eikonal).
+ *           Reads pred, gt, d_pred, n, lambda, kind and upstream; a segment whose gradient is not wanted has n = 0.
+ * Every segment off: nothing is launched (terms and total are left as they are), E3DGE_OK. */
+#define E3DGE_SHAPE_LOSS_SEGMENTS 4
+#define E3DGE_SHAPE_SMOOTH_L1 0
+#define E3DGE_SHAPE_EIKONAL 1
+typedef struct E3dgeShapeLossSegment {
+    const float* pred; const float* gt; float* d_pred;
+    int64_t n;
+    float lambda;
+    int32_t kind;
+} E3dgeShapeLossSegment;
+typedef struct E3dgeShapeLossArgs {
+    E3dgeShapeLossSegment seg[E3DGE_SHAPE_LOSS_SEGMENTS];
+    float* terms; float* total; float* partial;
+    int64_t partial_floats;
+    const float* upstream;
+} E3dgeShapeLossArgs;
+int64_t e3dge_shape_loss_partial_floats(const E3dgeShapeLossArgs* args);
+int e3dge_shape_loss_fwd(const E3dgeShapeLossArgs* args, e3dge_stream_t stream);
+int e3dge_shape_loss_bwd(const E3dgeShapeLossArgs* args, e3dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
