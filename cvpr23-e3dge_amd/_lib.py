@@ -254,6 +254,29 @@ class ShapeLossArgs(_Args):
                 ("upstream", _vp)]
 
 
+DISC_MAX_BLOCKS, DISC_TAP_STDDEV, DISC_TAP_FINAL, DISC_TAP_STEM, DISC_TAPS = 8, 8, 9, 10, 11     # E3DGE_DISC_* (include/e3dge_hip.h)
+
+
+class DiscPackSrc(_Args):
+    """Mirror of struct E3dgeDiscPackSrc (include/e3dge_hip.h)."""
+    _fields_ = [(n, _i32) for n in ("init_size", "channel_multiplier", "in_channels", "reserved")] + [("stem_w", _vp), ("stem_b", _vp)] + [
+        (n, _vp * DISC_MAX_BLOCKS) for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "skip_w")] + [
+        (n, _vp) for n in ("final_w", "final_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "blur")]
+
+
+class DiscArgs(_Args):
+    """Mirror of struct E3dgeDiscArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("images", _vp)] + [(n, _i32) for n in ("n", "height", "width", "init_size", "channel_multiplier", "in_channels")] + [
+        ("logits", _vp), ("taps", _vp * DISC_TAPS), ("ws", _vp), ("ws_bytes", _i64), ("saved", _vp), ("saved_bytes", _i64)]
+
+
+class DiscBwdArgs(_Args):
+    """Mirror of struct E3dgeDiscBwdArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("saved", _vp), ("saved_bytes", _i64)] + [
+        (n, _i32) for n in ("n", "height", "width", "init_size", "channel_multiplier", "in_channels")] + [
+        ("grad_logits", _vp), ("grad_images", _vp), ("gstage", _vp * DISC_TAPS), ("ws", _vp), ("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -382,6 +405,15 @@ SIGNATURES = {
     "e3dge_shape_loss_partial_floats": (_i64, [ctypes.POINTER(ShapeLossArgs)]),
     "e3dge_shape_loss_fwd": (_i32, [ctypes.POINTER(ShapeLossArgs), _vp]),
     "e3dge_shape_loss_bwd": (_i32, [ctypes.POINTER(ShapeLossArgs), _vp]),
+    "e3dge_disc_packed_floats": (_i64, [_i32] * 3),
+    "e3dge_disc_pack_weights": (_i32, [_vp, _vp, _vp]),
+    "e3dge_disc_ws_bytes": (_i64, [_i32] * 7),
+    "e3dge_disc_saved_bytes": (_i64, [_i32] * 4),
+    "e3dge_disc_forward": (_i32, [ctypes.POINTER(DiscArgs), _vp]),
+    "e3dge_disc_backward": (_i32, [ctypes.POINTER(DiscBwdArgs), _vp]),
+    "e3dge_disc_conv": (_i32, [_vp] * 6 + [_i32] * 9 + [_f32, _vp]),
+    "e3dge_disc_conv_dgrad": (_i32, [_vp] * 5 + [_f32, _f32, _vp] + [_i32] * 7 + [_f32, _vp]),
+    "e3dge_disc_stddev": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -3,6 +3,8 @@
 
     AvgPool2d(size)        AdaptiveAvgPool2d at an integer ratio: e3dge_avgpool_fwd / e3dge_avgpool_bwd
     eikonal_loss           the reference's function (plain torch; inside LossClass the term is one segment of the shape launch)
+    g_nonsaturating_loss, d_logistic_loss, d_r1_loss
+                           the reference's GAN terms (gan_loss.py:28-48, plain torch on the B logits of e3dge_amd.discriminator)
     LossClass              calc_shape_rec_loss: every enabled term in two forward launches and one backward launch
                            calc_2d_rec_loss:    MSE from e3dge_image_metrics' sums with e3dge_sqerr_bwd as its backward, LPIPS and the
                                                 identity term through e3dge_amd.lpips.LPIPS / e3dge_amd.id_loss.IDLoss (differentiable)
@@ -10,7 +12,7 @@
 GPU float32 tensors take the HIP kernels; CPU tensors, other dtypes, non-integer pool ratios and second-order gradients take the torch
 formulas, which are the reference's own.  The loss nodes are once-differentiable; the eikonal term's double backward belongs to the
 renderer node that produced it.  Out of scope, as in the reference's callers: the fg_mask products (the caller's, before the call),
-ConsistencyLoss, DepthLoss and the GAN terms."""
+ConsistencyLoss and DepthLoss; LossClass itself does not call the GAN terms (the trainer adds them, trainer.py:1233-1244)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -91,6 +93,22 @@ def eikonal_loss(eikonal_term, sdf=None, beta=100):
     else:
         minimal_surface = torch.exp(-beta * torch.abs(sdf)).mean()
     return eik, minimal_surface
+
+
+# ----------------------------------------------------------------------------------------------------------------- GAN terms
+# gan_loss.py:28-48, plain torch: they act on the B logits of e3dge_amd.discriminator.Discriminator.
+def d_logistic_loss(real_pred, fake_pred):
+    return F.softplus(-real_pred).mean() + F.softplus(fake_pred).mean()
+
+
+def d_r1_loss(real_pred, real_img):
+    """The R1 penalty: a double backward through the discriminator, which therefore runs its torch composition (trainable parameters)."""
+    grad_real, = torch.autograd.grad(outputs=real_pred.sum(), inputs=real_img, create_graph=True)
+    return grad_real.pow(2).reshape(grad_real.shape[0], -1).sum(1).mean()
+
+
+def g_nonsaturating_loss(fake_pred):
+    return F.softplus(-fake_pred).mean()
 
 
 # --------------------------------------------------------------------------------------------------------------- shape terms

@@ -186,6 +186,34 @@ def load_synthetic_idloss(module, seed=0):
     return module
 
 
+def discriminator_opt(D_init_size=256, channel_multiplier=2, **over):
+    """The model options `e3dge_amd.discriminator.Discriminator` reads (scripts/train/ffhq/stage2.2.sh: --D_init_size 256)."""
+    o = AttrDict(D_init_size=D_init_size, D_input_size=3, channel_multiplier=channel_multiplier)
+    o.update(over)
+    return o
+
+
+def load_synthetic_discriminator(module, seed=0, variant=None):
+    """Deterministic weights for an `e3dge_amd.discriminator.Discriminator` (or the reference's: the keys are the same) in the reference's
+    initialisation ranges: EqualConv2d / EqualLinear weights N(0, 1) (stylesdf_model.py:179-181, :221).  The reference initialises every
+    bias to zero, which would hide a bias-indexing error, so biases are 0.1 N(0, 1).  variant='stress': weights x 3 and biases N(0, 1):
+    every layer's gain is 3, so magnitudes grow with depth and the biases no longer dominate any layer.  Blur kernels are deterministic buffers and stay."""
+    if variant not in (None, 'stress'):
+        raise ValueError(f"variant={variant!r}: None or 'stress'")
+    sd = {}
+    for k, v in module.state_dict().items():
+        if k.endswith('.kernel'):
+            continue
+        t = torch.from_numpy(np.asarray(_rs('discriminator.' + k, seed).standard_normal(tuple(v.shape)), dtype=np.float32))
+        if k.endswith('.weight'):
+            sd[k] = t * 3.0 if variant == 'stress' else t
+        else:
+            sd[k] = t if variant == 'stress' else 0.1 * t
+    missing, unexpected = module.load_state_dict(sd, strict=False)
+    assert not unexpected and all(m.endswith('.kernel') for m in missing), (missing, unexpected)
+    return module
+
+
 STRESS_VARIANTS = {          # name: (SIREN hidden-weight factor, gamma-mapping weight factor, std of the W+ codes)
     "wide": (1.0, 1.0, 1.0),    # unit-variance styles: FiLM frequencies 13.5 .. 48 instead of 27.7 .. 32.3
     "s2": (2.0, 3.0, 0.3),      # per-layer gain 2: fp32 rounding amplified ~300x over the init-range fixtures, still well defined

@@ -1174,6 +1174,85 @@ int64_t e3dge_shape_loss_partial_floats(const E3dgeShapeLossArgs* args);
 int e3dge_shape_loss_fwd(const E3dgeShapeLossArgs* args, e3dge_stream_t stream);
 int e3dge_shape_loss_bwd(const E3dgeShapeLossArgs* args, e3dge_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * StyleGAN2 discriminator with frozen weights (csrc/disc.hip, csrc/disc_bwd.h): the logits and their gradient with respect
+ * to the input images -- the adversarial term of the stage-2.2 encoder step.  Additions to ABI 16.  No allocation, no
+ * synchronisation, no atomics: results are bit-identical from run to run, and everything up to the minibatch-stddev channel
+ * does not depend on the batch an image is in.  Replaces Discriminator.forward (project/models/stylesdf_model.py:1541-1617)
+ * and its autograd for a frozen network.  A network is named by (init_size, channel_multiplier, in_channels): init_size a power
+ * of two in 8..1024, channel_multiplier 1..4, in_channels 1..16 (D_input_size).
+ *
+ * e3dge_disc_packed_floats   floats of the packed image (-1: no such network): per convolution `weight * scale` (rounded once, as
+ *                            EqualConv2d rounds it on every call) in MFMA A-fragment order and once more transposed with flipped taps
+ *                            for the data gradient, the biases, both EqualLinear matrices scaled, the blur FIR and its flip.
+ * e3dge_disc_pack_weights    src: HOST struct of device pointers (blocks beyond the network's are not read).  Re-run after a weight
+ *                            update.
+ * e3dge_disc_ws_bytes        workspace bytes of a forward (backward = 0) or a backward (backward != 0) of n images of
+ *                            height x width (-1: bad sizes, or a batch the reference's minibatch-stddev reshape rejects).
+ *                            height = width = init_size, or, for init_size 256, 256 f with f in {2, 4, 8, 16} (pool_256).
+ * e3dge_disc_saved_bytes     bytes of the state the saving forward keeps for n images: the output of every lrelu and the last
+ *                            block's output.
+ * e3dge_disc_forward         images (n, in_channels, height, width) fp32 contiguous -> logits (n, 1).  taps[t] NULL or: t <
+ *                            E3DGE_DISC_MAX_BLOCKS the output of ResBlock t, E3DGE_DISC_TAP_STDDEV the n / group stddev scalars,
+ *                            E3DGE_DISC_TAP_FINAL final_conv's output (n, 512, 4, 4), E3DGE_DISC_TAP_STEM unused.  saved != NULL:
+ *                            the state-saving forward, the same launches with the activations written to `saved` (bit-identical
+ *                            logits and taps).  Fails with the field named: "null", "n=", "height", "init_size", "workspace", "saved".
+ * e3dge_disc_backward        saved: what e3dge_disc_forward left for the same n, sizes and network.  grad_logits (n, 1) ->
+ *                            grad_images (n, in_channels, height, width), every element written.  gstage[t] NULL or the gradient
+ *                            at tap t (E3DGE_DISC_TAP_STEM: at the stem's output; E3DGE_DISC_TAP_STDDEV unused).
+ * e3dge_disc_conv            debug entry: one convolution of the family.  in (n, cin, height, width), w (cout, cin, ksize, ksize)
+ *                            -> out (n, cout, OH, OW): stride 1 pads ksize / 2 (OH = height), stride 2 pads nothing (OH = (height -
+ *                            ksize) / 2 + 1).  v = conv(in, fl(w * scale)) [+ bias[c]] [lrelu 0.2, * sqrt 2 when act]
+ *                            [+ addend, / sqrt 2 when merge].  wfrag: scratch of ceil16(cout) * ceil32(cin ksize^2) floats.
+ * e3dge_disc_conv_dgrad      debug entry: its data gradient.  g (n, cout, OH, OW) -> out (n, cin, height, width) = conv^T(g m)
+ *                            [+ addend], m = s_pos where sign > 0 else s_neg (sign NULL: m = s_pos), sign shaped like g.
+ *                            wfrag_t: scratch of ceil16(cin) * ceil32(cout ksize^2) floats.
+ * e3dge_disc_stddev          debug entry: feat (n, channels, hw) -> cat (n, channels + 1, hw) with the minibatch-stddev channel;
+ *                            scalars NULL or (n / group,).
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_DISC_MAX_BLOCKS 8
+#define E3DGE_DISC_TAP_STDDEV 8
+#define E3DGE_DISC_TAP_FINAL 9
+#define E3DGE_DISC_TAP_STEM 10
+#define E3DGE_DISC_TAPS 11
+typedef struct E3dgeDiscPackSrc {
+    int32_t init_size, channel_multiplier, in_channels, reserved;
+    const float* stem_w; const float* stem_b;                              /* convs.0.0.weight, convs.0.1.bias */
+    const float* conv1_w[E3DGE_DISC_MAX_BLOCKS]; const float* conv1_b[E3DGE_DISC_MAX_BLOCKS];
+    const float* conv2_w[E3DGE_DISC_MAX_BLOCKS]; const float* conv2_b[E3DGE_DISC_MAX_BLOCKS];
+    const float* skip_w[E3DGE_DISC_MAX_BLOCKS];
+    const float* final_w; const float* final_b;
+    const float* lin1_w; const float* lin1_b; const float* lin2_w; const float* lin2_b;
+    const float* blur;                                                     /* the 4 x 4 Blur.kernel */
+} E3dgeDiscPackSrc;
+typedef struct E3dgeDiscArgs {
+    const float* packed; const float* images;
+    int32_t n, height, width, init_size, channel_multiplier, in_channels;
+    float* logits;
+    float* taps[E3DGE_DISC_TAPS];
+    void* ws; int64_t ws_bytes;
+    void* saved; int64_t saved_bytes;
+} E3dgeDiscArgs;
+typedef struct E3dgeDiscBwdArgs {
+    const float* packed; const void* saved; int64_t saved_bytes;
+    int32_t n, height, width, init_size, channel_multiplier, in_channels;
+    const float* grad_logits; float* grad_images;
+    float* gstage[E3DGE_DISC_TAPS];
+    void* ws; int64_t ws_bytes;
+} E3dgeDiscBwdArgs;
+int64_t e3dge_disc_packed_floats(int init_size, int channel_multiplier, int in_channels);
+int e3dge_disc_pack_weights(float* packed, const E3dgeDiscPackSrc* src, e3dge_stream_t stream);
+int64_t e3dge_disc_ws_bytes(int n, int height, int width, int init_size, int channel_multiplier, int in_channels, int backward);
+int64_t e3dge_disc_saved_bytes(int n, int init_size, int channel_multiplier, int in_channels);
+int e3dge_disc_forward(const E3dgeDiscArgs* args, e3dge_stream_t stream);
+int e3dge_disc_backward(const E3dgeDiscBwdArgs* args, e3dge_stream_t stream);
+int e3dge_disc_conv(float* out, const float* in, const float* w, float* wfrag, const float* bias, const float* addend, int n, int cin, int cout,
+                    int height, int width, int ksize, int stride, int act, int merge, float scale, e3dge_stream_t stream);
+int e3dge_disc_conv_dgrad(float* out, const float* g, const float* w, float* wfrag_t, const float* sign, float s_pos, float s_neg,
+                          const float* addend, int n, int cin, int cout, int height, int width, int ksize, int stride, float scale,
+                          e3dge_stream_t stream);
+int e3dge_disc_stddev(float* cat, float* scalars, const float* feat, int n, int channels, int hw, e3dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

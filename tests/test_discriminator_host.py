@@ -1,0 +1,302 @@
+"""StyleGAN2 discriminator, host side: the C-ABI additions of csrc/disc.hip / disc_bwd.h (symbols, struct layouts, refusals before any
+launch), the state-dict surface, the path selection of e3dge_amd.discriminator.Discriminator, and its torch composition on the CPU
+against the recording of the reference (tests/golden/discriminator.npz, tools/gen_golden_discriminator.py).
+
+The CPU path is the reference's torch operations in the reference's order under oracle.cpu_numerics, so on the host that made the
+recording every recorded tensor -- logits, taps, losses and the input gradient -- is reproduced bit for bit, and the test asserts that.
+
+Measured on a second x86-64 host (another CPU model, the same torch build, the same 8 threads, MKL_CBWR=COMPATIBLE and
+ATEN_CPU_CAPABILITY=default in force), test_cpu_path_reproduces_the_recording_bit_for_bit does NOT hold for 8 of its 14 cases, and
+the reference's own modules would miss there in the same way, since the composition is theirs operation for operation:
+  * every tap, the stddev scalars, the logits and both losses are bit-identical in 13 of 14 cases; in d16c1b4s16 (init weights) the stddev
+    scalar is 1 ulp off, final_conv's samples 2 ulp, the logits 8 ulp;
+  * the input gradient of g_nonsaturating_loss is bit-identical in 6 of 14 cases and otherwise off by 3e-7 to 7.5e-7 of its largest
+    element (26 to 5024 ulp of the element concerned, the small elements being the worst).
+Which library routine depends on the host was not established: a single-threaded run on the recording host changes only the B = 1
+gradients, so the thread count alone does not explain it.  Neither the 2-ulp allowance nor any bound derived from the formats covers
+the gradient figures, so the assertions stay as they are: bit for bit."""
+import ctypes
+import functools
+import json
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, REPO, load_golden
+
+import e3dge_amd  # noqa: F401
+from e3dge_amd import _lib, build, discriminator as disc, losses, synthetic as syn
+from e3dge_amd.discriminator import Discriminator
+from test_idloss_host import make_pair, tap_samples
+
+INVALID = -1                                                        # E3DGE_ERR_INVALID_ARG
+NEW_SYMBOLS = ["e3dge_disc_packed_floats", "e3dge_disc_pack_weights", "e3dge_disc_ws_bytes", "e3dge_disc_saved_bytes", "e3dge_disc_forward",
+               "e3dge_disc_backward", "e3dge_disc_conv", "e3dge_disc_conv_dgrad", "e3dge_disc_stddev"]
+# (D_init_size, channel_multiplier, batch, image size) of the recording
+CASES = [(16, 1, b, 16) for b in (1, 2, 4, 6, 8)] + [(256, 1, 2, 256), (256, 1, 2, 1024)]
+VARIANTS = (None, 'stress')
+TAP_NAMES = {disc.TAP_STDDEV: "stddev", disc.TAP_FINAL: "final"}
+
+
+def case_id(case, variant=None):
+    return "d{}c{}b{}s{}".format(*case) + ("" if variant is None else "_" + variant)
+
+
+def golden_images(n, size):
+    """The images of the recording: a formula, never stored (tanh of box-filtered noise with fresh noise on top, in [-1, 1])."""
+    return make_pair((n, 3, size, size), seed=2000 + size + n)[0]
+
+
+def tap_name(t):
+    return TAP_NAMES.get(t, f"block{t}")
+
+
+@functools.lru_cache(maxsize=None)
+def module_cpu(init, cm, variant=None):
+    m = syn.load_synthetic_discriminator(Discriminator(syn.discriminator_opt(init, cm)), variant=variant)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    return m
+
+
+def torch_taps(m, x):
+    """(logits, {tap index: tensor}) of the torch composition."""
+    tl = []
+    logits = m.forward_torch(x, taps=tl)
+    n_blocks = len(m.convs) - 1
+    taps = {i: t for i, t in enumerate(tl[:n_blocks])}
+    taps[disc.TAP_STDDEV], taps[disc.TAP_FINAL] = tl[n_blocks], tl[n_blocks + 1]
+    return logits, taps
+
+
+# ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
+def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
+    for name in NEW_SYMBOLS:
+        assert name in _lib.SIGNATURES and hasattr(lib, name)
+    assert lib.e3dge_abi_version() == 16 == _lib.ABI_VERSION
+    assert "disc.hip" in build.SOURCES
+    for init, cm in [(256, 2), (16, 1), (1024, 2)]:
+        m = Discriminator(syn.discriminator_opt(init, cm))
+        n_params = sum(p.numel() for p in m.parameters())
+        conv = sum(p.numel() for p in m.parameters() if p.ndim == 4)
+        # every conv weight twice (forward and transposed images, K and M padded), everything else once
+        floats = lib.e3dge_disc_packed_floats(init, cm, 3)
+        assert n_params + conv <= floats <= 1.02 * (n_params + conv) + 64 * 120, (init, cm, floats, n_params, conv)
+        lrelu_outputs = sum(int(np.prod(s)) for _, _, s in m.saved_layout(2))
+        assert m.saved_layout(2)[-1][1] + 2 * 512 <= lib.e3dge_disc_saved_bytes(2, init, cm, 3) // 4 <= lrelu_outputs + 64 * 40
+    assert lib.e3dge_disc_packed_floats(24, 1, 3) == -1 and lib.e3dge_disc_packed_floats(256, 0, 3) == -1
+    assert lib.e3dge_disc_ws_bytes(4, 1024, 1024, 256, 2, 3, 0) > 4 * 4 * 128 * 256 * 256
+    assert lib.e3dge_disc_ws_bytes(4, 1024, 1024, 256, 2, 3, 1) > 4 * 4 * 128 * 256 * 256
+    assert lib.e3dge_disc_ws_bytes(4, 300, 300, 256, 2, 3, 0) == -1 and b"height" in lib.e3dge_last_error()
+    assert lib.e3dge_disc_ws_bytes(4, 32, 32, 16, 1, 3, 0) == -1                     # pool_256 exists for init_size 256 only
+    assert lib.e3dge_disc_ws_bytes(5, 16, 16, 16, 1, 3, 0) == -1 and b"n=5" in lib.e3dge_last_error()
+    assert lib.e3dge_disc_saved_bytes(0, 16, 1, 3) == -1 and lib.e3dge_disc_saved_bytes(7, 16, 1, 3) == -1
+
+
+@pytest.mark.parametrize("struct,mirror,names", [
+    ("E3dgeDiscPackSrc", "DiscPackSrc", ["init_size", "channel_multiplier", "in_channels", "stem_w", "stem_b", "conv1_w", "conv1_b", "conv2_w",
+                                         "conv2_b", "skip_w", "final_w", "final_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "blur"]),
+    ("E3dgeDiscArgs", "DiscArgs", ["packed", "images", "n", "height", "width", "init_size", "channel_multiplier", "in_channels", "logits", "taps",
+                                   "ws", "ws_bytes", "saved", "saved_bytes"]),
+    ("E3dgeDiscBwdArgs", "DiscBwdArgs", ["packed", "saved", "saved_bytes", "n", "height", "width", "init_size", "channel_multiplier", "in_channels",
+                                         "grad_logits", "grad_images", "gstage", "ws", "ws_bytes"])])
+def test_struct_layouts_match_c(struct, mirror, names):
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "e3dge_hip.h"\nint main(void) {\n  printf("%zu", sizeof(' + struct + '));\n' + \
+          "".join(f'  printf(" %zu", offsetof({struct}, {n}));\n' for n in names) + \
+          '  printf(" %d %d %d %d %d", E3DGE_DISC_MAX_BLOCKS, E3DGE_DISC_TAP_STDDEV, E3DGE_DISC_TAP_FINAL, E3DGE_DISC_TAP_STEM, E3DGE_DISC_TAPS);\n' + \
+          "  return 0; }\n"
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c")
+        open(c, "w").write(src)
+        exe = os.path.join(d, "t")
+        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
+        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    A = getattr(_lib, mirror)
+    assert got[:-5] == [ctypes.sizeof(A)] + [getattr(A, n).offset for n in names]
+    assert got[-5:] == [_lib.DISC_MAX_BLOCKS, _lib.DISC_TAP_STDDEV, _lib.DISC_TAP_FINAL, _lib.DISC_TAP_STEM, _lib.DISC_TAPS]
+
+
+def test_bad_arguments_are_refused_before_any_launch(lib):
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.addressof(buf)                                        # never followed
+    err = lib.e3dge_last_error
+
+    def fwd_args():
+        a = _lib.DiscArgs()
+        a.packed = a.images = a.logits = a.ws = p
+        a.n, a.height, a.width, a.init_size, a.channel_multiplier, a.in_channels = 2, 1024, 1024, 256, 2, 3
+        a.ws_bytes = a.saved_bytes = 1 << 42
+        return a
+
+    fwd = lambda a: lib.e3dge_disc_forward(ctypes.byref(a), None)
+    for field, value, word in [("packed", None, b"null"), ("images", None, b"null"), ("logits", None, b"null"), ("ws", None, b"null"),
+                               ("n", 0, b"n=0"), ("n", 5, b"n=5"), ("n", 7, b"n=7"), ("height", 512, b"height"), ("width", 300, b"width"),
+                               ("init_size", 48, b"init_size"), ("channel_multiplier", 0, b"channel_multiplier"), ("in_channels", 0, b"in_channels"),
+                               ("ws_bytes", lib.e3dge_disc_ws_bytes(2, 1024, 1024, 256, 2, 3, 0) - 1, b"workspace")]:
+        a = fwd_args()
+        setattr(a, field, value)
+        assert fwd(a) == INVALID, field
+        assert word in err(), (field, err())
+    a = fwd_args()
+    a.saved, a.saved_bytes = p, lib.e3dge_disc_saved_bytes(2, 256, 2, 3) - 1
+    assert fwd(a) == INVALID and b"saved" in err()
+    assert lib.e3dge_disc_forward(None, None) == INVALID
+
+    def bwd_args():
+        a = _lib.DiscBwdArgs()
+        a.packed = a.saved = a.grad_logits = a.grad_images = a.ws = p
+        a.n, a.height, a.width, a.init_size, a.channel_multiplier, a.in_channels = 2, 256, 256, 256, 1, 3
+        a.ws_bytes = a.saved_bytes = 1 << 42
+        return a
+
+    bwd = lambda a: lib.e3dge_disc_backward(ctypes.byref(a), None)
+    for field, value, word in [("packed", None, b"null"), ("saved", None, b"null"), ("grad_logits", None, b"null"), ("grad_images", None, b"null"),
+                               ("ws", None, b"null"), ("n", 0, b"n=0"), ("n", 5, b"n=5"), ("height", 0, b"height"), ("init_size", 7, b"init_size"),
+                               ("saved_bytes", lib.e3dge_disc_saved_bytes(2, 256, 1, 3) - 1, b"saved"),
+                               ("ws_bytes", lib.e3dge_disc_ws_bytes(2, 256, 256, 256, 1, 3, 1) - 1, b"workspace")]:
+        a = bwd_args()
+        setattr(a, field, value)
+        assert bwd(a) == INVALID, field
+        assert word in err(), (field, err())
+    assert lib.e3dge_disc_backward(None, None) == INVALID
+
+    src = _lib.DiscPackSrc(init_size=16, channel_multiplier=1, in_channels=3)
+    assert lib.e3dge_disc_pack_weights(p, None, None) == INVALID and lib.e3dge_disc_pack_weights(None, ctypes.addressof(src), None) == INVALID
+    assert lib.e3dge_disc_pack_weights(p, ctypes.addressof(src), None) == INVALID and b"stem" in err()
+    for n in ("stem_w", "stem_b", "final_w", "final_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "blur"):
+        setattr(src, n, p)
+    for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "skip_w"):
+        getattr(src, n)[0] = p
+    assert lib.e3dge_disc_pack_weights(p, ctypes.addressof(src), None) == INVALID and b"block 1" in err()    # 16 -> 8 -> 4: two blocks
+    src.init_size = 20
+    assert lib.e3dge_disc_pack_weights(p, ctypes.addressof(src), None) == INVALID and b"init_size" in err()
+
+    conv = lambda *sizes, out=p, addend=None, merge=0: lib.e3dge_disc_conv(out, p, p, p, None, addend, *sizes, 1, merge, 1.0, None)
+    assert conv(1, 3, 64, 9, 11, 3, 1, out=None) == INVALID and b"null" in err()
+    assert conv(1, 3, 64, 9, 11, 3, 1, merge=1) == INVALID and b"merge" in err()
+    dgrad = lambda *sizes, out=p: lib.e3dge_disc_conv_dgrad(out, p, p, p, None, 1.0, 1.0, None, *sizes, 1.0, None)
+    assert dgrad(1, 3, 64, 9, 11, 3, 1, out=None) == INVALID and b"null" in err()
+    for sizes in [(0, 3, 64, 9, 11, 3, 1), (1, 0, 64, 9, 11, 3, 1), (1, 3, 0, 9, 11, 3, 1), (1, 3, 64, 2, 11, 3, 1), (1, 3, 64, 9, 11, 5, 1),
+                  (1, 3, 64, 9, 11, 3, 3)]:
+        assert conv(*sizes) == INVALID and dgrad(*sizes) == INVALID, sizes
+    assert lib.e3dge_disc_stddev(None, None, p, 4, 512, 16, None) == INVALID and b"null" in err()
+    assert lib.e3dge_disc_stddev(p, None, p, 5, 512, 16, None) == INVALID and b"n=5" in err()
+    assert lib.e3dge_disc_stddev(p, None, p, 4, 0, 16, None) == INVALID and b"channels" in err()
+
+
+# ---- the module -------------------------------------------------------------------------------------------------------------------
+def test_state_dict_keys_are_the_reference_ones_and_a_strict_load_works():
+    recorded = json.load(open(os.path.join(GOLDEN, "discriminator_state_dict_keys.json")))
+    for name, (init, cm) in {"256x2": (256, 2), "16x1": (16, 1)}.items():
+        m = Discriminator(syn.discriminator_opt(init, cm))
+        sd = m.state_dict()
+        assert sorted(sd) == recorded[name]["keys"]
+        assert {k: list(v.shape) for k, v in sd.items()} == recorded[name]["shapes"]
+        assert sum(k.endswith(".kernel") for k in sd) == 2 * (len(m.convs) - 1)
+        other = Discriminator(syn.discriminator_opt(init, cm))
+        other.load_state_dict({k: v.clone() for k, v in sd.items()}, strict=True)    # Blur.kernel buffers included
+    m = Discriminator(None)                                          # the reference's option defaults
+    assert (m.init_size, m.input_size, m.channel_multiplier) == (1024, 3, 2) and len(m.convs) == 9
+    assert "VolumeRenderDiscriminator" in disc.__doc__ and "StyleGANEncoder" in disc.__doc__ and "DEncoder" in disc.__doc__
+
+
+@pytest.mark.parametrize("variant", VARIANTS, ids=["init", "stress"])
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_cpu_path_reproduces_the_recording_bit_for_bit(case, variant):
+    init, cm, B, size = case
+    gold, key = load_golden("discriminator"), case_id(case, variant) + "/"
+    m = module_cpu(init, cm, variant)
+    x = golden_images(B, size).requires_grad_(True)
+    logits, taps = torch_taps(m, x)
+    assert logits.shape == (B, 1) and logits.dtype == torch.float32
+    assert np.array_equal(logits.detach().numpy(), gold[key + "logits"])
+    for t, v in taps.items():
+        v = v.detach()
+        assert np.array_equal(v.reshape(-1)[tap_samples(v.numel())].numpy(), gold[key + "tap_" + tap_name(t)]), tap_name(t)
+        assert float(v.double().sum()) == float(gold[key + "sum_" + tap_name(t)]), tap_name(t)
+    g_loss = losses.g_nonsaturating_loss(logits)
+    assert np.array_equal(g_loss.detach().numpy(), gold[key + "g_nonsaturating_loss"])
+    d_loss = losses.d_logistic_loss(logits.detach().flip(0), logits.detach())
+    assert np.array_equal(d_loss.numpy(), gold[key + "d_logistic_loss"])
+    g_loss.backward()
+    assert np.array_equal(x.grad.reshape(-1)[tap_samples(x.numel())].numpy(), gold[key + "grad"])
+    assert float(x.grad.double().sum()) == float(gold[key + "grad_sum"])
+    if not (variant == 'stress' and init == 256):                    # (logits of order 1e6: softplus' derivative is exactly 0 there)
+        assert float(x.grad.abs().max()) > 0
+
+
+def test_path_selection(monkeypatch):
+    m = module_cpu(16, 1)
+    x = golden_images(2, 16)
+    assert not m.uses_hip(x)                                         # a CPU input
+    assert not m.uses_hip(x.double())
+    monkeypatch.delenv("E3DGE_DISCRIMINATOR", raising=False)
+    assert disc.backend() == "hip"
+
+    class FakeCuda:                                                  # what uses_hip reads of a GPU tensor
+        def __init__(self, shape, dtype=torch.float32):
+            self.shape, self.dtype, self.ndim, self.device = shape, dtype, len(shape), torch.device("cuda", 0)
+
+    gpu = FakeCuda((2, 3, 16, 16))
+    assert m.uses_hip(gpu)
+    assert not m.uses_hip(FakeCuda((2, 3, 16, 16), torch.float64)) and not m.uses_hip(FakeCuda((2, 3, 16, 16), torch.float16))
+    assert not m.uses_hip(FakeCuda((2, 3, 32, 32)))                  # no pool_256 for init_size 16
+    assert not m.uses_hip(FakeCuda((2, 4, 16, 16)))
+    big = module_cpu(256, 1)
+    assert big.uses_hip(FakeCuda((2, 3, 256, 256))) and big.uses_hip(FakeCuda((2, 3, 1024, 1024)))
+    assert not big.uses_hip(FakeCuda((2, 3, 300, 300)))              # a non-integer pool ratio: the torch path
+    monkeypatch.setenv("E3DGE_DISCRIMINATOR", "torch")
+    assert not m.uses_hip(gpu)
+    monkeypatch.setenv("E3DGE_DISCRIMINATOR", "eager")
+    with pytest.raises(ValueError, match="E3DGE_DISCRIMINATOR"):
+        m.uses_hip(gpu)
+    monkeypatch.delenv("E3DGE_DISCRIMINATOR")
+    trainable = syn.load_synthetic_discriminator(Discriminator(syn.discriminator_opt(16, 1)))
+    assert all(p.requires_grad for p in trainable.parameters()) and not trainable.uses_hip(gpu)
+    for p in trainable.parameters():
+        p.requires_grad_(False)
+    assert trainable.uses_hip(gpu)
+    trainable.final_linear[1].bias.requires_grad_(True)              # one trainable parameter is enough
+    assert not trainable.uses_hip(gpu)
+
+
+def test_trainable_cpu_module_gives_parameter_gradients_and_an_r1_penalty():
+    m = syn.load_synthetic_discriminator(Discriminator(syn.discriminator_opt(16, 1)))
+    real = golden_images(2, 16).requires_grad_(True)
+    pred = m(real)
+    r1 = losses.d_r1_loss(pred, real)
+    (losses.d_logistic_loss(pred, m(golden_images(2, 16).flip(0))) + 5.0 * r1).backward()
+    assert float(r1.detach()) > 0 and all(p.grad is not None and float(p.grad.abs().max()) > 0 for p in m.parameters())
+
+
+def test_double_backward_through_the_frozen_gpu_node_is_refused(monkeypatch):
+    """On the Function itself, without a device: its launches are replaced by CPU stand-ins of the right shapes."""
+    m = module_cpu(16, 1)
+    monkeypatch.setattr(m, "_launch_forward", lambda x, taps=False, save=False: (x.detach().sum((1, 2, 3)).reshape(-1, 1) * 1.0, None, torch.zeros(4)))
+    monkeypatch.setattr(m, "_launch_backward", lambda saved, shape, g, stages=False: (g.reshape(-1, 1, 1, 1).expand(shape).contiguous(), None))
+    try:
+        x = golden_images(2, 16).requires_grad_(True)
+        out = disc._DiscriminatorFunction.apply(m, x)
+        assert out.shape == (2, 1) and out.requires_grad
+        first, = torch.autograd.grad((out ** 2).sum(), x, create_graph=True)           # the upstream 2 * out carries a graph
+        assert torch.equal(first.detach(), (2 * out.detach()).reshape(2, 1, 1, 1).expand_as(x)) and first.requires_grad
+        with pytest.raises(RuntimeError, match="once_differentiable|differentiated twice|only once"):
+            first.sum().backward()
+        y = golden_images(2, 16)                                     # an input that wants no gradient: nothing to return
+        assert not disc._DiscriminatorFunction.apply(m, y).requires_grad
+    finally:
+        monkeypatch.undo()
+
+
+@pytest.mark.parametrize("batch", [5, 7])
+def test_a_batch_the_stddev_reshape_rejects_raises(batch):
+    m = module_cpu(16, 1)
+    with pytest.raises(ValueError, match="minibatch-stddev"):
+        m(golden_images(batch, 16))
+    with pytest.raises(ValueError, match="minibatch-stddev"):
+        disc.stddev_group(batch)
+    assert [disc.stddev_group(b) for b in (1, 2, 3, 4, 6, 8, 9, 10)] == [1, 2, 3, 4, 3, 4, 3, 2]
