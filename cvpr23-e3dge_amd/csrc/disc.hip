@@ -10,16 +10,15 @@
 //   lrelu(v) = (v > 0 ? v : 0.2 v) * sqrt 2   (FusedLeakyReLU)
 //
 // Kernels:
-//   gemm_kernel    idnet_conv_kernel's implicit GEMM on v_mfma_f32_16x16x4_f32 (M = output channels, K = (ci, r, s) in tiles of 32 staged
-//                  in LDS with the next tile's loads in flight, weights from a packed A-fragment image that already carries EqualConv2d's
-//                  scale, N = the output pixels of ONE image per workgroup column).  Four fp32 accumulators (the groups of four k, modulo
-//                  4) run in ascending k and are folded every 128 k into an fp64 total, (0 + 1) + (2 + 3), which is rounded to fp32 once:
-//                  chains of eight matrix steps, so a K = 4608 sum is about as accurate as a blocked library GEMM's instead of carrying
-//                  288 sequential roundings.  The tile width depends on the layer alone, and tiles never straddle images, so an image's
-//                  convolution outputs do not depend on the batch.  Three gather modes: stride 1 with padding, stride 2 without (on a
-//                  blurred plane), and the transposed stride 2 of the backward.  Epilogue: optional bias and lrelu, optional addend,
-//                  merged as (v + addend) / sqrt 2 or added.  Staging: an optional factor chosen by the sign of a second tensor (the
-//                  backward's lrelu derivative from the saved activations).
+//   gemm_kernel    the implicit GEMM of conv_igemm.h (M = output channels, K = (ci, r, s), N = the output pixels of ONE image per workgroup
+//                  column; waves past M idle) on a packed A-fragment image that already carries EqualConv2d's scale.  Four fp32
+//                  accumulators (the groups of four k, modulo 4) run in ascending k and are folded every 128 k into an fp64 total,
+//                  (0 + 1) + (2 + 3), which is rounded to fp32 once: chains of eight matrix steps, so a K = 4608 sum is about as accurate
+//                  as a blocked library GEMM's instead of carrying 288 sequential roundings.  The tile width depends on the layer alone,
+//                  and tiles never straddle images, so an image's convolution outputs do not depend on the batch.  Gather, three modes:
+//                  stride 1 with padding, stride 2 without (on a blurred plane), and the transposed stride 2 of the backward; an optional
+//                  factor chosen by the sign of a second tensor (the backward's lrelu derivative from the saved activations).  Epilogue:
+//                  optional bias and lrelu, optional addend, merged as (v + addend) / sqrt 2 or added.
 //   blur           e3dge_upfirdn2d (csrc/upfirdn2d.hip): every blurred value is rounded to fp32 as the reference's separate op rounds it.
 //   stddev_kernel  one workgroup per sub-batch: per element the group's mean and variance (two passes), sqrt(var + 1e-8) in fp32, summed in
 //                  fp64 per thread in ascending order, then a fixed tree; writes the concatenated (C + 1)-channel tensor.
@@ -29,22 +28,14 @@
 // The state-saving forward is the same launches writing the activations into the caller's `saved` buffer instead of the workspace, so
 // its logits are bit-identical.  No atomics, no allocation, no synchronisation.  The backward is disc_bwd.h.
 // Measured times: DESIGN.md 4.11g.
-#include "common.h"
+#include "conv_igemm.h"
 
 namespace e3dge {
 
-typedef float dc_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kDcKC = 32;                       // k per staged tile (8 MFMA steps)
-constexpr int kDcBM = 64;                       // channels per workgroup (4 waves x 16)
 constexpr int kDcFlush = 4;                     // k tiles between two folds of the fp32 accumulators into the fp64 totals (a power of two)
-constexpr int kDcCUs = 256;
 constexpr int kDcMaxBlocks = E3DGE_DISC_MAX_BLOCKS;
 constexpr int kDcHeadK = 512 * 16, kDcHid = 512, kDcHeadRows = 2, kDcHeadImgs = 4;
 constexpr float kDcSqrt2 = 1.41421356237309515f, kDcSlope = 0.2f;
-
-static int dc_kpad(int cin, int ks) { return (cin * ks * ks + kDcKC - 1) / kDcKC * kDcKC; }
-static int dc_mpad(int M) { return (M + 15) / 16 * 16; }
 
 // ---- network description --------------------------------------------------------------------------------------------------------
 struct DcNet {
@@ -88,8 +79,8 @@ struct DcLayout {
 static void dc_layout(const DcNet& n, DcLayout* l) {
     int64_t off = 0;
     auto take = [&](int64_t floats) { const int64_t at = off; off += (floats + 63) / 64 * 64; return at; };
-    auto fw = [&](int ci, int co, int ks) { return take((int64_t)dc_mpad(co) * dc_kpad(ci, ks)); };
-    auto tw = [&](int ci, int co, int ks) { return take((int64_t)dc_mpad(ci) * dc_kpad(co, ks)); };
+    auto fw = [&](int ci, int co, int ks) { return take((int64_t)ig_mpad(co) * ig_kpad(ci * ks * ks)); };
+    auto tw = [&](int ci, int co, int ks) { return take((int64_t)ig_mpad(ci) * ig_kpad(co * ks * ks)); };
     l->stem_w = fw(n.cin, n.c[0], 1); l->stem_wt = tw(n.cin, n.c[0], 1); l->stem_b = take(n.c[0]);
     for (int i = 0; i < n.n_blocks; ++i) {
         const int ci = n.c[i], co = n.c[i + 1];
@@ -105,36 +96,8 @@ static void dc_layout(const DcNet& n, DcLayout* l) {
 }
 
 // ---- packing ----------------------------------------------------------------------------------------------------------------------
-// dst[(mt * KS4 + ks) * 64 + lane] = fl(W[mt * 16 + (lane & 15)][ks * 4 + (lane >> 4)] * scale) (0 past M or K): the A operand of
-// v_mfma_f32_16x16x4_f32; the product is rounded once, as EqualConv2d's `weight * scale` is on every call.
-__global__ void __launch_bounds__(256) disc_pack_conv_kernel(float* __restrict__ dst, const float* __restrict__ w, int M, int K, int KS4, float scale,
-                                                             int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int lane = (int)(i & 63);
-    const int64_t t = i >> 6;
-    const int ks = (int)(t % KS4), mt = (int)(t / KS4);
-    const int row = mt * 16 + (lane & 15), k = ks * 4 + (lane >> 4);
-    dst[i] = (row < M && k < K) ? __fmul_rn(w[(int64_t)row * K + k], scale) : 0.0f;
-}
-
-// the transposed image: Wt[ci][(co, r, s)] = fl(W[co][ci][ks - 1 - r][ks - 1 - s] * scale)
-__global__ void __launch_bounds__(256) disc_pack_conv_t_kernel(float* __restrict__ dst, const float* __restrict__ w, int Cin, int Cout, int KS, int KS4,
-                                                               float scale, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int lane = (int)(i & 63), KK = KS * KS;
-    const int64_t t = i >> 6;
-    const int ks = (int)(t % KS4), mt = (int)(t / KS4);
-    const int ci = mt * 16 + (lane & 15), k = ks * 4 + (lane >> 4);
-    float v = 0.0f;
-    if (ci < Cin && k < Cout * KK) {
-        const int co = k / KK, rs = k - co * KK, r = rs / KS, s = rs - r * KS;
-        v = __fmul_rn(w[(((int64_t)co * Cin + ci) * KS + (KS - 1 - r)) * KS + (KS - 1 - s)], scale);
-    }
-    dst[i] = v;
-}
-
+// The A-fragment images come from conv_igemm.h's packers with EqualConv2d's scale: the product is rounded once, as `weight * scale` is on
+// every call of the reference.
 // dst[i] = fl(src[i] * scale); flip: dst[i] = src[total - 1 - i] (the FIR of the blur's adjoint)
 __global__ void __launch_bounds__(256) disc_pack_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, float scale, int flip, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -154,12 +117,9 @@ struct DcGemmArgs {
 // stride 2: tap (r, s) of output (oy, ox) exists where oy - pad + r and ox - pad + s are even, at half those coordinates.
 template <int KS_, int MODE, int NT>
 __global__ void __launch_bounds__(256) disc_gemm_kernel(DcGemmArgs a) {
-    constexpr int BN = 16 * NT, BNP = NT == 1 ? 16 : BN + 16;      // row pitch: the four k rows of one read land in four bank groups
-    constexpr int ROWS = 256 / BN, PER = kDcKC / ROWS;
-    constexpr int KK = KS_ * KS_;
-    __shared__ float bs[kDcKC * BNP];
+    constexpr int BN = IgTile<NT>::BN, ROWS = IgTile<NT>::ROWS, PER = IgTile<NT>::PER;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mt = blockIdx.y * (kDcBM / 16) + wave;
+    const int mt = blockIdx.y * (kIgBM / 16) + wave;
     const bool live = mt * 16 < a.M;                                // wave-uniform
     const int OHW = a.OH * a.OW, IH = a.IH, IW = a.IW, K = a.K;
     const int img = blockIdx.x / a.tiles, tile = blockIdx.x - img * a.tiles;
@@ -177,7 +137,7 @@ __global__ void __launch_bounds__(256) disc_gemm_kernel(DcGemmArgs a) {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int k = k0 + srow + i * ROWS;
-            const int ci = k / KK, rs = k - ci * KK, r = rs / KS_, s = rs - r * KS_;
+            const auto [ci, r, s] = ig_decode<KS_>(k);
             int iy = iy0 + r, ix = ix0 + s;
             bool ok = n_ok && k < K && iy >= 0 && ix >= 0;
             if (MODE == 2) { ok = ok && !((iy | ix) & 1); iy >>= 1; ix >>= 1; }
@@ -191,52 +151,25 @@ __global__ void __launch_bounds__(256) disc_gemm_kernel(DcGemmArgs a) {
             v[i] = x;
         }
     };
-    dc_f32x4 acc[NT][4];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int h = 0; h < 4; ++h) acc[t][h] = dc_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 acc[NT][4];
     double tot[NT][4];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) tot[t][r] = 0.0;
-    const float* __restrict__ wa = a.wfrag + (int64_t)(live ? mt : 0) * a.KS4 * 64 + lane;
-    const int n_tiles = a.KS4 / (kDcKC / 4);
-    float stage[PER];
-    fetch(0, stage);
-    for (int kt = 0; kt < n_tiles; ++kt) {
-        __syncthreads();                                            // the previous tile's reads are done
+    auto fold = [&](int kt, bool last) {
+        if ((kt & (kDcFlush - 1)) == kDcFlush - 1 || last) {        // every 128 k: fold the fp32 chains into the fp64 totals
 #pragma unroll
-        for (int i = 0; i < PER; ++i) bs[(srow + i * ROWS) * BNP + sn] = stage[i];
-        __syncthreads();
-        float af[kDcKC / 4];
-        if (live) {
+            for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int j = 0; j < kDcKC / 4; ++j) af[j] = wa[(int64_t)(kt * (kDcKC / 4) + j) * 64];
-        }
-        if (kt + 1 < n_tiles) fetch((kt + 1) * kDcKC, stage);      // in flight during the MFMAs
-        if (live) {
+                for (int r = 0; r < 4; ++r) {
+                    tot[t][r] += ((double)acc[t][0][r] + (double)acc[t][1][r]) + ((double)acc[t][2][r] + (double)acc[t][3][r]);
 #pragma unroll
-            for (int j = 0; j < kDcKC / 4; ++j) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const float b = bs[(j * 4 + (lane >> 4)) * BNP + t * 16 + (lane & 15)];
-                    acc[t][j & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b, acc[t][j & 3], 0, 0, 0);
+                    for (int h = 0; h < 4; ++h) acc[t][h][r] = 0.0f;
                 }
-            }
-            if ((kt & (kDcFlush - 1)) == kDcFlush - 1 || kt + 1 == n_tiles) {      // every 128 k: fold the fp32 chains into the fp64 totals
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        tot[t][r] += ((double)acc[t][0][r] + (double)acc[t][1][r]) + ((double)acc[t][2][r] + (double)acc[t][3][r]);
-#pragma unroll
-                        for (int h = 0; h < 4; ++h) acc[t][h][r] = 0.0f;
-                    }
-            }
         }
-    }
+    };
+    ig_k_loop<NT, 4, true>(acc, a.wfrag + (int64_t)(live ? mt : 0) * a.KS4 * 64 + lane, a.KS4 / (kIgKC / 4), live, fetch, fold);
     if (!live) return;
     // C/D fragment: lane l, register r holds D[4 (l >> 4) + r][l & 15]
     const int row0 = mt * 16 + 4 * (lane >> 4);
@@ -261,32 +194,21 @@ __global__ void __launch_bounds__(256) disc_gemm_kernel(DcGemmArgs a) {
     }
 }
 
-// pixels per workgroup / 16: the widest tile that still gives every CU a workgroup for two images, chosen from the layer alone
-static int dc_tile_width(int OHW, int M) {
-    const int64_t gy = (M + kDcBM - 1) / kDcBM;
-    auto blocks = [&](int bn) { return (int64_t)(OHW + bn - 1) / bn; };
-    return blocks(64) * 2 * gy >= kDcCUs ? 4 : blocks(32) * 2 * gy >= kDcCUs ? 2 : 1;
-}
-
 // mode: 0 stride 1 (pad given), 1 stride 2 forward, 2 transposed stride 2 (pad = ks - 1); a.Cin, IH, IW, M, OH, OW, pad are set
 static int dc_gemm(DcGemmArgs a, int n, int ks, int mode, hipStream_t st) {
-    a.K = a.Cin * ks * ks; a.KS4 = dc_kpad(a.Cin, ks) / 4;
-    const int OHW = a.OH * a.OW, gy = (a.M + kDcBM - 1) / kDcBM, nt = dc_tile_width(OHW, a.M), bn = 16 * nt;
+    a.K = a.Cin * ks * ks; a.KS4 = ig_kpad(a.K) / 4;
+    const int OHW = a.OH * a.OW, gy = (a.M + kIgBM - 1) / kIgBM, nt = ig_tile_width(OHW, 2, gy), bn = 16 * nt;   // two images counted, whatever n
     a.tiles = (OHW + bn - 1) / bn;
     const dim3 grid((unsigned)((int64_t)n * a.tiles), (unsigned)gy);
-#define E3DGE_DC_LAUNCH(KS_, MODE_)                                                                  \
-    do {                                                                                            \
-        if (nt == 4) disc_gemm_kernel<KS_, MODE_, 4><<<grid, dim3(256), 0, st>>>(a);                \
-        else if (nt == 2) disc_gemm_kernel<KS_, MODE_, 2><<<grid, dim3(256), 0, st>>>(a);           \
-        else disc_gemm_kernel<KS_, MODE_, 1><<<grid, dim3(256), 0, st>>>(a);                        \
-    } while (0)
-    if (ks == 3 && mode == 0) E3DGE_DC_LAUNCH(3, 0);
-    else if (ks == 3 && mode == 1) E3DGE_DC_LAUNCH(3, 1);
-    else if (ks == 3) E3DGE_DC_LAUNCH(3, 2);
-    else if (mode == 0) E3DGE_DC_LAUNCH(1, 0);
-    else if (mode == 1) E3DGE_DC_LAUNCH(1, 1);
-    else E3DGE_DC_LAUNCH(1, 2);
-#undef E3DGE_DC_LAUNCH
+    ig_dispatch_nt(nt, [&](auto nt_c) {
+        constexpr int NT = decltype(nt_c)::value;
+        if (ks == 3 && mode == 0) disc_gemm_kernel<3, 0, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (ks == 3 && mode == 1) disc_gemm_kernel<3, 1, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (ks == 3) disc_gemm_kernel<3, 2, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (mode == 0) disc_gemm_kernel<1, 0, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (mode == 1) disc_gemm_kernel<1, 1, NT><<<grid, dim3(256), 0, st>>>(a);
+        else disc_gemm_kernel<1, 2, NT><<<grid, dim3(256), 0, st>>>(a);
+    });
     return check_launch("disc(conv)");
 }
 
@@ -517,10 +439,8 @@ extern "C" int e3dge_disc_pack_weights(float* packed, const E3dgeDiscPackSrc* sr
     auto eq_scale = [](int fan_in) { return (float)(1.0 / sqrt((double)fan_in)); };
     auto conv = [&](int64_t fw, int64_t tw, const float* w, int ci, int co, int ks) {
         const float scale = eq_scale(ci * ks * ks);
-        const int K = ci * ks * ks, kpad = dc_kpad(ci, ks), kpad_t = dc_kpad(co, ks);
-        const int64_t total = (int64_t)dc_mpad(co) * kpad, total_t = (int64_t)dc_mpad(ci) * kpad_t;
-        disc_pack_conv_kernel<<<blocks(total), dim3(256), 0, st>>>(packed + fw, w, co, K, kpad / 4, scale, total);
-        disc_pack_conv_t_kernel<<<blocks(total_t), dim3(256), 0, st>>>(packed + tw, w, ci, co, ks, kpad_t / 4, scale, total_t);
+        ig_pack(packed + fw, w, ci, co, ks, scale, st);
+        ig_pack_t(packed + tw, w, ci, co, ks, scale, st);
     };
     auto copy = [&](int64_t off, const float* from, int64_t n, float scale, int flip) {
         disc_pack_copy_kernel<<<blocks(n), dim3(256), 0, st>>>(packed + off, from, scale, flip, n);
@@ -649,9 +569,7 @@ extern "C" int e3dge_disc_conv(float* out, const float* in, const float* w, floa
                   n, cin, cout, height, width, ksize, stride);
     E3DGE_REQUIRE(!merge || addend, "disc_conv: merge without an addend");
     hipStream_t st = as_stream(stream);
-    const int K = cin * ksize * ksize, kpad = dc_kpad(cin, ksize);
-    const int64_t total = (int64_t)dc_mpad(cout) * kpad;
-    disc_pack_conv_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(wfrag, w, cout, K, kpad / 4, scale, total);
+    ig_pack(wfrag, w, cin, cout, ksize, scale, st);
     int rc;
     if ((rc = check_launch("disc_conv(pack)"))) return rc;
     return dc_conv(out, in, wfrag, bias, act != 0, addend, merge != 0, n, cin, cout, height, width, ksize, stride, st);

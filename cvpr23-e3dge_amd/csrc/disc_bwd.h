@@ -15,7 +15,8 @@
 //                         -> lrelu'(t) while staging -> transposed 3x3 + the skip branch's gradient in the epilogue.
 //   stem           lrelu' while staging, the 1x1 C0 -> in_channels gradient (one live wave), then pool_256's adjoint (e3dge_avgpool_bwd).
 //
-// The transposed stride 2 is a predicate in the staging (three quarters of the staged elements are zeros that still go through the
+// Every data gradient is disc_gemm_kernel (disc.hip) on the transposed, tap-flipped weight image with its sign-chosen staging factor.
+// The transposed stride 2 is a predicate in its gather (three quarters of the staged elements are zeros that still go through the
 // matrix unit), as in idnet_bwd.h.  No atomics, no allocation, no synchronisation.
 
 namespace e3dge {
@@ -171,9 +172,7 @@ extern "C" int e3dge_disc_conv_dgrad(float* out, const float* g, const float* w,
                   "disc_conv_dgrad: n=%d cin=%d cout=%d height=%d width=%d ksize=%d stride=%d (n, channels 1..4096, sizes ksize..4096, ksize 1 or 3, stride 1 or 2)",
                   n, cin, cout, height, width, ksize, stride);
     hipStream_t st = as_stream(stream);
-    const int kpad = dc_kpad(cout, ksize);
-    const int64_t total = (int64_t)dc_mpad(cin) * kpad;
-    disc_pack_conv_t_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(wfrag_t, w, cin, cout, ksize, kpad / 4, scale, total);
+    ig_pack_t(wfrag_t, w, cin, cout, ksize, scale, st);
     int rc;
     if ((rc = check_launch("disc_conv_dgrad(pack)"))) return rc;
     return dc_dgrad(out, g, wfrag_t, sign, s_pos, s_neg, addend, n, cin, cout, height, width, ksize, stride, st);

@@ -11,15 +11,13 @@
 // Kernels (103 launches for one embed, whatever the batch; one more for the dot products):
 //   prep_kernel   crop and both adaptive averages in one launch (the 256^2 average only where the crop needs it, each value rounded
 //                 to fp32 as the reference's separate pool would).
-//   conv_kernel   lpips_conv_kernel's implicit GEMM on v_mfma_f32_16x16x4_f32 (M = output channels, K = (ci, r, s), weights from the
-//                 packed A-fragment image, im2col tile of 32 k staged in LDS with the next tile's loads in flight), with N = the output
-//                 pixels of ONE image per workgroup column, an optional per-input-channel affine on in-image elements while staging
-//                 (the leading BN: padding stays 0, so it cannot be folded into the weights), and an epilogue of an optional
-//                 per-output-channel affine (trailing BN) and an optional PReLU.  Every output element is the sum of two accumulators
-//                 (even / odd groups of four k), each in ascending k, whatever the tile shape.  With `plane` it also writes one
-//                 partial plane sum per (image, channel, pixel tile): the tile's columns in ascending order per lane, then a fixed
-//                 butterfly over the 16 lanes.  Tiles never straddle images and the tile width depends on the layer alone, so an
-//                 image's values and partials do not depend on the batch.
+//   conv_kernel   the implicit GEMM of conv_igemm.h (M = output channels, K = (ci, r, s), weights from the packed A-fragment image) with
+//                 N = the output pixels of ONE image per workgroup column.  Gather: zero padding, and an optional per-input-channel
+//                 affine on in-image elements (the leading BN: padding stays 0, so it cannot be folded into the weights).  Epilogue:
+//                 the sum of the two accumulators, an optional per-output-channel affine (trailing BN) and an optional PReLU.  With
+//                 `plane` it also writes one partial plane sum per (image, channel, pixel tile): the tile's columns in ascending order
+//                 per lane, then a fixed butterfly over the 16 lanes.  Tiles never straddle images and the tile width depends on the
+//                 layer alone, so an image's values and partials do not depend on the batch.
 //   se_kernel     one workgroup per image: the partials in tile order, / HW, C -> C/16 ReLU, C/16 -> C sigmoid.
 //   merge_kernel  out = res * gate + shortcut (two roundings, as the reference), the shortcut picked with the stride or read.
 //   head_kernel   BN2d while loading, then 4 output rows x 1/7 of K per workgroup for up to 8 images at once (the 51 MB matrix is
@@ -28,15 +26,10 @@
 // The backward (the gradient to the y_hat images, 104 launches) is idnet_bwd.h; the conv, se, merge and head fold kernels have a SAVE
 // instantiation that keeps what it needs.
 // Measured times, the per-kernel split and what bounds each kernel: DESIGN.md 4.11d.
-#include "common.h"
+#include "conv_igemm.h"
 
 namespace e3dge {
 
-typedef float id_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kIdKC = 32;                       // k per staged tile (8 MFMA steps)
-constexpr int kIdBM = 64;                       // channels per workgroup (4 waves x 16)
-constexpr int kIdCUs = 256;
 constexpr int kIdUnits = E3DGE_IDNET_UNITS, kIdConvs = E3DGE_IDNET_CONVS, kIdBns = E3DGE_IDNET_BNS;
 constexpr int kIdNet = 112, kIdEmbed = 512, kIdHeadK = 512 * 7 * 7;
 constexpr int kIdHeadSlices = 7, kIdHeadSliceK = kIdHeadK / kIdHeadSlices, kIdHeadRows = 4, kIdHeadImgs = 8;
@@ -55,8 +48,6 @@ static IdUnit id_unit(int u) {
 }
 static int id_tap_of_unit(int u) { return u == 0 ? 2 : u == 3 ? 3 : u == 7 ? 4 : u == 21 ? 5 : u == 23 ? 6 : -1; }
 
-static int id_kpad(int cin, int ks) { return (cin * ks * ks + kIdKC - 1) / kIdKC * kIdKC; }
-
 // offsets (floats) into the packed image
 struct IdLayout {
     int cin[kIdConvs], cout[kIdConvs], ks[kIdConvs];
@@ -72,7 +63,7 @@ static const IdLayout& id_layout() {
         IdLayout l{};
         int64_t off = 0;
         auto take = [&](int64_t floats) { const int64_t at = off; off += (floats + 63) / 64 * 64; return at; };
-        auto conv = [&](int i, int ci, int co, int ks) { l.cin[i] = ci; l.cout[i] = co; l.ks[i] = ks; l.w_off[i] = take((int64_t)co * id_kpad(ci, ks)); };
+        auto conv = [&](int i, int ci, int co, int ks) { l.cin[i] = ci; l.cout[i] = co; l.ks[i] = ks; l.w_off[i] = take((int64_t)co * ig_kpad(ci * ks * ks)); };
         auto bn = [&](int i, int c) { l.bn_c[i] = c; l.bn_off[i] = take(2 * (int64_t)c); };
         conv(0, 3, 64, 3); bn(0, 64);
         l.prelu_c[0] = 64; l.prelu_off[0] = take(64);
@@ -93,17 +84,6 @@ static const IdLayout& id_layout() {
 }
 
 // ---- packing ------------------------------------------------------------------------------------------------------------------
-// dst[(mt * KS4 + ks) * 64 + lane] = W[mt * 16 + (lane & 15)][ks * 4 + (lane >> 4)] (0 past K): the A operand of v_mfma_f32_16x16x4_f32
-__global__ void __launch_bounds__(256) idnet_pack_conv_kernel(float* __restrict__ dst, const float* __restrict__ w, int K, int KS4, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int lane = (int)(i & 63);
-    const int64_t t = i >> 6;
-    const int ks = (int)(t % KS4), mt = (int)(t / KS4);
-    const int row = mt * 16 + (lane & 15), k = ks * 4 + (lane >> 4);
-    dst[i] = k < K ? w[(int64_t)row * K + k] : 0.0f;
-}
-
 __global__ void __launch_bounds__(256) idnet_pack_bn_kernel(float* __restrict__ dst, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             const float* __restrict__ mean, const float* __restrict__ var, int C) {
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -160,12 +140,10 @@ struct IdConvArgs {
 // parameter and not a null check so that the plain forward runs the instructions it ran before the backward existed.
 template <int KS_, int STRIDE, int NT, bool SAVE = false>
 __global__ void __launch_bounds__(256) idnet_conv_kernel(IdConvArgs a) {
-    constexpr int BN = 16 * NT, BNP = NT == 1 ? 16 : BN + 16;      // row pitch: the four k rows of one read land in four bank groups
-    constexpr int ROWS = 256 / BN, PER = kIdKC / ROWS;
-    constexpr int KK = KS_ * KS_, PAD = KS_ == 3 ? 1 : 0;
-    __shared__ float bs[kIdKC * BNP];
+    constexpr int BN = IgTile<NT>::BN, ROWS = IgTile<NT>::ROWS, PER = IgTile<NT>::PER;
+    constexpr int PAD = KS_ == 3 ? 1 : 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mt = blockIdx.y * (kIdBM / 16) + wave;
+    const int mt = blockIdx.y * (kIgBM / 16) + wave;
     const int OHW = a.OH * a.OW, IH = a.IH, IW = a.IW, K = a.K;
     const int img = blockIdx.x / a.tiles, tile = blockIdx.x - img * a.tiles;
     const int sn = tid % BN, srow = tid / BN;
@@ -179,7 +157,7 @@ __global__ void __launch_bounds__(256) idnet_conv_kernel(IdConvArgs a) {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int k = k0 + srow + i * ROWS;
-            const int ci = k / KK, rs = k - ci * KK, r = rs / KS_, s = rs - r * KS_;
+            const auto [ci, r, s] = ig_decode<KS_>(k);
             const int iy = iy0 + r, ix = ix0 + s;
             float x = 0.0f;
             if (n_ok && k < K && iy >= 0 && iy < IH && ix >= 0 && ix < IW) {
@@ -189,33 +167,8 @@ __global__ void __launch_bounds__(256) idnet_conv_kernel(IdConvArgs a) {
             v[i] = x;
         }
     };
-    id_f32x4 acc[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) acc[t][h] = id_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const float* __restrict__ wa = a.wfrag + (int64_t)mt * a.KS4 * 64 + lane;
-    const int n_tiles = a.KS4 / (kIdKC / 4);
-    float stage[PER];
-    fetch(0, stage);
-    for (int kt = 0; kt < n_tiles; ++kt) {
-        __syncthreads();                                            // the previous tile's reads are done
-#pragma unroll
-        for (int i = 0; i < PER; ++i) bs[(srow + i * ROWS) * BNP + sn] = stage[i];
-        __syncthreads();
-        float af[kIdKC / 4];
-#pragma unroll
-        for (int j = 0; j < kIdKC / 4; ++j) af[j] = wa[(int64_t)(kt * (kIdKC / 4) + j) * 64];
-        if (kt + 1 < n_tiles) fetch((kt + 1) * kIdKC, stage);      // in flight during the MFMAs
-#pragma unroll
-        for (int j = 0; j < kIdKC / 4; ++j) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float b = bs[(j * 4 + (lane >> 4)) * BNP + t * 16 + (lane & 15)];
-                acc[t][j & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b, acc[t][j & 1], 0, 0, 0);
-            }
-        }
-    }
+    f32x4 acc[NT][2];
+    ig_k_loop<NT, 2, false>(acc, a.wfrag + (int64_t)mt * a.KS4 * 64 + lane, a.KS4 / (kIgKC / 4), true, fetch, [](int, bool) {});
     // C/D fragment: lane l, register r holds D[4 (l >> 4) + r][l & 15]
     float psum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     const int row0 = mt * 16 + 4 * (lane >> 4);
@@ -431,13 +384,8 @@ __global__ void image_metric_row_full_kernel(float* __restrict__ row, const floa
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 static int id_out_size(int in, int stride) { return (in - 1) / stride + 1; }     // 3x3 pad 1 and 1x1 pad 0 alike
 
-// pixels per workgroup / 16: the widest tile that still gives every CU a workgroup for TWO images (the evaluation shape), chosen from
-// the layer alone so that the partial plane sums of an image do not depend on the batch
-static int id_tile_width(int OHW, int Cout) {
-    const int64_t gy = Cout / kIdBM;
-    auto blocks = [&](int bn) { return (int64_t)(OHW + bn - 1) / bn; };
-    return blocks(64) * 2 * gy >= kIdCUs ? 4 : blocks(32) * 2 * gy >= kIdCUs ? 2 : 1;
-}
+// the tile width comes from the layer alone (two images counted), so that the partial plane sums of an image do not depend on the batch
+static int id_tile_width(int OHW, int Cout) { return ig_tile_width(OHW, 2, Cout / kIgBM); }
 static int id_tiles(int OHW, int Cout) { const int bn = 16 * id_tile_width(OHW, Cout); return (OHW + bn - 1) / bn; }
 
 static int id_conv(float* out, const float* in, const float* wfrag, const float* in_ab, const float* epi_ab, const float* slope, float* plane,
@@ -447,26 +395,18 @@ static int id_conv(float* out, const float* in, const float* wfrag, const float*
     a.out = out; a.in = in; a.wfrag = wfrag;
     a.in_ab = reinterpret_cast<const float2*>(in_ab); a.epi_ab = reinterpret_cast<const float2*>(epi_ab); a.slope = slope; a.plane = plane;
     a.Cin = Cin; a.IH = IH; a.IW = IW; a.Cout = Cout; a.OH = id_out_size(IH, stride); a.OW = id_out_size(IW, stride);
-    a.K = Cin * ks * ks; a.KS4 = id_kpad(Cin, ks) / 4;
+    a.K = Cin * ks * ks; a.KS4 = ig_kpad(a.K) / 4;
     const int OHW = a.OH * a.OW, nt = id_tile_width(OHW, Cout);
     a.tiles = id_tiles(OHW, Cout);
-    const dim3 grid((unsigned)((int64_t)n * a.tiles), (unsigned)(Cout / kIdBM));
-#define E3DGE_ID_LAUNCH(KS_, S_)                                                                    \
-    do {                                                                                            \
-        if (nt == 4) idnet_conv_kernel<KS_, S_, 4><<<grid, dim3(256), 0, st>>>(a);                  \
-        else if (nt == 2) idnet_conv_kernel<KS_, S_, 2><<<grid, dim3(256), 0, st>>>(a);             \
-        else idnet_conv_kernel<KS_, S_, 1><<<grid, dim3(256), 0, st>>>(a);                          \
-    } while (0)
-    if (mask && ks == 3 && stride == 1) {                            // every PReLU follows a 3x3 of stride 1
-        if (nt == 4) idnet_conv_kernel<3, 1, 4, true><<<grid, dim3(256), 0, st>>>(a);
-        else if (nt == 2) idnet_conv_kernel<3, 1, 2, true><<<grid, dim3(256), 0, st>>>(a);
-        else idnet_conv_kernel<3, 1, 1, true><<<grid, dim3(256), 0, st>>>(a);
-    }
-    else if (ks == 3 && stride == 1) E3DGE_ID_LAUNCH(3, 1);
-    else if (ks == 3) E3DGE_ID_LAUNCH(3, 2);
-    else if (stride == 1) E3DGE_ID_LAUNCH(1, 1);
-    else E3DGE_ID_LAUNCH(1, 2);
-#undef E3DGE_ID_LAUNCH
+    const dim3 grid((unsigned)((int64_t)n * a.tiles), (unsigned)(Cout / kIgBM));
+    ig_dispatch_nt(nt, [&](auto nt_c) {
+        constexpr int NT = decltype(nt_c)::value;
+        if (mask && ks == 3 && stride == 1) idnet_conv_kernel<3, 1, NT, true><<<grid, dim3(256), 0, st>>>(a);   // every PReLU follows a 3x3 of stride 1
+        else if (ks == 3 && stride == 1) idnet_conv_kernel<3, 1, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (ks == 3) idnet_conv_kernel<3, 2, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (stride == 1) idnet_conv_kernel<1, 1, NT><<<grid, dim3(256), 0, st>>>(a);
+        else idnet_conv_kernel<1, 2, NT><<<grid, dim3(256), 0, st>>>(a);
+    });
     return check_launch("idnet(conv)");
 }
 
@@ -543,11 +483,7 @@ extern "C" int e3dge_idnet_pack_weights(float* packed, const E3dgeIdnetPackSrc* 
     hipStream_t st = as_stream(stream);
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     auto copy = [&](int64_t off, const float* from, int64_t n) { idnet_copy_kernel<<<blocks(n), dim3(256), 0, st>>>(packed + off, from, n); };
-    for (int i = 0; i < kIdConvs; ++i) {
-        const int K = l.cin[i] * l.ks[i] * l.ks[i], kpad = id_kpad(l.cin[i], l.ks[i]);
-        const int64_t total = (int64_t)l.cout[i] * kpad;
-        idnet_pack_conv_kernel<<<blocks(total), dim3(256), 0, st>>>(packed + l.w_off[i], s.conv_w[i], K, kpad / 4, total);
-    }
+    for (int i = 0; i < kIdConvs; ++i) ig_pack(packed + l.w_off[i], s.conv_w[i], l.cin[i], l.cout[i], l.ks[i], 1.0f, st);
     for (int i = 0; i < kIdBns; ++i)
         idnet_pack_bn_kernel<<<blocks(l.bn_c[i]), dim3(256), 0, st>>>(packed + l.bn_off[i], s.bn_weight[i], s.bn_bias[i], s.bn_mean[i], s.bn_var[i],
                                                                      l.bn_c[i]);
@@ -688,7 +624,7 @@ extern "C" int e3dge_id_loss(const E3dgeIdLossArgs* args, e3dge_stream_t stream)
 }
 
 static bool id_conv_sizes_ok(int cout, int height, int width, int ksize, int stride) {
-    return cout >= kIdBM && cout % kIdBM == 0 && cout <= 65535 * kIdBM && height >= 1 && width >= 1 && height <= 4096 && width <= 4096 &&
+    return cout >= kIgBM && cout % kIgBM == 0 && cout <= 65535 * kIgBM && height >= 1 && width >= 1 && height <= 4096 && width <= 4096 &&
            (ksize == 1 || ksize == 3) && (stride == 1 || stride == 2);
 }
 
@@ -710,9 +646,7 @@ extern "C" int e3dge_idnet_conv(float* out, const float* in, const float* w, flo
                   cout, height, width, ksize, stride);
     E3DGE_REQUIRE((int64_t)cin * height * width < ((int64_t)1 << 31), "idnet_conv: image too large");
     hipStream_t st = as_stream(stream);
-    const int K = cin * ksize * ksize, kpad = id_kpad(cin, ksize);
-    const int64_t total = (int64_t)cout * kpad;
-    idnet_pack_conv_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(wfrag, w, K, kpad / 4, total);
+    ig_pack(wfrag, w, cin, cout, ksize, 1.0f, st);
     int rc;
     if ((rc = check_launch("idnet_conv(pack)"))) return rc;
     return id_conv(out, in, wfrag, in_ab, epi_ab, slope, plane, n, cin, cout, height, width, ksize, stride, st);

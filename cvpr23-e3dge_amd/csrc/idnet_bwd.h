@@ -19,18 +19,18 @@
 //   input layer     PReLU derivative and BN scale in place, then the 64 -> 3 dgrad (wave 0 of a workgroup holds the 3 rows).
 //   prep_bwd        the adjoint of the crop and both adaptive averages as a gather per image pixel: every element is written.
 //
-// dgrad_kernel is idnet_conv_kernel's implicit GEMM on the transposed weight image (W^T with flipped taps, M = C_in, K = (co, r, s)):
-// same tile, same two accumulators in ascending k, tile width from the layer alone.  Stride 2 is a predicate in the staging: the tap
+// dgrad_kernel is the implicit GEMM of conv_igemm.h on the transposed weight image (W^T with flipped taps, M = C_in, K = (co, r, s)):
+// idnet_conv_kernel's tile and two accumulators, tile width from the layer alone; waves past M idle (the 64 -> 3 gradient has one live
+// wave).  Gather: g with an optional per-image affine or per-channel factor on in-image elements; stride 2 is a predicate: the tap
 // (r, s) of output pixel (y, x) exists where y - pad + r and x - pad + s are even and in range, so three quarters of the staged
-// elements of a stride-2 dgrad are zeros that still go through the matrix unit (cost: DESIGN.md 4.11e).
+// elements of a stride-2 dgrad are zeros that still go through the matrix unit (cost: DESIGN.md 4.11e).  Epilogue: the saved PReLU
+// branch or a per-channel factor, then an optional addend read with stride 1 or 2.
 // 104 launches, no atomics, no allocation, no synchronisation.
 
 namespace e3dge {
 
 constexpr int kIdPrelus = E3DGE_IDNET_PRELUS;
 static_assert(kIdPrelus == kIdUnits + 1, "one PReLU per unit and the input layer's");
-
-static int id_mpad(int M) { return (M + 15) / 16 * 16; }
 
 struct IdLayoutT { int64_t w_off[kIdConvs], total; };
 
@@ -41,29 +41,12 @@ static const IdLayoutT& id_layout_t() {
         int64_t off = 0;
         for (int i = 0; i < kIdConvs; ++i) {
             t.w_off[i] = off;
-            off += ((int64_t)id_mpad(l.cin[i]) * id_kpad(l.cout[i], l.ks[i]) + 63) / 64 * 64;
+            off += ((int64_t)ig_mpad(l.cin[i]) * ig_kpad(l.cout[i] * l.ks[i] * l.ks[i]) + 63) / 64 * 64;
         }
         t.total = off;
         return t;
     }();
     return lay;
-}
-
-// dst[(mt * KS4 + ks) * 64 + lane] = Wt[mt * 16 + (lane & 15)][ks * 4 + (lane >> 4)],  Wt[ci][(co, r, s)] = W[co][ci][ks - 1 - r][ks - 1 - s]
-__global__ void __launch_bounds__(256) idnet_pack_conv_t_kernel(float* __restrict__ dst, const float* __restrict__ w, int Cin, int Cout, int KS,
-                                                                int KS4, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int lane = (int)(i & 63), KK = KS * KS;
-    const int64_t t = i >> 6;
-    const int ks = (int)(t % KS4), mt = (int)(t / KS4);
-    const int ci = mt * 16 + (lane & 15), k = ks * 4 + (lane >> 4);
-    float v = 0.0f;
-    if (ci < Cin && k < Cout * KK) {
-        const int co = k / KK, rs = k - co * KK, r = rs / KS, s = rs - r * KS;
-        v = w[(((int64_t)co * Cin + ci) * KS + (KS - 1 - r)) * KS + (KS - 1 - s)];
-    }
-    dst[i] = v;
 }
 
 // ---- data gradient of one convolution --------------------------------------------------------------------------------------------
@@ -79,12 +62,10 @@ struct IdDgradArgs {
 
 template <int KS_, int STRIDE, int NT>
 __global__ void __launch_bounds__(256) idnet_dgrad_kernel(IdDgradArgs a) {
-    constexpr int BN = 16 * NT, BNP = NT == 1 ? 16 : BN + 16;
-    constexpr int ROWS = 256 / BN, PER = kIdKC / ROWS;
-    constexpr int KK = KS_ * KS_, PAD = KS_ == 3 ? 1 : 0;
-    __shared__ float bs[kIdKC * BNP];
+    constexpr int BN = IgTile<NT>::BN, ROWS = IgTile<NT>::ROWS, PER = IgTile<NT>::PER;
+    constexpr int PAD = KS_ == 3 ? 1 : 0;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mt = blockIdx.y * (kIdBM / 16) + wave;
+    const int mt = blockIdx.y * (kIgBM / 16) + wave;
     const bool live = mt * 16 < a.M;                                 // wave-uniform: the 64 -> 3 gradient has one live wave
     const int HW = a.H * a.W, GH = a.GH, GW = a.GW, K = a.K;
     const int img = blockIdx.x / a.tiles, tile = blockIdx.x - img * a.tiles;
@@ -99,7 +80,7 @@ __global__ void __launch_bounds__(256) idnet_dgrad_kernel(IdDgradArgs a) {
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int k = k0 + srow + i * ROWS;
-            const int co = k / KK, rs = k - co * KK, r = rs / KS_, s = rs - r * KS_;
+            const auto [co, r, s] = ig_decode<KS_>(k);
             const int ny = y0 + r, nx = x0 + s;
             bool ok = n_ok && k < K && ny >= 0 && nx >= 0;
             int gy = ny, gx = nx;
@@ -114,37 +95,8 @@ __global__ void __launch_bounds__(256) idnet_dgrad_kernel(IdDgradArgs a) {
             v[i] = x;
         }
     };
-    id_f32x4 acc[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) acc[t][h] = id_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const float* __restrict__ wa = a.wfrag + (int64_t)(live ? mt : 0) * a.KS4 * 64 + lane;
-    const int n_tiles = a.KS4 / (kIdKC / 4);
-    float stage[PER];
-    fetch(0, stage);
-    for (int kt = 0; kt < n_tiles; ++kt) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < PER; ++i) bs[(srow + i * ROWS) * BNP + sn] = stage[i];
-        __syncthreads();
-        float af[kIdKC / 4];
-        if (live) {
-#pragma unroll
-            for (int j = 0; j < kIdKC / 4; ++j) af[j] = wa[(int64_t)(kt * (kIdKC / 4) + j) * 64];
-        }
-        if (kt + 1 < n_tiles) fetch((kt + 1) * kIdKC, stage);
-        if (live) {
-#pragma unroll
-            for (int j = 0; j < kIdKC / 4; ++j) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const float b = bs[(j * 4 + (lane >> 4)) * BNP + t * 16 + (lane & 15)];
-                    acc[t][j & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], b, acc[t][j & 1], 0, 0, 0);
-                }
-            }
-        }
-    }
+    f32x4 acc[NT][2];
+    ig_k_loop<NT, 2, true>(acc, a.wfrag + (int64_t)(live ? mt : 0) * a.KS4 * 64 + lane, a.KS4 / (kIgKC / 4), live, fetch, [](int, bool) {});
     if (!live) return;
     const int row0 = mt * 16 + 4 * (lane >> 4);
 #pragma unroll
@@ -170,22 +122,18 @@ __global__ void __launch_bounds__(256) idnet_dgrad_kernel(IdDgradArgs a) {
 }
 
 static int id_dgrad(IdDgradArgs a, int n, int ks, int stride, hipStream_t st) {
-    a.K = a.Cg * ks * ks; a.KS4 = id_kpad(a.Cg, ks) / 4;
+    a.K = a.Cg * ks * ks; a.KS4 = ig_kpad(a.K) / 4;
     a.GH = id_out_size(a.H, stride); a.GW = id_out_size(a.W, stride);
-    const int HW = a.H * a.W, gy = (a.M + kIdBM - 1) / kIdBM, nt = id_tile_width(HW, gy * kIdBM);
-    a.tiles = id_tiles(HW, gy * kIdBM);
+    const int HW = a.H * a.W, gy = (a.M + kIgBM - 1) / kIgBM, nt = id_tile_width(HW, gy * kIgBM);
+    a.tiles = id_tiles(HW, gy * kIgBM);
     const dim3 grid((unsigned)((int64_t)n * a.tiles), (unsigned)gy);
-#define E3DGE_ID_LAUNCH(KS_, S_)                                                                     \
-    do {                                                                                            \
-        if (nt == 4) idnet_dgrad_kernel<KS_, S_, 4><<<grid, dim3(256), 0, st>>>(a);                 \
-        else if (nt == 2) idnet_dgrad_kernel<KS_, S_, 2><<<grid, dim3(256), 0, st>>>(a);            \
-        else idnet_dgrad_kernel<KS_, S_, 1><<<grid, dim3(256), 0, st>>>(a);                         \
-    } while (0)
-    if (ks == 3 && stride == 1) E3DGE_ID_LAUNCH(3, 1);
-    else if (ks == 3) E3DGE_ID_LAUNCH(3, 2);
-    else if (stride == 1) E3DGE_ID_LAUNCH(1, 1);
-    else E3DGE_ID_LAUNCH(1, 2);
-#undef E3DGE_ID_LAUNCH
+    ig_dispatch_nt(nt, [&](auto nt_c) {
+        constexpr int NT = decltype(nt_c)::value;
+        if (ks == 3 && stride == 1) idnet_dgrad_kernel<3, 1, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (ks == 3) idnet_dgrad_kernel<3, 2, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (stride == 1) idnet_dgrad_kernel<1, 1, NT><<<grid, dim3(256), 0, st>>>(a);
+        else idnet_dgrad_kernel<1, 2, NT><<<grid, dim3(256), 0, st>>>(a);
+    });
     return check_launch("idnet(dgrad)");
 }
 
@@ -366,12 +314,7 @@ extern "C" int e3dge_idnet_pack_weights_t(float* packed_t, const E3dgeIdnetPackS
     const IdLayout& l = id_layout();
     const IdLayoutT& t = id_layout_t();
     hipStream_t st = as_stream(stream);
-    for (int i = 0; i < kIdConvs; ++i) {
-        const int kpad = id_kpad(l.cout[i], l.ks[i]);
-        const int64_t total = (int64_t)id_mpad(l.cin[i]) * kpad;
-        idnet_pack_conv_t_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(packed_t + t.w_off[i], src->conv_w[i], l.cin[i], l.cout[i],
-                                                                                              l.ks[i], kpad / 4, total);
-    }
+    for (int i = 0; i < kIdConvs; ++i) ig_pack_t(packed_t + t.w_off[i], src->conv_w[i], l.cin[i], l.cout[i], l.ks[i], 1.0f, st);
     return check_launch("idnet_pack_weights_t");
 }
 
@@ -517,9 +460,7 @@ extern "C" int e3dge_idnet_conv_bwd(float* out, const float* g, const float* w, 
                   n, cin, cout, height, width, ksize, stride);
     E3DGE_REQUIRE((int64_t)(cin > cout ? cin : cout) * height * width < ((int64_t)1 << 31), "idnet_conv_bwd: image too large");
     hipStream_t st = as_stream(stream);
-    const int kpad = id_kpad(cout, ksize);
-    const int64_t total = (int64_t)id_mpad(cin) * kpad;
-    idnet_pack_conv_t_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(wfrag_t, w, cin, cout, ksize, kpad / 4, total);
+    ig_pack_t(wfrag_t, w, cin, cout, ksize, 1.0f, st);
     int rc;
     if ((rc = check_launch("idnet_conv_bwd(pack)"))) return rc;
     IdDgradArgs a{};

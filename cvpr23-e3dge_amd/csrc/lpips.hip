@@ -13,14 +13,12 @@
 // The backward (the gradient with respect to x and y, eight launches) is lpips_bwd.h.
 //
 // Kernels (nine launches for one forward, whatever the batch):
-//   conv_kernel      implicit GEMM on v_mfma_f32_16x16x4_f32, fp32 throughout.  M = output channels, N = the output pixels of all 2B
-//                    images (x then y) flattened, K = (ci, r, s).  A workgroup is 4 waves = 64 channels x 16 NT pixels (NT = 1, 2, 4
-//                    by the size of N, so that the 15^2 maps still spread over the chip); every wave owns one 16-channel tile.  The
-//                    weights are read from the packed image in A-fragment order (one coalesced dword per lane and MFMA, no LDS); the
-//                    im2col tile of 32 k is staged in LDS, next tile's loads in flight during the MFMAs.  A staged element outside the
-//                    image (padding), past N or past K is 0 and is never loaded.  Every output element is the sum of two accumulators
-//                    (even / odd groups of four k), each in ascending k, whatever the tile shape: a pixel's value does not depend on
-//                    its position in the batch, on the batch size or on which of the two images it belongs to.
+//   conv_kernel      the implicit GEMM of conv_igemm.h.  M = output channels, N = the output pixels of all 2B images (x then y)
+//                    flattened, K = (ci, r, s); NT = 1, 2, 4 by the size of N, so that the 15^2 maps still spread over the chip.
+//                    Gather: zero padding (a staged element outside the image, past N or past K is 0 and is never loaded), conv 1
+//                    z-scores while staging.  Epilogue: the sum of the two accumulators, + bias, ReLU (the backward's two epilogues:
+//                    lpips_bwd.h).  A pixel's value does not depend on its position in the batch, on the batch size or on which of
+//                    the two images it belongs to.
 //   pool_kernel      the two 3x3 stride-2 floor-mode max-pools.
 //   tap_kernel       all five taps in one launch: 16 pixels x 16 channel groups per workgroup, both images of the pair; channel norms,
 //                    then sum_c lin_c (x^_c - y^_c)^2 with the same fp32 operations as the reference (true divisions), folded in a
@@ -28,23 +26,18 @@
 //   fold_kernel      one workgroup: the partials of every (image, layer) in a fixed order (double accumulation), the spatial mean,
 //                    per_layer, per_image and their batch mean.  Bit-reproducible.
 // Measured times, the per-kernel split and what bounds each kernel: DESIGN.md 4.11b.
-#include "common.h"
+#include "conv_igemm.h"
 
 namespace e3dge {
-
-typedef float lp_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kLpLayers = 5;
 __host__ __device__ constexpr int lp_cin(int l) { return l == 0 ? 3 : l == 1 ? 64 : l == 2 ? 192 : l == 3 ? 384 : 256; }
 __host__ __device__ constexpr int lp_cout(int l) { return l == 0 ? 64 : l == 1 ? 192 : l == 2 ? 384 : 256; }
 __host__ __device__ constexpr int lp_ks(int l) { return l == 0 ? 11 : l == 1 ? 5 : 3; }
-constexpr int kLpKC = 32;                       // k per staged tile (8 MFMA steps)
-constexpr int kLpBM = 64;                       // channels per workgroup (4 waves x 16)
 constexpr int kLpTapPix = 16, kLpTapGroups = 16;
-constexpr int kLpCUs = 256;                     // compute units of the MI355X: the tile width is chosen to give each a workgroup
 
 __host__ __device__ constexpr int lp_k(int l) { return lp_cin(l) * lp_ks(l) * lp_ks(l); }
-__host__ __device__ constexpr int lp_kpad(int l) { return (lp_k(l) + kLpKC - 1) / kLpKC * kLpKC; }
+__host__ __device__ constexpr int lp_kpad(int l) { return ig_kpad(lp_k(l)); }
 __host__ __device__ constexpr int64_t lp_w_floats(int l) { return (int64_t)lp_cout(l) * lp_kpad(l); }
 __host__ __device__ constexpr int64_t lp_w_off(int l) { int64_t o = 0; for (int q = 0; q < l; ++q) o += lp_w_floats(q); return o; }
 __host__ __device__ constexpr int64_t lp_c_off(int l) { int64_t o = 0; for (int q = 0; q < l; ++q) o += lp_cout(q); return o; }   // bias / lin rows
@@ -103,12 +96,9 @@ __global__ void __launch_bounds__(256)
 lpips_conv_kernel(float* __restrict__ out, const float* __restrict__ in0, const float* __restrict__ in1, int n_first,
                   const float* __restrict__ wfrag, const float* __restrict__ bias, int Cin, int IH, int IW, int Cout, int OH, int OW,
                   int64_t N, int K, int KS4, LpNorm nrm, int f_first = 0) {
-    constexpr int BN = 16 * NT, BNP = NT == 1 ? 16 : BN + 16;      // row pitch: the four k rows of one read land in four bank groups
-    constexpr int ROWS = 256 / BN, PER = kLpKC / ROWS;               // staged elements per thread and tile
-    constexpr int KK = KS_ * KS_;
-    __shared__ float bs[kLpKC * BNP];
+    constexpr int BN = IgTile<NT>::BN, ROWS = IgTile<NT>::ROWS, PER = IgTile<NT>::PER;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mt = blockIdx.y * (kLpBM / 16) + wave;
+    const int mt = blockIdx.y * (kIgBM / 16) + wave;
     const int OHW = OH * OW;
     // the pixel this thread stages
     const int sn = tid % BN, srow = tid / BN;
@@ -126,7 +116,7 @@ lpips_conv_kernel(float* __restrict__ out, const float* __restrict__ in0, const 
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int k = k0 + srow + i * ROWS;
-            const int ci = k / KK, rs = k - ci * KK, r = rs / KS_, s = rs - r * KS_;
+            const auto [ci, r, s] = ig_decode<KS_>(k);
             const int iy = iy0 + r, ix = ix0 + s;
             float x = 0.0f;
             if (n_ok && k < K && iy >= 0 && iy < IH && ix >= 0 && ix < IW) {
@@ -140,33 +130,8 @@ lpips_conv_kernel(float* __restrict__ out, const float* __restrict__ in0, const 
             v[i] = x;
         }
     };
-    lp_f32x4 acc[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) acc[t][h] = lp_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const float* __restrict__ wa = wfrag + (int64_t)mt * KS4 * 64 + lane;
-    const int n_tiles = KS4 / (kLpKC / 4);
-    float stage[PER];
-    fetch(0, stage);
-    for (int tile = 0; tile < n_tiles; ++tile) {
-        __syncthreads();                                            // the previous tile's reads are done
-#pragma unroll
-        for (int i = 0; i < PER; ++i) bs[(srow + i * ROWS) * BNP + sn] = stage[i];
-        __syncthreads();
-        float a[kLpKC / 4];
-#pragma unroll
-        for (int j = 0; j < kLpKC / 4; ++j) a[j] = wa[(int64_t)(tile * (kLpKC / 4) + j) * 64];
-        if (tile + 1 < n_tiles) fetch((tile + 1) * kLpKC, stage);  // in flight during the MFMAs
-#pragma unroll
-        for (int j = 0; j < kLpKC / 4; ++j) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float b = bs[(j * 4 + (lane >> 4)) * BNP + t * 16 + (lane & 15)];
-                acc[t][j & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b, acc[t][j & 1], 0, 0, 0);
-            }
-        }
-    }
+    f32x4 acc[NT][2];
+    ig_k_loop<NT, 2, false>(acc, wfrag + (int64_t)mt * KS4 * 64 + lane, KS4 / (kIgKC / 4), true, fetch, [](int, bool) {});
     // C/D fragment: lane l, register r holds D[4 (l >> 4) + r][l & 15]
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -362,28 +327,21 @@ static bool lp_dims(int batch, int height, int width, LpDims* d) {
     return true;
 }
 
-// the widest pixel tile (16 NT pixels) that still gives every CU a workgroup
-static int lp_tile_width(int64_t N, int gy) {
-    auto blocks = [&](int bn) { return (N + bn - 1) / bn; };
-    return blocks(64) * gy >= kLpCUs ? 4 : blocks(32) * gy >= kLpCUs ? 2 : 1;
-}
-
 template <int KS_, int STRIDE, int PAD, bool FIRST>
 static int lp_conv(float* out, const float* in0, const float* in1, int n_first, const float* packed, int l, int IH, int IW, int OH, int OW,
                    int n_img, const LpNorm& nrm, hipStream_t st) {
     const int64_t N = (int64_t)n_img * OH * OW;
-    const int Cout = lp_cout(l), gy = Cout / kLpBM;
+    const int Cout = lp_cout(l), gy = Cout / kIgBM;
     const float* wf = packed + lp_w_off(l);
     const float* bias = packed + kLpBiasOff + lp_c_off(l);
     const int K = lp_k(l), KS4 = lp_kpad(l) / 4;
     auto blocks = [&](int bn) { return (N + bn - 1) / bn; };
     E3DGE_REQUIRE(blocks(16) < ((int64_t)1 << 31), "lpips_forward: grid too large");
-    const int nt = lp_tile_width(N, gy);
-#define E3DGE_LP_LAUNCH(NT)                                                                                                     \
-    lpips_conv_kernel<KS_, STRIDE, PAD, NT, FIRST><<<dim3((unsigned)blocks(16 * NT), gy), dim3(256), 0, st>>>(                 \
-        out, in0, in1, n_first, wf, bias, lp_cin(l), IH, IW, Cout, OH, OW, N, K, KS4, nrm)
-    if (nt == 4) E3DGE_LP_LAUNCH(4); else if (nt == 2) E3DGE_LP_LAUNCH(2); else E3DGE_LP_LAUNCH(1);
-#undef E3DGE_LP_LAUNCH
+    ig_dispatch_nt(ig_tile_width(N, 1, gy), [&](auto nt_c) {
+        constexpr int NT = decltype(nt_c)::value;
+        lpips_conv_kernel<KS_, STRIDE, PAD, NT, FIRST><<<dim3((unsigned)blocks(16 * NT), gy), dim3(256), 0, st>>>(
+            out, in0, in1, n_first, wf, bias, lp_cin(l), IH, IW, Cout, OH, OW, N, K, KS4, nrm);
+    });
     return check_launch("lpips_forward(conv)");
 }
 

@@ -10,11 +10,11 @@
 // Kernels (eight launches for one backward, whatever the batch; no atomics, every sum in a fixed order):
 //   tap_bwd_kernel    the tap kernel's geometry, all five layers in one launch: channel norms of both images of the pair, then
 //                     dtap_l [f_l > 0] of the images that get a gradient, into the G_l buffers (for layer 5 that is G_5).
-//   conv_kernel       the forward's implicit GEMM on the transposed, tap-flipped weight image: M = C_in(l), K = (co, r, s), N = the
-//                     pixels of the gradient images.  3x3 / p1 and 5x5 / p2 are their own adjoints' geometry.  Epilogue kLpEpiMask
-//                     (data gradients of conv 5 and 4: (acc + dtap) [f > 0] in place, G_4 and G_3) or kLpEpiStore (conv 3 and 2: the
-//                     gradients of the two pooled maps).  The forward's order of sums holds, so a pixel's gradient does not depend on
-//                     the batch or the tile width.
+//   conv_kernel       the forward's kernel (the implicit GEMM of conv_igemm.h, the forward's gather) on the transposed, tap-flipped
+//                     weight image: M = C_in(l), K = (co, r, s), N = the pixels of the gradient images.  3x3 / p1 and 5x5 / p2 are
+//                     their own adjoints' geometry.  Epilogue kLpEpiMask (data gradients of conv 5 and 4: (acc + dtap) [f > 0] in
+//                     place, G_4 and G_3) or kLpEpiStore (conv 3 and 2: the gradients of the two pooled maps).  The forward's order of
+//                     sums holds, so a pixel's gradient does not depend on the batch or the tile width.
 //   pool_bwd_kernel   a gather: an element sums the gradients of the at most four windows whose FIRST maximum in row-major order it
 //                     is (torch's rule), then + dtap_l and the ReLU mask: G_2 and G_1.
 //   conv1_bwd_kernel  64 -> 3 channels, k 11, stride 4, pad 2, phase-decomposed on the VALU: a thread owns the 4 x 4 input pixels
@@ -29,13 +29,13 @@
 // layer l = 1..4 (conv 2..5): Wt_l[ci][(co, r, s)] = W_l[co][ci][ks - 1 - r][ks - 1 - s] in A-fragment order as the forward image holds
 // W_l, M = lp_cin(l); then conv 1 as [c][co][11 x 11], the order conv1_bwd_kernel reads.
 __host__ __device__ constexpr int lp_kt(int l) { return lp_cout(l) * lp_ks(l) * lp_ks(l); }
-__host__ __device__ constexpr int lp_ktpad(int l) { return (lp_kt(l) + kLpKC - 1) / kLpKC * kLpKC; }
+__host__ __device__ constexpr int lp_ktpad(int l) { return ig_kpad(lp_kt(l)); }
 __host__ __device__ constexpr int64_t lp_wt_floats(int l) { return (int64_t)lp_cin(l) * lp_ktpad(l); }
 __host__ __device__ constexpr int64_t lp_wt_off(int l) { int64_t o = 0; for (int q = 1; q < l; ++q) o += lp_wt_floats(q); return o; }
 constexpr int64_t kLpW1tOff = lp_wt_off(kLpLayers);
 constexpr int64_t kLpW1tFloats = (int64_t)lp_cin(0) * lp_cout(0) * lp_ks(0) * lp_ks(0);
 constexpr int64_t kLpPackedTFloats = kLpW1tOff + kLpW1tFloats;
-static_assert(lp_cin(1) % kLpBM == 0 && lp_cin(2) % kLpBM == 0 && lp_cin(3) % kLpBM == 0 && lp_cin(4) % kLpBM == 0, "whole channel tiles");
+static_assert(lp_cin(1) % kIgBM == 0 && lp_cin(2) % kIgBM == 0 && lp_cin(3) % kIgBM == 0 && lp_cin(4) % kIgBM == 0, "whole channel tiles");
 
 struct LpPackTSrc { const float* w[kLpLayers]; };
 
@@ -257,18 +257,17 @@ template <int KS_, int PAD, int EPI>
 static int lp_dgrad(float* out, const float* g, const float* packed_t, int l, int H, int W, int n_img, const float* f, int f_first,
                     hipStream_t st) {
     const int64_t N = (int64_t)n_img * H * W;
-    const int M = lp_cin(l), gy = M / kLpBM;
+    const int M = lp_cin(l), gy = M / kIgBM;
     const float* wf = packed_t + lp_wt_off(l);
     const int K = lp_kt(l), KS4 = lp_ktpad(l) / 4;
     auto blocks = [&](int bn) { return (N + bn - 1) / bn; };
     E3DGE_REQUIRE(blocks(16) < ((int64_t)1 << 31), "lpips_backward: grid too large");
-    const int nt = lp_tile_width(N, gy);                               // the forward's rule
     const LpNorm nrm{};
-#define E3DGE_LP_LAUNCH(NT)                                                                                                     \
-    lpips_conv_kernel<KS_, 1, PAD, NT, false, EPI><<<dim3((unsigned)blocks(16 * NT), gy), dim3(256), 0, st>>>(                 \
-        out, g, g, n_img, wf, f, lp_cout(l), H, W, M, H, W, N, K, KS4, nrm, f_first)
-    if (nt == 4) E3DGE_LP_LAUNCH(4); else if (nt == 2) E3DGE_LP_LAUNCH(2); else E3DGE_LP_LAUNCH(1);
-#undef E3DGE_LP_LAUNCH
+    ig_dispatch_nt(ig_tile_width(N, 1, gy), [&](auto nt_c) {           // the forward's rule
+        constexpr int NT = decltype(nt_c)::value;
+        lpips_conv_kernel<KS_, 1, PAD, NT, false, EPI><<<dim3((unsigned)blocks(16 * NT), gy), dim3(256), 0, st>>>(
+            out, g, g, n_img, wf, f, lp_cout(l), H, W, M, H, W, N, K, KS4, nrm, f_first);
+    });
     return check_launch("lpips_backward(dgrad)");
 }
 
