@@ -11,7 +11,7 @@ import weakref
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E3DGE_LIB_PATH") or os.path.join(_HERE, "lib", "libe3dge_hip.so")   # override: kernel A/B variants
-ABI_VERSION = 16
+ABI_VERSION = 17
 PREC_F32, PREC_F16X3, PREC_F16X3_V1, PREC_F16X3_G2 = 0, 1, 2, 3
 AMAX_FLOATS = 64 * 32           # E3DGE_AMAX_FLOATS: one amax buffer (include/e3dge_hip.h)
 MC_MAX_TRIS = 16                # E3DGE_MC_MAX_TRIS: triangles per case in e3dge_marching_cubes_tables (include/e3dge_hip.h)
@@ -349,12 +349,11 @@ SIGNATURES = {
     "e3dge_pos_encoding": (_i32, [_vp, _i32, _i32, _vp, _i64, _i32, _vp]),
     "e3dge_image_metrics_scratch_floats": (_i64, [_i32, _i32, _i32, _i32]),
     "e3dge_image_metrics": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
-    "e3dge_image_metric_row": (_i32, [_vp, _vp, _i32, _f32, _vp]),
+    "e3dge_image_metric_row": (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp]),
     "e3dge_lpips_packed_floats": (_i64, []),
     "e3dge_lpips_pack_weights": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "e3dge_lpips_ws_bytes": (_i64, [_i32, _i32, _i32]),
     "e3dge_lpips_forward": (_i32, [ctypes.POINTER(LpipsArgs), _vp]),
-    "e3dge_image_metric_row_lpips": (_i32, [_vp, _vp, _vp, _i32, _f32, _f32, _vp]),
     "e3dge_lpips_packed_t_floats": (_i64, []),
     "e3dge_lpips_pack_weights_t": (_i32, [_vp, _vp, _vp]),
     "e3dge_lpips_bwd_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
@@ -374,7 +373,6 @@ SIGNATURES = {
     "e3dge_idnet_backward": (_i32, [ctypes.POINTER(IdnetBwdArgs), _vp]),
     "e3dge_idnet_conv_bwd": (_i32, [_vp] * 9 + [_i32] * 7 + [_vp]),
     "e3dge_idnet_prep_bwd": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
-    "e3dge_image_metric_row_full": (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _vp]),
     "e3dge_hitprob_points": (_i32, [_vp] * 8 + [_i32, _i64, _i32, _i32, _vp]),
     "e3dge_hitprob_composite": (_i32, [_vp] * 6 + [_f32, _i32, _i32, _i64, _i32, _i32, _vp]),
     "e3dge_align_volume": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
@@ -463,6 +461,16 @@ def check(rc, what):
     if rc != 0:
         msg = load().e3dge_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+
+
+def query(name, *args, exc=RuntimeError):
+    """The value of the size entry `name` (a *_bytes / *_floats query: a plain call, no stream); a negative one raises `exc` with the
+    entry's name and the library's message."""
+    lib = load()
+    v = getattr(lib, name)(*args)
+    if v < 0:
+        raise exc(f"{name}: {lib.e3dge_last_error().decode(errors='replace')}")
+    return v
 
 
 STAMP_UNITS = ("siren", "siren_bwd", "resblock", "modconv", "decoder2")      # kStampUnit* (csrc/stamps.h), in order
@@ -607,6 +615,16 @@ def cached(module, slot, sources, build, extra=(), limit=1):
     entries[:] = keep[max(0, len(keep) - (limit - 1)):]
     entries.append((list(sources), sig, extra, _fingerprint(sources) if STRICT_WEIGHT_CACHE else None, value))
     return value
+
+
+def weight_image(module, slot, sources, device, who, build):
+    """cached(module, slot, sources, build) for a packed weight image that a launch on `device` will read: every source must be float32
+    and live there (a pointer from elsewhere would fault inside the pack kernel), or it raises RuntimeError naming `who`."""
+    import torch
+    for t in sources:
+        if t.device != device or t.dtype != torch.float32:
+            raise RuntimeError(f"{who} weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
+    return cached(module, slot, sources, build)
 
 
 def latest(module, slot):

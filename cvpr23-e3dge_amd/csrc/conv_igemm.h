@@ -7,7 +7,8 @@
 //   A operand   read from a packed weight image in fragment order, one coalesced dword per lane and matrix step, no LDS:
 //               image[(mt * KS4 + ks) * 64 + lane] = A[mt * 16 + (lane & 15)][ks * 4 + (lane >> 4)], 0 past M or K, K padded to kIgKC
 //               (ig_kpad) and M to 16 (ig_mpad).  conv_pack_kernel writes it from W[M][K], conv_pack_t_kernel writes the transposed,
-//               tap-flipped image of a data gradient; both round `w * scale` once (scale 1 is exact).
+//               tap-flipped image of a data gradient; both round `w * scale` once (scale 1 is exact).  conv_copy_kernel moves what
+//               is not a fragment image (biases, linear layers, FIRs) into the same packed buffer, with the same rounding.
 //   B operand   the im2col tile of kIgKC = 32 k x 16 NT pixels, staged in LDS by the kernel's gather with the NEXT tile's loads in
 //               flight during the matrix steps.  Row pitch BN + 16: the four k rows of one read land in four bank groups.
 //   k loop      ig_k_loop: per staged tile eight A fragments and eight matrix steps per pixel tile; step j adds into accumulator
@@ -118,6 +119,18 @@ static __global__ void __launch_bounds__(256) conv_pack_t_kernel(float* __restri
         v = __fmul_rn(w[(((int64_t)co * Cin + ci) * KS + (KS - 1 - r)) * KS + (KS - 1 - s)], scale);
     }
     dst[i] = v;
+}
+
+// dst[i] = fl(src[i] * scale); flip: src is read back to front.  Everything of a packed image that is not an A-fragment image: biases,
+// the linear layers, the FIR of a blur (flipped: its adjoint's).
+static __global__ void __launch_bounds__(256) conv_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, float scale, int flip,
+                                                               int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) dst[i] = __fmul_rn(src[flip ? total - 1 - i : i], scale);
+}
+
+static inline void ig_copy(float* dst, const float* src, int64_t total, float scale, int flip, hipStream_t st) {
+    conv_copy_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(dst, src, scale, flip, total);
 }
 
 // W (cout, cin, ks, ks) -> the forward image: ig_mpad(cout) * ig_kpad(cin ks ks) floats

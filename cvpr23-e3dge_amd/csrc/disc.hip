@@ -97,12 +97,7 @@ static void dc_layout(const DcNet& n, DcLayout* l) {
 
 // ---- packing ----------------------------------------------------------------------------------------------------------------------
 // The A-fragment images come from conv_igemm.h's packers with EqualConv2d's scale: the product is rounded once, as `weight * scale` is on
-// every call of the reference.
-// dst[i] = fl(src[i] * scale); flip: dst[i] = src[total - 1 - i] (the FIR of the blur's adjoint)
-__global__ void __launch_bounds__(256) disc_pack_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, float scale, int flip, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < total) dst[i] = __fmul_rn(src[flip ? total - 1 - i : i], scale);
-}
+// every call of the reference.  Biases, the two linear layers and the FIR (flipped: the blur's adjoint's) go through ig_copy.
 
 // ---- convolution ----------------------------------------------------------------------------------------------------------------
 struct DcGemmArgs {
@@ -435,16 +430,13 @@ extern "C" int e3dge_disc_pack_weights(float* packed, const E3dgeDiscPackSrc* sr
     DcLayout l;
     dc_layout(net, &l);
     hipStream_t st = as_stream(stream);
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     auto eq_scale = [](int fan_in) { return (float)(1.0 / sqrt((double)fan_in)); };
     auto conv = [&](int64_t fw, int64_t tw, const float* w, int ci, int co, int ks) {
         const float scale = eq_scale(ci * ks * ks);
         ig_pack(packed + fw, w, ci, co, ks, scale, st);
         ig_pack_t(packed + tw, w, ci, co, ks, scale, st);
     };
-    auto copy = [&](int64_t off, const float* from, int64_t n, float scale, int flip) {
-        disc_pack_copy_kernel<<<blocks(n), dim3(256), 0, st>>>(packed + off, from, scale, flip, n);
-    };
+    auto copy = [&](int64_t off, const float* from, int64_t n, float scale, int flip) { ig_copy(packed + off, from, n, scale, flip, st); };
     conv(l.stem_w, l.stem_wt, s.stem_w, net.cin, net.c[0], 1);
     copy(l.stem_b, s.stem_b, net.c[0], 1.0f, 0);
     for (int i = 0; i < net.n_blocks; ++i) {

@@ -93,11 +93,6 @@ __global__ void __launch_bounds__(256) idnet_pack_bn_kernel(float* __restrict__ 
     dst[2 * c + 1] = __fsub_rn(beta[c], __fmul_rn(mean[c], a));
 }
 
-__global__ void __launch_bounds__(256) idnet_copy_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < total) dst[i] = src[i];
-}
-
 // ---- crop and pool ------------------------------------------------------------------------------------------------------------
 struct IdPrepArgs { float* out; const float* set[3]; int n_per_set, n, H, W; };
 
@@ -364,23 +359,6 @@ __global__ void __launch_bounds__(192) idnet_dot_kernel(float* __restrict__ dots
     }
 }
 
-// image_metric_row_lpips_kernel (lpips.hip) with the identity columns: builder.py:168, :174-184
-__global__ void image_metric_row_full_kernel(float* __restrict__ row, const float* __restrict__ sums, const float* __restrict__ lp,
-                                             const float* __restrict__ id, int batch, float l2_lambda, float vgg_lambda, float id_lambda) {
-    if (threadIdx.x != 0) return;
-    float t0 = 0.f, t1 = 0.f, t2 = 0.f, n = 0.f, tl = 0.f;
-    for (int b = 0; b < batch; ++b) {
-        t0 += sums[b * 4]; t1 += sums[b * 4 + 1]; t2 += sums[b * 4 + 2]; n += sums[b * 4 + 3];
-        if (lp) tl += lp[b];
-    }
-    const float mse = t0 / n, mae = t1 / n, ssim_loss = t2 / n, lpips = lp ? tl / (float)batch : 0.0f, loss_id = id ? id[0] : 0.0f;
-    row[0] = mse; row[1] = loss_id; row[2] = lpips;
-    row[3] = __fadd_rn(__fadd_rn(__fmul_rn(mse, l2_lambda), __fmul_rn(lpips, vgg_lambda)), __fmul_rn(loss_id, id_lambda));
-    row[4] = mae;
-    row[5] = 10.0f * log10f(1.0f / (mse * 0.25f));
-    row[6] = 1.0f - ssim_loss; row[7] = __fsub_rn(1.0f, loss_id);
-}
-
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 static int id_out_size(int in, int stride) { return (in - 1) / stride + 1; }     // 3x3 pad 1 and 1x1 pad 0 alike
 
@@ -482,7 +460,7 @@ extern "C" int e3dge_idnet_pack_weights(float* packed, const E3dgeIdnetPackSrc* 
     const IdLayout& l = id_layout();
     hipStream_t st = as_stream(stream);
     auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    auto copy = [&](int64_t off, const float* from, int64_t n) { idnet_copy_kernel<<<blocks(n), dim3(256), 0, st>>>(packed + off, from, n); };
+    auto copy = [&](int64_t off, const float* from, int64_t n) { ig_copy(packed + off, from, n, 1.0f, 0, st); };
     for (int i = 0; i < kIdConvs; ++i) ig_pack(packed + l.w_off[i], s.conv_w[i], l.cin[i], l.cout[i], l.ks[i], 1.0f, st);
     for (int i = 0; i < kIdBns; ++i)
         idnet_pack_bn_kernel<<<blocks(l.bn_c[i]), dim3(256), 0, st>>>(packed + l.bn_off[i], s.bn_weight[i], s.bn_bias[i], s.bn_mean[i], s.bn_var[i],
@@ -650,15 +628,6 @@ extern "C" int e3dge_idnet_conv(float* out, const float* in, const float* w, flo
     int rc;
     if ((rc = check_launch("idnet_conv(pack)"))) return rc;
     return id_conv(out, in, wfrag, in_ab, epi_ab, slope, plane, n, cin, cout, height, width, ksize, stride, st);
-}
-
-extern "C" int e3dge_image_metric_row_full(float* row, const float* sums, const float* lpips_per_image, const float* id_loss, int batch,
-                                           float l2_lambda, float vgg_lambda, float id_lambda, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(batch >= 1, "image_metric_row_full: batch=%d", batch);
-    E3DGE_REQUIRE(row && sums, "image_metric_row_full: null pointer");
-    image_metric_row_full_kernel<<<dim3(1), dim3(64), 0, as_stream(stream)>>>(row, sums, lpips_per_image, id_loss, batch, l2_lambda, vgg_lambda,
-                                                                               id_lambda);
-    return check_launch("image_metric_row_full");
 }
 
 #include "idnet_bwd.h"

@@ -46,42 +46,9 @@ constexpr int64_t kLpChannels = lp_c_off(kLpLayers - 1) + lp_cout(kLpLayers - 1)
 constexpr int64_t kLpLinOff = kLpBiasOff + kLpChannels;
 constexpr int64_t kLpPackedFloats = kLpLinOff + kLpChannels;
 
-struct LpPackSrc { const float* w[kLpLayers]; const float* b[kLpLayers]; const float* lin[kLpLayers]; };
-
-// packed[lp_w_off(l) + ((mt * KS + ks) * 64 + lane)] = W_l[mt * 16 + (lane & 15)][ks * 4 + (lane >> 4)]   (0 past K), KS = Kpad / 4:
-// the A operand of v_mfma_f32_16x16x4_f32 for channel tile mt and k-step ks, one dword per lane.
-template <typename T> __device__ __forceinline__ T lp_pick(const T (&a)[kLpLayers], int l) {     // (no dynamic index into kernel arguments)
-    T v = a[0];
-#pragma unroll
-    for (int q = 1; q < kLpLayers; ++q) if (l == q) v = a[q];
-    return v;
-}
-
-__global__ void __launch_bounds__(256) lpips_pack_kernel(float* __restrict__ packed, LpPackSrc src) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= kLpPackedFloats) return;
-    if (i >= kLpBiasOff) {
-        int64_t c = i - kLpBiasOff;
-        const bool is_lin = c >= kLpChannels;
-        if (is_lin) c -= kLpChannels;
-        int l = 0, first = 0;
-#pragma unroll
-        for (int q = 1; q < kLpLayers; ++q) if (c >= lp_c_off(q)) { l = q; first = (int)lp_c_off(q); }
-        const int j = (int)c - first;
-        packed[i] = is_lin ? lp_pick(src.lin, l)[j] : lp_pick(src.b, l)[j];
-        return;
-    }
-    int l = 0, K = lp_k(0), KS = lp_kpad(0) / 4;
-    int64_t first = 0;
-#pragma unroll
-    for (int q = 1; q < kLpLayers; ++q) if (i >= lp_w_off(q)) { l = q; first = lp_w_off(q); K = lp_k(q); KS = lp_kpad(q) / 4; }
-    const int64_t e = i - first;
-    const int lane = (int)(e & 63);
-    const int64_t t = e >> 6;
-    const int ks = (int)(t % KS), mt = (int)(t / KS);
-    const int row = mt * 16 + (lane & 15), k = ks * 4 + (lane >> 4);
-    packed[i] = k < K ? lp_pick(src.w, l)[(int64_t)row * K + k] : 0.0f;
-}
+// The packed image: at lp_w_off(l) conv_igemm.h's forward image of W_l (ig_pack; every C_out is a multiple of 16, so no rows are added),
+// then the five biases at kLpBiasOff + lp_c_off(l) and the five lin rows at kLpLinOff + lp_c_off(l), as they are.
+static_assert(lp_cout(0) % 16 == 0 && lp_cout(1) % 16 == 0 && lp_cout(2) % 16 == 0 && lp_cout(3) % 16 == 0, "lp_w_floats has no padded rows");
 
 struct LpNorm { float mean[3], std[3]; };
 
@@ -281,18 +248,6 @@ __global__ void __launch_bounds__(64 * kLpLayers) lpips_fold_kernel(LpFoldArgs a
     if (threadIdx.x == 0 && a.mean) a.mean[0] = total / (float)a.batch;
 }
 
-// image_metric_row_kernel (metrics.hip) with the LPIPS column filled: builder.py:168 with id_lambda = 0, :174-184
-__global__ void image_metric_row_lpips_kernel(float* __restrict__ row, const float* __restrict__ sums, const float* __restrict__ lp,
-                                              int batch, float l2_lambda, float vgg_lambda) {
-    if (threadIdx.x != 0) return;
-    float t0 = 0.f, t1 = 0.f, t2 = 0.f, n = 0.f, tl = 0.f;
-    for (int b = 0; b < batch; ++b) { t0 += sums[b * 4]; t1 += sums[b * 4 + 1]; t2 += sums[b * 4 + 2]; n += sums[b * 4 + 3]; tl += lp[b]; }
-    const float mse = t0 / n, mae = t1 / n, ssim_loss = t2 / n, lpips = tl / (float)batch;
-    row[0] = mse; row[1] = 0.0f; row[2] = lpips; row[3] = __fadd_rn(__fmul_rn(mse, l2_lambda), __fmul_rn(lpips, vgg_lambda)); row[4] = mae;
-    row[5] = 10.0f * log10f(1.0f / (mse * 0.25f));
-    row[6] = 1.0f - ssim_loss; row[7] = 1.0f;
-}
-
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 struct LpDims {
     int h[kLpLayers], w[kLpLayers];            // the five conv outputs (= taps)
@@ -362,12 +317,13 @@ extern "C" int64_t e3dge_lpips_packed_floats(void) { return kLpPackedFloats; }
 extern "C" int e3dge_lpips_pack_weights(float* packed, const float* const* w, const float* const* b, const float* const* lin,
                                         e3dge_stream_t stream) {
     E3DGE_REQUIRE(packed && w && b && lin, "lpips_pack_weights: null pointer");
-    LpPackSrc src;
+    for (int l = 0; l < kLpLayers; ++l) E3DGE_REQUIRE(w[l] && b[l] && lin[l], "lpips_pack_weights: null pointer (layer %d)", l);
+    hipStream_t st = as_stream(stream);
     for (int l = 0; l < kLpLayers; ++l) {
-        E3DGE_REQUIRE(w[l] && b[l] && lin[l], "lpips_pack_weights: null pointer (layer %d)", l);
-        src.w[l] = w[l]; src.b[l] = b[l]; src.lin[l] = lin[l];
+        ig_pack(packed + lp_w_off(l), w[l], lp_cin(l), lp_cout(l), lp_ks(l), 1.0f, st);
+        ig_copy(packed + kLpBiasOff + lp_c_off(l), b[l], lp_cout(l), 1.0f, 0, st);
+        ig_copy(packed + kLpLinOff + lp_c_off(l), lin[l], lp_cout(l), 1.0f, 0, st);
     }
-    lpips_pack_kernel<<<dim3((unsigned)((kLpPackedFloats + 255) / 256)), dim3(256), 0, as_stream(stream)>>>(packed, src);
     return check_launch("lpips_pack_weights");
 }
 
@@ -426,12 +382,10 @@ extern "C" int64_t e3dge_lpips_packed_t_floats(void) { return kLpPackedTFloats; 
 
 extern "C" int e3dge_lpips_pack_weights_t(float* packed_t, const float* const* w, e3dge_stream_t stream) {
     E3DGE_REQUIRE(packed_t && w, "lpips_pack_weights_t: null pointer");
-    LpPackTSrc src;
-    for (int l = 0; l < kLpLayers; ++l) {
-        E3DGE_REQUIRE(w[l], "lpips_pack_weights_t: null pointer (layer %d)", l);
-        src.w[l] = w[l];
-    }
-    lpips_pack_t_kernel<<<dim3((unsigned)((kLpPackedTFloats + 255) / 256)), dim3(256), 0, as_stream(stream)>>>(packed_t, src);
+    for (int l = 0; l < kLpLayers; ++l) E3DGE_REQUIRE(w[l], "lpips_pack_weights_t: null pointer (layer %d)", l);
+    hipStream_t st = as_stream(stream);
+    for (int l = 1; l < kLpLayers; ++l) ig_pack_t(packed_t + lp_wt_off(l), w[l], lp_cin(l), lp_cout(l), lp_ks(l), 1.0f, st);
+    lpips_pack_w1t_kernel<<<dim3((unsigned)((kLpW1tFloats + 255) / 256)), dim3(256), 0, st>>>(packed_t + kLpW1tOff, w[0]);
     return check_launch("lpips_pack_weights_t");
 }
 
@@ -449,12 +403,4 @@ extern "C" int64_t e3dge_lpips_bwd_ws_bytes(int batch, int height, int width, in
 extern "C" int e3dge_lpips_backward(const E3dgeLpipsBwdArgs* args, e3dge_stream_t stream) {
     E3DGE_REQUIRE(args, "lpips_backward: null argument struct");
     return lp_backward(*args, as_stream(stream));
-}
-
-extern "C" int e3dge_image_metric_row_lpips(float* row, const float* sums, const float* lpips_per_image, int batch, float l2_lambda,
-                                            float vgg_lambda, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(batch >= 1, "image_metric_row_lpips: batch=%d", batch);
-    E3DGE_REQUIRE(row && sums && lpips_per_image, "image_metric_row_lpips: null pointer");
-    image_metric_row_lpips_kernel<<<dim3(1), dim3(64), 0, as_stream(stream)>>>(row, sums, lpips_per_image, batch, l2_lambda, vgg_lambda);
-    return check_launch("image_metric_row_lpips");
 }

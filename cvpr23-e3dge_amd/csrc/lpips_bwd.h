@@ -37,32 +37,13 @@ constexpr int64_t kLpW1tFloats = (int64_t)lp_cin(0) * lp_cout(0) * lp_ks(0) * lp
 constexpr int64_t kLpPackedTFloats = kLpW1tOff + kLpW1tFloats;
 static_assert(lp_cin(1) % kIgBM == 0 && lp_cin(2) % kIgBM == 0 && lp_cin(3) % kIgBM == 0 && lp_cin(4) % kIgBM == 0, "whole channel tiles");
 
-struct LpPackTSrc { const float* w[kLpLayers]; };
-
-__global__ void __launch_bounds__(256) lpips_pack_t_kernel(float* __restrict__ packed_t, LpPackTSrc src) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= kLpPackedTFloats) return;
-    if (i >= kLpW1tOff) {
-        constexpr int KK = lp_ks(0) * lp_ks(0);
-        const int e = (int)(i - kLpW1tOff), c = e / (lp_cout(0) * KK), rest = e - c * (lp_cout(0) * KK), co = rest / KK, rs = rest - co * KK;
-        packed_t[i] = src.w[0][(co * lp_cin(0) + c) * KK + rs];
-        return;
-    }
-    int l = 1;
-#pragma unroll
-    for (int q = 2; q < kLpLayers; ++q) if (i >= lp_wt_off(q)) l = q;
-    int K = lp_kt(1), KS = lp_ktpad(1) / 4, KK = lp_ks(1) * lp_ks(1), Cin = lp_cin(1);
-    int64_t first = lp_wt_off(1);
-#pragma unroll
-    for (int q = 2; q < kLpLayers; ++q)
-        if (l == q) { K = lp_kt(q); KS = lp_ktpad(q) / 4; KK = lp_ks(q) * lp_ks(q); Cin = lp_cin(q); first = lp_wt_off(q); }
-    const int64_t e = i - first;
-    const int lane = (int)(e & 63);
-    const int64_t t = e >> 6;
-    const int ks = (int)(t % KS), mt = (int)(t / KS);
-    const int ci = mt * 16 + (lane & 15), k = ks * 4 + (lane >> 4);
-    const int co = k / KK, rs = k - co * KK;
-    packed_t[i] = k < K ? lp_pick(src.w, l)[((int64_t)co * Cin + ci) * KK + (KK - 1 - rs)] : 0.0f;
+// conv 1's block, the one layout conv_igemm.h does not know: w1t[c][co][rs] = W_1[co][c][rs]
+__global__ void __launch_bounds__(256) lpips_pack_w1t_kernel(float* __restrict__ w1t, const float* __restrict__ w) {
+    constexpr int KK = lp_ks(0) * lp_ks(0);
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kLpW1tFloats) return;
+    const int c = e / (lp_cout(0) * KK), rest = e - c * (lp_cout(0) * KK), co = rest / KK, rs = rest - co * KK;
+    w1t[e] = w[(co * lp_cin(0) + c) * KK + rs];
 }
 
 // ---- tap backward ---------------------------------------------------------------------------------------------------------------------

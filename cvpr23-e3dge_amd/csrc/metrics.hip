@@ -3,8 +3,8 @@
 //
 // Reference: Loss.calc_2d_rec_loss (project/losses/builder.py:130-184): loss_l2 = MSE, mae = L1, PSNR on the [0,1]-scaled
 // images, SSIM = 1 - kornia.losses.ssim_loss(pred, gt, window 5) (Gaussian window sigma 1.5, reflect padding,
-// C1 = 0.01^2, C2 = 0.03^2, loss = mean(clamp((1 - ssim) / 2, 0, 1))).  The identity term needs a pretrained network and is
-// outside the path (reported as 0); the LPIPS term is csrc/lpips.hip, whose row kernel fills the loss_lpips column.
+// C1 = 0.01^2, C2 = 0.03^2, loss = mean(clamp((1 - ssim) / 2, 0, 1))).  The LPIPS term is csrc/lpips.hip and the identity term
+// csrc/idnet.hip; the row kernel here takes their results and fills the loss_lpips, loss_id and ID_SIM columns.
 //
 // One 32x32-pixel tile of one channel per workgroup: both images (+2-pixel reflected halo) staged in LDS once, the five
 // windowed moments of every pixel from 25 taps, per-workgroup partial sums (squared error, absolute error, SSIM loss) to a
@@ -110,26 +110,35 @@ image_metrics_fold_kernel(float* __restrict__ out, const float* __restrict__ par
     if (threadIdx.x == 3) out[b * 4 + 3] = count;
 }
 
-// the eight reported columns from the per-image sums (builder.py:174-184): means over the whole batch tensor, PSNR on images
-// rescaled to [0, 1] (squared error / 4); the identity / LPIPS columns are the reference's values at lambda = 0
-__global__ void image_metric_row_kernel(float* __restrict__ row, const float* __restrict__ sums, int batch, float l2_lambda) {
+// the eight reported columns from the per-image sums (builder.py:168, :174-184): means over the whole batch tensor, PSNR on images
+// rescaled to [0, 1] (squared error / 4).  lp (per-image LPIPS, csrc/lpips.hip) and id (the identity loss, csrc/idnet.hip) may be NULL:
+// the column is then the reference's value at lambda = 0 and the term is not added to `loss`.
+__global__ void image_metric_row_kernel(float* __restrict__ row, const float* __restrict__ sums, const float* __restrict__ lp,
+                                        const float* __restrict__ id, int batch, float l2_lambda, float vgg_lambda, float id_lambda) {
     if (threadIdx.x != 0) return;
-    float t0 = 0.f, t1 = 0.f, t2 = 0.f, n = 0.f;
-    for (int b = 0; b < batch; ++b) { t0 += sums[b * 4]; t1 += sums[b * 4 + 1]; t2 += sums[b * 4 + 2]; n += sums[b * 4 + 3]; }
-    const float mse = t0 / n, mae = t1 / n, ssim_loss = t2 / n;
-    row[0] = mse; row[1] = 0.0f; row[2] = 0.0f; row[3] = mse * l2_lambda; row[4] = mae;
+    float t0 = 0.f, t1 = 0.f, t2 = 0.f, n = 0.f, tl = 0.f;
+    for (int b = 0; b < batch; ++b) {
+        t0 += sums[b * 4]; t1 += sums[b * 4 + 1]; t2 += sums[b * 4 + 2]; n += sums[b * 4 + 3];
+        if (lp) tl += lp[b];
+    }
+    const float mse = t0 / n, mae = t1 / n, ssim_loss = t2 / n, lpips = lp ? tl / (float)batch : 0.0f, loss_id = id ? id[0] : 0.0f;
+    float loss = __fmul_rn(mse, l2_lambda);
+    if (lp) loss = __fadd_rn(loss, __fmul_rn(lpips, vgg_lambda));
+    if (id) loss = __fadd_rn(loss, __fmul_rn(loss_id, id_lambda));
+    row[0] = mse; row[1] = loss_id; row[2] = lpips; row[3] = loss; row[4] = mae;
     row[5] = 10.0f * log10f(1.0f / (mse * 0.25f));
-    row[6] = 1.0f - ssim_loss; row[7] = 1.0f;
+    row[6] = 1.0f - ssim_loss; row[7] = __fsub_rn(1.0f, loss_id);
 }
 
 }  // namespace e3dge
 
 using namespace e3dge;
 
-extern "C" int e3dge_image_metric_row(float* row, const float* sums, int batch, float l2_lambda, e3dge_stream_t stream) {
+extern "C" int e3dge_image_metric_row(float* row, const float* sums, const float* lpips_per_image, const float* id_loss, int batch,
+                                      float l2_lambda, float vgg_lambda, float id_lambda, e3dge_stream_t stream) {
     E3DGE_REQUIRE(batch >= 1, "image_metric_row: batch=%d", batch);
     E3DGE_REQUIRE(row && sums, "image_metric_row: null pointer");
-    image_metric_row_kernel<<<dim3(1), dim3(64), 0, as_stream(stream)>>>(row, sums, batch, l2_lambda);
+    image_metric_row_kernel<<<dim3(1), dim3(64), 0, as_stream(stream)>>>(row, sums, lpips_per_image, id_loss, batch, l2_lambda, vgg_lambda, id_lambda);
     return check_launch("image_metric_row");
 }
 

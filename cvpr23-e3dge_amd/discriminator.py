@@ -204,9 +204,6 @@ class Discriminator(nn.Module):
     def _packed(self, device):
         groups = self._sources()
         src = [t for g in groups.values() for t in g]
-        for t in src:
-            if t.device != device or t.dtype != torch.float32:
-                raise RuntimeError(f"Discriminator weights must be float32 on the input's device {device} (got {t.dtype} on {t.device})")
 
         def build():
             with torch.no_grad():
@@ -222,20 +219,11 @@ class Discriminator(nn.Module):
                 s.final_w, s.final_b = keep["final"]
                 s.lin1_w, s.lin1_b, s.lin2_w, s.lin2_b = keep["lin"]
                 s.blur = keep["blur"][0]
-                floats = _lib.load().e3dge_disc_packed_floats(*self._key())
-                if floats < 0:
-                    raise RuntimeError(f"e3dge_disc_packed_floats: {_lib.load().e3dge_last_error().decode(errors='replace')}")
-                packed = torch.empty(floats, device=device, dtype=torch.float32)
+                packed = torch.empty(_lib.query("e3dge_disc_packed_floats", *self._key()), device=device, dtype=torch.float32)
                 _lib.launch("e3dge_disc_pack_weights", packed, s)
                 return packed
 
-        return _lib.cached(self, "disc_packed", src, build)
-
-    def _sizes(self, what, *args):
-        v = getattr(_lib.load(), what)(*args)
-        if v < 0:
-            raise ValueError(f"{what}: {_lib.load().e3dge_last_error().decode(errors='replace')}")
-        return v
+        return _lib.weight_image(self, "disc_packed", src, device, "Discriminator", build)
 
     def tap_shapes(self, batch):
         """{tap index: shape} of the tensors e3dge_disc_forward can write beside the logits."""
@@ -255,7 +243,7 @@ class Discriminator(nn.Module):
         stddev_group(B, self.stddev_group)
         dev = input.device
         x = input.detach().contiguous()
-        ws_bytes = self._sizes("e3dge_disc_ws_bytes", B, H, W, *self._key(), 0)
+        ws_bytes = _lib.query("e3dge_disc_ws_bytes", B, H, W, *self._key(), 0, exc=ValueError)
         ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         logits = torch.empty((B, 1), device=dev, dtype=torch.float32)
         a = _lib.DiscArgs(packed=self._packed(dev), images=x, n=B, height=H, width=W, init_size=self.init_size,
@@ -266,7 +254,7 @@ class Discriminator(nn.Module):
             for t, v in tl.items():
                 a.taps[t] = v.data_ptr()
         if save:
-            saved_bytes = self._sizes("e3dge_disc_saved_bytes", B, *self._key())
+            saved_bytes = _lib.query("e3dge_disc_saved_bytes", B, *self._key(), exc=ValueError)
             saved = torch.empty(saved_bytes, device=dev, dtype=torch.uint8)
             a.saved, a.saved_bytes = saved, saved_bytes
         _lib.launch("e3dge_disc_forward", a)
@@ -276,7 +264,7 @@ class Discriminator(nn.Module):
         """(grad_images, {tap: gradient} or None) from the state a saving forward of an input of `shape` left behind."""
         B, _, H, W = shape
         dev = saved.device
-        ws_bytes = self._sizes("e3dge_disc_ws_bytes", B, H, W, *self._key(), 1)
+        ws_bytes = _lib.query("e3dge_disc_ws_bytes", B, H, W, *self._key(), 1, exc=ValueError)
         ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         grad = torch.empty(shape, device=dev, dtype=torch.float32)
         g = grad_logits.detach().to(torch.float32).reshape(B, 1).contiguous()

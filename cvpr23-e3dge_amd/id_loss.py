@@ -150,9 +150,6 @@ class IDLoss(nn.Module):
     def _packed(self, device):
         groups = self._sources()
         src = [t for g in groups.values() for t in g]
-        for t in src:
-            if t.device != device or t.dtype != torch.float32:
-                raise RuntimeError(f"IDLoss weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
 
         def build():
             with torch.no_grad():
@@ -163,30 +160,27 @@ class IDLoss(nn.Module):
                         setattr(s, k, g[0].data_ptr())
                     else:
                         getattr(s, k)[:] = [t.data_ptr() for t in g]
-                packed = torch.empty(_lib.load().e3dge_idnet_packed_floats(), device=device, dtype=torch.float32)
+                packed = torch.empty(_lib.query("e3dge_idnet_packed_floats"), device=device, dtype=torch.float32)
                 _lib.launch("e3dge_idnet_pack_weights", packed, ctypes.addressof(s))
                 return packed
 
-        return _lib.cached(self, "idnet_packed", src, build)
+        return _lib.weight_image(self, "idnet_packed", src, device, "IDLoss", build)
 
     def _packed_t(self, device):
         """The transposed weight image of the backward, on the same sources as the forward image."""
         groups = self._sources()
         src = [t for g in groups.values() for t in g]
-        for t in src:
-            if t.device != device or t.dtype != torch.float32:
-                raise RuntimeError(f"IDLoss weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
 
         def build():
             with torch.no_grad():
                 keep = [t.detach().contiguous() for t in groups["conv_w"]]
                 s = _lib.IdnetPackSrc()
                 s.conv_w[:] = [t.data_ptr() for t in keep]
-                packed_t = torch.empty(_lib.load().e3dge_idnet_packed_t_floats(), device=device, dtype=torch.float32)
+                packed_t = torch.empty(_lib.query("e3dge_idnet_packed_t_floats"), device=device, dtype=torch.float32)
                 _lib.launch("e3dge_idnet_pack_weights_t", packed_t, ctypes.addressof(s))
                 return packed_t
 
-        return _lib.cached(self, "idnet_packed_t", src, build)
+        return _lib.weight_image(self, "idnet_packed_t", src, device, "IDLoss", build)
 
     def _check(self, sets):
         self._check_shapes(sets)
@@ -228,12 +222,9 @@ class IDLoss(nn.Module):
             return torch.cat(embs), ([torch.cat(t) for t in zip(*per_set)] if taps else None)
         for i, t in enumerate(sets):
             _lib.require_gpu(t, f"IDLoss input {i}")
-        lib = _lib.load()
         packed = self._packed(dev)
         keep = [t.detach().contiguous() for t in sets]
-        ws_bytes = lib.e3dge_idnet_ws_bytes(n)
-        if ws_bytes < 0:
-            raise RuntimeError(f"e3dge_idnet_ws_bytes: {lib.e3dge_last_error().decode(errors='replace')}")
+        ws_bytes = _lib.query("e3dge_idnet_ws_bytes", n)
         ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         emb = torch.empty((n, EMBED), device=dev, dtype=torch.float32)
         a = _lib.IdnetArgs(packed=packed, n_per_set=B, n_sets=len(sets), height=S, width=S, embeddings=emb, ws=ws, ws_bytes=ws_bytes)
@@ -246,9 +237,7 @@ class IDLoss(nn.Module):
                 a.taps[i] = t.data_ptr()
         a._note(dev)
         if n_saved:
-            saved_bytes = lib.e3dge_idnet_saved_bytes(n_saved)
-            if saved_bytes < 0:
-                raise RuntimeError(f"e3dge_idnet_saved_bytes: {lib.e3dge_last_error().decode(errors='replace')}")
+            saved_bytes = _lib.query("e3dge_idnet_saved_bytes", n_saved)
             saved = torch.empty(saved_bytes, device=dev, dtype=torch.uint8)
             sa = _lib.IdnetSaveArgs(net=a, saved=saved, saved_bytes=saved_bytes, n_saved=n_saved)
             _lib.launch("e3dge_idnet_embed_save", sa)
@@ -261,10 +250,7 @@ class IDLoss(nn.Module):
         `shape` left behind; grad_emb (B, 512) = dL / d f_hat."""
         B, _, S, _ = shape
         dev = saved.device
-        lib = _lib.load()
-        ws_bytes = lib.e3dge_idnet_bwd_ws_bytes(B, S, S)
-        if ws_bytes < 0:
-            raise RuntimeError(f"e3dge_idnet_bwd_ws_bytes: {lib.e3dge_last_error().decode(errors='replace')}")
+        ws_bytes = _lib.query("e3dge_idnet_bwd_ws_bytes", B, S, S)
         ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         grad = torch.empty(shape, device=dev, dtype=torch.float32)
         a = _lib.IdnetBwdArgs(packed=self._packed(dev), packed_t=self._packed_t(dev), saved=saved, saved_bytes=saved.numel(), n=B, height=S,

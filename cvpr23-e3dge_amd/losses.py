@@ -176,7 +176,7 @@ class _MseFunction(torch.autograd.Function):
         scratch = torch.empty(_lib.load().e3dge_image_metrics_scratch_floats(B, C, H, W), device=p.device, dtype=torch.float32)
         _lib.launch("e3dge_image_metrics", sums, scratch, p, g, B, C, H, W, 1.0)
         row = torch.empty(8, device=p.device, dtype=torch.float32)
-        _lib.launch("e3dge_image_metric_row", row, sums, B, 1.0)
+        _lib.launch("e3dge_image_metric_row", row, sums, None, None, B, 1.0, 0.0, 0.0)
         side['sums'], side['pred'], side['gt'] = sums, p, g
         ctx.save_for_backward(p, g)
         ctx.set_materialize_grads(False)
@@ -295,7 +295,7 @@ class LossClass(nn.Module):
             lid = id_mod.run(pred, g)['loss'] if id_mod is not None else torch.zeros((), device=pred.device)
             loss = (mse * l2 + lp * vgg) + lid * idl
             row = torch.empty(8, device=pred.device, dtype=torch.float32)
-            _lib.launch("e3dge_image_metric_row_full", row, side['sums'], lp_res['per_image'].detach(),
+            _lib.launch("e3dge_image_metric_row", row, side['sums'], lp_res['per_image'].detach(),
                         lid.detach() if id_mod is not None else None, pred.shape[0], l2, vgg, idl)
             cols = [mse, lid, lp, loss, row[4], row[5], row[6], row[7]]
         else:

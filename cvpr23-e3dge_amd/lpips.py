@@ -110,35 +110,29 @@ class LPIPS(nn.Module):
 
     def _packed(self, device):
         src = self._sources()
-        for t in src:
-            if t.device != device or t.dtype != torch.float32:
-                raise RuntimeError(f"LPIPS weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
 
         def build():
             with torch.no_grad():
                 keep = [t.detach().contiguous() for t in src]
-                packed = torch.empty(_lib.load().e3dge_lpips_packed_floats(), device=device, dtype=torch.float32)
+                packed = torch.empty(_lib.query("e3dge_lpips_packed_floats"), device=device, dtype=torch.float32)
                 ptrs = [(ctypes.c_void_p * 5)(*[t.data_ptr() for t in keep[5 * i:5 * i + 5]]) for i in range(3)]
                 _lib.launch("e3dge_lpips_pack_weights", packed, *ptrs)
                 return packed
 
-        return _lib.cached(self, "lpips_packed", src, build)
+        return _lib.weight_image(self, "lpips_packed", src, device, "LPIPS", build)
 
     def _packed_t(self, device):
         """The transposed weight image of the backward, on the same sources as the forward image."""
         src = self._sources()
-        for t in src:
-            if t.device != device or t.dtype != torch.float32:
-                raise RuntimeError(f"LPIPS weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
 
         def build():
             with torch.no_grad():
                 keep = [t.detach().contiguous() for t in src[:5]]
-                packed_t = torch.empty(_lib.load().e3dge_lpips_packed_t_floats(), device=device, dtype=torch.float32)
+                packed_t = torch.empty(_lib.query("e3dge_lpips_packed_t_floats"), device=device, dtype=torch.float32)
                 _lib.launch("e3dge_lpips_pack_weights_t", packed_t, (ctypes.c_void_p * 5)(*[t.data_ptr() for t in keep]))
                 return packed_t
 
-        return _lib.cached(self, "lpips_packed_t", src, build)
+        return _lib.weight_image(self, "lpips_packed_t", src, device, "LPIPS", build)
 
     def _norm(self):
         """net.mean / net.std as host floats (read back once per buffer update, not per call)."""
@@ -166,9 +160,7 @@ class LPIPS(nn.Module):
         packed = self._packed(dev)
         mean, std = self._norm()
         x, y = x.detach().contiguous(), y.detach().contiguous()
-        ws_bytes = _lib.load().e3dge_lpips_ws_bytes(B, H, W)
-        if ws_bytes < 0:
-            raise RuntimeError(f"e3dge_lpips_ws_bytes: {_lib.load().e3dge_last_error().decode(errors='replace')}")
+        ws_bytes = _lib.query("e3dge_lpips_ws_bytes", B, H, W)
         ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         out = torch.empty(B + 1, device=dev, dtype=torch.float32)
         a = _lib.LpipsArgs(packed=packed, x=x, y=y, batch=B, height=H, width=W, per_image=out, mean_out=out.data_ptr() + 4 * B,
@@ -191,11 +183,8 @@ class LPIPS(nn.Module):
         upstream (B,) = dL / d per_image."""
         B, _, H, W = shape
         dev = ws.device
-        lib = _lib.load()
         both = bool(want_x and want_y)
-        ws_bytes = lib.e3dge_lpips_bwd_ws_bytes(B, H, W, int(both))
-        if ws_bytes < 0:
-            raise RuntimeError(f"e3dge_lpips_bwd_ws_bytes: {lib.e3dge_last_error().decode(errors='replace')}")
+        ws_bytes = _lib.query("e3dge_lpips_bwd_ws_bytes", B, H, W, int(both))
         bws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         gx = torch.empty(shape, device=dev, dtype=torch.float32) if want_x else None
         gy = torch.empty(shape, device=dev, dtype=torch.float32) if want_y else None

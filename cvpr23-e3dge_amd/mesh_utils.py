@@ -344,7 +344,7 @@ class MeshRenderer:
                     raise RuntimeError(f"mesh renderer: {name} must be (V, 3) on the device of verts, got {tuple(t.shape)}")
         normals = normals.detach().contiguous()
         colors = None if colors is None else colors.detach().contiguous()
-        lib, dev, S, K = _lib.load(), verts.device, self.image_size, self.faces_per_pixel
+        dev, S, K = verts.device, self.image_size, self.faces_per_pixel
         nv, nf = verts.shape[0], faces.shape[0]
         tiles = ((S + 15) // 16) ** 2
         fixed = bin_capacity is not None
@@ -359,9 +359,7 @@ class MeshRenderer:
         a.image, a.zbuf, a.pix_to_face, a.status = image, zbuf, pix, status
         for attempt in range(2):
             cap = min(cap, nf * tiles)
-            nbytes = lib.e3dge_mesh_render_ws_bytes(nv, nf, S, cap)
-            if nbytes < 0:
-                raise RuntimeError("mesh renderer: " + lib.e3dge_last_error().decode(errors="replace"))
+            nbytes = _lib.query("e3dge_mesh_render_ws_bytes", nv, nf, S, cap)
             ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
             a.ws, a.ws_bytes, a.bin_capacity = ws, nbytes, cap
             _lib.launch("e3dge_mesh_render", a)
@@ -570,7 +568,6 @@ def project_vertex_noise(verts, faces, vert_noise, camera, image_size, prev=None
         if prev.numel() != C * S * S or prev.device != dev:
             raise RuntimeError(f"project_vertex_noise: prev must be ({C}, {S}, {S}) on the device of verts, got {tuple(prev.shape)}")
         prev = prev.detach().contiguous()
-    lib = _lib.load()
     tiles = ((S + 15) // 16) ** 2
     fixed = bin_capacity is not None
     cap = int(bin_capacity) if fixed else 4 * nf + 64 * tiles
@@ -586,9 +583,7 @@ def project_vertex_noise(verts, faces, vert_noise, camera, image_size, prev=None
     a.out, a.valid, a.status = out, valid, status
     for attempt in range(2):
         cap = min(cap, nf * tiles, 2 ** 31 - 2)
-        nbytes = lib.e3dge_noise_project_ws_bytes(nv, nf, S, cap)
-        if nbytes < 0:
-            raise RuntimeError("project_vertex_noise: " + lib.e3dge_last_error().decode(errors="replace"))
+        nbytes = _lib.query("e3dge_noise_project_ws_bytes", nv, nf, S, cap)
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         a.ws, a.ws_bytes, a.bin_capacity = ws, nbytes, cap
         _lib.launch("e3dge_noise_project", a)

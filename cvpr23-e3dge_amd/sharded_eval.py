@@ -121,15 +121,9 @@ def image_metrics(pred, gt, l2_lambda=1.0, lpips=None, vgg_lambda=0.0, id_loss=N
         # the reference's losses are means over the whole batch tensor; the eight columns in one more launch (as torch ops
         # this tail was thirteen 5-us kernels: 3 % of an evaluated image)
         row = torch.empty(8, device=p.device, dtype=torch.float32)
-        if id_loss is not None:
-            per_image = None if lpips is None else lpips(p, g, per_image=True)
-            lid = id_loss.run(p, g)['loss']
-            _lib.launch("e3dge_image_metric_row_full", row, sums, per_image, lid, B, float(l2_lambda), float(vgg_lambda), float(id_lambda))
-        elif lpips is None:
-            _lib.launch("e3dge_image_metric_row", row, sums, B, float(l2_lambda))
-        else:
-            per_image = lpips(p, g, per_image=True)
-            _lib.launch("e3dge_image_metric_row_lpips", row, sums, per_image, B, float(l2_lambda), float(vgg_lambda))
+        per_image = None if lpips is None else lpips(p, g, per_image=True)
+        lid = None if id_loss is None else id_loss.run(p, g)['loss']
+        _lib.launch("e3dge_image_metric_row", row, sums, per_image, lid, B, float(l2_lambda), float(vgg_lambda), float(id_lambda))
         return row
     return image_metrics_torch(pred, gt, l2_lambda, lpips, vgg_lambda, id_loss, id_lambda)
 

@@ -670,11 +670,17 @@ int64_t e3dge_image_metrics_scratch_floats(int batch, int channels, int height, 
 int e3dge_image_metrics(float* sums, float* scratch, const float* pred, const float* gt, int batch, int channels,
                         int height, int width, float max_val, e3dge_stream_t stream);
 /* The eight columns builder.py:174-184 reports, from those sums (means over the whole batch tensor, as the reference's
- * losses are): row (8) = [loss_l2 = MSE, loss_id = 0, loss_lpips = 0, loss = l2_lambda * MSE, mae, PSNR of the images
- * rescaled to [0,1], SSIM = 1 - ssim_loss, ID_SIM = 1] -- the identity network is outside the path; this entry reports the
- * identity and LPIPS columns as the reference does with those lambdas at 0 (:145, :158-163).  The LPIPS column is filled by
- * e3dge_image_metric_row_lpips below. */
-int e3dge_image_metric_row(float* row, const float* sums, int batch, float l2_lambda, e3dge_stream_t stream);
+ * losses are), in one launch: row (8) = [loss_l2 = MSE, loss_id, loss_lpips, loss, mae, PSNR of the images rescaled to
+ * [0,1], SSIM = 1 - ssim_loss, ID_SIM = 1 - loss_id].  lpips_per_image: NULL or (batch), e3dge_lpips_forward's per_image;
+ * loss_lpips = (sum_b lpips_per_image[b]) / batch, the same fp32 sum as its mean_out.  id_loss: NULL or a device scalar,
+ * e3dge_id_loss's loss.  A NULL pointer reports its column as the reference does with that lambda at 0 (:145, :158-163:
+ * loss_lpips = 0; loss_id = 0, ID_SIM = 1) and adds no term to loss, whatever the lambda (an infinite one included).
+ * loss = fl(l2_lambda MSE), + fl(vgg_lambda loss_lpips) when lpips_per_image is given, + fl(id_lambda loss_id) when id_loss
+ * is given, in that fp32 order (builder.py:168).
+ * ABI 17: this one entry replaces e3dge_image_metric_row(row, sums, batch, l2_lambda), e3dge_image_metric_row_lpips and
+ * e3dge_image_metric_row_full; it reproduces the first two bit for bit and the third wherever that one added an exact zero. */
+int e3dge_image_metric_row(float* row, const float* sums, const float* lpips_per_image, const float* id_loss, int batch,
+                           float l2_lambda, float vgg_lambda, float id_lambda, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * LPIPS-alex perceptual distance (csrc/lpips.hip).  Additions to ABI 16.  No allocation, no synchronisation.  Replaces
@@ -691,7 +697,7 @@ int e3dge_image_metric_row(float* row, const float* sums, int batch, float l2_la
  *                            multiple of 32 with zeros), the five biases, the five lin rows.
  * e3dge_lpips_pack_weights   w, b, lin: HOST arrays of five device pointers -- w[l] (C_out, C_in, k, k) contiguous as torchvision's
  *                            features.{0,3,6,8,10}.weight, b[l] (C_out), lin[l] (C_out of layer l) the 1x1 weight of lin layer l
- *                            (the renamed keys of utils.py:31-37).  One launch; call once per weight update.
+ *                            (the renamed keys of utils.py:31-37).  Fifteen small launches (conv_igemm.h's packers); call once per weight update.
  * e3dge_lpips_ws_bytes       workspace bytes of a forward (-1: batch < 1 or height / width < 31, the smallest image for which every
  *                            layer has an output).
  * e3dge_lpips_forward        x, y (batch, 3, height, width) fp32 contiguous.  per_image (batch); per_layer NULL or (batch, 5) = d_l[b];
@@ -699,9 +705,7 @@ int e3dge_image_metric_row(float* row, const float* sums, int batch, float l2_la
  *                            lpips.py:39 returns; taps[l] NULL or (2 batch, C_l, H_l, W_l): the normalised features of x (images
  *                            0..batch-1) and y (batch..2 batch-1).  Nine launches.  Fails before any launch on a null required pointer,
  *                            batch < 1, height or width < 31, ws_bytes below e3dge_lpips_ws_bytes().
- * e3dge_image_metric_row_lpips  e3dge_image_metric_row with the LPIPS column filled, in one launch: row[2] = (sum_b
- *                            lpips_per_image[b]) / batch (the same fp32 sum as mean_out), row[3] = l2_lambda MSE + vgg_lambda row[2]
- *                            (builder.py:168 with id_lambda = 0); the other six columns are e3dge_image_metric_row's, bit for bit.
+ * per_image is what e3dge_image_metric_row takes as lpips_per_image.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct E3dgeLpipsArgs {
     const float* packed; const float* x; const float* y;
@@ -716,8 +720,6 @@ int64_t e3dge_lpips_packed_floats(void);
 int e3dge_lpips_pack_weights(float* packed, const float* const* w, const float* const* b, const float* const* lin, e3dge_stream_t stream);
 int64_t e3dge_lpips_ws_bytes(int batch, int height, int width);
 int e3dge_lpips_forward(const E3dgeLpipsArgs* args, e3dge_stream_t stream);
-int e3dge_image_metric_row_lpips(float* row, const float* sums, const float* lpips_per_image, int batch, float l2_lambda,
-                                 float vgg_lambda, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * LPIPS backward (csrc/lpips_bwd.h): the gradient of per_image[b] with respect to x, y or both; the AlexNet and lin weights
@@ -732,7 +734,7 @@ int e3dge_image_metric_row_lpips(float* row, const float* sums, const float* lpi
  * e3dge_lpips_packed_t_floats floats of the transposed weight image: W_l^T with flipped taps for conv 2..5 (M = C_in, K = (co, r, s)
  *                            padded to a multiple of 32) in MFMA A-fragment order, then conv 1 as (3, 64, 11, 11).  A buffer of
  *                            its own; the forward image is unchanged.
- * e3dge_lpips_pack_weights_t w: HOST array of the five device pointers e3dge_lpips_pack_weights takes.  One launch per weight update.
+ * e3dge_lpips_pack_weights_t w: HOST array of the five device pointers e3dge_lpips_pack_weights takes.  Five launches per weight update.
  * e3dge_lpips_bwd_ws_bytes   workspace bytes of a backward for `batch` gradient images (both = 0) or 2 batch (both != 0); -1 as
  *                            e3dge_lpips_ws_bytes.
  * e3dge_lpips_backward       upstream (batch) = dL / d per_image[b] (for the scalar mean: dL / d mean / batch).  grad_x, grad_y: NULL
@@ -795,9 +797,7 @@ int e3dge_lpips_backward(const E3dgeLpipsBwdArgs* args, e3dge_stream_t stream);
  *                            cout * roundup(cin ksize^2, 32) floats for the A-fragment image.  in_ab NULL or (cin, 2): x <- a x + b
  *                            on in-image elements (padding stays 0); epi_ab NULL or (cout, 2); slope NULL or (cout): PReLU after
  *                            the affine; plane NULL or (n, cout, tiles) partial sums of the stored plane.  Two launches.
- * e3dge_image_metric_row_full  e3dge_image_metric_row_lpips with the identity columns: lpips_per_image NULL: LPIPS = 0; id_loss
- *                            NULL (a device scalar otherwise): loss_id = 0.  row[1] = loss_id, row[7] = 1 - loss_id, row[3] =
- *                            ((l2_lambda MSE) + (vgg_lambda LPIPS)) + (id_lambda loss_id) in that fp32 order (builder.py:168).
+ * e3dge_id_loss's loss is what e3dge_image_metric_row takes as id_loss.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define E3DGE_IDNET_CONVS 52
 #define E3DGE_IDNET_BNS 54
@@ -834,8 +834,6 @@ int e3dge_idnet_conv_tiles(int cout, int height, int width, int ksize, int strid
 int e3dge_idnet_conv(float* out, const float* in, const float* w, float* wfrag, const float* in_ab, const float* epi_ab,
                      const float* slope, float* plane, int n, int cin, int cout, int height, int width, int ksize, int stride,
                      e3dge_stream_t stream);
-int e3dge_image_metric_row_full(float* row, const float* sums, const float* lpips_per_image, const float* id_loss, int batch,
-                                float l2_lambda, float vgg_lambda, float id_lambda, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * ArcFace identity term, backward (csrc/idnet_bwd.h): the gradient of the loss with respect to the y_hat images; the network is

@@ -1,12 +1,10 @@
-"""CPU: the C-ABI library builds, loads and exports every symbol include/e3dge_hip.h declares; the ctypes
-mirror of E3dgeRenderArgs matches the C layout; host-side logic (state-dict keys, adjoint geometry, camera
-mirror, loud failure without a GPU)."""
+"""CPU: the C-ABI library builds, loads and exports every symbol include/e3dge_hip.h declares (the ctypes mirror
+itself is checked in tests/test_abi_mirror.py); argument checks and size formulas of the older entries; host-side
+logic (state-dict keys, adjoint geometry, camera mirror, loud failure without a GPU)."""
 import ctypes
 import json
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -53,53 +51,8 @@ def test_variant_build_links_every_source_of_the_library(lib):
         build.build_variant("hosttest", only="no_such_source", verbose=False)
 
 
-def test_render_args_struct_layout_matches_c():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu\n", sizeof(E3dgeRenderArgs), offsetof(E3dgeRenderArgs, sigmoid_beta),
-         offsetof(E3dgeRenderArgs, batch), offsetof(E3dgeRenderArgs, force_background),
-         offsetof(E3dgeRenderArgs, rgb), offsetof(E3dgeRenderArgs, dists));
-  return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    R = _lib.RenderArgs
-    assert got == [ctypes.sizeof(R), R.sigmoid_beta.offset, R.batch.offset, R.force_background.offset,
-                   R.rgb.offset, R.dists.offset]
-
-
 def test_render_bwd_args_struct_layout_matches_c():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(E3dgeRenderBwdArgs), offsetof(E3dgeRenderBwdArgs, d_rgb_map),
-         offsetof(E3dgeRenderBwdArgs, tang), offsetof(E3dgeRenderBwdArgs, sigmoid_beta),
-         offsetof(E3dgeRenderBwdArgs, force_background), offsetof(E3dgeRenderBwdArgs, dstyles),
-         offsetof(E3dgeRenderBwdArgs, tex_alpha), offsetof(E3dgeRenderBwdArgs, d_tex_beta));
-  printf("%zu %zu %zu %zu %zu %zu\n", sizeof(E3dgeSirenBwdArgs), offsetof(E3dgeSirenBwdArgs, tex_alpha),
-         offsetof(E3dgeSirenBwdArgs, precision), offsetof(E3dgeSirenBwdArgs, n_pts), offsetof(E3dgeSirenBwdArgs, box_scale),
-         offsetof(E3dgeSirenBwdArgs, d_tex_beta));
-  return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    R, Sb = _lib.RenderBwdArgs, _lib.SirenBwdArgs
-    assert got == [ctypes.sizeof(R), R.d_rgb_map.offset, R.tang.offset, R.sigmoid_beta.offset,
-                   R.force_background.offset, R.dstyles.offset, R.tex_alpha.offset, R.d_tex_beta.offset,
-                   ctypes.sizeof(Sb), Sb.tex_alpha.offset, Sb.precision.offset, Sb.n_pts.offset, Sb.box_scale.offset,
-                   Sb.d_tex_beta.offset]
-    # argument validation of the training entry points happens before any launch
+    """(The layout itself: tests/test_abi_mirror.py.)  Argument validation of the training entry points happens before any launch."""
     lib = _lib.load()
     assert lib.e3dge_siren_render_bwd(None, None) == -1
     bad = _lib.RenderBwdArgs(batch=1, height=4, width=4, n_samples=0)
@@ -112,25 +65,7 @@ int main(void) {
 
 
 def test_modconv_structs_layout_matches_c():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu\n", sizeof(E3dgeModconvArgs), offsetof(E3dgeModconvArgs, out_amax), offsetof(E3dgeModconvArgs, negative_slope),
-         offsetof(E3dgeModconvArgs, act), offsetof(E3dgeModconvArgs, noise_batch));
-  printf("%zu %zu %zu %zu %zu %d\n", sizeof(E3dgeModLayer), offsetof(E3dgeModLayer, s_amax_out), offsetof(E3dgeModLayer, ci),
-         offsetof(E3dgeModLayer, co_start), offsetof(E3dgeModLayer, lr_mul), E3DGE_AMAX_FLOATS);
-  return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    A, L = _lib.ModconvArgs, _lib.ModLayer
-    assert got == [ctypes.sizeof(A), A.out_amax.offset, A.negative_slope.offset, A.act.offset, A.noise_batch.offset,
-                   ctypes.sizeof(L), L.s_amax_out.offset, L.ci.offset, L.co_start.offset, L.lr_mul.offset, _lib.AMAX_FLOATS]
+    """(The layout itself: tests/test_abi_mirror.py.)  Argument checks and the packed-image size."""
     lib = _lib.load()
     assert lib.e3dge_modconv3x3(None, None) == -1
     bad = _lib.ModconvArgs(batch=1, ci=24, co=32, height=8, width=8)
@@ -141,24 +76,8 @@ int main(void) {
 
 
 def test_dec2_structs_match_c_in_every_plan_field():
-    C, R, P = _lib.Dec2Conv, _lib.Dec2Rgb, _lib.Dec2Plan
-    plan_fields = [f[0] for f in P._fields_]          # every field of the plan, in order
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu\n", sizeof(E3dgeDec2Conv), offsetof(E3dgeDec2Conv, bias_amax), offsetof(E3dgeDec2Conv, noise_batch), sizeof(E3dgeDec2Rgb));
-  printf("%zu %d\n", sizeof(E3dgeDec2Plan), E3DGE_DEC2_MAX_UP);
-''' + "".join(f'  printf("%zu\\n", offsetof(E3dgeDec2Plan, {n}));\n' for n in plan_fields) + "  return 0; }"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [ctypes.sizeof(C), C.bias_amax.offset, C.noise_batch.offset, ctypes.sizeof(R), ctypes.sizeof(P), _lib.DEC2_MAX_UP] + \
-        [getattr(P, n).offset for n in plan_fields]
+    """(Every plan field's offset and size: tests/test_abi_mirror.py.)  Argument checks and size formulas of the forward."""
+    P = _lib.Dec2Plan
     lib = _lib.load()
     assert lib.e3dge_dec2_forward(None, None) == -1
     assert lib.e3dge_dec2_forward(ctypes.byref(P(batch=1, n_up=7, in_res=64, in_ch=256)), None) == -1       # more levels than the plan holds
@@ -183,26 +102,9 @@ def test_blur_factor_accepts_only_symmetric_rank_one_kernels():
 
 
 def test_dec2_backward_structs_layout_matches_c():
-    """ABI 12: the backward plan of the packed decoder pipeline (e3dge_dec2_backward) and the forward plan's new flag."""
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(E3dgeDec2BwdConv), sizeof(E3dgeDec2BwdPlan), offsetof(E3dgeDec2BwdPlan, conv1),
-         offsetof(E3dgeDec2BwdPlan, up), offsetof(E3dgeDec2BwdPlan, conv), offsetof(E3dgeDec2BwdPlan, gact), offsetof(E3dgeDec2BwdPlan, pbuf),
-         offsetof(E3dgeDec2BwdPlan, drgb), offsetof(E3dgeDec2BwdPlan, bounds), offsetof(E3dgeDec2BwdPlan, kernel_ms),
-         offsetof(E3dgeDec2BwdPlan, n_kernel_ms), offsetof(E3dgeDec2Plan, save_for_backward));
-  return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    C, Q, P = _lib.Dec2BwdConv, _lib.Dec2BwdPlan, _lib.Dec2Plan
-    assert got == [ctypes.sizeof(C), ctypes.sizeof(Q), Q.conv1.offset, Q.up.offset, Q.conv.offset, Q.gact.offset, Q.pbuf.offset, Q.drgb.offset,
-                   Q.bounds.offset, Q.kernel_ms.offset, Q.n_kernel_ms.offset, P.save_for_backward.offset]
+    """The backward plan of the packed decoder pipeline (e3dge_dec2_backward): argument checks and size formulas (the layout itself:
+    tests/test_abi_mirror.py)."""
+    Q, P = _lib.Dec2BwdPlan, _lib.Dec2Plan
     lib = _lib.load()
     assert lib.e3dge_dec2_backward(None, None, None) == -1
     plan = P(batch=1, n_up=1, in_res=8, in_ch=32)
@@ -213,22 +115,8 @@ int main(void) {
 
 
 def test_ws_linear_struct_layout_matches_c_and_arguments_are_checked():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu\n", sizeof(E3dgeWsLinear), offsetof(E3dgeWsLinear, n_rows), offsetof(E3dgeWsLinear, ld_x),
-         offsetof(E3dgeWsLinear, off_y), offsetof(E3dgeWsLinear, post), offsetof(E3dgeWsLinear, w_fuse));
-  return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    """(The layout itself: tests/test_abi_mirror.py.)"""
     W = _lib.WsLinear
-    assert got == [ctypes.sizeof(W), W.n_rows.offset, W.ld_x.offset, W.off_y.offset, W.post.offset, W.w_fuse.offset]
     lib = _lib.load()
     assert lib.e3dge_ws_image_bytes(1) == 8 * 8 * 2 * 2 * 64 * 16 and lib.e3dge_ws_image_bytes(8) == 8 * 262144
     assert lib.e3dge_ws_linear(None, None) == -1
@@ -241,25 +129,8 @@ int main(void) {
 
 
 def test_wgrad_and_texhead_bwd_layout_and_argument_checks():
-    """Round 5: struct E3dgeWgrad against the ctypes mirror (compiled C probe), the workspace formulas, and validation before any launch."""
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(E3dgeWgrad), offsetof(E3dgeWgrad, c), offsetof(E3dgeWgrad, ws_floats), offsetof(E3dgeWgrad, n_rows),
-         offsetof(E3dgeWgrad, lda), offsetof(E3dgeWgrad, ldc), offsetof(E3dgeWgrad, relu_b), offsetof(E3dgeWgrad, xcol), offsetof(E3dgeWgrad, ccol),
-         offsetof(E3dgeWgrad, ld_xcol), offsetof(E3dgeWgrad, b_gap));
-  return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    """The workspace formulas, and validation before any launch (the layout of struct E3dgeWgrad: tests/test_abi_mirror.py)."""
     G = _lib.Wgrad
-    assert got == [ctypes.sizeof(G), G.c.offset, G.ws_floats.offset, G.n_rows.offset, G.lda.offset, G.ldc.offset, G.relu_b.offset, G.xcol.offset, G.ccol.offset,
-                   G.ld_xcol.offset, G.b_gap.offset]
     lib = _lib.load()
     # round 6: blocks of 256 x 256.  98,304 points, 512 x 301 outputs: 2 x 2 blocks, 256 // 4 = 64 slabs; behind the partial blocks the column
     # partials (2 x 256 per slab and block row).  256 x 256: one block, 256 slabs.

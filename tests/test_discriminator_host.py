@@ -1,5 +1,4 @@
-"""StyleGAN2 discriminator, host side: the C-ABI additions of csrc/disc.hip / disc_bwd.h (symbols, struct layouts, refusals before any
-launch), the state-dict surface, the path selection of e3dge_amd.discriminator.Discriminator, and its torch composition on the CPU
+"""StyleGAN2 discriminator, host side: the C-ABI entries of csrc/disc.hip / disc_bwd.h (sizes, struct layouts, refusals before any launch), the state-dict surface, the path selection of e3dge_amd.discriminator.Discriminator, and its torch composition on the CPU
 against the recording of the reference (tests/golden/discriminator.npz, tools/gen_golden_discriminator.py).
 
 The CPU path is the reference's torch operations in the reference's order under oracle.cpu_numerics, so on the host that made the
@@ -34,8 +33,6 @@ from e3dge_amd.discriminator import Discriminator
 from test_idloss_host import make_pair, tap_samples
 
 INVALID = -1                                                        # E3DGE_ERR_INVALID_ARG
-NEW_SYMBOLS = ["e3dge_disc_packed_floats", "e3dge_disc_pack_weights", "e3dge_disc_ws_bytes", "e3dge_disc_saved_bytes", "e3dge_disc_forward",
-               "e3dge_disc_backward", "e3dge_disc_conv", "e3dge_disc_conv_dgrad", "e3dge_disc_stddev"]
 # (D_init_size, channel_multiplier, batch, image size) of the recording
 CASES = [(16, 1, b, 16) for b in (1, 2, 4, 6, 8)] + [(256, 1, 2, 256), (256, 1, 2, 1024)]
 VARIANTS = (None, 'stress')
@@ -74,10 +71,7 @@ def torch_taps(m, x):
 
 
 # ---- C-ABI ------------------------------------------------------------------------------------------------------------------------
-def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    for name in NEW_SYMBOLS:
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.e3dge_abi_version() == 16 == _lib.ABI_VERSION
+def test_source_list_and_packed_saved_and_workspace_sizes(lib):
     assert "disc.hip" in build.SOURCES
     for init, cm in [(256, 2), (16, 1), (1024, 2)]:
         m = Discriminator(syn.discriminator_opt(init, cm))

@@ -1,23 +1,18 @@
-"""CPU: the training-loss additions of the C-ABI (csrc/losses.hip) -- exported symbols, struct layout, argument validation -- and the
+"""CPU: the training-loss additions of the C-ABI (csrc/losses.hip) -- the source list, argument validation -- and the
 torch branches of e3dge_amd.losses against tests/golden/losses_shape.npz (tools/gen_golden_losses.py recorded it from the reference's
 LossClass.calc_shape_rec_loss, gan_loss.eikonal_loss and AdaptiveAvgPool2d)."""
 import ctypes
-import os
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO, load_golden
+from conftest import load_golden
 
 import e3dge_amd  # noqa: F401
 from e3dge_amd import _lib, losses
 
-NEW_SYMBOLS = ("e3dge_avgpool_fwd", "e3dge_avgpool_bwd", "e3dge_sqerr_bwd", "e3dge_shape_loss_partial_floats", "e3dge_shape_loss_fwd",
-               "e3dge_shape_loss_bwd")
 LAMBDAS_A = dict(uniform_pts_sdf_lambda=1.0, surf_sdf_lambda=0.1, surf_normal_lambda=0.05, eikonal_lambda=0.1)
 LAMBDAS_B = dict(LAMBDAS_A, surf_sdf_lambda=0.0)
 ALL_ON = dict(supervise_sdf=True, supervise_surface=True, supervise_surface_normal=True, supervise_eikonal=True)
@@ -49,37 +44,9 @@ def stub_loss_class(opt, calls=None):
     return losses.LossClass("cpu", opt, lpips=lp, id_loss=idl)
 
 
-def test_new_symbols_are_exported_and_abi_is_unchanged(lib):
-    for name in NEW_SYMBOLS:
-        assert name in _lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.e3dge_abi_version() == 16 == _lib.ABI_VERSION
+def test_losses_source_is_part_of_the_build():
     from e3dge_amd import build
     assert "losses.hip" in build.SOURCES
-
-
-def test_shape_loss_struct_layout_matches_c():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "e3dge_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu ", sizeof(E3dgeShapeLossSegment), offsetof(E3dgeShapeLossSegment, pred), offsetof(E3dgeShapeLossSegment, gt),
-         offsetof(E3dgeShapeLossSegment, d_pred), offsetof(E3dgeShapeLossSegment, n), offsetof(E3dgeShapeLossSegment, lambda),
-         offsetof(E3dgeShapeLossSegment, kind));
-  printf("%zu %zu %zu %zu %zu %zu %zu %d %d %d\n", sizeof(E3dgeShapeLossArgs), offsetof(E3dgeShapeLossArgs, seg), offsetof(E3dgeShapeLossArgs, terms),
-         offsetof(E3dgeShapeLossArgs, total), offsetof(E3dgeShapeLossArgs, partial), offsetof(E3dgeShapeLossArgs, partial_floats),
-         offsetof(E3dgeShapeLossArgs, upstream), E3DGE_SHAPE_LOSS_SEGMENTS, E3DGE_SHAPE_SMOOTH_L1, E3DGE_SHAPE_EIKONAL);
-  return 0; }'''
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    S, A = _lib.ShapeLossSegment, _lib.ShapeLossArgs
-    assert got == [ctypes.sizeof(S), S.pred.offset, S.gt.offset, S.d_pred.offset, S.n.offset, S.lambda_.offset, S.kind.offset,
-                   ctypes.sizeof(A), A.seg.offset, A.terms.offset, A.total.offset, A.partial.offset, A.partial_floats.offset, A.upstream.offset,
-                   _lib.SHAPE_LOSS_SEGMENTS, _lib.SHAPE_SMOOTH_L1, _lib.SHAPE_EIKONAL]
 
 
 def _fails(lib, rc, *words):

@@ -1,48 +1,24 @@
-"""LPIPS backward, host side: the C-ABI additions of csrc/lpips_bwd.h (symbols, struct layout, argument checks that fail before any
-launch) and the opt-in switch of e3dge_amd.lpips.LPIPS, as far as they need no GPU."""
+"""LPIPS backward, host side: the C-ABI entries of csrc/lpips_bwd.h (packed-image sizes, argument checks that fail before any launch)
+and the opt-in switch of e3dge_amd.lpips.LPIPS, as far as they need no GPU."""
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import pytest
 import torch
-
-from conftest import REPO
 
 import e3dge_amd  # noqa: F401
 from e3dge_amd import _lib, synthetic as syn
 from e3dge_amd.lpips import LPIPS
 
 INVALID = -1                                                        # E3DGE_ERR_INVALID_ARG
-NEW_SYMBOLS = ["e3dge_lpips_packed_t_floats", "e3dge_lpips_pack_weights_t", "e3dge_lpips_bwd_ws_bytes", "e3dge_lpips_backward"]
 
 
-def test_new_symbols_are_exported_and_the_abi_and_forward_image_stay(lib):
-    for name in NEW_SYMBOLS:
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.e3dge_abi_version() == 16 == _lib.ABI_VERSION
+def test_the_forward_image_stays_and_the_transposed_one_holds_every_layer(lib):
     convs = 64 * 384 + 192 * 1600 + 384 * 1728 + 256 * 3456 + 256 * 2304
     assert lib.e3dge_lpips_packed_floats() == convs + 2 * (64 + 192 + 384 + 256 + 256)      # the forward image is as it was
     # W^T of conv 2..5: M = C_in, K = C_out k k (already multiples of 32), then conv 1
     pad = lambda k: (k + 31) // 32 * 32
     transposed = 64 * pad(192 * 25) + 192 * pad(384 * 9) + 384 * pad(256 * 9) + 256 * pad(256 * 9)
     assert lib.e3dge_lpips_packed_t_floats() >= transposed + 3 * 64 * 121
-
-
-def test_lpips_bwd_args_struct_layout_matches_c():
-    names = ["packed", "packed_t", "fwd_ws", "fwd_ws_bytes", "batch", "height", "width", "std", "upstream", "grad_x", "grad_y", "gpre",
-             "ws", "ws_bytes"]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "e3dge_hip.h"\nint main(void) {\n  printf("%zu", sizeof(E3dgeLpipsBwdArgs));\n' + \
-          "".join(f'  printf(" %zu", offsetof(E3dgeLpipsBwdArgs, {n}));\n' for n in names) + "  return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(d, "t")
-        subprocess.run(["gcc", "-I", os.path.join(REPO, "include"), c, "-o", exe], check=True)
-        got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    A = _lib.LpipsBwdArgs
-    assert got == [ctypes.sizeof(A)] + [getattr(A, n).offset for n in names]
 
 
 def good_args(keep, lib, both=False):

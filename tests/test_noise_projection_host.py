@@ -166,15 +166,6 @@ def test_subdivision_follows_the_rule_on_repeated_indices_and_open_meshes():
 
 
 # ---- 3. the ABI ------------------------------------------------------------------------------------------------------------------------------
-NEW_SYMBOLS = ["e3dge_mesh_subdivide", "e3dge_noise_project_ws_bytes", "e3dge_noise_project"]
-
-
-def test_new_symbols_are_exported_and_the_abi_version_stays(lib):
-    for name in NEW_SYMBOLS:
-        assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.e3dge_abi_version() == 16 == _lib.ABI_VERSION
-
-
 def test_noise_project_args_struct_layout_matches_c():
     names = [n for n, _ in _lib.NoiseProjectArgs._fields_]
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "e3dge_hip.h"\nint main(void) {\n  printf("%zu %d %d %d", sizeof(E3dgeNoiseProjectArgs), ' \
