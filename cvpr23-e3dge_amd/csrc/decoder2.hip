@@ -1522,7 +1522,12 @@ extern "C" int64_t e3dge_dec2_dlatent_ws_floats(const E3dgeDec2Plan* P) {
         e3dge::dec2_act_shape(P, i, &C, &R);
         n += (int64_t)P->batch * (C / 8) * ((((int64_t)R * R + e3dge::kDsChunk - 1) / e3dge::kDsChunk) + 1) * 24;      // chunk partials + their fold
     }
-    return n + (int64_t)P->batch * (3 * P->n_up + 2) * 1024;                                                           // dL/ds per modulation row
+    n += (int64_t)P->batch * (3 * P->n_up + 2) * 1024;                                                                 // dL/ds per modulation row
+    // small styles (decoder2_bwd.h): per (sample, 3x3 layer) the channel list (1024 ints), per sample a block of counts, and kDsDirSplit slices
+    // per input channel of the 3x3 layers
+    int64_t n_ch = P->in_ch;
+    for (int u = 0; u < P->n_up; ++u) n_ch += (int64_t)P->up[u].ci + P->conv[u].ci;
+    return n + (int64_t)P->batch * (2 * P->n_up + 1) * 1024 + (int64_t)P->batch * 4 * (E3DGE_DEC2_MAX_UP + 1) + (int64_t)P->batch * n_ch * e3dge::kDsDirSplit;
 }
 
 extern "C" int e3dge_dec2_backward(const E3dgeDec2Plan* P, const E3dgeDec2BwdPlan* Q, e3dge_stream_t stream) {
@@ -1724,8 +1729,39 @@ extern "C" int e3dge_dec2_backward(const E3dgeDec2Plan* P, const E3dgeDec2BwdPla
         pk_dstyle_fold_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(kf);
         if ((rc = check_launch("dec2 bwd style sums (fold)")) != 0) return finish(rc);
         float* ds = cursor; cursor += (int64_t)B * P->n_mod * 1024;
+        // the first term of the 3x3 layers' small styles, from its definition (decoder2_bwd.h, "small styles")
+        PkDsDirK kx{};
+        kx.n_layers = 2 * n_up + 1; kx.fir = P->fir_blur;
+        kx.list = reinterpret_cast<int*>(cursor); cursor += (int64_t)B * kx.n_layers * 1024;
+        kx.count = reinterpret_cast<int*>(cursor); cursor += (int64_t)B * 4 * (E3DGE_DEC2_MAX_UP + 1);
+        kx.first = cursor;
+        for (int l = 0; l < kx.n_layers; ++l) {                                // 0 conv1, 1 + 2u up[u], 2 + 2u conv[u]
+            const int u = (l - 1) / 2;
+            const bool up = l > 0 && (l & 1) != 0;
+            const E3dgeDec2Conv& c = l == 0 ? P->conv1 : (up ? P->up[u] : P->conv[u]);
+            const int out_act = l == 0 ? 1 : (up ? 2 + 2 * u : 3 + 2 * u), in_act = l == 0 ? 0 : (up ? (u == 0 ? 1 : 3 + 2 * (u - 1)) : 2 + 2 * u);
+            PkDsDirL& d = kx.l[l];
+            if (l == 0) d.xf = P->features;
+            else { d.x = reinterpret_cast<const unsigned char*>(P->act[in_act]); d.x_meta = P->meta + in_act; }
+            d.g = reinterpret_cast<const unsigned char*>(Q->gact[out_act]);
+            d.g_meta = l == 0 ? mt_g2(-1) : (up ? mt_g1(u) : mt_g2(u));
+            d.wpre = c.wpre; d.style = c.style; d.demod = c.demod; d.ci = c.ci; d.co = c.co; d.up = up ? 1 : 0;
+            d.R = l == 0 ? P->in_res : P->in_res << (u + 1);
+            d.ch0 = kx.n_ch; kx.n_ch += c.ci;
+            if (!(c.wpre && c.ci <= 1024 && c.ci % 16 == 0 && c.co % 32 == 0))
+                return finish(fail(E3DGE_ERR_INVALID_ARG, "dec2_backward: d_latent needs the forward's wpre images and ci <= 1024"));
+        }
+        if (kx.n_ch != P->in_ch + [&] { int s = 0; for (int u = 0; u < n_up; ++u) s += P->up[u].ci + P->conv[u].ci; return s; }())
+            return finish(fail(E3DGE_ERR_INVALID_ARG, "dec2_backward: conv1.ci differs from in_ch"));
+        cursor += (int64_t)B * kx.n_ch * kDsDirSplit;
+        pk_dstyle_small_kernel<<<dim3((unsigned)kx.n_layers, (unsigned)B), dim3(256), 0, st>>>(kx);
+        if ((rc = check_launch("dec2 bwd small styles")) != 0) return finish(rc);
+        pk_dstyle_direct_kernel<<<dim3((unsigned)kDsDirSlots, (unsigned)kDsDirSplit, (unsigned)(kx.n_layers * B)), dim3(256), 0, st>>>(kx);
+        if ((rc = check_launch("dec2 bwd small styles (direct)")) != 0) return finish(rc);
         PkDsK kd{};
-        kd.tab = P->mod_table; kd.n_rows = P->n_mod; kd.ds = ds;
+        kd.tab = P->mod_table; kd.n_rows = P->n_mod; kd.ds = ds; kd.first = kx.first; kd.n_ch = kx.n_ch;
+        kd.ch0[0] = kx.l[0].ch0;                                                // (ToRGB rows never read theirs)
+        for (int u = 0; u < n_up; ++u) { kd.ch0[2 + 3 * u] = kx.l[1 + 2 * u].ch0; kd.ch0[3 + 3 * u] = kx.l[2 + 2 * u].ch0; }
         // table rows (Decoder._mod_layers): 0 conv1, 1 rgb1, then per level up (2 + 3u), conv (3 + 3u), rgb (4 + 3u)
         kd.row[0] = PkDsRow{p_conv1, sums[1], 3};
         kd.row[1] = PkDsRow{sums[1], nullptr, 2};

@@ -473,7 +473,8 @@ __global__ void __launch_bounds__(256) pkconv_down_kernel(const PkConvK a) {
 // has left in its workspace: for every activation tensor A (packed forward) with G = dL/d(pre) (packed gradient), mask gain m and v:
 //     dx = G / m - v,   S1 = sum_p A dx  (-> the 3x3 layer that CONSUMES A),   S2 = sum_p G y  (-> the layer that PRODUCED A),   S3 = sum_p A v  (-> A's ToRGB)
 // (pk_dstyle_sums_kernel: one streaming pass over A and G, per-chunk partials; pk_dstyle_fold_kernel: the chunks, fixed order), then dL/ds per
-// modulation row (pk_dstyle_kernel) and dL/dlatent = modulation^T dL/ds (pk_dlatent_kernel; EqualLinear :234-244).
+// modulation row (pk_dstyle_kernel) and dL/dlatent = modulation^T dL/ds (pk_dlatent_kernel; EqualLinear :234-244).  S1 / s is used where
+// |s[ci]| > kDsSmallStyle max|s| of the layer; the other channels' first term comes from "small styles" below.
 struct PkDsSumsK {
     const unsigned char* act; const unsigned char* g; const int* act_meta; const int* g_meta;
     const float* noise; const float* noise_w; const float* bias;      // of the PRODUCING layer (noise (noise_batch, R, R) or null)
@@ -582,16 +583,189 @@ __global__ void __launch_bounds__(256) pk_dstyle_fold_kernel(const PkDsFoldK a) 
     }
 }
 
+// ---- small styles: the first term of dL/ds without the division ------------------------------------------------------------------------
+// S1 / s[ci] divides a sum of QUANTISED data gradients by the style: dx[ci] is proportional to s[ci], it is stored (inside G of the tensor
+// below) at the ONE exponent of that tensor and was computed from the f16 hi / lo image of 128 w'', whose lo half is subnormal below
+// |w''| ~ 1e-3.  For a channel whose |s| is a small fraction of the layer's maximum the stored dx is mostly quantisation error and the
+// division amplifies it (measured: two channels at |s| = 1e-6 max|s| put 6e-2 and 1.3e-1 of the row's maximum into d latent), and at
+// s == 0 there is nothing left to divide.  For the channels of a 3x3 layer with |s[ci]| <= kDsSmallStyle max_ci |s| the first term is
+// therefore taken from its definition, the weight gradient contracted with (scale W) demod -- for these few channels only:
+//     sum_co demod[co] sum_tap (scale W)[co][ci][tap] C[co][tap],   C[co][tap] = sum_q g[co][q] X_tap[q]
+// with g = dL/d(pre-activation) of the layer's output and X_tap the layer's input channel ci as tap `tap` sees it from output pixel q:
+// stride 1: x[qy + ky - 1][qx + kx - 1]; up-sampling (transposed conv + Blur): sum_{m,n} K[m][n] x[(qy + 2 - m - ky) / 2][(qx + 2 - n - kx) / 2]
+// over the (m, n) for which both are integers (pre = Blur T, T[2i + ky][2j + kx] += x[i][j] w''[ky][kx]).  Nothing in it is divided
+// by s or scaled by it, so it is as exact at s == 0 (the limit of S1 / s) as anywhere.  pk_dstyle_small_kernel lists the channels per
+// (layer, sample) in ascending order; pk_dstyle_direct_kernel forms the term for the listed ones in kDsDirSplit fixed slices of the
+// (output-channel group, pixel) range, which pk_dstyle_kernel folds in fixed order -- the result does not depend on the launch.
+constexpr int kDsDirSplit = 128, kDsDirSlots = 4;
+constexpr float kDsSmallStyle = 0x1p-10f;
+struct PkDsDirL {
+    const unsigned char* x; const float* xf; const int* x_meta;       // the layer's input: packed (x, x_meta) or fp32 planes (xf: conv1's feature map)
+    const unsigned char* g; const int* g_meta;                        // packed dL/d(pre) of the layer's output, resolution R
+    const float* wpre; const float* style; const float* demod;        // e3dge_dec2_prepack_weights image of scale W, (B, ci), (B, co)
+    int ci, co, R, up;
+    int ch0;                                                          // sum of ci over the layers before this one: its channels' slices start there
+};
+struct PkDsDirK { PkDsDirL l[2 * E3DGE_DEC2_MAX_UP + 1]; int n_layers, n_ch; const float* fir; int* list; int* count; float* first; };      // first: (B, n_ch = sum of ci, kDsDirSplit)
+
+// max_ci |s[ci]| of one sample's style row, the same value in every thread (fixed order: the listing and its consumer must agree)
+__device__ __forceinline__ float block_max_abs(const float* __restrict__ s, int n, float* red) {
+    float m = 0.0f;
+    for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(s[i]));
+    m = wave_max(m);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+__global__ void __launch_bounds__(256) pk_dstyle_small_kernel(const PkDsDirK a) {
+    __shared__ float red[4];
+    __shared__ int cnt[256];
+    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const PkDsDirL L = a.l[l];
+    const float* __restrict__ s = L.style + (size_t)b * L.ci;
+    const float thr = kDsSmallStyle * block_max_abs(s, L.ci, red);
+    const int per = (L.ci + 255) / 256, c0 = min(L.ci, tid * per), c1 = min(L.ci, c0 + per);      // (ci <= 1024: checked by the host)
+    int n = 0;
+    for (int ci = c0; ci < c1; ++ci) n += fabsf(s[ci]) <= thr ? 1 : 0;
+    cnt[tid] = n;
+    __syncthreads();
+    int off = 0;
+    for (int i = 0; i < tid; ++i) off += cnt[i];
+    int* __restrict__ list = a.list + (size_t)(b * a.n_layers + l) * 1024;
+    for (int ci = c0; ci < c1; ++ci)
+        if (fabsf(s[ci]) <= thr) list[off++] = ci;
+    if (tid == 255) a.count[b * a.n_layers + l] = off;
+}
+
+__global__ void __launch_bounds__(256) pk_dstyle_direct_kernel(const PkDsDirK a) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int slot = blockIdx.x, sp = blockIdx.y, l = (int)blockIdx.z % a.n_layers, b = (int)blockIdx.z / a.n_layers;
+    const int n = a.count[b * a.n_layers + l];
+    if (slot >= n) return;                                                   // (block-uniform; the usual case: nothing listed)
+    const PkDsDirL L = a.l[l];
+    const int R = L.R, h = R >> 1, NG = L.co >> 3, NGS = min(NG, kDsDirSplit), PS = kDsDirSplit / NGS;
+    const bool active = sp < NGS * PS;
+    const int g0 = sp % NGS, ps = sp / NGS;
+    const int npos = L.up ? h * h : R * R;                                   // up-sampling: one position = a 2 x 2 block of output pixels
+    const int per = (npos + PS - 1) / PS, q_lo = min(npos, ps * per), q_hi = min(npos, q_lo + per);
+    const int Rx = L.up ? h : R;                                             // resolution of the input
+    const int64_t plane_g = (int64_t)(R + 2) * (R + 2), plane_x = (int64_t)(Rx + 2) * (Rx + 2);
+    const float inv_g = pow2_bits((unsigned)L.g_meta[0] - 14u), inv_x = L.x ? pow2_bits((unsigned)L.x_meta[0] - 14u) : 1.0f;
+    float K[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) K[i] = a.fir[i];
+    const int* __restrict__ list = a.list + (size_t)(b * a.n_layers + l) * 1024;
+    for (int k = slot; k < n; k += kDsDirSlots) {
+        const int ci = list[k];
+        const uint32_t* __restrict__ xw = L.x ? reinterpret_cast<const uint32_t*>(L.x) + (((int64_t)(b * (L.ci >> 3) + (ci >> 3)) * 2) * plane_x) * 4 + ((ci & 7) >> 1) : nullptr;
+        auto x_at = [&](int64_t e) {                                         // padded entry e of channel ci's plane (the border is zero)
+            const uint32_t hw_ = xw[e * 4], lw_ = xw[(e + plane_x) * 4];
+            return ((ci & 1) ? f16hi(hw_) + f16hi(lw_) : f16lo(hw_) + f16lo(lw_)) * inv_x;
+        };
+        float total = 0.0f;
+        if (active)
+            for (int g = g0; g < NG; g += NGS) {
+                const u32x4* __restrict__ gp = reinterpret_cast<const u32x4*>(L.g) + ((int64_t)(b * NG + g) * 2) * plane_g;
+                float acc[8][9];
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+#pragma unroll
+                    for (int tp = 0; tp < 9; ++tp) acc[j][tp] = 0.0f;
+                auto add = [&](int y, int x, const float (&X)[9]) {          // acc += g[.][y][x] (x) X
+                    const int64_t e = (int64_t)(y + 1) * (R + 2) + x + 1;
+                    const u32x4 gh = gp[e], gl = gp[e + plane_g];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const float gv = ((j & 1) ? f16hi(gh[j >> 1]) + f16hi(gl[j >> 1]) : f16lo(gh[j >> 1]) + f16lo(gl[j >> 1])) * inv_g;
+#pragma unroll
+                        for (int tp = 0; tp < 9; ++tp) acc[j][tp] = fmaf(gv, X[tp], acc[j][tp]);
+                    }
+                };
+                if (!L.up) {
+                    for (int q = q_lo + tid; q < q_hi; q += 256) {
+                        const int y = q / R, x = q - y * R;
+                        float X[9];
+#pragma unroll
+                        for (int tp = 0; tp < 9; ++tp) {
+                            const int yy = y + tp / 3 - 1, xx = x + tp % 3 - 1;
+                            if (L.xf) X[tp] = (yy >= 0 && yy < R && xx >= 0 && xx < R) ? L.xf[((int64_t)(b * L.ci + ci) * R + yy) * R + xx] : 0.0f;
+                            else X[tp] = x_at((int64_t)(yy + 1) * (R + 2) + xx + 1);
+                        }
+                        add(y, x, X);
+                    }
+                } else {
+                    for (int q = q_lo + tid; q < q_hi; q += 256) {
+                        const int iy = q / h, jx = q - iy * h;
+                        float xs[3][3];                                      // xs[a][c] = x[iy + 1 - a][jx + 1 - c] (padded rows iy + 2 - a: always inside)
+#pragma unroll
+                        for (int a_ = 0; a_ < 3; ++a_)
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) xs[a_][c] = x_at((int64_t)(iy + 2 - a_) * (h + 2) + jx + 2 - c);
+#pragma unroll
+                        for (int py = 0; py < 2; ++py)
+#pragma unroll
+                            for (int px = 0; px < 2; ++px) {
+                                // output pixel (2 iy + py, 2 jx + px): qy + 2 = 2 (iy + 1) + py, so tap ky meets blur tap m at input row iy + 1 - (m + ky - py) / 2
+                                float X[9];
+#pragma unroll
+                                for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                                    for (int kx = 0; kx < 3; ++kx) {
+                                        float v = 0.0f;
+#pragma unroll
+                                        for (int m = 0; m < 4; ++m) {
+                                            if (((m + ky - py) & 1) || m + ky - py < 0) continue;
+#pragma unroll
+                                            for (int n_ = 0; n_ < 4; ++n_) {
+                                                if (((n_ + kx - px) & 1) || n_ + kx - px < 0) continue;
+                                                v = fmaf(K[m * 4 + n_], xs[(m + ky - py) >> 1][(n_ + kx - px) >> 1], v);
+                                            }
+                                        }
+                                        X[ky * 3 + kx] = v;
+                                    }
+                                add(2 * iy + py, 2 * jx + px, X);
+                            }
+                    }
+                }
+                // (scale W)[co][ci][tap] demod[co] of this group's eight output channels (block-uniform addresses)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int co = 8 * g + j;
+                    const float dm = L.demod[(size_t)b * L.co + co];
+                    const float* __restrict__ wp = L.wpre + ((((int64_t)(co >> 5) * (L.ci >> 4) + (ci >> 4)) * 9) * 64 + ((co & 31) + 32 * ((ci >> 3) & 1))) * 8 + (ci & 7);
+#pragma unroll
+                    for (int tp = 0; tp < 9; ++tp) total = fmaf(acc[j][tp], wp[(int64_t)tp * 512] * dm, total);
+                }
+            }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, kWave);
+        __syncthreads();
+        if (lane == 0) red[tid >> 6] = total;
+        __syncthreads();
+        if (tid == 0) a.first[((int64_t)b * a.n_ch + L.ch0 + ci) * kDsDirSplit + sp] = (red[0] + red[1]) + (red[2] + red[3]);
+    }
+}
+
 // dL/ds of one modulation row (table rows of Decoder._mod_layers), one block per (row, sample):  ds[(b * n_rows + t) * 1024 + ci]
+// First term: S1 / s[ci], or for the small styles of a 3x3 layer (above) the kDsDirSplit slices of pk_dstyle_direct_kernel.  ToRGB rows
+// keep S3 / s everywhere: S3 = sum_p act (ToRGB^T d rgb) is summed in fp32 from fp32 (scale W) s, so the quotient is as exact as fp32
+// is for any s != 0; for |s| <= 1e-30 (in practice s == 0: modulation bias zero AND the latent row zero) the table row is zero, S3 is
+// zero, and the row's share sum_c (scale W)[c][ci] sum_p act d rgb[c] is NOT recovered: dL/ds = 0 there (finite; pinned by
+// test_a_style_that_is_exactly_zero in tests/test_gpu_decoder_bwd_shapes.py).
 struct PkDsRow { const float* p1; const float* p2; int sum1; };               // folded sums of the consumed / produced tensor; sum1: 0 = S1, 2 = S3, 3 = p1 is a plain (b, ci) array
-struct PkDsK { const E3dgeModLayer* tab; PkDsRow row[3 * E3DGE_DEC2_MAX_UP + 2]; int n_rows; float* ds; };
+struct PkDsK { const E3dgeModLayer* tab; PkDsRow row[3 * E3DGE_DEC2_MAX_UP + 2]; int n_rows; float* ds; const float* first; int ch0[3 * E3DGE_DEC2_MAX_UP + 2]; int n_ch; };      // ch0 / n_ch: PkDsDirL / PkDsDirK
 __global__ void __launch_bounds__(256) pk_dstyle_kernel(const PkDsK a) {
     __shared__ float r2[1024];
+    __shared__ float red[4];
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const E3dgeModLayer L = a.tab[t];
     const PkDsRow rw = a.row[t];
     const float* __restrict__ s = L.style_out + (size_t)b * L.ci;
     const bool conv = L.demod_out != nullptr;
+    const float thr = kDsSmallStyle * block_max_abs(s, L.ci, red);           // pk_dstyle_small_kernel's criterion, bit for bit
     if (conv) {                                                             // r2[co] = demod^2 sum_p g y
         for (int co = tid; co < L.co; co += 256) {
             const float v = rw.p2[((int64_t)b * (L.co >> 3) + (co >> 3)) * 24 + 8 + (co & 7)];
@@ -603,7 +777,14 @@ __global__ void __launch_bounds__(256) pk_dstyle_kernel(const PkDsK a) {
     for (int ci = tid; ci < L.ci; ci += 256) {
         const float r1 = rw.sum1 == 3 ? rw.p1[(int64_t)b * L.ci + ci] : rw.p1[((int64_t)b * (L.ci >> 3) + (ci >> 3)) * 24 + 8 * rw.sum1 + (ci & 7)];
         const float sv = s[ci];
-        float d = fabsf(sv) > 1e-30f ? r1 / sv : 0.0f;
+        float d;
+        if (conv && fabsf(sv) <= thr) {
+            const float* __restrict__ fp = a.first + ((int64_t)b * a.n_ch + a.ch0[t] + ci) * kDsDirSplit;
+            d = 0.0f;
+            for (int q = 0; q < kDsDirSplit; ++q) d += fp[q];
+        } else {
+            d = fabsf(sv) > 1e-30f ? r1 / sv : 0.0f;
+        }
         if (conv) {
             float tb[4] = {0.f, 0.f, 0.f, 0.f};                              // four independent chains (co is a multiple of 32), folded in fixed order
             for (int co = 0; co < L.co; co += 16) {                          // sixteen loads in flight: the loop is latency-, not bandwidth-bound

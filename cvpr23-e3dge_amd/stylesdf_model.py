@@ -900,7 +900,7 @@ class Decoder(nn.Module):
 
     def _backward_packed(self, features, d_img, kernel_ms=None, want_latent=False, latent_shape=None):
         """(d features, d latent or None) for the LAST packed forward of this (batch, resolution, stream) -- it must have run with
-        save=True.  d latent (B, n_latent, style_dim): 2 n_up + 3 more launches inside the same native call."""
+        save=True.  d latent (B, n_latent, style_dim): 2 n_up + 7 more launches inside the same native call."""
         B, res = features.shape[0], features.shape[2]
         dev = features.device
         st = self._dec2_state(B, res, dev)

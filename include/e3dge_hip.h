@@ -305,8 +305,9 @@ typedef struct E3dgeDec2BwdPlan {
     int32_t n_kernel_ms, reserved;
     /* optional: the gradient to the decoder's W+ latent, (batch, n_latent, style_dim), or NULL.  Formed from per-channel dot products of
      * the tensors the chain leaves in its workspace -- dL/ds[ci] = (1/s) sum_p x dx - s sum_co demod^2 wsq sum_p g y (3x3 layers),
-     * (1/s) sum_p act (ToRGB^T d rgb) (ToRGB), then modulation^T -- no weight-gradient contraction (csrc/decoder2_bwd.h).  2 n_up + 3 more
-     * launches.  Needs plan->features / mod_table as the forward had them and ds_part = e3dge_dec2_dlatent_ws_floats(plan) floats. */
+     * (1/s) sum_p act (ToRGB^T d rgb) (ToRGB), then modulation^T -- no weight-gradient contraction (csrc/decoder2_bwd.h), except for the
+     * channels of a 3x3 layer whose |s| is at most 2^-10 of the layer's maximum: their first term is contracted directly, without the
+     * division.  2 n_up + 7 more launches.  Needs plan->features / mod_table as the forward had them and ds_part = e3dge_dec2_dlatent_ws_floats(plan) floats. */
     float* d_latent;
     float* ds_part;
     int64_t ds_part_floats;

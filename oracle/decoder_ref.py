@@ -115,3 +115,43 @@ def decoder_forward(sd, features, latent, noises=None, prefix='decoder.', dtype=
         skip = to_rgb(sd, f'{prefix}to_rgbs.{u}.', out, latent[:, i + 2], skip)
         i += 2
     return skip
+
+
+def decoder_pinned_backward(sd, features, latent, noises, d_img, masks=None, prefix='decoder.', dtype=torch.float64):
+    """decoder_forward and its autograd with the branch of every leaky relu PINNED: StyledConv i (conv1, then up / conv per level)
+    computes pre = modulated_conv + noise.weight * noise + activate.bias and returns where(masks[i], pre, 0.2 pre) * sqrt 2, masks[i] a
+    boolean tensor of pre's shape (None: pre > 0, the function's own branch -- then this is decoder_forward).  With the masks of the
+    implementation under test the step function lrelu' is the same on both sides of a comparison, and what is left is arithmetic: in
+    float64 this is the truth for that implementation's gradients, in float32 the yardstick of what fp32 arithmetic can reach.
+    On the CPU, in `dtype`.  Returns img, d_features, d_latent (gradients of sum(img * d_img)), d_pre (one per StyledConv), signs
+    (pre > 0 per StyledConv) and styles (the modulation output s (B, Ci) of every StyledConv)."""
+    cpu = lambda t: t.detach().cpu()
+    sd = {k: cpu(v) for k, v in sd.items() if k.startswith(prefix)}
+    f = cpu(features).to(dtype).requires_grad_(True)
+    lat = cpu(latent).to(dtype).requires_grad_(True)
+    noises = [cpu(n).to(dtype) for n in noises]
+    n_up = 0
+    while f'{prefix}convs.{2 * n_up}.conv.weight' in sd:
+        n_up += 1
+    pres, styles = [], []
+
+    def styled(p, x, style, noise, upsample=False):
+        pre = modulated_conv(sd, p + 'conv.', x, style, True, upsample)
+        pre = pre + _w(sd, p + 'noise.weight', dtype) * noise + _w(sd, p + 'activate.bias', dtype).reshape(1, -1, 1, 1)
+        pre.retain_grad()
+        m = pre.detach() > 0 if masks is None else cpu(masks[len(pres)])
+        assert m.dtype == torch.bool and m.shape == pre.shape, (m.dtype, tuple(m.shape), tuple(pre.shape))
+        pres.append(pre)
+        styles.append(equal_linear(sd, p + 'conv.modulation.', style.detach()))
+        return torch.where(m, pre, 0.2 * pre) * (2 ** 0.5)
+    out = styled(prefix + 'conv1.', f, lat[:, 0], noises[0])
+    skip = to_rgb(sd, prefix + 'to_rgb1.', out, lat[:, 1], None, upsample=False)
+    i = 1
+    for u in range(n_up):
+        out = styled(f'{prefix}convs.{2 * u}.', out, lat[:, i], noises[2 * u + 1], upsample=True)
+        out = styled(f'{prefix}convs.{2 * u + 1}.', out, lat[:, i + 1], noises[2 * u + 2])
+        skip = to_rgb(sd, f'{prefix}to_rgbs.{u}.', out, lat[:, i + 2], skip)
+        i += 2
+    skip.backward(cpu(d_img).to(dtype))
+    return dict(img=skip.detach(), d_features=f.grad, d_latent=lat.grad, d_pre=[p.grad for p in pres],
+                signs=[p.detach() > 0 for p in pres], styles=styles)
