@@ -277,6 +277,15 @@ class DiscBwdArgs(_Args):
         ("grad_logits", _vp), ("grad_images", _vp), ("gstage", _vp * DISC_TAPS), ("ws", _vp), ("ws_bytes", _i64)]
 
 
+HGF_MAX_STACK, HGF_FRONT_SRC = 8, 16                               # E3DGE_HGF_* (include/e3dge_hip.h)
+
+
+class HgfArgs(_Args):
+    """Mirror of struct E3dgeHgfArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("input", _vp)] + [(n, _i32) for n in ("n", "height", "width", "num_stack", "num_hourglass", "reserved")] + [
+        ("outputs", _vp * HGF_MAX_STACK), ("tmpx", _vp), ("normx", _vp), ("ws", _vp), ("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -412,6 +421,15 @@ SIGNATURES = {
     "e3dge_disc_conv": (_i32, [_vp] * 6 + [_i32] * 9 + [_f32, _vp]),
     "e3dge_disc_conv_dgrad": (_i32, [_vp] * 5 + [_f32, _f32, _vp] + [_i32] * 7 + [_f32, _vp]),
     "e3dge_disc_stddev": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "e3dge_hgf_packed_floats": (_i64, [_i32, _i32]),
+    "e3dge_hgf_pack_weights": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "e3dge_hgf_ws_bytes": (_i64, [_i32] * 5),
+    "e3dge_hgf_forward": (_i32, [ctypes.POINTER(HgfArgs), _vp]),
+    "e3dge_hgf_front": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp, _i64, _vp]),
+    "e3dge_hgf_conv": (_i32, [_vp] * 8 + [_i32] * 12 + [_vp]),
+    "e3dge_hgf_norm": (_i32, [_vp] * 4 + [_i32] * 7 + [_vp]),
+    "e3dge_hgf_pool": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
+    "e3dge_hgf_up_add": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
 }
 
 _lib = None

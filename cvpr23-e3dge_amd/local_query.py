@@ -12,8 +12,9 @@ What runs where: projection + bilinear gather + masks (e3dge_local_query) and th
 are HIP kernels that write straight into the column slices of the buffers the MLPs read (no concatenation copies); the
 texture head is the fused HIP kernel of round 1.  Fuse_sft_MLP (590 k MAC per point: a ResnetBlockFC(513 -> 256) and four
 256x256 linears) runs as nine weight-stationary split-f16 launches (e3dge_ws_linear, round 3) when no autograd graph is
-needed, as torch modules (library GEMMs) otherwise.  The hourglass image filters that PRODUCE the feature maps stay outside the
-path."""
+needed, as torch modules (library GEMMs) otherwise.  The hourglass image filter that PRODUCES the feature maps is
+hg_filter.ResidualImageFilter (csrc/hgfilter.hip, forward with frozen weights): `netLocal.filter(residual_images, depth_feat)` when the
+renderer was built with PIFu-style `local_options`."""
 import os
 
 import torch

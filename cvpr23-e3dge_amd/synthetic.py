@@ -214,6 +214,47 @@ def load_synthetic_discriminator(module, seed=0, variant=None):
     return module
 
 
+def pifu_opt(**over):
+    """The PIFu-style `local_options` that `e3dge_amd.hg_filter.HGFilter` / `ResidualImageFilter` read, at the reference's defaults
+    (vendor/pifu/lib/options.py with the stage-2 scripts' --norm group --hg_input_channel 64)."""
+    o = AttrDict(num_stack=4, num_hourglass=2, norm='group', hg_down='ave_pool', hourglass_dim=256, hg_input_channel=64, skip_hourglass=False)
+    o.update(over)
+    return o
+
+
+HGFILTER_PARTS = ('image_filter.', 'residual_conv.', 'depth_conv.', 'downsample_channel_conv.')
+
+
+def load_synthetic_hgfilter(module, seed=0):
+    """Deterministic weights for an `e3dge_amd.hg_filter.ResidualImageFilter` (or a module that carries one's parts, or the reference's:
+    the keys are the same) or a bare `HGFilter`, which gets the values it would have as `image_filter`.  4-D weights N(0, 2 / fan_in),
+    norm weights 1 + 0.2 N, every bias and norm bias 0.2 N.  `downsample.0` is `bn4`: one value for
+    both keys.  With this recipe every ReLU passes 36-53 % of its inputs and every stack output has std of about 1.1 (float64, CPU;
+    tests/test_hgfilter_host.py asserts the ranges)."""
+    own = module.state_dict()
+    bare = not any(k.startswith(HGFILTER_PARTS) for k in own)
+    kinds = dict(module.named_modules(remove_duplicate=False))       # bn4 is listed under `downsample.0` too
+    sd = {}
+    for k, v in own.items():
+        if not bare and not k.startswith(HGFILTER_PARTS):
+            continue
+        owner, leaf = k.rsplit('.', 1)
+        if leaf in ('running_mean', 'running_var', 'num_batches_tracked'):       # norm='batch': the statistics stay at (0, 1)
+            continue
+        name = 'hgfilter.' + ('image_filter.' if bare else '') + k.replace('.downsample.0.', '.bn4.')
+        t = synthetic_tensor(name, v.shape, seed)                     # 'weight': N(0, 1); everything else: 0.05 N(0, 1)
+        if v.ndim == 4:
+            t = t * math.sqrt(2.0 / (v.shape[1] * v.shape[2] * v.shape[3]))
+        elif leaf == 'weight' and not isinstance(kinds[owner], torch.nn.Conv2d):
+            t = 1.0 + 0.2 * t
+        else:
+            t = 4.0 * t
+        sd[k] = t.to(v.dtype)
+    missing, unexpected = module.load_state_dict(sd, strict=False)
+    assert not unexpected and not any(m in sd for m in missing), (missing, unexpected)
+    return module
+
+
 STRESS_VARIANTS = {          # name: (SIREN hidden-weight factor, gamma-mapping weight factor, std of the W+ codes)
     "wide": (1.0, 1.0, 1.0),    # unit-variance styles: FiLM frequencies 13.5 .. 48 instead of 27.7 .. 32.3
     "s2": (2.0, 3.0, 0.3),      # per-layer gain 2: fp32 rounding amplified ~300x over the init-range fixtures, still well defined

@@ -33,6 +33,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .hg_filter import ResidualImageFilter
 
 
 MFMA_MODES = {"f32": _lib.PREC_F32, "f16x3": _lib.PREC_F16X3, "f16x3_v1": _lib.PREC_F16X3_V1}
@@ -1038,10 +1039,10 @@ class ResnetBlockFC(nn.Module):
 
 
 class LocalTexHead(nn.Module):
-    """`netLocal` as far as this build goes: only the texture-modulation head (state-dict key
-    `netLocal.local_feat_to_tex_modulations_linear.*`).  The hourglass image filters and the feature query of the PIFu
-    branch are outside the path; their output, the (B,H,W,S,C) local features, comes in through
-    `local_data_batch['feats']`."""
+    """`netLocal` without PIFu options: only the texture-modulation head (state-dict key
+    `netLocal.local_feat_to_tex_modulations_linear.*`).  The local features come in through `local_data_batch['feats']` (B,H,W,S,C)
+    or are queried from `local_data_batch['feature_maps']` (local_query.py); the hourglass image filter that produces those maps is
+    LocalFilterHead's, below."""
 
     def __init__(self, feats_dim):
         super().__init__()
@@ -1052,11 +1053,24 @@ class LocalTexHead(nn.Module):
         return tex_modulations_from_maps(self, renderer, cam_poses, focal, near, far, local_data_batch, lazy=lazy)
 
 
+class LocalFilterHead(ResidualImageFilter):
+    """`netLocal` with PIFu-style `local_options`: the texture-modulation head of LocalTexHead and, beside it, the hourglass image
+    filter (hg_filter.py: residual_conv, depth_conv, downsample_channel_conv, image_filter and `filter()`), whose maps are what
+    `local_data_batch['feature_maps']` takes."""
+
+    def __init__(self, feats_dim, local_options):
+        super().__init__(local_options)
+        self.local_feat_to_tex_modulations_linear = ResnetBlockFC(feats_dim, 512)
+
+    tex_modulations_from_maps = LocalTexHead.tex_modulations_from_maps
+
+
 class SirenLocalGlobal(nn.Module):
     """Keeps the `network.netGlobal.*` / `network.netLocal.local_feat_to_tex_modulations_linear.*` checkpoint keys of
     the reference's local+global wrapper (:267-558).  Second-pass inputs (`local_data_batch`): either the local features
     'feats' (B,H,W,S,C) -- the texture FiLM (alpha, beta) is then computed by the fused head above (:327-336) -- or
-    'tex' = (alpha, beta) directly; both are applied inside the fused render kernel (:217-220)."""
+    'tex' = (alpha, beta) directly; both are applied inside the fused render kernel (:217-220).  With PIFu-style `local_options`
+    netLocal also carries the hourglass image filter (LocalFilterHead); with None it and every state dict are as without."""
 
     def __init__(self, D=8, W=256, style_dim=256, input_ch=3, input_ch_views=3, output_ch=4,
                  output_features=True, scene_scale=0.12, local_options=None, opt=None):
@@ -1065,7 +1079,8 @@ class SirenLocalGlobal(nn.Module):
         self.netGlobal = SirenGenerator(opt, D, W, style_dim, input_ch, input_ch_views, output_ch,
                                         output_features, scene_scale)
         if _opt_get(opt, 'L_pred_tex_modulations', False):
-            self.netLocal = LocalTexHead(int(_opt_get(opt, 'residual_local_feats_dim', 301)))
+            feats_dim = int(_opt_get(opt, 'residual_local_feats_dim', 301))
+            self.netLocal = LocalTexHead(feats_dim) if local_options is None else LocalFilterHead(feats_dim, local_options)
         else:
             self.netLocal = None
 

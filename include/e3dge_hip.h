@@ -1252,6 +1252,73 @@ int e3dge_disc_conv_dgrad(float* out, const float* g, const float* w, float* wfr
                           e3dge_stream_t stream);
 int e3dge_disc_stddev(float* cat, float* scalars, const float* feat, int n, int channels, int hw, e3dge_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Hourglass image filter of the local branch, forward (csrc/hgfilter.hip).  Additions to ABI 17.  No allocation, no
+ * synchronisation, no atomics; bit-reproducible, and an image's maps do not depend on its position in the batch or on the batch
+ * size.  Replaces HGPIFuNetGANResidualResnetFC.filter (vendor/pifu/lib/model/HGPIFuGANNetResidualInputResnetFC.py:33-76): residual_conv and
+ * depth_conv (reflect padding, InstanceNorm2d(affine)), the concatenation and HGFilter (vendor/pifu/lib/model/HGFilters.py) with
+ * norm='group', hg_down='ave_pool', hg_input_channel=64, hourglass_dim=256.  Frozen weights, fp32, forward only.
+ *
+ * Source tensors of the filter, in this order (ConvBlock(cin, cout) = bn1.weight, bn1.bias, conv1.weight, bn2.weight, bn2.bias,
+ * conv2.weight, bn3.weight, bn3.bias, conv3.weight and, where cin != cout, bn4.weight, bn4.bias, downsample.2.weight;
+ * level(d) = b1_d, b2_d, level(d - 1) or b2_plus_1 for d = 1, b3_d):
+ *   conv1.weight, conv1.bias, bn1.weight, bn1.bias, ConvBlock conv2, conv3, conv4; then per stack i: level(num_hourglass) of m<i>,
+ *   ConvBlock top_m_<i>, conv_last<i>.weight, .bias, bn_end<i>.weight, .bias, l<i>.weight, .bias and, for all but the last stack,
+ *   bl<i>.weight, .bias, al<i>.weight, .bias.
+ * Source tensors of the two front nets (E3DGE_HGF_FRONT_SRC = 16), residual_conv's eight then depth_conv's: 0.weight,
+ *   1.conv.0.weight, 1.conv.0.bias, 1.conv.2.weight, 1.conv.3.weight, 1.conv.3.bias, 1.conv.5.weight, 2.weight.
+ *
+ * e3dge_hgf_packed_floats   floats of the packed image of (num_stack 1..8, num_hourglass 1..4), front nets included (-1: outside).
+ * e3dge_hgf_pack_weights    filter_src, front_src: HOST arrays of device pointers; front_src NULL: the front nets' part of the
+ *                           image stays unwritten and e3dge_hgf_front must not be called with it.  Re-run after a weight update.
+ * e3dge_hgf_ws_bytes        workspace bytes of e3dge_hgf_forward and e3dge_hgf_front for n images of height x width (the INPUT
+ *                           size of the filter: the image size) (-1: bad sizes).
+ * e3dge_hgf_forward         input (n, 64, height, width) -> outputs[i] (n, 256, height / 4, width / 4) for every stack i < num_stack,
+ *                           tmpx (n, 64, height / 2, width / 2), normx (n, 128, height / 4, width / 4).  252 launches at the default
+ *                           (4, 2).  Fails before any launch on a null pointer ("null"), n outside 1..4096, num_stack or
+ *                           num_hourglass out of range, height or width not a multiple of 4 * 2^num_hourglass or above 4096, and a
+ *                           workspace that is too small ("workspace").
+ * e3dge_hgf_front           image (n, 3, height, width), depth (n, 1, height, width) -> out (n, 64, height, width): residual_conv
+ *                           into channels 0..31, depth_conv into 32..63.  12 launches.  Same refusals.
+ * e3dge_hgf_conv            debug entry: one convolution of the family.  in (n, cin, height, width), w (cout, cin, ksize, ksize) with
+ *                           (ksize, stride) = (7, 2), (3, 1) or (1, 1), padding ksize / 2, zeros or (reflect != 0, ksize 3) mirrored;
+ *                           cout a multiple of 16.  wfrag: scratch of cout * roundup(cin ksize^2, 32) floats.  in_ab NULL or
+ *                           (n, cin, 2): x <- relu(a x + b) on in-image elements.  bias NULL or (cout).  raw NULL or (n, cout, OH, OW):
+ *                           the result before the residual.  res NULL or (n, res_channels, OH, OW), added from channel res_c0 on.
+ *                           out (n, out_channels, OH, OW), written from channel out_c0 on.  Two launches.
+ * e3dge_hgf_norm            debug entry: ab (n, channels, 2) = (gamma rstd, beta - mean gamma rstd) of GroupNorm(groups, channels),
+ *                           eps 1e-5, over the channels [c0, c0 + channels) of x (n, channels_total, height, width); moments in
+ *                           float64.  groups = channels is InstanceNorm2d(affine).  One launch.
+ * e3dge_hgf_pool            debug entry: out (planes, height / 2, width / 2) = avg_pool2d(in, 2, 2); height and width even.
+ * e3dge_hgf_up_add          debug entry: out (planes, 2 height, 2 width) = up1 + bicubic x2 of low (planes, height, width),
+ *                           align_corners, A = -0.75, source indices clamped at the border.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_HGF_MAX_STACK 8
+#define E3DGE_HGF_FRONT_SRC 16
+typedef struct E3dgeHgfArgs {
+    const float* packed;              /* e3dge_hgf_pack_weights */
+    const float* input;
+    int32_t n, height, width, num_stack, num_hourglass, reserved;
+    float* outputs[E3DGE_HGF_MAX_STACK];
+    float* tmpx; float* normx;
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeHgfArgs;
+int64_t e3dge_hgf_packed_floats(int num_stack, int num_hourglass);
+int e3dge_hgf_pack_weights(float* packed, const float* const* filter_src, int n_filter_src, const float* const* front_src, int num_stack,
+                           int num_hourglass, e3dge_stream_t stream);
+int64_t e3dge_hgf_ws_bytes(int n, int height, int width, int num_stack, int num_hourglass);
+int e3dge_hgf_forward(const E3dgeHgfArgs* args, e3dge_stream_t stream);
+int e3dge_hgf_front(const float* packed, const float* image, const float* depth, float* out, int n, int height, int width, int num_stack,
+                    int num_hourglass, void* ws, int64_t ws_bytes, e3dge_stream_t stream);
+int e3dge_hgf_conv(float* out, float* raw, const float* in, const float* w, float* wfrag, const float* in_ab, const float* bias,
+                   const float* res, int n, int cin, int cout, int height, int width, int ksize, int stride, int reflect, int out_channels,
+                   int out_c0, int res_channels, int res_c0, e3dge_stream_t stream);
+int e3dge_hgf_norm(float* ab, const float* x, const float* gamma, const float* beta, int n, int channels_total, int c0, int channels,
+                   int groups, int height, int width, e3dge_stream_t stream);
+int e3dge_hgf_pool(float* out, const float* in, int64_t planes, int height, int width, e3dge_stream_t stream);
+int e3dge_hgf_up_add(float* out, const float* up1, const float* low, int64_t planes, int height, int width, e3dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
