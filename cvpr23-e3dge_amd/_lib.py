@@ -286,6 +286,13 @@ class HgfArgs(_Args):
         ("outputs", _vp * HGF_MAX_STACK), ("tmpx", _vp), ("normx", _vp), ("ws", _vp), ("ws_bytes", _i64)]
 
 
+class HgfBwdArgs(_Args):
+    """Mirror of struct E3dgeHgfBwdArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("packed_t", _vp), ("saved", _vp), ("saved_bytes", _i64), ("tmpx", _vp), ("normx", _vp)] + [
+        (n, _i32) for n in ("n", "height", "width", "num_stack", "num_hourglass", "reserved")] + [
+        ("g_outputs", _vp * HGF_MAX_STACK), ("g_normx", _vp), ("g_input", _vp), ("ws", _vp), ("ws_bytes", _i64), ("branch", _vp), ("branch_bytes", _i64), ("grads", _vp), ("input", _vp), ("outputs", _vp * HGF_MAX_STACK)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -430,6 +437,22 @@ SIGNATURES = {
     "e3dge_hgf_norm": (_i32, [_vp] * 4 + [_i32] * 7 + [_vp]),
     "e3dge_hgf_pool": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "e3dge_hgf_up_add": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "e3dge_hgf_saved_bytes": (_i64, [_i32] * 5),
+    "e3dge_hgf_forward_saving": (_i32, [ctypes.POINTER(HgfArgs), _vp, _i64, _vp]),
+    "e3dge_hgf_front_saving": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp, _i64, _vp, _i64, _vp]),
+    "e3dge_hgf_packed_t_floats": (_i64, [_i32, _i32]),
+    "e3dge_hgf_pack_weights_t": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "e3dge_hgf_bwd_ws_bytes": (_i64, [_i32] * 5),
+    "e3dge_hgf_backward": (_i32, [ctypes.POINTER(HgfBwdArgs), _vp]),
+    "e3dge_hgf_front_backward": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp] + [_i32] * 5 + [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "e3dge_hgf_branch_bytes": (_i64, [_i32] * 5),
+    "e3dge_hgf_conv_dgrad": (_i32, [_vp] * 7 + [_i32] * 10 + [_vp]),
+    "e3dge_hgf_norm_bwd": (_i32, [_vp] * 6 + [_i32, _i32, _vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp]),
+    "e3dge_hgf_grad_floats": (_i64, [_i32, _i32]),
+    "e3dge_hgf_wgrad_ws_floats": (_i64, [_i32] * 7),
+    "e3dge_hgf_conv_wgrad": (_i32, [_vp] * 5 + [_i32] * 10 + [_vp, _i64, _vp]),
+    "e3dge_hgf_pool_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "e3dge_hgf_up_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
 }
 
 _lib = None

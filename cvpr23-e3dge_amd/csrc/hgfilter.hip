@@ -25,7 +25,8 @@
 //                      group's shape alone.  InstanceNorm2d(affine) is the case groups = channels.
 //   hgf_act_kernel     relu(a x + b): tmpx, the one activated tensor the filter returns.
 //   hgf_pool_kernel    avg_pool2d(2, 2).      hgf_up_add_kernel    up1 + bicubic x2 (align_corners, A = -0.75, clamped indices).
-// Launch count and measured times: DESIGN.md 4.15.
+// Launch count and measured times: DESIGN.md 4.15.  The backward (hgfilter_bwd.h) is included at the end; its saving
+// forward is the same launches with every tensor the backward reads again kept in a buffer of its own (HgfSaved below).
 #include "conv_igemm.h"
 
 namespace e3dge {
@@ -367,8 +368,62 @@ static HgfWs hgf_ws(int64_t n, int64_t H, int64_t W, int D) {
     return d;
 }
 
+// ---- host side: the saved state of the saving forward -----------------------------------------------------------------------------
+// What the backward reads again, each in a buffer of its own: every convolution's pre-norm input and every norm's (a, b).  The plain
+// forward reuses t1, t2, ab[], hg, top, last and the level buffers across blocks and stacks; the saving forward takes them from here.
+struct HgfBlockBuf { int64_t t1, t2, ab[4]; };
+struct HgfSaved {
+    HgfBlockBuf blk[kHgfMaxBlocks];
+    HgfWs stack[kHgfMaxStack];                                        // up1 .. low3 of every level, hg, top, last; ab[0]: bn_end's
+    int64_t stem, ab_stem, c2, c3, prev[kHgfMaxStack];
+    int64_t f0[2], f1[2], f2[2], fab[2][2];                           // the front nets: the three later convolutions' inputs and the norms' (a, b)
+    int64_t filter_floats, floats;
+};
+
+static void hgf_saved(int64_t n, int64_t H, int64_t W, int S, int D, const HgfLayout& l, HgfSaved* out) {
+    HgfSaved& v = *out;
+    int64_t off = 0;
+    auto take = [&](int64_t floats) { const int64_t at = off; off += (floats + 63) / 64 * 64; return at; };
+    const int64_t p2 = (H / 2) * (W / 2), p4 = (H / 4) * (W / 4);
+    auto block = [&](int bi, int64_t HW) {
+        const HgfBlock& b = l.blocks[bi];
+        HgfBlockBuf& k = v.blk[bi];
+        k.t1 = take(n * (b.cout / 2) * HW); k.t2 = take(n * (b.cout / 4) * HW);
+        k.ab[0] = take(n * b.cin * 2); k.ab[1] = take(n * (b.cout / 2) * 2); k.ab[2] = take(n * (b.cout / 4) * 2); k.ab[3] = take(n * b.cin * 2);
+    };
+    v.stem = take(n * 64 * p2); v.ab_stem = take(n * 64 * 2);
+    v.c2 = take(n * 128 * p2); v.c3 = take(n * 128 * p4);
+    block(l.conv2, p2); block(l.conv3, p4); block(l.conv4, p4);
+    for (int s = 0; s < S; ++s) {
+        v.prev[s] = take(n * 256 * p4);
+        HgfWs& w = v.stack[s];
+        w = HgfWs{};
+        int bi = l.stack[s].first_block;
+        int64_t p = p4;
+        for (int lv = D; lv >= 1; --lv, p /= 4) {                     // the layout's order: b1_d, b2_d, the inner level, b3_d
+            w.up1[lv] = take(n * 256 * p);
+            w.pooled[lv] = take(n * 256 * (p / 4)); w.low1[lv] = take(n * 256 * (p / 4));
+            w.low2[lv] = take(n * 256 * (p / 4)); w.low3[lv] = take(n * 256 * (p / 4));
+            block(bi++, p); block(bi++, p / 4);
+        }
+        p *= 4;
+        block(bi++, p / 4);                                           // b2_plus_1
+        for (int lv = 1; lv <= D; ++lv, p *= 4) block(bi++, p / 4);   // b3_1 .. b3_D
+        block(l.stack[s].top, p4);
+        w.hg = take(n * 256 * p4); w.top = take(n * 256 * p4); w.last = take(n * 256 * p4);
+        w.ab[0] = take(n * 256 * 2);
+    }
+    v.filter_floats = off;
+    for (int f = 0; f < 2; ++f) {
+        v.f0[f] = take(n * 32 * H * W); v.f1[f] = take(n * 32 * H * W); v.f2[f] = take(n * 32 * H * W);
+        v.fab[f][0] = take(n * 32 * 2); v.fab[f][1] = take(n * 32 * 2);
+    }
+    v.floats = off;
+}
+
 struct HgfRun {
     const float* P; const HgfLayout* lay; const HgfWs* w; float* ws; hipStream_t st; int n;
+    const HgfBlockBuf* bb; float* sv;                                 // the saving forward: per-block buffers in sv; null otherwise
     const float* at(int entry) const { return P + lay->e[entry].off; }
 };
 
@@ -376,9 +431,11 @@ struct HgfRun {
 static int hgf_block(const HgfRun& r, const HgfBlock& b, const float* x, float* out, int H, int W) {
     int rc;
     const int HW = H * W, co = b.cout;
-    float* ab[4] = {r.ws + r.w->ab[0], r.ws + r.w->ab[1], r.ws + r.w->ab[2], r.ws + r.w->ab[3]};
-    float* t1 = r.ws + r.w->t1;
-    float* t2 = r.ws + r.w->t2;
+    const HgfBlockBuf* k = r.bb ? r.bb + (&b - r.lay->blocks) : nullptr;
+    float* ab[4];
+    for (int i = 0; i < 4; ++i) ab[i] = k ? r.sv + k->ab[i] : r.ws + r.w->ab[i];
+    float* t1 = k ? r.sv + k->t1 : r.ws + r.w->t1;
+    float* t2 = k ? r.sv + k->t2 : r.ws + r.w->t2;
     const float* res = x;
     if (b.down) {                                                     // the residual goes into `out` first; the three slices add to it in place
         if ((rc = hgf_norm(ab[3], x, r.at(b.bn[3]), r.at(b.bn[3] + 1), r.n, b.cin, 0, b.cin, 32, HW, r.st))) return rc;
@@ -458,7 +515,8 @@ extern "C" int64_t e3dge_hgf_ws_bytes(int n, int height, int width, int num_stac
     return (d.filter_floats > d.front_floats ? d.filter_floats : d.front_floats) * (int64_t)sizeof(float);
 }
 
-extern "C" int e3dge_hgf_forward(const E3dgeHgfArgs* args, e3dge_stream_t stream) {
+// saved == null: the plain forward.  Otherwise the same launches with the buffers of HgfSaved in place of the reused ones.
+static int hgf_forward_impl(const E3dgeHgfArgs* args, float* saved, int64_t saved_bytes, e3dge_stream_t stream) {
     E3DGE_REQUIRE(args, "hgf_forward: null argument struct");
     const E3dgeHgfArgs& a = *args;
     const int S = a.num_stack, D = a.num_hourglass, n = a.n, H = a.height, W = a.width;
@@ -471,21 +529,27 @@ extern "C" int e3dge_hgf_forward(const E3dgeHgfArgs* args, e3dge_stream_t stream
                   (long long)(w.filter_floats * (int64_t)sizeof(float)));
     HgfLayout l;
     hgf_layout(S, D, &l);
+    HgfSaved sv;
+    if (saved) {
+        hgf_saved(n, H, W, S, D, l, &sv);
+        E3DGE_REQUIRE(saved_bytes >= sv.floats * (int64_t)sizeof(float), "hgf_forward: saved state of %lld bytes, %lld needed", (long long)saved_bytes,
+                      (long long)(sv.floats * (int64_t)sizeof(float)));
+    }
     hipStream_t st = as_stream(stream);
     float* ws = static_cast<float*>(a.ws);
-    const HgfRun r{a.packed, &l, &w, ws, st, n};
+    const HgfRun r{a.packed, &l, &w, ws, st, n, saved ? sv.blk : nullptr, saved};
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
     int rc;
-    float* stem = ws + w.stem;
-    float* ab0 = ws + w.ab[0];
+    float* stem = saved ? saved + sv.stem : ws + w.stem;
+    float* ab0 = saved ? saved + sv.ab_stem : ws + w.ab[0];
     if ((rc = hgf_conv({stem, nullptr, a.input, r.at(l.stem_w), nullptr, r.at(l.stem_w + 1), nullptr, n, 64, 64, H, W, 7, 2, 0, 64, 0, 0, 0}, st))) return rc;
     if ((rc = hgf_norm(ab0, stem, r.at(l.stem_bn), r.at(l.stem_bn + 1), n, 64, 0, 64, 32, H2 * W2, st))) return rc;
     const int64_t stem_total = (int64_t)n * 64 * H2 * W2;
     hgf_act_kernel<<<dim3((unsigned)((stem_total + 255) / 256)), dim3(256), 0, st>>>(a.tmpx, stem, reinterpret_cast<const float2*>(ab0), H2 * W2, stem_total);
     if ((rc = check_launch("hgf_forward(act)"))) return rc;
-    float* c2 = ws + w.c2;
-    float* c3 = ws + w.c3;
-    float* prev = ws + w.prev[0];
+    float* c2 = saved ? saved + sv.c2 : ws + w.c2;
+    float* c3 = saved ? saved + sv.c3 : ws + w.c3;
+    float* prev = saved ? saved + sv.prev[0] : ws + w.prev[0];
     float* next = ws + w.prev[1];
     if ((rc = hgf_block(r, l.blocks[l.conv2], a.tmpx, c2, H2, W2))) return rc;
     if ((rc = hgf_pool(a.normx, c2, (int64_t)n * 128, H2, W2, st))) return rc;
@@ -494,10 +558,16 @@ extern "C" int e3dge_hgf_forward(const E3dgeHgfArgs* args, e3dge_stream_t stream
     float* hg = ws + w.hg;
     float* top = ws + w.top;
     float* last = ws + w.last;
+    HgfRun rs = r;                                                    // the stack's level buffers
     for (int s = 0; s < S; ++s) {
         const HgfStack& k = l.stack[s];
         int bi = k.first_block;
-        if ((rc = hgf_level(r, D, bi, prev, hg, H4, W4))) return rc;
+        if (saved) {
+            rs.w = &sv.stack[s]; rs.ws = saved;
+            hg = saved + rs.w->hg; top = saved + rs.w->top; last = saved + rs.w->last; ab0 = saved + rs.w->ab[0];
+            if (s + 1 < S) next = saved + sv.prev[s + 1];
+        }
+        if ((rc = hgf_level(rs, D, bi, prev, hg, H4, W4))) return rc;
         if ((rc = hgf_block(r, l.blocks[k.top], hg, top, H4, W4))) return rc;
         if ((rc = hgf_conv({last, nullptr, top, r.at(k.last_w), nullptr, r.at(k.last_w + 1), nullptr, n, 256, 256, H4, W4, 1, 1, 0, 256, 0, 0, 0}, st))) return rc;
         if ((rc = hgf_norm(ab0, last, r.at(k.bn_end), r.at(k.bn_end + 1), n, 256, 0, 256, 32, H4 * W4, st))) return rc;
@@ -512,8 +582,18 @@ extern "C" int e3dge_hgf_forward(const E3dgeHgfArgs* args, e3dge_stream_t stream
     return E3DGE_OK;
 }
 
+extern "C" int e3dge_hgf_forward(const E3dgeHgfArgs* args, e3dge_stream_t stream) { return hgf_forward_impl(args, nullptr, 0, stream); }
+
+static int hgf_front_impl(const float* packed, const float* image, const float* depth, float* out, int n, int height, int width, int num_stack,
+                          int num_hourglass, void* ws, int64_t ws_bytes, float* saved, int64_t saved_bytes, e3dge_stream_t stream);
+
 extern "C" int e3dge_hgf_front(const float* packed, const float* image, const float* depth, float* out, int n, int height, int width,
                                int num_stack, int num_hourglass, void* ws, int64_t ws_bytes, e3dge_stream_t stream) {
+    return hgf_front_impl(packed, image, depth, out, n, height, width, num_stack, num_hourglass, ws, ws_bytes, nullptr, 0, stream);
+}
+
+static int hgf_front_impl(const float* packed, const float* image, const float* depth, float* out, int n, int height, int width,
+                          int num_stack, int num_hourglass, void* ws, int64_t ws_bytes, float* saved, int64_t saved_bytes, e3dge_stream_t stream) {
     E3DGE_REQUIRE(packed && image && depth && out && ws, "hgf_front: null pointer");
     E3DGE_REQUIRE(hgf_config_ok(num_stack, num_hourglass), "hgf_front: num_stack=%d (1..%d) num_hourglass=%d (1..%d)", num_stack, kHgfMaxStack,
                   num_hourglass, kHgfMaxDepth);
@@ -524,9 +604,16 @@ extern "C" int e3dge_hgf_front(const float* packed, const float* image, const fl
                   (long long)(w.front_floats * (int64_t)sizeof(float)));
     HgfLayout l;
     hgf_layout(num_stack, num_hourglass, &l);
+    HgfSaved sv;
+    if (saved) {
+        hgf_saved(n, height, width, num_stack, num_hourglass, l, &sv);
+        E3DGE_REQUIRE(saved_bytes >= sv.floats * (int64_t)sizeof(float), "hgf_front: saved state of %lld bytes, %lld needed", (long long)saved_bytes,
+                      (long long)(sv.floats * (int64_t)sizeof(float)));
+    }
     hipStream_t st = as_stream(stream);
     float* base = static_cast<float*>(ws);
     float* ab = base + w.fab;
+    float* ab2 = ab;
     float* f0 = base + w.f[0];
     float* f1 = base + w.f[1];
     float* f2 = base + w.f[2];
@@ -537,11 +624,12 @@ extern "C" int e3dge_hgf_front(const float* packed, const float* image, const fl
         const HgfFront& q = l.front[f];
         const float* x = f == 0 ? image : depth;
         const int cin = f == 0 ? 3 : 1;
+        if (saved) { f0 = saved + sv.f0[f]; f1 = saved + sv.f1[f]; f2 = saved + sv.f2[f]; ab = saved + sv.fab[f][0]; ab2 = saved + sv.fab[f][1]; }
         if ((rc = hgf_conv({f0, nullptr, x, at(q.w0), nullptr, nullptr, nullptr, n, cin, 32, height, width, 3, 1, 1, 32, 0, 0, 0}, st))) return rc;
         if ((rc = hgf_norm(ab, f0, at(q.n1), at(q.n1 + 1), n, 32, 0, 32, 32, HW, st))) return rc;
         if ((rc = hgf_conv({f1, nullptr, f0, at(q.w1), ab, nullptr, nullptr, n, 32, 32, height, width, 3, 1, 1, 32, 0, 0, 0}, st))) return rc;
-        if ((rc = hgf_norm(ab, f1, at(q.n2), at(q.n2 + 1), n, 32, 0, 32, 32, HW, st))) return rc;
-        if ((rc = hgf_conv({f2, nullptr, f1, at(q.w2), ab, nullptr, f0, n, 32, 32, height, width, 3, 1, 1, 32, 0, 32, 0}, st))) return rc;
+        if ((rc = hgf_norm(ab2, f1, at(q.n2), at(q.n2 + 1), n, 32, 0, 32, 32, HW, st))) return rc;
+        if ((rc = hgf_conv({f2, nullptr, f1, at(q.w2), ab2, nullptr, f0, n, 32, 32, height, width, 3, 1, 1, 32, 0, 32, 0}, st))) return rc;
         if ((rc = hgf_conv({out, nullptr, f2, at(q.w3), nullptr, nullptr, nullptr, n, 32, 32, height, width, 1, 1, 0, 64, 32 * f, 0, 0}, st))) return rc;
     }
     return E3DGE_OK;
@@ -600,3 +688,5 @@ extern "C" int e3dge_hgf_up_add(float* out, const float* up1, const float* low, 
     E3DGE_REQUIRE(planes * 4 * height * width < ((int64_t)1 << 38), "hgf_up_add: tensor too large");
     return hgf_up_add(out, up1, low, planes, height, width, as_stream(stream));
 }
+
+#include "hgfilter_bwd.h"

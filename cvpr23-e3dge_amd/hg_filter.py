@@ -7,17 +7,21 @@
 The classes have the reference's constructor arguments, attribute names and state-dict keys (vendor/pifu/lib/model/HGFilters.py,
 vendor/pifu/lib/net_util.py:399-453, vendor/pifu/lib/model/HGPIFuGANNetResidualInputResnetFC.py:19-76; `conv` of
 models/helper_modules/helpers.py:432-455), so that class's `netLocal` state dict loads with strict=True; the code is
-this package's own.  Forward only on the kernels: a GPU float32 input runs csrc/hgfilter.hip when no gradient is wanted (grad mode off,
-or neither the input nor a parameter requires grad) and the options are norm='group', hg_down='ave_pool', hg_input_channel=64,
-hourglass_dim=256.  Everything else -- CPU tensors, other dtypes and options, a wanted gradient, E3DGE_HGFILTER=torch -- runs the torch
-composition below: F.conv2d, F.group_norm, F.interpolate and the rest in the reference's order.  The backward of the filter is not
-in this build."""
+this package's own.  A GPU float32 input runs csrc/hgfilter.hip when no gradient is wanted (grad mode off, or neither the input nor a
+parameter requires grad) and the options are norm='group', hg_down='ave_pool', hg_input_channel=64, hourglass_dim=256.  With
+`differentiable=True` (opt-in; the constructors' keyword, an attribute, or `differentiable_filter` in the options) a wanted gradient --
+to the residual image, the depth map or HGFilter's own 64-channel input, or to any parameter the forward reads -- runs there too: one
+autograd node whose forward is the state-saving form of the same launches and whose backward is csrc/hgfilter_bwd.h, once
+differentiable (a second differentiation raises).  With trainable weights the packed images are rebuilt after every optimiser step
+(_lib.weight_image).  Everything else -- CPU tensors, other dtypes and options, E3DGE_HGFILTER=torch, `differentiable` off -- runs the
+torch composition below under plain autograd: F.conv2d, F.group_norm, F.interpolate and the rest in the reference's order."""
 import ctypes
 import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -113,9 +117,10 @@ class HGFilter(nn.Module):
     """`HGFilter(opt)(x)` = (outputs: one (B, hourglass_dim, H / 4, W / 4) map per stack, tmpx: the stem's activation, detached,
     normx: the pooled first ConvBlock) for x (B, opt.hg_input_channel, H, W)."""
 
-    def __init__(self, opt):
+    def __init__(self, opt, differentiable=False):
         super().__init__()
         self.opt = opt
+        self.differentiable = bool(differentiable)
         self.num_modules = int(_opt(opt, 'num_stack'))
         self.num_hourglass = int(_opt(opt, 'num_hourglass'))
         self.front_nets = None      # (residual_conv, depth_conv) of the ResidualImageFilter that owns this filter: packed into the same image
@@ -155,12 +160,20 @@ class HGFilter(nn.Module):
         m = 4 << self.num_hourglass
         return 1 <= n <= 4096 and m <= height <= 4096 and m <= width <= 4096 and height % m == 0 and width % m == 0
 
-    def _runs_hip(self, x):
+    def _covers(self, x):
         if os.environ.get("E3DGE_HGFILTER", "hip") == "torch" or not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32):
             return False
-        if x.ndim != 4 or x.shape[1] != 64 or not self.hip_options() or not self.hip_shape(x.shape[0], x.shape[2], x.shape[3]):
+        return x.ndim == 4 and x.shape[1] == 64 and self.hip_options() and self.hip_shape(x.shape[0], x.shape[2], x.shape[3])
+
+    def _runs_hip(self, x):
+        if not self._covers(x):
             return False
         return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in _lib.params_of(self))))
+
+    def _runs_hip_grad(self, x):
+        """The autograd node on the kernels: opted in, and a gradient is wanted: to the input or to a parameter the forward reads."""
+        return (self.differentiable and torch.is_grad_enabled() and self._covers(x) and
+                (x.requires_grad or any(p.requires_grad for p in self.sources())))
 
     # ---- launch plumbing ------------------------------------------------------------------------------------------------------------
     def sources(self):
@@ -178,6 +191,13 @@ class HGFilter(nn.Module):
     def packed(self, device):
         """The packed weight image on `device`: one per filter.  The front nets' part of it is written when the filter belongs to a
         ResidualImageFilter (`front_nets`) and stays unwritten, and unread, otherwise."""
+        return self._image(device, "hgf_packed", "e3dge_hgf_packed_floats", "e3dge_hgf_pack_weights")
+
+    def packed_t(self, device):
+        """The transposed image beside it: every convolution's data-gradient image, for the backward."""
+        return self._image(device, "hgf_packed_t", "e3dge_hgf_packed_t_floats", "e3dge_hgf_pack_weights_t")
+
+    def _image(self, device, slot, size_entry, pack_entry):
         front = [t for net in self.front_nets for t in _front_sources(net)] if self.front_nets else None
         src = self.sources() + list(front or ())
         S, D = self.num_modules, self.num_hourglass
@@ -188,19 +208,20 @@ class HGFilter(nn.Module):
                 n = len(keep) - (len(front) if front else 0)
                 filt = (ctypes.c_void_p * n)(*[t.data_ptr() for t in keep[:n]])
                 fr = (ctypes.c_void_p * len(front))(*[t.data_ptr() for t in keep[n:]]) if front else None
-                image = torch.empty(_lib.query("e3dge_hgf_packed_floats", S, D), device=device, dtype=torch.float32)
-                _lib.launch("e3dge_hgf_pack_weights", image, ctypes.addressof(filt), n, ctypes.addressof(fr) if front else None, S, D)
+                image = torch.empty(_lib.query(size_entry, S, D), device=device, dtype=torch.float32)
+                _lib.launch(pack_entry, image, ctypes.addressof(filt), n, ctypes.addressof(fr) if front else None, S, D)
                 return image
 
-        return _lib.weight_image(self, "hgf_packed", src, device, "HGFilter", build)
+        return _lib.weight_image(self, slot, src, device, "HGFilter", build)
 
     def invalidate(self):
         """Drop the packed weight images (needed only after writes through `.data`)."""
         _lib.invalidate(self)
 
-    def forward_hip(self, x, ws=None):
+    def forward_hip(self, x, ws=None, saved=None):
         """The forward on csrc/hgfilter.hip, no synchronisation; x (B, 64, H, W) float32 on the GPU.  ws: a workspace of
-        e3dge_hgf_ws_bytes that the caller already holds (filter_maps: the front nets' and the filter's are one)."""
+        e3dge_hgf_ws_bytes that the caller already holds (filter_maps: the front nets' and the filter's are one).  saved: a buffer of
+        e3dge_hgf_saved_bytes: the state-saving form of the same launches, for the backward."""
         _lib.require_gpu(x, "HGFilter input")
         n, c, H, W = x.shape
         if c != 64 or not self.hip_options() or not self.hip_shape(n, H, W):
@@ -217,7 +238,10 @@ class HGFilter(nn.Module):
         a = _lib.HgfArgs(packed=image, input=x, n=n, height=H, width=W, num_stack=S, num_hourglass=D, tmpx=tmpx, normx=normx, ws=ws, ws_bytes=ws_bytes)
         for i, t in enumerate(outs):
             a.outputs[i] = t.data_ptr()
-        _lib.launch("e3dge_hgf_forward", a)
+        if saved is None:
+            _lib.launch("e3dge_hgf_forward", a)
+        else:
+            _lib.launch("e3dge_hgf_forward_saving", a, saved, saved.numel())
         return outs, tmpx, normx
 
     def forward_torch(self, x, probe=None):
@@ -248,7 +272,100 @@ class HGFilter(nn.Module):
         return outputs, tmpx.detach(), normx
 
     def forward(self, x):
+        if self._runs_hip_grad(x):
+            *outs, tmpx, normx = _FilterNode.apply(self, x, None, *self.sources())
+            return list(outs), tmpx, normx
         return self.forward_hip(x) if self._runs_hip(x) else self.forward_torch(x)
+
+
+class _FilterNode(torch.autograd.Function):
+    """(*outputs, tmpx, normx) of HGFilter on the kernels from its 64-channel input (depth None), or from the residual image and the depth
+    map through the front nets.  params: HGFilter.sources() and, with a depth map, the front nets' sixteen tensors, so that autograd asks
+    for their gradients.  Forward: the state-saving form of the plain forward's launches, bit-identical results.  Backward:
+    csrc/hgfilter_bwd.h, once; absent upstream gradients are skipped, tmpx has none, and each gradient is computed only where autograd
+    asks for it (the parameter gradients as a whole: one buffer in the order of the sources)."""
+    branches = None                                                  # debug: a list that receives every backward's e3dge_hgf_branch_bytes buffer
+
+    @staticmethod
+    def forward(ctx, hg, x, depth, *params):
+        ctx.set_materialize_grads(False)
+        n, _, H, W = x.shape
+        dev, S, D = x.device, hg.num_modules, hg.num_hourglass
+        saved = torch.empty(_lib.query("e3dge_hgf_saved_bytes", n, H, W, S, D), device=dev, dtype=torch.uint8)
+        image = hg.packed(dev)
+        ws, first, second = None, x.detach().contiguous(), None
+        x = first                                                    # (what the stem's weight gradient reads again must be dense too)
+        if depth is not None:
+            ws_bytes = _lib.query("e3dge_hgf_ws_bytes", n, H, W, S, D)
+            ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+            feats = torch.empty((n, 64, H, W), device=dev, dtype=torch.float32)
+            second = depth.detach().contiguous()
+            _lib.launch("e3dge_hgf_front_saving", image, first, second, feats, n, H, W, S, D, ws, ws_bytes, saved, saved.numel())
+            x = feats
+        outs, tmpx, normx = hg.forward_hip(x, ws, saved)
+        ctx.mark_non_differentiable(tmpx)
+        wants = any(ctx.needs_input_grad[3:])
+        keep = [x.detach(), first, second] + list(outs) if wants else []                 # what the weight gradients read beside the saved state
+        ctx.save_for_backward(tmpx, normx, saved, image, hg.packed_t(dev), *[t for t in keep if t is not None])
+        ctx.shape = (n, H, W, S, D, depth is not None)
+        ctx.numels = [p.numel() for p in params]
+        ctx.shapes = [tuple(p.shape) for p in params]
+        return (*outs, tmpx, normx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        n, H, W, S, D, front = ctx.shape
+        g_outs, g_normx = grads[:S], grads[S + 1]
+        nothing = (None,) * (3 + len(ctx.numels))
+        if g_normx is None and all(g is None for g in g_outs):
+            return nothing
+        tmpx, normx, saved, image, image_t, *kept = ctx.saved_tensors
+        dev = tmpx.device
+        dense = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        g_outs, g_normx = [dense(g) for g in g_outs], dense(g_normx)
+        ws_bytes = _lib.query("e3dge_hgf_bwd_ws_bytes", n, H, W, S, D)
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        g_input = torch.empty((n, 64, H, W), device=dev, dtype=torch.float32)
+        branch = None
+        if _FilterNode.branches is not None:                         # debug: the ReLU branches of this run (tests: a branch-pinned truth)
+            branch = torch.zeros(_lib.query("e3dge_hgf_branch_bytes", n, H, W, S, D), device=dev, dtype=torch.uint8)
+            _FilterNode.branches.append(branch)
+        wants = any(ctx.needs_input_grad[3:])
+        buf = torch.zeros(_lib.query("e3dge_hgf_grad_floats", S, D), device=dev, dtype=torch.float32) if wants else None
+        a = _lib.HgfBwdArgs(packed=image, packed_t=image_t, saved=saved, saved_bytes=saved.numel(), tmpx=tmpx, normx=normx, n=n, height=H, width=W,
+                            num_stack=S, num_hourglass=D, g_normx=g_normx, g_input=g_input, ws=ws, ws_bytes=ws_bytes, branch=branch,
+                            branch_bytes=0 if branch is None else branch.numel(), grads=buf)
+        for i, g in enumerate(g_outs):
+            a.g_outputs[i] = None if g is None else g.data_ptr()
+        first = second = None
+        if wants:
+            a.input, first = kept[0], kept[1]
+            second = kept[2] if front else None
+            for i, t in enumerate(kept[3 if front else 2:]):
+                a.outputs[i] = t.data_ptr()
+        _lib.launch("e3dge_hgf_backward", a)
+        g_first, g_second = g_input if ctx.needs_input_grad[1] else None, None
+        if front:
+            g_first = torch.empty((n, 3, H, W), device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+            g_second = torch.empty((n, 1, H, W), device=dev, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+            if g_first is not None or g_second is not None or wants:
+                _lib.launch("e3dge_hgf_front_backward", image, image_t, saved, saved.numel(), g_input, g_first, g_second, n, H, W, S, D, ws, ws_bytes, branch,
+                            0 if branch is None else branch.numel(), buf, first if wants else None, second if wants else None)
+        if not wants:
+            return (None, g_first, g_second) + nothing[3:]
+        # which sources an upstream gradient reaches: without a stack's gradient only the stem and conv2 (through normx); otherwise
+        # everything up to the last stack with a gradient, without that stack's bl / al; the front nets always
+        s_max = max([i for i, g in enumerate(g_outs) if g is not None], default=-1)
+        per_stack = (3 * D + 2) * 9 + 6
+        reached = 16 if s_max < 0 else 37 + (s_max + 1) * per_stack + 4 * s_max
+        n_filter = 37 + S * per_stack + 4 * (S - 1)
+        out, off = [], 0
+        for i, (numel, shape) in enumerate(zip(ctx.numels, ctx.shapes)):
+            live = ctx.needs_input_grad[3 + i] and (i < reached or i >= n_filter)
+            out.append(buf[off:off + numel].view(shape) if live else None)
+            off += numel
+        return (None, g_first, g_second, *out)
 
 
 class _FrontResidual(nn.Module):
@@ -294,10 +411,12 @@ class ResidualImageFilter(nn.Module):
     image_filter = HGFilter(local_options).  filter() keeps
     im_feat_dict[feat_key] = [the last stack's map], tmpx and normx, as the reference does."""
 
-    def __init__(self, local_options):
+    def __init__(self, local_options, differentiable=None):
         super().__init__()
         self.local_options = local_options
-        self.image_filter = HGFilter(local_options)
+        if differentiable is None:                                   # LocalFilterHead / SirenLocalGlobal: from the options; off by default
+            differentiable = bool(_opt(local_options, 'differentiable_filter', False))
+        self.image_filter = HGFilter(local_options, differentiable)
         self.downsample_channel_conv = _ChannelConv(512, 64, 3, 1)
         self.depth_conv = _front_net(1)
         self.residual_conv = _front_net(3)
@@ -308,7 +427,15 @@ class ResidualImageFilter(nn.Module):
     def invalidate(self):
         _lib.invalidate(self)
 
-    def _runs_hip(self, image, depth):
+    @property
+    def differentiable(self):
+        return self.image_filter.differentiable
+
+    @differentiable.setter
+    def differentiable(self, value):
+        self.image_filter.differentiable = bool(value)
+
+    def _covers(self, image, depth):
         hg = self.image_filter
         if depth is None or os.environ.get("E3DGE_HGFILTER", "hip") == "torch":
             return False
@@ -317,15 +444,30 @@ class ResidualImageFilter(nn.Module):
                 return False
         if depth.device != image.device or depth.shape[0] != image.shape[0] or depth.shape[2:] != image.shape[2:]:
             return False
-        if not hg.hip_options() or not hg.hip_shape(image.shape[0], image.shape[2], image.shape[3]):
+        return hg.hip_options() and hg.hip_shape(image.shape[0], image.shape[2], image.shape[3])
+
+    def _trainable(self):
+        return any(p.requires_grad for mod in (self.residual_conv, self.depth_conv, self.image_filter) for p in _lib.params_of(mod))
+
+    def _runs_hip(self, image, depth):
+        if not self._covers(image, depth):
             return False
         if not torch.is_grad_enabled():
             return True
-        used = [p for mod in (self.residual_conv, self.depth_conv, hg) for p in _lib.params_of(mod)]
-        return not (image.requires_grad or depth.requires_grad or any(p.requires_grad for p in used))
+        return not (image.requires_grad or depth.requires_grad or self._trainable())
+
+    def _runs_hip_grad(self, image, depth):
+        if not (self.differentiable and torch.is_grad_enabled() and self._covers(image, depth)):
+            return False
+        used = self.image_filter.sources() + _front_sources(self.residual_conv) + _front_sources(self.depth_conv)
+        return image.requires_grad or depth.requires_grad or any(p.requires_grad for p in used)
 
     def filter_maps(self, residual_images, depth_feat=None):
         """(outputs, tmpx, normx) of the image filter for the residual image and the depth map."""
+        if self._runs_hip_grad(residual_images, depth_feat):
+            params = self.image_filter.sources() + _front_sources(self.residual_conv) + _front_sources(self.depth_conv)
+            *outs, tmpx, normx = _FilterNode.apply(self.image_filter, residual_images, depth_feat, *params)
+            return list(outs), tmpx, normx
         if self._runs_hip(residual_images, depth_feat):
             hg = self.image_filter
             n, _, H, W = residual_images.shape

@@ -1253,11 +1253,11 @@ int e3dge_disc_conv_dgrad(float* out, const float* g, const float* w, float* wfr
 int e3dge_disc_stddev(float* cat, float* scalars, const float* feat, int n, int channels, int hw, e3dge_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * Hourglass image filter of the local branch, forward (csrc/hgfilter.hip).  Additions to ABI 17.  No allocation, no
- * synchronisation, no atomics; bit-reproducible, and an image's maps do not depend on its position in the batch or on the batch
+ * Hourglass image filter of the local branch, forward (csrc/hgfilter.hip; the backward is the next section).  Additions to
+ * ABI 17.  No allocation, no synchronisation, no atomics; bit-reproducible, and an image's maps do not depend on its position in the batch or on the batch
  * size.  Replaces HGPIFuNetGANResidualResnetFC.filter (vendor/pifu/lib/model/HGPIFuGANNetResidualInputResnetFC.py:33-76): residual_conv and
  * depth_conv (reflect padding, InstanceNorm2d(affine)), the concatenation and HGFilter (vendor/pifu/lib/model/HGFilters.py) with
- * norm='group', hg_down='ave_pool', hg_input_channel=64, hourglass_dim=256.  Frozen weights, fp32, forward only.
+ * norm='group', hg_down='ave_pool', hg_input_channel=64, hourglass_dim=256.  fp32; the entries of this section are the forward.
  *
  * Source tensors of the filter, in this order (ConvBlock(cin, cout) = bn1.weight, bn1.bias, conv1.weight, bn2.weight, bn2.bias,
  * conv2.weight, bn3.weight, bn3.bias, conv3.weight and, where cin != cout, bn4.weight, bn4.bias, downsample.2.weight;
@@ -1318,6 +1318,99 @@ int e3dge_hgf_norm(float* ab, const float* x, const float* gamma, const float* b
                    int groups, int height, int width, e3dge_stream_t stream);
 int e3dge_hgf_pool(float* out, const float* in, int64_t planes, int height, int width, e3dge_stream_t stream);
 int e3dge_hgf_up_add(float* out, const float* up1, const float* low, int64_t planes, int height, int width, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Hourglass image filter of the local branch, backward (csrc/hgfilter_bwd.h).  Additions to ABI 17.  The gradient to the filter's
+ * input and, through the front nets, to the residual image and the depth map, and (grads != NULL) to every parameter the forward
+ * reads; once differentiable, fp32.
+ * No allocation, no synchronisation, no atomics; two runs are bit-identical and an image's gradient does not depend on the batch.
+ * Every entry refuses null pointers, sizes and configurations outside the forward's, a workspace that is too small ("workspace") and
+ * a saved state that is too small ("saved state") before any launch.
+ *
+ * e3dge_hgf_saved_bytes     bytes of the saved state of n images of height x width, the front nets' part included (-1: bad sizes):
+ *                           every convolution's pre-norm input and every norm's (a, b), each in a buffer of its own.  No masks: a
+ *                           ReLU's branch is recomputed as fmaf(a, x, b) > 0; no mean or rstd: the moments are summed again.
+ * e3dge_hgf_forward_saving  e3dge_hgf_forward with the same launches and bit-identical results, the state kept in `saved`.
+ * e3dge_hgf_front_saving    e3dge_hgf_front likewise, into the same `saved` buffer.
+ * e3dge_hgf_packed_t_floats floats of the transposed image: the data gradient's A-fragment image of every convolution (-1: outside).
+ * e3dge_hgf_pack_weights_t  as e3dge_hgf_pack_weights; norm weights are read from the forward image.  Re-run after a weight update.
+ * e3dge_hgf_bwd_ws_bytes    workspace bytes of e3dge_hgf_backward and e3dge_hgf_front_backward (-1: bad sizes).
+ * e3dge_hgf_backward        g_outputs[i] (n, 256, height / 4, width / 4) or NULL (absent: skipped, not zeros), g_normx likewise, at
+ *                           least one of them; tmpx, normx: the forward's results -> g_input (n, 64, height, width).
+ * e3dge_hgf_front_backward  g_feats (n, 64, height, width) -> g_image (n, 3, height, width), g_depth (n, 1, height, width); either
+ *                           may be NULL (not wanted).  grads: NULL, or the same buffer as e3dge_hgf_backward's: the front nets'
+ *                           sixteen gradients are written behind the filter's; then image and depth are the forward's inputs.
+ * e3dge_hgf_grad_floats     floats of `grads`: one gradient per source tensor of e3dge_hgf_pack_weights, filter_src then front_src,
+ *                           in that order and in the sources' own shapes, back to back (-1: outside).  Gradients of layers that no
+ *                           upstream gradient reaches (stacks above the last one with a gradient) are left unwritten.
+ * e3dge_hgf_branch_bytes    bytes of the optional debug buffer `branch` of the two entries above (one buffer for both): one byte per
+ *                           element of every norm's input, 1 where this run's ReLU passed -- what a branch-pinned float64 truth
+ *                           takes its ReLU derivatives from.  Order: the stem's norm; bn1, bn2, bn3 and, where the block has a
+ *                           downsample, bn4 of every ConvBlock in the order of the source tensors; bn_end of every stack; the two
+ *                           norms of residual_conv, then of depth_conv.  Every buffer starts at a multiple of 256 bytes.
+ * e3dge_hgf_conv_dgrad      debug entry: out (n, cin, height, width) = addend + [fmaf(a, x, b) > 0] * the data gradient of the
+ *                           convolution of e3dge_hgf_conv from g = the channels [g_c0, g_c0 + cout) of (n, g_channels, OH, OW);
+ *                           (a, b) = x_ab (n, cin, 2), x (n, cin, height, width), both or neither; addend optional; wfrag_t:
+ *                           ig_mpad(cin) * ig_kpad(cout ksize^2) floats, written here.  Two launches.
+ * e3dge_hgf_norm_bwd        debug entry: gx (n, channels, height, width) = add1 + (add0 + d norm / d x applied to gy) for the norm
+ *                           of e3dge_hgf_norm; add0 the channels [add0_c0, ..) of (n, add0_channels, height, width), add1 dense,
+ *                           both optional; mask_ab (n, channels, 2) optional: gy is first multiplied by fmaf(a, x, b) > 0; coef:
+ *                           n * channels * 5 float64 of scratch.  dgamma, dbeta (channels) optional, together: the norm's
+ *                           parameter gradients, summed over the images in ascending order in float64.  Two or three launches.
+ * e3dge_hgf_pool_bwd        debug entry: gin (planes, height, width) = addend + the adjoint of avg_pool2d(2, 2) applied to gout.
+ * e3dge_hgf_conv_wgrad      debug entry: dw (cout, cin, ksize, ksize) = the weight gradient of the convolution of e3dge_hgf_conv from g
+ *                           (as e3dge_hgf_conv_dgrad's) and its input x (n, cin, height, width), activated by relu(a x + b) where
+ *                           x_ab is given; dbias (cout) optional, from a dense g.  ws: e3dge_hgf_wgrad_ws_floats floats.  Split K
+ *                           over images and 2048-pixel segments, partials folded in float64 in ascending order: no atomics.
+ * e3dge_hgf_up_bwd          debug entry: glow (planes, height, width) = the adjoint of e3dge_hgf_up_add's bicubic x2 applied to g
+ *                           (planes, 2 height, 2 width).
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct E3dgeHgfBwdArgs {
+    const float* packed;              /* e3dge_hgf_pack_weights */
+    const float* packed_t;            /* e3dge_hgf_pack_weights_t */
+    const float* saved;               /* e3dge_hgf_forward_saving */
+    int64_t saved_bytes;
+    const float* tmpx; const float* normx;
+    int32_t n, height, width, num_stack, num_hourglass, reserved;
+    const float* g_outputs[E3DGE_HGF_MAX_STACK];
+    const float* g_normx;
+    float* g_input;
+    void* ws;
+    int64_t ws_bytes;
+    unsigned char* branch;            /* debug, or NULL: e3dge_hgf_branch_bytes */
+    int64_t branch_bytes;
+    float* grads;                     /* NULL (frozen), or e3dge_hgf_grad_floats floats: the parameter gradients */
+    const float* input;               /* with grads: the forward's input and its outputs below the last one with a gradient */
+    const float* outputs[E3DGE_HGF_MAX_STACK];
+} E3dgeHgfBwdArgs;
+int64_t e3dge_hgf_saved_bytes(int n, int height, int width, int num_stack, int num_hourglass);
+int e3dge_hgf_forward_saving(const E3dgeHgfArgs* args, void* saved, int64_t saved_bytes, e3dge_stream_t stream);
+int e3dge_hgf_front_saving(const float* packed, const float* image, const float* depth, float* out, int n, int height, int width,
+                           int num_stack, int num_hourglass, void* ws, int64_t ws_bytes, void* saved, int64_t saved_bytes,
+                           e3dge_stream_t stream);
+int64_t e3dge_hgf_packed_t_floats(int num_stack, int num_hourglass);
+int e3dge_hgf_pack_weights_t(float* packed_t, const float* const* filter_src, int n_filter_src, const float* const* front_src,
+                             int num_stack, int num_hourglass, e3dge_stream_t stream);
+int64_t e3dge_hgf_bwd_ws_bytes(int n, int height, int width, int num_stack, int num_hourglass);
+int64_t e3dge_hgf_branch_bytes(int n, int height, int width, int num_stack, int num_hourglass);
+int e3dge_hgf_backward(const E3dgeHgfBwdArgs* args, e3dge_stream_t stream);
+int e3dge_hgf_front_backward(const float* packed, const float* packed_t, const void* saved, int64_t saved_bytes, const float* g_feats,
+                             float* g_image, float* g_depth, int n, int height, int width, int num_stack, int num_hourglass, void* ws,
+                             int64_t ws_bytes, unsigned char* branch, int64_t branch_bytes, float* grads, const float* image,
+                             const float* depth, e3dge_stream_t stream);
+int e3dge_hgf_conv_dgrad(float* out, const float* g, const float* w, float* wfrag_t, const float* x, const float* x_ab, const float* addend,
+                         int n, int cin, int cout, int height, int width, int ksize, int stride, int reflect, int g_channels, int g_c0,
+                         e3dge_stream_t stream);
+int e3dge_hgf_norm_bwd(float* gx, const float* gy, const float* x, const float* gamma, const float* mask_ab, const float* add0,
+                       int add0_channels, int add0_c0, const float* add1, double* coef, float* dgamma, float* dbeta, int n, int channels_total, int c0,
+                       int channels, int groups, int height, int width, e3dge_stream_t stream);
+int e3dge_hgf_pool_bwd(float* gin, const float* gout, const float* addend, int64_t planes, int height, int width, e3dge_stream_t stream);
+int e3dge_hgf_up_bwd(float* glow, const float* g, int64_t planes, int height, int width, e3dge_stream_t stream);
+int64_t e3dge_hgf_grad_floats(int num_stack, int num_hourglass);
+int64_t e3dge_hgf_wgrad_ws_floats(int n, int cin, int cout, int height, int width, int ksize, int stride);
+int e3dge_hgf_conv_wgrad(float* dw, float* dbias, const float* g, const float* x, const float* x_ab, int n, int cin, int cout, int height,
+                         int width, int ksize, int stride, int reflect, int g_channels, int g_c0, float* ws, int64_t ws_floats,
+                         e3dge_stream_t stream);
 
 #ifdef __cplusplus
 }
