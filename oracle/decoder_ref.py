@@ -117,6 +117,47 @@ def decoder_forward(sd, features, latent, noises=None, prefix='decoder.', dtype=
     return skip
 
 
+def decoder_stages(sd, prefix='decoder.'):
+    """The stages of decoder_forward in execution order: [(kind, layer prefix, latent row, upsample)], kind 'conv' (a styled_conv) or
+    'rgb' (a to_rgb; its `upsample` says whether the previous skip image is FIR-up-sampled: not for to_rgb1, which has none)."""
+    out = [('conv', prefix + 'conv1.', 0, False), ('rgb', prefix + 'to_rgb1.', 1, False)]
+    u = 0
+    while f'{prefix}convs.{2 * u}.conv.weight' in sd:
+        out += [('conv', f'{prefix}convs.{2 * u}.', 2 * u + 1, True), ('conv', f'{prefix}convs.{2 * u + 1}.', 2 * u + 2, False),
+                ('rgb', f'{prefix}to_rgbs.{u}.', 2 * u + 3, True)]
+        u += 1
+    return out
+
+
+def decoder_stage(sd, stage, x, style, other, dtype=torch.float32):
+    """ONE stage of decoder_forward (an entry of decoder_stages) in `dtype` on GIVEN inputs: the input activation x, the stage's latent
+    row `style` (B, 512), and `other`: the noise image of a 'conv', the previous skip image (or None) of an 'rgb'.  Chained over
+    decoder_stages with its own outputs it is decoder_forward, operation for operation."""
+    kind, p, _, upsample = stage
+    x, style = x.to(dtype), style.to(dtype)
+    if kind == 'conv':
+        return styled_conv(sd, p, x, style, other, upsample=upsample)
+    return to_rgb(sd, p, x, style, None if other is None else other.to(dtype), upsample=upsample)
+
+
+def decoder_modulations(sd, latent, prefix='decoder.', dtype=torch.float32):
+    """[(s, demod)] of every modulated layer in execution order (decoder_stages): s (B, Ci) = the modulation output (equal_linear of the
+    layer's latent row); demod (B, Co) = rsqrt(sum over (Ci, k, k) of (scale W s)^2 + 1e-8) for the 3x3 layers (ModulatedConv2d.forward
+    :321-326, as modulated_weights applies it), None for the ToRGB layers (no demodulation)."""
+    latent = latent.to(dtype)
+    out = []
+    for kind, p, row, _ in decoder_stages(sd, prefix):
+        s = equal_linear(sd, p + 'conv.modulation.', latent[:, row])
+        demod = None
+        if kind == 'conv':
+            weight = _w(sd, p + 'conv.weight', dtype)
+            _, _, Ci, k, _ = weight.shape
+            w = (1 / math.sqrt(Ci * k * k)) * weight * s.reshape(s.shape[0], 1, Ci, 1, 1)
+            demod = torch.rsqrt(w.pow(2).sum([2, 3, 4]) + 1e-8)
+        out.append((s, demod))
+    return out
+
+
 def decoder_pinned_backward(sd, features, latent, noises, d_img, masks=None, prefix='decoder.', dtype=torch.float64):
     """decoder_forward and its autograd with the branch of every leaky relu PINNED: StyledConv i (conv1, then up / conv per level)
     computes pre = modulated_conv + noise.weight * noise + activate.bias and returns where(masks[i], pre, 0.2 pre) * sqrt 2, masks[i] a
