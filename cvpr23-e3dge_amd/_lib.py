@@ -293,6 +293,15 @@ class HgfBwdArgs(_Args):
         ("g_outputs", _vp * HGF_MAX_STACK), ("g_normx", _vp), ("g_input", _vp), ("ws", _vp), ("ws_bytes", _i64), ("branch", _vp), ("branch_bytes", _i64), ("grads", _vp), ("input", _vp), ("outputs", _vp * HGF_MAX_STACK)]
 
 
+ENC_HEADS, ENC_MAX_HEAD_CONVS = 9, 8                               # E3DGE_ENC_* (include/e3dge_hip.h)
+
+
+class EncArgs(_Args):
+    """Mirror of struct E3dgeEncArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("images", _vp)] + [(n, _i32) for n in ("n", "size", "geo_dim", "tex_dim", "enable_decoder", "reserved")] + [
+        (n, _vp) for n in ("thumb_out", "stylegan_out", "p32", "p64", "ws")] + [("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -453,6 +462,13 @@ SIGNATURES = {
     "e3dge_hgf_conv_wgrad": (_i32, [_vp] * 5 + [_i32] * 10 + [_vp, _i64, _vp]),
     "e3dge_hgf_pool_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "e3dge_hgf_up_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
+    "e3dge_enc_packed_floats": (_i64, [_i32] * 4),
+    "e3dge_enc_pack_weights": (_i32, [_vp, _vp] + [_i32] * 5 + [_vp]),
+    "e3dge_enc_ws_bytes": (_i64, [_i32] * 5),
+    "e3dge_enc_forward": (_i32, [ctypes.POINTER(EncArgs), _vp]),
+    "e3dge_enc_lateral": (_i32, [_vp] * 6 + [_i32] * 7 + [_vp]),
+    "e3dge_enc_head_conv": (_i32, [_vp] * 5 + [_i32] * 7 + [_vp]),
+    "e3dge_enc_head_tail": (_i32, [_vp] * 7 + [_i64] + [_i32] * 5 + [_vp]),
 }
 
 _lib = None

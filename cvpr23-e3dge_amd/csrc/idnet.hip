@@ -26,6 +26,7 @@
 // The backward (the gradient to the y_hat images, 104 launches) is idnet_bwd.h; the conv, se, merge and head fold kernels have a SAVE
 // instantiation that keeps what it needs.
 // Measured times, the per-kernel split and what bounds each kernel: DESIGN.md 4.11d.
+// The E0 image encoder (encoder.h, included at the end) runs the same units at a run-time size with a driver of its own.
 #include "conv_igemm.h"
 
 namespace e3dge {
@@ -631,3 +632,4 @@ extern "C" int e3dge_idnet_conv(float* out, const float* in, const float* w, flo
 }
 
 #include "idnet_bwd.h"
+#include "encoder.h"

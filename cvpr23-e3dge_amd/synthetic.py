@@ -186,6 +186,55 @@ def load_synthetic_idloss(module, seed=0):
     return module
 
 
+def encoder_opt(**over):
+    """The options `e3dge_amd.encoders.HybridGradualStyleEncoder_V2` reads, at the scripts' values (scripts/test/*.sh: --full_pipeline,
+    --fpn_pigan_geo_layer_dim 128; utils/options.py:1412-1424 for the rest)."""
+    o = AttrDict(input_nc=3, full_pipeline=True, disable_decoder_fpn=False, single_decoder_layer=False, fpn_pigan_geo_layer_dim=128,
+                 fpn_pigan_tex_layer_dim=128)
+    o.update(over)
+    return o
+
+
+ENC_LATERAL_GAIN = 1.0 / math.sqrt(2.0)
+
+
+def load_synthetic_encoder(module, seed=0):
+    """Deterministic stand-ins for the encoder checkpoint of an `e3dge_amd.encoders.HybridGradualStyleEncoder_V2` (or the reference's: the
+    keys are the same).  input_layer and body follow load_synthetic_idloss's recipe (He-scaled convolutions with its per-role gains, its
+    PReLU slopes and BatchNorm statistics); the heads' convolutions are He-scaled with gain 1, the laterals with 1 / sqrt(2) (two maps
+    are added); EqualLinear weights are N(0, 1) as the reference initialises them; every bias is 0.05 N.  With this recipe the float64
+    forward stays alive at 256^2, 64^2 and 48^2 (tests/test_gpu_encoder.py asserts the ranges before it compares)."""
+    sd = {}
+    kinds = dict(module.named_modules())
+    for k, v in module.state_dict().items():
+        owner, leaf = k.rsplit('.', 1)
+        m = kinds[owner]
+        if leaf == 'num_batches_tracked':
+            sd[k] = torch.zeros_like(v)
+            continue
+        t = synthetic_tensor('encoder.' + k, v.shape, seed)           # 'weight': N(0, 1); everything else: 0.05 N(0, 1)
+        if isinstance(m, torch.nn.Conv2d) and leaf == 'weight':
+            fan_in = v.shape[1] * v.shape[2] * v.shape[3]
+            if '.fc1' in k or '.fc2' in k:
+                gain = ID_SE_GAIN
+            elif '.shortcut_layer.' in k:
+                gain = ID_SHORTCUT_GAIN / math.sqrt(2.0)
+            elif k.endswith('res_layer.3.weight'):
+                gain = ID_CONV2_GAIN
+            elif k.startswith('latlayer'):
+                gain = ENC_LATERAL_GAIN
+            else:
+                gain = 1.0
+            t = t * (gain * math.sqrt(2.0 / fan_in))
+        elif isinstance(m, torch.nn.PReLU):
+            t = 0.25 + 0.05 * t
+        elif isinstance(m, torch.nn.BatchNorm2d):
+            t = {'weight': 1.0 + 0.1 * t, 'bias': 2.0 * t, 'running_mean': 2.0 * t, 'running_var': 1.0 + 4.0 * t}[leaf]
+        sd[k] = t.to(v.dtype)
+    module.load_state_dict(sd, strict=True)
+    return module
+
+
 def discriminator_opt(D_init_size=256, channel_multiplier=2, **over):
     """The model options `e3dge_amd.discriminator.Discriminator` reads (scripts/train/ffhq/stage2.2.sh: --D_init_size 256)."""
     o = AttrDict(D_init_size=D_init_size, D_input_size=3, channel_multiplier=channel_multiplier)

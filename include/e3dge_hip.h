@@ -1412,6 +1412,69 @@ int e3dge_hgf_conv_wgrad(float* dw, float* dbias, const float* g, const float* x
                          int width, int ksize, int stride, int reflect, int g_channels, int g_c0, float* ws, int64_t ws_floats,
                          e3dge_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The E0 image encoder, forward, eval form (csrc/encoder.h, compiled with csrc/idnet.hip).  Additions to ABI 17.  No allocation, no
+ * synchronisation, no atomics; bit-reproducible, and an image's results do not depend on its position in the batch or on the batch
+ * size.  Replaces HybridGradualStyleEncoder_V2.forward (project/models/encoders/fpn_encoders.py:266-433) for num_layers 50, mode
+ * 'ir_se', input_nc 3, BatchNorm on its running statistics: input_layer and the 24 bottleneck_IR_SE units, the three lateral layers of
+ * the pyramid and the style heads (GradualStyleBlock, helpers.py:472-497).  fp32.  No backward.
+ *
+ * Configuration: size (the square input: a multiple of 16 in 32..256), geo_dim and tex_dim (fpn_pigan_geo_layer_dim,
+ * fpn_pigan_tex_layer_dim: 32, 64 or 128; a head has log2(dim) convolutions; the three texture heads read p64 when tex_dim is 64 and
+ * p32 otherwise), enable_decoder (0 / 1: the decoder head styles_stylegan.0 on p128).  A head layer whose input map is larger than
+ * 2 x 2 is a convolution; from the 2 x 2 (or 1 x 1) map on the packed image holds the taps that see the map and nothing else, so the
+ * image depends on the size.
+ *
+ * Source tensors, in this order (BN = weight, bias, running_mean, running_var):
+ *   input_layer.0.weight, BN input_layer.1, input_layer.2.weight; per unit body.<u>: BN res_layer.0, res_layer.1.weight,
+ *   res_layer.2.weight, res_layer.3.weight, BN res_layer.4, res_layer.5.fc1.weight, res_layer.5.fc2.weight and, for units 3, 7 and 21,
+ *   shortcut_layer.0.weight, BN shortcut_layer.1; latlayer256, latlayer128, latlayer64 (.weight, .bias each); per head
+ *   styles_pigan.0 .. 8 and then, with enable_decoder, styles_stylegan.0: convs.0.weight, convs.0.bias, convs.2.weight, ... (every
+ *   convolution), linear.weight, linear.bias.  styles_stylegan.1-9 are never read by the reference's forward and are not sources.
+ *
+ * e3dge_enc_packed_floats   floats of the packed image (-1: outside the configurations above).
+ * e3dge_enc_pack_weights    src: HOST array of n_src device pointers.  Re-run after a weight update.
+ * e3dge_enc_ws_bytes        workspace bytes of e3dge_enc_forward for n images (1..256) (-1: bad sizes).
+ * e3dge_enc_forward         images (n, 3, size, size) -> thumb_out (n, 9, 256), stylegan_out (n, 512) (head 0 of the decoder latent; may
+ *                           be NULL without enable_decoder, when no p128 work is done), p32 (n, 512, size / 8, size / 8), p64
+ *                           (n, 512, size / 4, size / 4).  Fails before any launch on a null pointer ("null"), n, size or dims out of range
+ *                           and a workspace that is too small ("workspace").
+ * e3dge_enc_lateral         debug entry: out (n, cout, height, width) = bilinear(coarse (n, cout, coarse_height, coarse_width) -> height
+ *                           x width, align_corners) + (conv1x1(in (n, cin, height, width), w (cout, cin)) + bias).  cout a multiple of
+ *                           64; wfrag: scratch of cout * roundup(cin, 32) floats.  Two launches.
+ * e3dge_enc_head_conv       debug entry: out (heads, n, cout, ceil(height / 2), ceil(width / 2)) = LeakyReLU_0.01(conv3x3 stride 2 pad 1
+ *                           + bias) per head; in (n, cin, height, width) with shared = 1, (heads, n, cin, height, width) with 0;
+ *                           w (heads, cout, cin, 3, 3), bias (heads, cout).  wfrag: heads * cout * roundup(9 cin, 32) floats.
+ * e3dge_enc_head_tail       debug entry: a head group's tail from a start x start map (start 1 or 2): in (heads, n, channels, start,
+ *                           start) -> n_convs stride-2 layers (the first one sees the start x start map, the rest 1 x 1 maps;
+ *                           conv_w (heads, n_convs, channels, channels, 3, 3) whose dead taps are never read, conv_b (heads, n_convs,
+ *                           channels)) -> EqualLinear (lin_w (heads, channels, channels) times 1 / sqrt(channels), lin_b (heads,
+ *                           channels)) -> out (n, heads, channels).  scratch: at least heads * channels * (channels * (n_convs + 4) +
+ *                           n_convs + 1 + 2 n) floats.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_ENC_HEADS 9
+#define E3DGE_ENC_MAX_HEAD_CONVS 8
+typedef struct E3dgeEncArgs {
+    const float* packed;              /* e3dge_enc_pack_weights, for the same size and dims */
+    const float* images;
+    int32_t n, size, geo_dim, tex_dim, enable_decoder, reserved;
+    float* thumb_out; float* stylegan_out; float* p32; float* p64;
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeEncArgs;
+int64_t e3dge_enc_packed_floats(int size, int geo_dim, int tex_dim, int enable_decoder);
+int e3dge_enc_pack_weights(float* packed, const float* const* src, int n_src, int size, int geo_dim, int tex_dim, int enable_decoder,
+                           e3dge_stream_t stream);
+int64_t e3dge_enc_ws_bytes(int n, int size, int geo_dim, int tex_dim, int enable_decoder);
+int e3dge_enc_forward(const E3dgeEncArgs* args, e3dge_stream_t stream);
+int e3dge_enc_lateral(float* out, const float* coarse, const float* in, const float* w, const float* bias, float* wfrag, int n, int cin,
+                      int cout, int coarse_height, int coarse_width, int height, int width, e3dge_stream_t stream);
+int e3dge_enc_head_conv(float* out, const float* in, const float* w, const float* bias, float* wfrag, int n, int heads, int shared, int cin,
+                        int cout, int height, int width, e3dge_stream_t stream);
+int e3dge_enc_head_tail(float* out, const float* in, const float* conv_w, const float* conv_b, const float* lin_w, const float* lin_b,
+                        float* scratch, int64_t scratch_floats, int n, int heads, int channels, int start, int n_convs,
+                        e3dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
