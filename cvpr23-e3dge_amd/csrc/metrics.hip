@@ -73,8 +73,14 @@ image_metrics_tile_kernel(float* __restrict__ partial, const float* __restrict__
             mx = fmaf(g1[i], rx, mx); my = fmaf(g1[i], ry, my);
             sxx = fmaf(g1[i], rxx, sxx); syy = fmaf(g1[i], ryy, syy); sxy = fmaf(g1[i], rxy, sxy);
         }
-        sxx -= mx * mx; syy -= my * my; sxy -= mx * my;
-        const float ssim = ((2.0f * mx * my + c1) * (2.0f * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2));
+        // every product and sum below is rounded on its own (no fma contraction): where pred == gt, numerator and denominator are then
+        // the same bits (2 mx my = mx^2 + my^2 and 2 sxy = sxx + syy exactly) and the loss is exactly 0, as the plain-torch formulation
+        // gives it; contracted, mx * mx + my * my became fma(mx, mx, my * my) and identical images kept a loss of ~1e-8 per pixel
+        const float mxx = __fmul_rn(mx, mx), myy = __fmul_rn(my, my), mxy = __fmul_rn(mx, my);
+        sxx = __fsub_rn(sxx, mxx); syy = __fsub_rn(syy, myy); sxy = __fsub_rn(sxy, mxy);
+        const float num = __fmul_rn(__fadd_rn(2.0f * mxy, c1), __fadd_rn(2.0f * sxy, c2));
+        const float den = __fmul_rn(__fadd_rn(__fadd_rn(mxx, myy), c1), __fadd_rn(__fadd_rn(sxx, syy), c2));
+        const float ssim = num / den;
         sl += fminf(fmaxf((1.0f - ssim) * 0.5f, 0.0f), 1.0f);
         const float d = px[r + kMtHalo][c + kMtHalo] - py[r + kMtHalo][c + kMtHalo];
         se = fmaf(d, d, se);

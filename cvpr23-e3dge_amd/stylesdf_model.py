@@ -681,7 +681,7 @@ class Decoder(nn.Module):
                 return False
         if features.shape[1] != self.conv1.conv.in_channel:
             return False
-        if self.to_rgbs and self._blur_factor() is None:     # the planar path applies any 4x4 blur kernel as it is
+        if self.to_rgbs and self._blur_factor() is None:     # the planar path applies any 4x4 blur kernel, and each level's own, as it is
             return False
         B, res = features.shape[0], features.shape[2]
         # 32-bit byte offsets inside one packed tensor
@@ -691,10 +691,17 @@ class Decoder(nn.Module):
         return all(n is None or (n.device == features.device and n.dtype == torch.float32) for n in noise)
 
     def _blur_factor(self):
-        """blur_factor of the first up-sampling layer's Blur kernel (the plan hands it to every level), cached: _dec2_ok asks on every
-        forward, and the kernel is a device buffer."""
-        k = self.convs[0].conv.blur.kernel
-        return _lib.cached(self, 'blur_factor', (k,), lambda: blur_factor(k))
+        """blur_factor of the first up-sampling layer's Blur kernel (the plan hands it, and the first ToRGB's up-sampling kernel, to
+        every level), or None when another level's Blur or Upsample buffer differs from the first level's: the planar path applies
+        each layer's own.  Cached on every FIR buffer: _dec2_ok asks on every forward, and the kernels are device buffers."""
+        blurs = [self.convs[2 * u].conv.blur.kernel for u in range(len(self.to_rgbs))]
+        ups = [tr.upsample.kernel for tr in self.to_rgbs]
+
+        def build():
+            if any(k.shape != ks[0].shape or not torch.equal(k, ks[0]) for ks in (blurs, ups) for k in ks[1:]):
+                return None
+            return blur_factor(blurs[0])
+        return _lib.cached(self, 'blur_factor', blurs + ups, build)
 
     def invalidate(self):
         """Drop every packed weight image, style table and plan of the decoder and its layers (needed after writes through `.data`;

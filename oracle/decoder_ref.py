@@ -62,8 +62,9 @@ def modulated_weights(weight, s, demodulate=True):
     return w
 
 
-def modulated_conv(sd, prefix, x, style, demodulate=True, upsample=False):
-    """ModulatedConv2d.forward :317-362 (no downsample branch on this path)."""
+def modulated_conv(sd, prefix, x, style, demodulate=True, upsample=False, blur_fir=None):
+    """ModulatedConv2d.forward :317-362 (no downsample branch on this path).  blur_fir: the 4x4 kernel of the up-sampling layer's Blur
+    (its registered buffer, gain included); None: make_kernel([1, 3, 3, 1]) * 4, what the module registers."""
     dt = x.dtype
     weight = _w(sd, prefix + 'weight', dt)                          # (1, Co, Ci, k, k)
     _, Co, Ci, k, _ = weight.shape
@@ -75,31 +76,35 @@ def modulated_conv(sd, prefix, x, style, demodulate=True, upsample=False):
         out = F.conv_transpose2d(x.reshape(1, B * Ci, H, W), wt, padding=0, stride=2, groups=B)
         out = out.reshape(B, Co, out.shape[2], out.shape[3])
         p = (4 - 2) - (k - 1)                                       # :285-287
-        return upfirdn2d_ref_simple(out, fir(gain=4.0, dtype=dt), pad=((p + 1) // 2 + 1, p // 2 + 1))
+        k4 = fir(gain=4.0, dtype=dt) if blur_fir is None else blur_fir.to(dt)
+        return upfirdn2d_ref_simple(out, k4, pad=((p + 1) // 2 + 1, p // 2 + 1))
     out = F.conv2d(x.reshape(1, B * Ci, H, W), w.reshape(B * Co, Ci, k, k), padding=k // 2, groups=B)
     return out.reshape(B, Co, out.shape[2], out.shape[3])
 
 
-def styled_conv(sd, prefix, x, style, noise, upsample=False):
+def styled_conv(sd, prefix, x, style, noise, upsample=False, blur_fir=None):
     """StyledConv.forward :494-507: mod-conv, + noise.weight * noise (:466), lrelu(x + activate.bias) * sqrt 2."""
-    out = modulated_conv(sd, prefix + 'conv.', x, style, True, upsample)
+    out = modulated_conv(sd, prefix + 'conv.', x, style, True, upsample, blur_fir)
     out = out + _w(sd, prefix + 'noise.weight', x.dtype) * noise.to(x.dtype)
     return fused_leaky_relu_ref(out, _w(sd, prefix + 'activate.bias', x.dtype))
 
 
-def to_rgb(sd, prefix, x, style, skip=None, upsample=True):
-    """ToRGB.forward :531-541."""
+def to_rgb(sd, prefix, x, style, skip=None, upsample=True, up_fir=None):
+    """ToRGB.forward :531-541.  up_fir: the 4x4 kernel of its Upsample (the registered buffer, gain included); None:
+    make_kernel([1, 3, 3, 1]) * 4."""
     out = modulated_conv(sd, prefix + 'conv.', x, style, demodulate=False) + _w(sd, prefix + 'bias', x.dtype)
     if skip is not None:
         if upsample:
-            skip = upfirdn2d_ref_simple(skip, fir(gain=4.0, dtype=x.dtype), up=2, pad=(2, 1))   # Upsample :96-119
+            k4 = fir(gain=4.0, dtype=x.dtype) if up_fir is None else up_fir.to(x.dtype)
+            skip = upfirdn2d_ref_simple(skip, k4, up=2, pad=(2, 1))                             # Upsample :96-119
         out = out + skip
     return out
 
 
-def decoder_forward(sd, features, latent, noises=None, prefix='decoder.', dtype=torch.float32):
+def decoder_forward(sd, features, latent, noises=None, prefix='decoder.', dtype=torch.float32, blur_firs=None, up_firs=None):
     """Decoder.forward :742-797 with input_is_latent=True, randomize_noise=False (noise buffers) unless
-    `noises` is given.  features (B,256,r,r), latent (B,n_latent,512)."""
+    `noises` is given.  features (B,256,r,r), latent (B,n_latent,512).  blur_firs / up_firs: per level, the Blur kernel of the
+    up-sampling layer and the Upsample kernel of the ToRGB (None: the default of modulated_conv / to_rgb)."""
     features, latent = features.to(dtype), latent.to(dtype)
     n_up = 0
     while f'{prefix}convs.{2 * n_up}.conv.weight' in sd:
@@ -110,9 +115,10 @@ def decoder_forward(sd, features, latent, noises=None, prefix='decoder.', dtype=
     skip = to_rgb(sd, prefix + 'to_rgb1.', out, latent[:, 1], None, upsample=False)
     i = 1
     for u in range(n_up):                                           # :773-792
-        out = styled_conv(sd, f'{prefix}convs.{2 * u}.', out, latent[:, i], noises[2 * u + 1], upsample=True)
+        out = styled_conv(sd, f'{prefix}convs.{2 * u}.', out, latent[:, i], noises[2 * u + 1], upsample=True,
+                          blur_fir=None if blur_firs is None else blur_firs[u])
         out = styled_conv(sd, f'{prefix}convs.{2 * u + 1}.', out, latent[:, i + 1], noises[2 * u + 2])
-        skip = to_rgb(sd, f'{prefix}to_rgbs.{u}.', out, latent[:, i + 2], skip)
+        skip = to_rgb(sd, f'{prefix}to_rgbs.{u}.', out, latent[:, i + 2], skip, up_fir=None if up_firs is None else up_firs[u])
         i += 2
     return skip
 
@@ -129,15 +135,16 @@ def decoder_stages(sd, prefix='decoder.'):
     return out
 
 
-def decoder_stage(sd, stage, x, style, other, dtype=torch.float32):
+def decoder_stage(sd, stage, x, style, other, dtype=torch.float32, fir=None):
     """ONE stage of decoder_forward (an entry of decoder_stages) in `dtype` on GIVEN inputs: the input activation x, the stage's latent
     row `style` (B, 512), and `other`: the noise image of a 'conv', the previous skip image (or None) of an 'rgb'.  Chained over
-    decoder_stages with its own outputs it is decoder_forward, operation for operation."""
+    decoder_stages with its own outputs it is decoder_forward, operation for operation.  fir: the stage's own 4x4 kernel (the Blur of an
+    up-sampling 'conv', the Upsample of an 'rgb'); None: the default."""
     kind, p, _, upsample = stage
     x, style = x.to(dtype), style.to(dtype)
     if kind == 'conv':
-        return styled_conv(sd, p, x, style, other, upsample=upsample)
-    return to_rgb(sd, p, x, style, None if other is None else other.to(dtype), upsample=upsample)
+        return styled_conv(sd, p, x, style, other, upsample=upsample, blur_fir=fir)
+    return to_rgb(sd, p, x, style, None if other is None else other.to(dtype), upsample=upsample, up_fir=fir)
 
 
 def decoder_modulations(sd, latent, prefix='decoder.', dtype=torch.float32):
@@ -158,14 +165,15 @@ def decoder_modulations(sd, latent, prefix='decoder.', dtype=torch.float32):
     return out
 
 
-def decoder_pinned_backward(sd, features, latent, noises, d_img, masks=None, prefix='decoder.', dtype=torch.float64):
+def decoder_pinned_backward(sd, features, latent, noises, d_img, masks=None, prefix='decoder.', dtype=torch.float64, blur_firs=None,
+                            up_firs=None):
     """decoder_forward and its autograd with the branch of every leaky relu PINNED: StyledConv i (conv1, then up / conv per level)
     computes pre = modulated_conv + noise.weight * noise + activate.bias and returns where(masks[i], pre, 0.2 pre) * sqrt 2, masks[i] a
     boolean tensor of pre's shape (None: pre > 0, the function's own branch -- then this is decoder_forward).  With the masks of the
     implementation under test the step function lrelu' is the same on both sides of a comparison, and what is left is arithmetic: in
     float64 this is the truth for that implementation's gradients, in float32 the yardstick of what fp32 arithmetic can reach.
     On the CPU, in `dtype`.  Returns img, d_features, d_latent (gradients of sum(img * d_img)), d_pre (one per StyledConv), signs
-    (pre > 0 per StyledConv) and styles (the modulation output s (B, Ci) of every StyledConv)."""
+    (pre > 0 per StyledConv) and styles (the modulation output s (B, Ci) of every StyledConv).  blur_firs / up_firs: as decoder_forward."""
     cpu = lambda t: t.detach().cpu()
     sd = {k: cpu(v) for k, v in sd.items() if k.startswith(prefix)}
     f = cpu(features).to(dtype).requires_grad_(True)
@@ -176,8 +184,8 @@ def decoder_pinned_backward(sd, features, latent, noises, d_img, masks=None, pre
         n_up += 1
     pres, styles = [], []
 
-    def styled(p, x, style, noise, upsample=False):
-        pre = modulated_conv(sd, p + 'conv.', x, style, True, upsample)
+    def styled(p, x, style, noise, upsample=False, blur_fir=None):
+        pre = modulated_conv(sd, p + 'conv.', x, style, True, upsample, blur_fir)
         pre = pre + _w(sd, p + 'noise.weight', dtype) * noise + _w(sd, p + 'activate.bias', dtype).reshape(1, -1, 1, 1)
         pre.retain_grad()
         m = pre.detach() > 0 if masks is None else cpu(masks[len(pres)])
@@ -189,9 +197,10 @@ def decoder_pinned_backward(sd, features, latent, noises, d_img, masks=None, pre
     skip = to_rgb(sd, prefix + 'to_rgb1.', out, lat[:, 1], None, upsample=False)
     i = 1
     for u in range(n_up):
-        out = styled(f'{prefix}convs.{2 * u}.', out, lat[:, i], noises[2 * u + 1], upsample=True)
+        out = styled(f'{prefix}convs.{2 * u}.', out, lat[:, i], noises[2 * u + 1], upsample=True,
+                     blur_fir=None if blur_firs is None else blur_firs[u])
         out = styled(f'{prefix}convs.{2 * u + 1}.', out, lat[:, i + 1], noises[2 * u + 2])
-        skip = to_rgb(sd, f'{prefix}to_rgbs.{u}.', out, lat[:, i + 2], skip)
+        skip = to_rgb(sd, f'{prefix}to_rgbs.{u}.', out, lat[:, i + 2], skip, up_fir=None if up_firs is None else up_firs[u])
         i += 2
     skip.backward(cpu(d_img).to(dtype))
     return dict(img=skip.detach(), d_features=f.grad, d_latent=lat.grad, d_pre=[p.grad for p in pres],

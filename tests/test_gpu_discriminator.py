@@ -393,6 +393,75 @@ def test_whole_backward_matches_float64_with_pinned_branches(case, variant):
 
 
 @pytest.mark.gpu
+def test_asymmetric_blur_kernel_forward_and_backward_match_float64():
+    """Every Blur.kernel of the discriminator is make_kernel([1, 3, 3, 1]): equal to its own 180-degree flip, so the flipped copy the
+    backward reads (disc.hip: blur_flip) is the same image as the forward's and a dropped or doubled flip changes no bit of any other
+    test.  Here the asymmetric 4 x 4 FIR of tests/test_fir_host.py (mixed signs, not rank one, sum|k| = 1) is written into every
+    Blur.kernel of a GPU, a float32 CPU and a float64 CPU module of case d16c1b4s16: forward taps and logits by conv_bound, the backward's
+    stage gradients and the image gradient by max(5e-5, 3 f32) relative with the branches pinned to the HIP forward's and the flip
+    conditions (a) and (b) of this file."""
+    from e3dge_amd.stylesdf_model import Blur
+    from test_fir_host import asym_fir
+    case = (16, 1, 4, 16)
+    init, cm, B, size = case
+    k32 = asym_fir().float()
+    assert float((k32 - k32.flip(0, 1)).abs().max()) > 0.5 * float(k32.abs().max())
+
+    def make(dtype, dev):
+        m = syn.load_synthetic_discriminator(Discriminator(syn.discriminator_opt(init, cm))).to(dtype).to(dev)
+        for p in m.parameters():
+            p.requires_grad_(False)
+        blurs = [mod for mod in m.modules() if isinstance(mod, Blur)]
+        assert len(blurs) == 2 * (len(m.convs) - 1)
+        with torch.no_grad():
+            for mod in blurs:
+                assert tuple(mod.kernel.shape) == (4, 4) and abs(float(mod.kernel.sum()) - 1) < 1e-6
+                mod.kernel.copy_(k32.to(dtype))                       # the same fp32 taps in every precision
+        return m
+    mg, m32, m64 = make(torch.float32, DEV), make(torch.float32, "cpu"), make(torch.float64, "cpu")
+    x, u = golden_images(B, size), upstream_of(B)
+    assert mg.uses_hip(x.to(DEV))
+    hip = mg.run(x.to(DEV), taps=True)
+    b = mg.run_backward(x.to(DEV), u.to(DEV), stages=True)
+    torch.cuda.synchronize()
+    assert torch.equal(b['logits'], hip['logits'])
+    masks = masks_of(mg, b['saved'], B)
+    t64, t32 = pinned_run(m64, x, masks, u), pinned_run(m32, x, masks, u)
+    sym64 = pinned_run(module_f64(init, cm), x, None, u)
+    moved = dict(logits=dist(sym64['logits'], t64['logits']), grad=dist(sym64['grad'], t64['grad']) / float(t64['grad'].abs().max()))
+    failed = []
+    for name, h, a, c in [("logits", hip['logits'], t64['logits'], t32['logits'])] + \
+                         [(tap_name(t), hip['taps'][t], t64['taps'][t], t32['taps'][t]) for t in sorted(hip['taps'])]:
+        assert h.shape == a.shape, name
+        rec = dict(err=dist(h, a), f32=dist(c, a), bound=conv_bound(a, c), top=float(a.abs().max()))
+        record("disc_asym_blur_forward", tap=name, **rec)
+        if not (rec['top'] > 0 and rec['err'] <= rec['bound']):
+            failed.append((name, rec))
+    flips, worst, near5 = 0, 0.0, 0
+    assert len(masks) == len(t64['pre'])
+    for mask, p64 in zip(masks, t64['pre']):
+        diff = mask != (p64 > 0)
+        flips += int(diff.sum())
+        if diff.any():
+            worst = max(worst, float(p64[diff].abs().max()))
+        near5 += int((p64.abs() < 1e-5).sum())
+    record("disc_asym_blur_masks", flips=flips, worst_flip=worst, near_1e5=near5, truth_moved_logits=moved['logits'], truth_moved_grad=moved['grad'])
+    order = [disc.TAP_FINAL] + list(range(len(m32.convs) - 2, -1, -1)) + [disc.TAP_STEM]
+    for name, h, a, c in [(tap_name(t) if t != disc.TAP_STEM else "stem", b['stages'][t], t64['stages'][t], t32['stages'][t]) for t in order] + \
+                         [("image", b['grad'], t64['grad'], t32['grad'])]:
+        assert h.shape == a.shape, name
+        top = float(a.abs().max())
+        r = dict(err=dist(h, a) / top, f32=dist(c, a) / top, top=top)
+        r['bound'] = max(5e-5, 3 * r['f32'])
+        record("disc_asym_blur_backward", stage=name, **r)
+        if not (top > 0 and r['err'] <= r['bound']):
+            failed.append((name, r))
+    assert moved['grad'] > 0.05, moved                                # the asymmetric kernel is felt: 1000 x the backward's bound
+    assert worst <= 1e-4 and flips <= near5, (flips, worst, near5)    # (a), (b)
+    assert not failed, failed
+
+
+@pytest.mark.gpu
 def test_generator_loss_backward_through_the_pool_from_a_1024_leaf():
     """g_nonsaturating_loss(D(x)).backward() through the autograd Function, pool_256's adjoint included."""
     init, cm, B, size = 256, 1, 2, 1024
