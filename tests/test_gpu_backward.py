@@ -14,7 +14,7 @@ from oracle import renderer_ref
 
 import e3dge_amd  # noqa: F401
 from e3dge_amd import synthetic as syn
-from e3dge_amd.volume_renderer import saved_state_buffer, saved_state_point_major, siren_backward
+from e3dge_amd.volume_renderer import BWD_MODES, saved_state_buffer, saved_state_point_major, siren_backward
 from test_gpu_renderer import make_renderer
 
 pytestmark = pytest.mark.gpu
@@ -135,7 +135,7 @@ def oracle_render_grads(sd, cams, styles, G, res, S, dtype):
     return s.grad
 
 
-@pytest.mark.parametrize("mode", ["f16x3", "f32"])
+@pytest.mark.parametrize("mode", contraction_modes(*BWD_MODES))       # every backward mode, the default ('f16x3_g2') included
 @pytest.mark.parametrize("res,S,batch,keys", [
     (8, 18, 2, RENDER_KEYS), (16, 24, 1, RENDER_KEYS), (16, 24, 1, ('gen_thumb_imgs',)), (16, 24, 1, ('features',)),
     (16, 24, 1, ('xyz', 'depth')), (16, 24, 1, ('sdf',)), (32, 24, 1, RENDER_KEYS)])
@@ -384,7 +384,7 @@ def test_stage1_step_against_reference_golden_gradients():
     assert rel(out['surface_eikonal_term'], g['ref_surface_eikonal_term']) <= 1e-4
 
 
-@pytest.mark.parametrize("mode", ["f16x3", "f32"])
+@pytest.mark.parametrize("mode", contraction_modes(*BWD_MODES))
 def test_c5_step_against_reference_golden_gradients(mode):
     """SURVEY.md 8d's C5 loss, mean(rgb^2) + mean((|eik|-1)^2) + mean(surf_eik^2), recorded from the reference
     (tests/golden/grads_c5_8x18.npz): its last term reaches the styles also through the integrated surface point, which the

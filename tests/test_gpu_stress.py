@@ -12,12 +12,13 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import full_state_dict, load_golden, maxerr, record
+from conftest import contraction_modes, full_state_dict, load_golden, maxerr, record
 from oracle import decoder_ref, renderer_ref
 from test_gpu_renderer import ATOL, MODES, make_renderer
 
 import e3dge_amd  # noqa: F401
 from e3dge_amd import synthetic as syn
+from e3dge_amd.volume_renderer import BWD_MODES
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -105,7 +106,7 @@ def c5_truth():
                 surf=o['surface_eikonal_term'].detach(), eik=o['eikonal_term'].detach())
 
 
-@pytest.mark.parametrize("mode", ["f16x3", "f32"])
+@pytest.mark.parametrize("mode", contraction_modes(*BWD_MODES))       # every backward mode, the default ('f16x3_g2') included
 def test_c5_loss_full_size_against_float64_autograd(c5_truth, mode):
     """The whole stage-1 renderer loss of SURVEY.md 8d -- mean(rgb^2) + mean((|eik|-1)^2) + mean(surf_eik^2), the last term with the
     integrated surface point kept in the graph (volume_renderer.py:921-930) -- at 64x64x18, forward and backward to the styles."""

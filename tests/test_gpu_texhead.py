@@ -316,14 +316,17 @@ def test_second_pass_from_local_feats():
     assert e['features'] <= 1e-4 and e['rgb'] <= 5e-6 and e['sdf'] <= 1e-5, e
 
 
-@pytest.mark.parametrize("res,S,B", [(8, 24, 1), (16, 18, 2), (16, 48, 1), (64, 24, 1)])
+# (5, 17, 2), (5, 129, 1), (12, 24, 3): the record's (workgroup * bb_subs + sub) index with a short last workgroup, a second
+# sub-tile of one point, three images; (24, 21, 3): a last workgroup (4 of 11 rays) that has one sub-tile where the others have two, so
+# a slab of the record that nobody writes (the geometries of tests/test_gpu_render_geometry.py)
+@pytest.mark.parametrize("res,S,B", [(8, 24, 1), (16, 18, 2), (16, 48, 1), (64, 24, 1), (5, 17, 2), (5, 129, 1), (12, 24, 3), (24, 21, 3)])
 def test_second_pass_reads_the_first_passs_backbone(res, S, B, monkeypatch):
     """The second pass of an evaluated image (same styles / poses, texture FiLM behind the sdf head) reads the layer-7 record
     and the composite weights the first pass left behind (e3dge_siren_render_fwd backbone_out / backbone_in) instead of
     recomputing layers 0..7 + sdf head + transmittance scan: every output must be BIT-identical to a full second pass; a
     changed latent / pose / weight, grad mode, or E3DGE_REUSE_BACKBONE=0 must fall back to the full launch."""
     from e3dge_amd import volume_renderer as vr
-    g, sd = full_state_dict(res=res, n_samples=S)
+    g, sd = full_state_dict(n_samples=S)      # (the renderer's weights do not depend on res; the generator's decoder wants a power of two)
     r = VolumeFeatureRenderer(syn.rendering_opt(N_samples=S, enable_local_model=True, L_pred_tex_modulations=True),
                               out_im_res=res, mode='test')
     own = {k: (syn.synthetic_tensor('renderer.' + k, v.shape) * 0.05 if 'netLocal' in k else
@@ -392,7 +395,7 @@ def test_second_pass_reads_the_first_passs_backbone(res, S, B, monkeypatch):
 
 
 def _local_renderer(res, S):
-    g, sd = full_state_dict(res=res, n_samples=S)
+    g, sd = full_state_dict(n_samples=S)      # (the renderer's weights do not depend on res; the generator's decoder wants a power of two)
     r = VolumeFeatureRenderer(syn.rendering_opt(N_samples=S, enable_local_model=True, L_pred_tex_modulations=True),
                               out_im_res=res, mode='test')
     r.load_state_dict({k: (syn.synthetic_tensor('renderer.' + k, v.shape) * 0.05 if 'netLocal' in k else
@@ -472,7 +475,7 @@ def test_backbone_record_notices_an_edited_first_pass_output():
         assert torch.equal(again['features'], keep)
 
 
-@pytest.mark.parametrize("res,S,B", [(8, 24, 1), (16, 18, 2), (16, 21, 1), (64, 24, 1)])
+@pytest.mark.parametrize("res,S,B", [(8, 24, 1), (16, 18, 2), (16, 21, 1), (64, 24, 1), (5, 17, 2), (5, 129, 1), (12, 24, 3), (24, 21, 3)])
 def test_head_and_film_in_one_launch_is_bit_identical(res, S, B, monkeypatch):
     """SURVEY 8 f1 as specified: on the record path the texture head applies (alpha + 1) h8 + beta itself and hands pass #2 the
     FiLM-ed layer-7 record (e3dge_tex_film_fwd) -- (alpha, beta) never reach HBM.  Every output must equal, bit for bit, the
