@@ -302,6 +302,15 @@ class EncArgs(_Args):
         (n, _vp) for n in ("thumb_out", "stylegan_out", "p32", "p64", "ws")] + [("ws_bytes", _i64)]
 
 
+ALIGNER_TAPS, ALIGNER_SOURCES = 7, 249                            # E3DGE_ALIGNER_* (include/e3dge_hip.h)
+
+
+class AlignerArgs(_Args):
+    """Mirror of struct E3dgeAlignerArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("packed_floats", _i64), ("res_gt", _vp), ("thumb", _vp)] + [(n, _i32) for n in ("n", "size", "split", "thumb_up4")] + [
+        ("out", _vp), ("taps", _vp * ALIGNER_TAPS), ("ws", _vp), ("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -469,6 +478,12 @@ SIGNATURES = {
     "e3dge_enc_lateral": (_i32, [_vp] * 6 + [_i32] * 7 + [_vp]),
     "e3dge_enc_head_conv": (_i32, [_vp] * 5 + [_i32] * 7 + [_vp]),
     "e3dge_enc_head_tail": (_i32, [_vp] * 7 + [_i64] + [_i32] * 5 + [_vp]),
+    "e3dge_aligner_packed_floats": (_i64, []),
+    "e3dge_aligner_pack": (_i32, [_vp, _i64, _vp, _i32, _vp]),
+    "e3dge_aligner_workspace_bytes": (_i64, [_i32]),
+    "e3dge_aligner_forward": (_i32, [ctypes.POINTER(AlignerArgs), _vp]),
+    "e3dge_aln_conv": (_i32, [_vp] * 9 + [_i64] + [_i32] * 10 + [_vp]),
+    "e3dge_aln_up2": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
 }
 
 _lib = None

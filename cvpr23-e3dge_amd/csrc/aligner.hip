@@ -1,0 +1,414 @@
+// The 2-D residual aligner (ADA), forward, eval form: cat(res_gt, up(thumb)) (B, 6, 256, 256) -> aligned_res (B, 3, 256, 256).
+//
+// Reference: ResidualAligner (project/models/helper_modules/alignment_old.py:316-398) on bottleneck_IR (helpers.py:161-201) with
+// aligner_norm_type 'batch' (BatchNorm on its running statistics) and no demodulation; called as self.grid_align
+// (project/trainers/E3DGE/e3dge_full_runner.py:138, :257).
+//
+//   unit(in, depth, stride):  res = BN(conv3x3_stride(PReLU(conv3x3(BN(x)))));  out = res + (in == depth ? x[::stride] : BN(conv1x1_stride(x)))
+//   feat1 = PReLU(BN(conv3x3 6->16))                                                  256^2
+//   feat2 = units (16,32,2) (32,32,1) (32,32,1)       feat3 = (32,48,2) (48,48,1) x2       feat4 = (48,64,2) (64,64,1) x2      128^2, 64^2, 32^2
+//   dfea1 = units (112,64,1) (64,32,1) (32,32,1) of cat(up2(feat4), feat3)            64^2
+//   dfea2 = units (64,32,1) (32,16,1) (16,16,1) of cat(up2(dfea1), feat2)             128^2
+//   dfea3 = units (32,16,1) (16,3,1) (3,3,1) of cat(up2(dfea2), feat1)                256^2, the output
+//
+// Kernels (49 launches for one forward, whatever the batch):
+//   aln_conv_kernel  the narrow-layer form of the fp32 implicit GEMM of conv_igemm.h: the same v_mfma_f32_16x16x4_f32 steps, the same packed
+//                    A-fragment image (ig_pack), K staged through LDS in tiles of kIgKC with the next tile's loads in flight during the
+//                    matrix steps, two accumulator chains per output element (even / odd groups of four k), each in ascending k.  The
+//                    network's layers have 3 to 64 output channels, so here the four waves split the PIXELS: a workgroup is 64 NT pixels of
+//                    ONE image, every wave owns 16 NT of them and all MT = ceil(Cout / 16) channel tiles, and a B fragment read from LDS
+//                    feeds MT matrix steps.  No wave idles below 64 channels.  Cout = 3 runs on a zero-padded 16-row tile.
+//                    Gather: zero padding; an optional per-input-channel affine on in-image elements (the leading BN: a padded tap stays
+//                    0); input channels from up to two tensors split at a run-time channel (the three cats and the call site's
+//                    cat(res_gt, thumb), no concatenated copy), the second one optionally read at nearest x4 (src = dst >> 2).
+//                    Epilogue: the sum of the two chains, an optional per-output-channel affine (trailing BN), an optional PReLU, an optional
+//                    shortcut added after that rounding: a strided pick from a tensor of the input's size (MaxPool2d(1, stride)) or a
+//                    read of a tensor of the output's size (the 1x1 branch, a launch of its own).
+//   aln_up2_kernel   bilinear x2, align_corners = False, in the separable form of ATen's upsample_bilinear2d:
+//                    hy (hx a + lx b) + ly (hx c + lx d), every product and sum rounded on its own.
+// No atomics, a fixed summation order, tiles that never straddle images and a tile width from the layer alone (aln_tile_width): results
+// are bit-reproducible and an image's values do not depend on the batch.
+// Measured errors and times: DESIGN.md 4.17.
+#include "conv_igemm.h"
+
+namespace e3dge {
+
+constexpr int kAlnSize = 256, kAlnUnits = 18, kAlnTaps = E3DGE_ALIGNER_TAPS, kAlnSources = E3DGE_ALIGNER_SOURCES, kAlnIn = 6, kAlnStem = 16;
+constexpr int kAlnMaxCout = 64;
+
+struct AlnUnit { int cin, depth, stride; };
+constexpr AlnUnit kAlnUnit[kAlnUnits] = {{16, 32, 2}, {32, 32, 1}, {32, 32, 1}, {32, 48, 2}, {48, 48, 1}, {48, 48, 1}, {48, 64, 2}, {64, 64, 1}, {64, 64, 1},
+                                         {112, 64, 1}, {64, 32, 1}, {32, 32, 1}, {64, 32, 1}, {32, 16, 1}, {16, 16, 1}, {32, 16, 1}, {16, 3, 1}, {3, 3, 1}};
+
+enum { kAlnScNone = 0, kAlnScPick = 1, kAlnScRead = 2 };
+
+template <int NT>
+struct AlnTile {
+    static constexpr int BN = 64 * NT;                               // pixels per workgroup: 16 NT per wave
+    static constexpr int BNP = BN + 16;                              // LDS row pitch: the four k rows of one read land in four bank groups
+    static constexpr int ROWS = 256 / BN, PER = kIgKC / ROWS;        // k rows staged per pass, staged elements per thread and tile
+};
+
+// The k loop of one workgroup, beside ig_k_loop (conv_igemm.h): the same staging and the same order of the matrix steps per output element
+// (step j adds into chain j & 1), with the waves side by side along the pixels.  acc[m][t]: channel tile m, pixel tile t of this wave.
+// wa: this lane's dword of the first A fragment of channel tile 0; channel tile m starts m * KS4 fragments later.
+template <int MT, int NT, typename Fetch>
+__device__ __forceinline__ void aln_k_loop(f32x4 (&acc)[MT][NT][2], const float* wa, int KS4, int n_tiles, Fetch&& fetch) {
+    constexpr int BN = AlnTile<NT>::BN, BNP = AlnTile<NT>::BNP, ROWS = AlnTile<NT>::ROWS, PER = AlnTile<NT>::PER;
+    __shared__ float bs[kIgKC * BNP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sn = tid % BN, srow = tid / BN;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[m][t][0] = acc[m][t][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    float stage[PER];
+    fetch(0, stage);
+    const float* bw = bs + (lane >> 4) * BNP + wave * 16 * NT + (lane & 15);
+#pragma unroll 1
+    for (int kt = 0; kt < n_tiles; ++kt) {
+        __syncthreads();                                            // the previous tile's reads are done
+#pragma unroll
+        for (int i = 0; i < PER; ++i) bs[(srow + i * ROWS) * BNP + sn] = stage[i];
+        __syncthreads();
+        float af[MT][kIgKC / 4];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int j = 0; j < kIgKC / 4; ++j) af[m][j] = wa[((int64_t)m * KS4 + kt * (kIgKC / 4) + j) * 64];
+        if (kt + 1 < n_tiles) fetch((kt + 1) * kIgKC, stage);      // in flight during the MFMAs
+#pragma unroll
+        for (int j = 0; j < kIgKC / 4; ++j) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float b = bw[j * 4 * BNP + t * 16];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[m][t][j & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][j], b, acc[m][t][j & 1], 0, 0, 0);
+            }
+        }
+    }
+}
+
+struct AlnConvArgs {
+    float* out; const float* in0; const float* in1; const float* wfrag;
+    const float2* in_ab; const float2* epi_ab; const float* slope; const float* sc;
+    int C0, C1, IH, IW, Cout, OH, OW, K, KS4, tiles, stride, up4, sc_mode;
+};
+
+template <int KS_, int MT, int NT>
+__global__ void __launch_bounds__(256) aln_conv_kernel(AlnConvArgs a) {
+    constexpr int BN = AlnTile<NT>::BN, ROWS = AlnTile<NT>::ROWS, PER = AlnTile<NT>::PER;
+    constexpr int PAD = KS_ == 3 ? 1 : 0;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int OHW = a.OH * a.OW, IH = a.IH, IW = a.IW, K = a.K, C0 = a.C0;
+    const int img = blockIdx.x / a.tiles, tile = blockIdx.x - img * a.tiles;
+    const int sn = tid % BN, srow = tid / BN;
+    const int spix = tile * BN + sn;
+    const bool n_ok = spix < OHW;
+    const int soy = spix / a.OW, sox = spix - soy * a.OW;
+    const int iy0 = soy * a.stride - PAD, ix0 = sox * a.stride - PAD;
+    const int H1 = a.up4 ? IH >> 2 : IH, W1 = a.up4 ? IW >> 2 : IW, sh1 = a.up4 ? 2 : 0;
+    const float* __restrict__ src0 = a.in0 + (int64_t)img * C0 * IH * IW;
+    const float* __restrict__ src1 = a.in1 + (int64_t)img * a.C1 * H1 * W1;          // (never read when C1 == 0)
+    const float2* __restrict__ in_ab = a.in_ab;
+    auto fetch = [&](int k0, float (&v)[PER]) {
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int k = k0 + srow + i * ROWS;
+            const auto [ci, r, s] = ig_decode<KS_>(k);
+            const int iy = iy0 + r, ix = ix0 + s;
+            float x = 0.0f;
+            if (n_ok && k < K && iy >= 0 && iy < IH && ix >= 0 && ix < IW) {
+                x = ci < C0 ? src0[((int64_t)ci * IH + iy) * IW + ix] : src1[((int64_t)(ci - C0) * H1 + (iy >> sh1)) * W1 + (ix >> sh1)];
+                if (in_ab) { const float2 ab = in_ab[ci]; x = __fmaf_rn(ab.x, x, ab.y); }   // the leading BN; padding stays 0
+            }
+            v[i] = x;
+        }
+    };
+    f32x4 acc[MT][NT][2];
+    aln_k_loop<MT, NT>(acc, a.wfrag + lane, a.KS4, a.KS4 / (kIgKC / 4), fetch);
+    // C/D fragment: lane l, register r holds D[4 (l >> 4) + r][l & 15]
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int pix = tile * BN + wave * 16 * NT + t * 16 + (lane & 15);
+        if (pix >= OHW) continue;
+        const int oy = pix / a.OW, ox = pix - oy * a.OW;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = m * 16 + 4 * (lane >> 4) + r;
+                if (row >= a.Cout) continue;                          // the zero-padded rows of a partial channel tile
+                float v = __fadd_rn(acc[m][t][0][r], acc[m][t][1][r]);
+                if (a.epi_ab) { const float2 e = a.epi_ab[row]; v = __fmaf_rn(e.x, v, e.y); }
+                if (a.slope) v = v > 0.0f ? v : __fmul_rn(a.slope[row], v);
+                const int64_t plane = (int64_t)img * a.Cout + row;
+                if (a.sc_mode == kAlnScPick) v = __fadd_rn(v, a.sc[(plane * IH + (int64_t)oy * a.stride) * IW + ox * a.stride]);
+                else if (a.sc_mode == kAlnScRead) v = __fadd_rn(v, a.sc[plane * OHW + pix]);
+                a.out[plane * OHW + pix] = v;                         // helpers.py:198-201: res + shortcut
+            }
+        }
+    }
+}
+
+static int aln_out_size(int in, int ks, int stride) { return (in + (ks == 3 ? 2 : 0) - ks) / stride + 1; }
+
+// Pixel tiles per wave: two where 128-pixel workgroups of two images (the evaluation shape) still give every CU one, from the layer alone.
+static int aln_tile_width(int64_t pixels) { return (pixels + 127) / 128 * 2 >= kIgCUs ? 2 : 1; }
+
+struct AlnConv {
+    float* out; const float* in0; const float* in1; const float* wfrag; const float* in_ab; const float* epi_ab; const float* slope; const float* sc;
+    int n, cin, split, up4, cout, h, w, ks, stride, sc_mode;
+};
+
+static int aln_conv(const AlnConv& c, hipStream_t st) {
+    AlnConvArgs a;
+    a.out = c.out; a.in0 = c.in0; a.in1 = c.in1; a.wfrag = c.wfrag; a.slope = c.slope; a.sc = c.sc;
+    a.in_ab = reinterpret_cast<const float2*>(c.in_ab); a.epi_ab = reinterpret_cast<const float2*>(c.epi_ab);
+    a.C0 = c.split; a.C1 = c.cin - c.split; a.IH = c.h; a.IW = c.w; a.Cout = c.cout;
+    a.OH = aln_out_size(c.h, c.ks, c.stride); a.OW = aln_out_size(c.w, c.ks, c.stride);
+    a.K = c.cin * c.ks * c.ks; a.KS4 = ig_kpad(a.K) / 4; a.stride = c.stride; a.up4 = c.up4; a.sc_mode = c.sc_mode;
+    const int OHW = a.OH * a.OW, nt = aln_tile_width(OHW), bn = 64 * nt, mt = ig_mpad(c.cout) / 16;
+    a.tiles = (OHW + bn - 1) / bn;
+    const dim3 grid((unsigned)((int64_t)c.n * a.tiles));
+    auto with_mt = [&](auto ks_c, auto nt_c) {
+        constexpr int KS_ = decltype(ks_c)::value, NT = decltype(nt_c)::value;
+        if (mt == 1) aln_conv_kernel<KS_, 1, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (mt == 2) aln_conv_kernel<KS_, 2, NT><<<grid, dim3(256), 0, st>>>(a);
+        else if (mt == 3) aln_conv_kernel<KS_, 3, NT><<<grid, dim3(256), 0, st>>>(a);
+        else aln_conv_kernel<KS_, 4, NT><<<grid, dim3(256), 0, st>>>(a);
+    };
+    auto with_nt = [&](auto ks_c) {
+        if (nt == 2) with_mt(ks_c, std::integral_constant<int, 2>{});
+        else with_mt(ks_c, std::integral_constant<int, 1>{});
+    };
+    if (c.ks == 3) with_nt(std::integral_constant<int, 3>{});
+    else with_nt(std::integral_constant<int, 1>{});
+    return check_launch("aln(conv)");
+}
+
+// ---- bilinear x2, align_corners = False ---------------------------------------------------------------------------------------------
+// ATen's source index: src = 0.5 (dst + 0.5) - 0.5 clamped at 0, i0 = trunc(src), i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1: taps
+// 0.25 / 0.75 with the edges clamped; all of it exact in fp32.
+__device__ __forceinline__ void aln_up2_tap(int o, int in, int& i0, int& i1, float& l0, float& l1) {
+    const float src = fmaxf(__fsub_rn(__fmul_rn(0.5f, __fadd_rn((float)o, 0.5f)), 0.5f), 0.0f);
+    i0 = min((int)src, in - 1);
+    i1 = i0 + (i0 < in - 1);
+    l1 = fminf(fmaxf(__fsub_rn(src, (float)i0), 0.0f), 1.0f);
+    l0 = __fsub_rn(1.0f, l1);
+}
+
+__global__ void __launch_bounds__(256) aln_up2_kernel(float* __restrict__ out, const float* __restrict__ in, int H, int W, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int OW = 2 * W, OHW = 4 * H * W;
+    const int64_t plane = i / OHW;
+    const int pix = (int)(i - plane * OHW), oy = pix / OW, ox = pix - oy * OW;
+    int y0, y1, x0, x1;
+    float hy, ly, hx, lx;
+    aln_up2_tap(oy, H, y0, y1, hy, ly);
+    aln_up2_tap(ox, W, x0, x1, hx, lx);
+    const float* __restrict__ p = in + plane * H * W;
+    const float top = __fadd_rn(__fmul_rn(hx, p[y0 * W + x0]), __fmul_rn(lx, p[y0 * W + x1]));
+    const float bot = __fadd_rn(__fmul_rn(hx, p[y1 * W + x0]), __fmul_rn(lx, p[y1 * W + x1]));
+    out[i] = __fadd_rn(__fmul_rn(hy, top), __fmul_rn(ly, bot));
+}
+
+static int aln_up2(float* out, const float* in, int64_t planes, int H, int W, hipStream_t st) {
+    const int64_t total = planes * 4 * H * W;
+    aln_up2_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(out, in, H, W, total);
+    return check_launch("aln(up2)");
+}
+
+// ---- packed image ------------------------------------------------------------------------------------------------------------------
+// BatchNorm on its running statistics as the pair (a, b) = (gamma / sqrt(var + 1e-5), beta - mean a)
+__global__ void __launch_bounds__(256) aln_pack_bn_kernel(float* __restrict__ dst, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          const float* __restrict__ mean, const float* __restrict__ var, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float a = __fdiv_rn(gamma[c], __fsqrt_rn(__fadd_rn(var[c], 1e-5f)));
+    dst[2 * c] = a;
+    dst[2 * c + 1] = __fsub_rn(beta[c], __fmul_rn(mean[c], a));
+}
+
+struct AlnLayout {
+    int64_t stem_w, stem_bn, stem_prelu;
+    int64_t bn0[kAlnUnits], w1[kAlnUnits], prelu[kAlnUnits], w2[kAlnUnits], bn4[kAlnUnits], wsc[kAlnUnits], bnsc[kAlnUnits], total;
+};
+
+static int64_t aln_image_floats(int cin, int cout, int ks) { return (int64_t)ig_mpad(cout) * ig_kpad(cin * ks * ks); }
+
+static const AlnLayout& aln_layout() {
+    static const AlnLayout lay = [] {
+        AlnLayout l{};
+        int64_t off = 0;
+        auto take = [&](int64_t floats) { const int64_t at = off; off += (floats + 63) / 64 * 64; return at; };
+        l.stem_w = take(aln_image_floats(kAlnIn, kAlnStem, 3)); l.stem_bn = take(2 * kAlnStem); l.stem_prelu = take(kAlnStem);
+        for (int u = 0; u < kAlnUnits; ++u) {
+            const AlnUnit q = kAlnUnit[u];
+            l.bn0[u] = take(2 * q.cin); l.w1[u] = take(aln_image_floats(q.cin, q.depth, 3)); l.prelu[u] = take(q.depth);
+            l.w2[u] = take(aln_image_floats(q.depth, q.depth, 3)); l.bn4[u] = take(2 * q.depth);
+            if (q.cin != q.depth) { l.wsc[u] = take(aln_image_floats(q.cin, q.depth, 1)); l.bnsc[u] = take(2 * q.depth); }
+        }
+        l.total = off;
+        return l;
+    }();
+    return lay;
+}
+
+// ---- workspace (floats per image; every block starts on a multiple of 64 floats of the whole) -------------------------------------------
+struct AlnWs { int64_t feat[4], dfea[2], t1, sc, x[2], up, total_bytes; };
+
+static bool aln_ws(int64_t n, AlnWs* d) {
+    if (n < 1 || n > 256) return false;
+    int64_t off = 0;
+    auto take = [&](int64_t floats) { const int64_t at = off; off += (floats + 63) / 64 * 64; return at; };
+    const int64_t P = (int64_t)kAlnSize * kAlnSize;
+    d->feat[0] = take(n * 16 * P); d->feat[1] = take(n * 32 * (P / 4)); d->feat[2] = take(n * 48 * (P / 16)); d->feat[3] = take(n * 64 * (P / 64));
+    d->dfea[0] = take(n * 32 * (P / 16)); d->dfea[1] = take(n * 16 * (P / 4));
+    d->t1 = take(n * 32 * P);                                        // a unit's first convolution: depth channels at the input's size
+    d->sc = take(n * 16 * P);                                        // the 1x1 branch
+    d->x[0] = take(n * 16 * P); d->x[1] = take(n * 16 * P);         // unit outputs inside a stage
+    d->up = take(n * 16 * P);                                        // an up-sampled map
+    d->total_bytes = off * (int64_t)sizeof(float);
+    return true;
+}
+
+// one stage: three units from (in0 | in1 at channel `split`) at size S; the last one writes `out`
+static int aln_stage(float* out, const float* in0, const float* in1, int split, int u0, int S, const float* P, float* ws, const AlnWs& d, int n,
+                     hipStream_t st) {
+    const AlnLayout& l = aln_layout();
+    float* t1 = ws + d.t1;
+    float* sc = ws + d.sc;
+    int rc, size = S;
+    for (int i = 0; i < 3; ++i) {
+        const int u = u0 + i;
+        const AlnUnit q = kAlnUnit[u];
+        const int osize = aln_out_size(size, 3, q.stride);
+        float* y = i == 2 ? out : ws + d.x[i];
+        const bool conv_sc = q.cin != q.depth;
+        if (conv_sc &&
+            (rc = aln_conv({sc, in0, in1, P + l.wsc[u], nullptr, P + l.bnsc[u], nullptr, nullptr, n, q.cin, split, 0, q.depth, size, size, 1, q.stride,
+                            kAlnScNone}, st)))
+            return rc;
+        if ((rc = aln_conv({t1, in0, in1, P + l.w1[u], P + l.bn0[u], nullptr, P + l.prelu[u], nullptr, n, q.cin, split, 0, q.depth, size, size, 3, 1,
+                            kAlnScNone}, st)))
+            return rc;
+        if ((rc = aln_conv({y, t1, nullptr, P + l.w2[u], nullptr, P + l.bn4[u], nullptr, conv_sc ? sc : in0, n, q.depth, q.depth, 0, q.depth, size, size, 3,
+                            q.stride, conv_sc ? kAlnScRead : kAlnScPick}, st)))
+            return rc;
+        in0 = y; in1 = nullptr; split = q.depth;
+        size = osize;
+    }
+    return E3DGE_OK;
+}
+
+}  // namespace e3dge
+
+using namespace e3dge;
+
+extern "C" int64_t e3dge_aligner_packed_floats(void) { return aln_layout().total; }
+
+extern "C" int e3dge_aligner_pack(float* packed, int64_t packed_floats, const float* const* src, int n_src, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(packed && src, "aligner_pack: null pointer");
+    const AlnLayout& l = aln_layout();
+    E3DGE_REQUIRE(packed_floats >= l.total, "aligner_pack: packed buffer of %lld floats, %lld needed", (long long)packed_floats, (long long)l.total);
+    E3DGE_REQUIRE(n_src == kAlnSources, "aligner_pack: n_src=%d, %d source tensors expected", n_src, kAlnSources);
+    for (int i = 0; i < n_src; ++i) E3DGE_REQUIRE(src[i], "aligner_pack: null pointer (source %d)", i);
+    hipStream_t st = as_stream(stream);
+    int at = 0;
+    auto next = [&]() { return src[at++]; };
+    auto conv = [&](int64_t off, int ci, int co, int ks) { ig_pack(packed + off, next(), ci, co, ks, 1.0f, st); };
+    auto copy = [&](int64_t off, int64_t cnt) { ig_copy(packed + off, next(), cnt, 1.0f, 0, st); };
+    auto bn = [&](int64_t off, int ch) {
+        const float* gamma = next(); const float* beta = next(); const float* mean = next(); const float* var = next();
+        aln_pack_bn_kernel<<<dim3((unsigned)((ch + 255) / 256)), dim3(256), 0, st>>>(packed + off, gamma, beta, mean, var, ch);
+    };
+    conv(l.stem_w, kAlnIn, kAlnStem, 3); bn(l.stem_bn, kAlnStem); copy(l.stem_prelu, kAlnStem);
+    for (int u = 0; u < kAlnUnits; ++u) {                             // res_layer.0 .. 4, then the shortcut
+        const AlnUnit q = kAlnUnit[u];
+        bn(l.bn0[u], q.cin); conv(l.w1[u], q.cin, q.depth, 3); copy(l.prelu[u], q.depth); conv(l.w2[u], q.depth, q.depth, 3); bn(l.bn4[u], q.depth);
+        if (q.cin != q.depth) { conv(l.wsc[u], q.cin, q.depth, 1); bn(l.bnsc[u], q.depth); }
+    }
+    return check_launch("aligner_pack");
+}
+
+extern "C" int64_t e3dge_aligner_workspace_bytes(int n) {
+    AlnWs d;
+    if (!aln_ws(n, &d)) {
+        fail(E3DGE_ERR_INVALID_ARG, "aligner_workspace_bytes: n=%d (1..256)", n);
+        return -1;
+    }
+    return d.total_bytes;
+}
+
+extern "C" int e3dge_aligner_forward(const E3dgeAlignerArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "aligner_forward: null argument struct");
+    const E3dgeAlignerArgs& a = *args;
+    E3DGE_REQUIRE(a.n >= 1 && a.n <= 256, "aligner_forward: n=%d (1..256)", a.n);
+    E3DGE_REQUIRE(a.size == kAlnSize, "aligner_forward: size=%d (the network's up-samplings are fixed: 256)", a.size);
+    E3DGE_REQUIRE(a.split >= 0 && a.split <= kAlnIn, "aligner_forward: split=%d (0..6)", a.split);
+    E3DGE_REQUIRE(a.thumb_up4 == 0 || a.thumb_up4 == 1, "aligner_forward: thumb_up4=%d (0 or 1)", a.thumb_up4);
+    E3DGE_REQUIRE(a.packed && a.out && a.ws && (a.split == 0 || a.res_gt) && (a.split == kAlnIn || a.thumb), "aligner_forward: null pointer");
+    const AlnLayout& l = aln_layout();
+    E3DGE_REQUIRE(a.packed_floats >= l.total, "aligner_forward: packed buffer of %lld floats, %lld needed", (long long)a.packed_floats, (long long)l.total);
+    AlnWs d;
+    E3DGE_REQUIRE(aln_ws(a.n, &d), "aligner_forward: n=%d", a.n);
+    E3DGE_REQUIRE(a.ws_bytes >= d.total_bytes, "aligner_forward: workspace of %lld bytes, %lld needed", (long long)a.ws_bytes, (long long)d.total_bytes);
+    hipStream_t st = as_stream(stream);
+    float* ws = static_cast<float*>(a.ws);
+    const float* P = a.packed;
+    const int n = a.n, S = kAlnSize;
+    float* feat[4];
+    for (int i = 0; i < 4; ++i) feat[i] = a.taps[i] ? a.taps[i] : ws + d.feat[i];
+    float* dfea[2];
+    for (int i = 0; i < 2; ++i) dfea[i] = a.taps[4 + i] ? a.taps[4 + i] : ws + d.dfea[i];
+    float* up = ws + d.up;
+    int rc;
+    if ((rc = aln_conv({feat[0], a.res_gt, a.thumb, P + l.stem_w, nullptr, P + l.stem_bn, P + l.stem_prelu, nullptr, n, kAlnIn, a.split, a.thumb_up4,
+                        kAlnStem, S, S, 3, 1, kAlnScNone}, st)))
+        return rc;
+    if ((rc = aln_stage(feat[1], feat[0], nullptr, 16, 0, S, P, ws, d, n, st))) return rc;
+    if ((rc = aln_stage(feat[2], feat[1], nullptr, 32, 3, S / 2, P, ws, d, n, st))) return rc;
+    if ((rc = aln_stage(feat[3], feat[2], nullptr, 48, 6, S / 4, P, ws, d, n, st))) return rc;
+    if ((rc = aln_up2(up, feat[3], (int64_t)n * 64, S / 8, S / 8, st))) return rc;
+    if ((rc = aln_stage(dfea[0], up, feat[2], 64, 9, S / 4, P, ws, d, n, st))) return rc;
+    if ((rc = aln_up2(up, dfea[0], (int64_t)n * 32, S / 4, S / 4, st))) return rc;
+    if ((rc = aln_stage(dfea[1], up, feat[1], 32, 12, S / 2, P, ws, d, n, st))) return rc;
+    if ((rc = aln_up2(up, dfea[1], (int64_t)n * 16, S / 2, S / 2, st))) return rc;
+    if ((rc = aln_stage(a.out, up, feat[0], 16, 15, S, P, ws, d, n, st))) return rc;
+    if (a.taps[6]) {
+        ig_copy(a.taps[6], a.out, (int64_t)n * 3 * S * S, 1.0f, 0, st);
+        return check_launch("aligner_forward(tap)");
+    }
+    return E3DGE_OK;
+}
+
+extern "C" int e3dge_aln_conv(float* out, const float* in0, const float* in1, const float* w, const float* in_ab, const float* epi_ab,
+                              const float* slope, const float* shortcut, float* wfrag, int64_t wfrag_floats, int n, int cin, int split, int up4,
+                              int cout, int height, int width, int ksize, int stride, int shortcut_mode, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(out && w && wfrag, "aln_conv: null pointer");
+    E3DGE_REQUIRE(n >= 1 && n <= 256 && cin >= 1 && cin <= 4096, "aln_conv: n=%d (1..256) cin=%d (1..4096)", n, cin);
+    E3DGE_REQUIRE(cout >= 1 && cout <= kAlnMaxCout, "aln_conv: cout=%d (1..64: the wide layers are the core's)", cout);
+    E3DGE_REQUIRE(split >= 0 && split <= cin, "aln_conv: split=%d outside [0, cin=%d]", split, cin);
+    E3DGE_REQUIRE((split == 0 || in0) && (split == cin || in1), "aln_conv: null pointer (a source with channels)");
+    E3DGE_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "aln_conv: ksize=%d (1 or 3) stride=%d (1 or 2)", ksize, stride);
+    E3DGE_REQUIRE(height >= 1 && width >= 1 && height <= 1024 && width <= 1024, "aln_conv: height=%d width=%d (1..1024)", height, width);
+    E3DGE_REQUIRE(up4 == 0 || (up4 == 1 && height % 4 == 0 && width % 4 == 0), "aln_conv: up4=%d at %d x %d (0, or 1 at multiples of 4)", up4, height, width);
+    E3DGE_REQUIRE(shortcut_mode >= kAlnScNone && shortcut_mode <= kAlnScRead && (shortcut_mode == kAlnScNone || shortcut),
+                  "aln_conv: shortcut_mode=%d (0 none, 1 strided pick, 2 read) needs its tensor", shortcut_mode);
+    E3DGE_REQUIRE(wfrag_floats >= aln_image_floats(cin, cout, ksize), "aln_conv: wfrag of %lld floats, %lld needed", (long long)wfrag_floats,
+                  (long long)aln_image_floats(cin, cout, ksize));
+    hipStream_t st = as_stream(stream);
+    ig_pack(wfrag, w, cin, cout, ksize, 1.0f, st);
+    int rc;
+    if ((rc = check_launch("aln_conv(pack)"))) return rc;
+    return aln_conv({out, in0, in1, wfrag, in_ab, epi_ab, slope, shortcut, n, cin, split, up4, cout, height, width, ksize, stride, shortcut_mode}, st);
+}
+
+extern "C" int e3dge_aln_up2(float* out, const float* in, int64_t planes, int height, int width, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(out && in, "aln_up2: null pointer");
+    E3DGE_REQUIRE(planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024,
+                  "aln_up2: planes=%lld (1..2^20) height=%d width=%d (1..1024)", (long long)planes, height, width);
+    return aln_up2(out, in, planes, height, width, as_stream(stream));
+}

@@ -235,6 +235,47 @@ def load_synthetic_encoder(module, seed=0):
     return module
 
 
+def aligner_opt(**over):
+    """The training options `e3dge_amd.alignment.ResidualAligner` reads, at the scripts' values (utils/options.py:143-151:
+    --aligner_norm_type batch, no --aligner_demodulate)."""
+    o = AttrDict(aligner_demodulate=False, aligner_norm_type='batch')
+    o.update(over)
+    return o
+
+
+ALN_CONV1_GAIN, ALN_CONV2_GAIN, ALN_SHORTCUT_GAIN = 1.0 / math.sqrt(2.0), 0.45, 0.52
+
+
+def load_synthetic_aligner(module, seed=0):
+    """Deterministic stand-ins for the `grid_align` checkpoint of an `e3dge_amd.alignment.ResidualAligner` (or the reference's: the keys
+    are the same).  Convolutions are He-scaled, N(0, 2 / fan_in), times a per-role gain chosen so that 19 layers of residual adds keep
+    the activations at unit scale (a unit's first 3x3 reads an un-rectified map: ALN_CONV1_GAIN; its second 3x3 makes the residual a
+    quarter of the variance: ALN_CONV2_GAIN; the 1x1 shortcuts: ALN_SHORTCUT_GAIN; conv_layer1: 1).  Nothing is at its initial value,
+    so a dropped or swapped layer shows: PReLU slopes 0.5 + 0.25 tanh(N) per channel (0.25..0.75), BatchNorm gamma 1 + 0.2 tanh(N)
+    (0.8..1.2), beta 0.1 N, running_mean 0.2 N, running_var 1 + 0.5 tanh(0.5 N) (0.5..1.5)."""
+    sd = {}
+    kinds = dict(module.named_modules())
+    for k, v in module.state_dict().items():
+        owner, leaf = k.rsplit('.', 1)
+        m = kinds[owner]
+        if leaf == 'num_batches_tracked':
+            sd[k] = torch.zeros_like(v)
+            continue
+        t = synthetic_tensor('aligner.' + k, v.shape, seed)           # 'weight': N(0, 1); everything else: 0.05 N(0, 1)
+        if isinstance(m, torch.nn.PReLU):
+            t = 0.5 + 0.25 * torch.tanh(t)
+        elif isinstance(m, torch.nn.BatchNorm2d):
+            t = {'weight': 1.0 + 0.2 * torch.tanh(t), 'bias': 2.0 * t, 'running_mean': 4.0 * t, 'running_var': 1.0 + 0.5 * torch.tanh(10.0 * t)}[leaf]
+        elif leaf == 'weight':                                        # Conv2d (4-D) or DemodulatedConv2d (5-D, a leading 1)
+            fan_in = v.shape[-3] * v.shape[-2] * v.shape[-1]
+            gain = (ALN_SHORTCUT_GAIN if '.shortcut_layer.' in k else ALN_CONV2_GAIN if k.endswith('res_layer.3.weight') else
+                    ALN_CONV1_GAIN if k.endswith('res_layer.1.weight') else 1.0)
+            t = t * (gain * math.sqrt(2.0 / fan_in))
+        sd[k] = t.to(v.dtype)
+    module.load_state_dict(sd, strict=True)
+    return module
+
+
 def discriminator_opt(D_init_size=256, channel_multiplier=2, **over):
     """The model options `e3dge_amd.discriminator.Discriminator` reads (scripts/train/ffhq/stage2.2.sh: --D_init_size 256)."""
     o = AttrDict(D_init_size=D_init_size, D_input_size=3, channel_multiplier=channel_multiplier)

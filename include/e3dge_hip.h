@@ -1475,6 +1475,62 @@ int e3dge_enc_head_tail(float* out, const float* in, const float* conv_w, const 
                         float* scratch, int64_t scratch_floats, int n, int heads, int channels, int start, int n_convs,
                         e3dge_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The 2-D residual aligner (ADA), forward, eval form (csrc/aligner.hip).  Additions to ABI 17.  No allocation, no synchronisation, no
+ * atomics; bit-reproducible, and an image's results do not depend on its position in the batch or on the batch size.  Replaces
+ * ResidualAligner.forward (project/models/helper_modules/alignment_old.py:316-398) with aligner_norm_type 'batch' (BatchNorm on its
+ * running statistics, eps 1e-5) and no demodulation: conv_layer1, the 18 bottleneck_IR units of conv_layer2-4 and dconv_layer1-3 and
+ * the three bilinear x2 up-samplings.  fp32.  No backward.  The network's up-sampling sizes are fixed: the input is 256 x 256.
+ *
+ * Source tensors, in this order (BN = weight, bias, running_mean, running_var): conv_layer1.0.weight, BN conv_layer1.1,
+ * conv_layer1.2.weight; per unit of conv_layer2, 3, 4, dconv_layer1, 2, 3 (three each): BN res_layer.0, res_layer.1.weight,
+ * res_layer.2.weight, res_layer.3.weight, BN res_layer.4 and, where the unit changes the channel count (the first of every stage and
+ * dconv_layer1.1, dconv_layer2.1, dconv_layer3.1), shortcut_layer.0.weight, BN shortcut_layer.1.  E3DGE_ALIGNER_SOURCES in all.
+ *
+ * e3dge_aligner_packed_floats    floats of the packed image: A-fragment images of the convolutions, every BatchNorm folded to (a, b)
+ *                                pairs, the PReLU slopes.
+ * e3dge_aligner_pack             src: HOST array of n_src device pointers.  Re-run after a weight update.
+ * e3dge_aligner_workspace_bytes  workspace bytes of e3dge_aligner_forward for n images (1..256) (-1: bad n).
+ * e3dge_aligner_forward          the six input channels are the `split` channels of res_gt (n, split, 256, 256) followed by those of
+ *                                thumb (n, 6 - split, 256, 256), or (n, 6 - split, 64, 64) read at nearest x4 with thumb_up4: split 6
+ *                                is the module's forward on one tensor, split 3 the call site's cat(res_gt, interpolate(thumb)) with no
+ *                                concatenated copy.  out (n, 3, 256, 256).  taps: feat1 (n, 16, 256, 256), feat2 (n, 32, 128, 128),
+ *                                feat3 (n, 48, 64, 64), feat4 (n, 64, 32, 32), dfea1 (n, 32, 64, 64), dfea2 (n, 16, 128, 128) -- each
+ *                                stage's output before its up-sampling -- and dfea3 (= out); any may be NULL.  Fails before any launch on
+ *                                a null pointer ("null"), n out of range, a size other than 256, a split outside 0..6, a packed buffer
+ *                                ("packed") or workspace ("workspace") that is too small.  49 launches (50 with the dfea3 tap).
+ * e3dge_aln_conv                 debug entry for aln_conv_kernel: out (n, cout, oh, ow) = conv ksize x ksize (1 pad 0, or 3 pad 1), stride
+ *                                1 or 2, of the cin input channels: `split` from in0 (n, split, height, width), the rest from in1
+ *                                (n, cin - split, height, width), or (n, cin - split, height / 4, width / 4) read at nearest x4 with up4.
+ *                                w (cout, cin, ksize, ksize), cout 1..64.  in_ab (cin, 2): a x + b on in-image elements (NULL: none);
+ *                                epi_ab (cout, 2) and slope (cout): the affine and the PReLU after the sum (NULL: none); shortcut_mode 0:
+ *                                none, 1: + shortcut[:, :, ::stride, ::stride] of a (n, cout, height, width) tensor, 2: + a
+ *                                (n, cout, oh, ow) tensor.  wfrag: scratch of roundup(cout, 16) * roundup(cin ksize^2, 32) floats.  Two
+ *                                launches.
+ * e3dge_aln_up2                  debug entry for aln_up2_kernel: out (planes, 2 height, 2 width) = bilinear x2 of in (planes, height,
+ *                                width), align_corners = False.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_ALIGNER_TAPS 7
+#define E3DGE_ALIGNER_SOURCES 249
+typedef struct E3dgeAlignerArgs {
+    const float* packed;              /* e3dge_aligner_pack */
+    int64_t packed_floats;
+    const float* res_gt; const float* thumb;
+    int32_t n, size, split, thumb_up4;
+    float* out;
+    float* taps[E3DGE_ALIGNER_TAPS];
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeAlignerArgs;
+int64_t e3dge_aligner_packed_floats(void);
+int e3dge_aligner_pack(float* packed, int64_t packed_floats, const float* const* src, int n_src, e3dge_stream_t stream);
+int64_t e3dge_aligner_workspace_bytes(int n);
+int e3dge_aligner_forward(const E3dgeAlignerArgs* args, e3dge_stream_t stream);
+int e3dge_aln_conv(float* out, const float* in0, const float* in1, const float* w, const float* in_ab, const float* epi_ab, const float* slope,
+                   const float* shortcut, float* wfrag, int64_t wfrag_floats, int n, int cin, int split, int up4, int cout, int height,
+                   int width, int ksize, int stride, int shortcut_mode, e3dge_stream_t stream);
+int e3dge_aln_up2(float* out, const float* in, int64_t planes, int height, int width, e3dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
