@@ -575,6 +575,19 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def dense(t, align=16):
+    """`t` itself when a kernel may take it as it is -- contiguous, base pointer a multiple of `align` bytes -- and a fresh contiguous
+    copy otherwise (a strided, expanded or permuted view; a contiguous slice such as `pts[1:]` of (B, 125, 3) floats, whose pointer
+    is 12 mod 16).  None stays None.  DESIGN.md 'What a kernel may be handed' lists the entries that take 4-byte alignment (pass
+    align=4 there); every other pointer of a caller's tensor goes through this with the default."""
+    if t is None:
+        return None
+    if t.is_contiguous() and t.data_ptr() % align == 0:
+        return t
+    import torch
+    return t.clone(memory_format=torch.contiguous_format)      # (the allocators align a fresh block far beyond 16 bytes)
+
+
 def stream_of(t):
     """The current HIP stream of the tensor's device (or of a device), as the void* the C-ABI wants."""
     import torch

@@ -66,7 +66,7 @@ def query_feature_map(pts, calibs, fmap=None, out=None, col_off=0, mask_out=None
         if fmap.shape[0] != B:
             raise RuntimeError(f"feature map batch {fmap.shape[0]} != points batch {B}")
         C, h, w = fmap.shape[1], fmap.shape[2], fmap.shape[3]
-        fm = fmap.permute(0, 2, 3, 1).contiguous()                   # channel-last rows: a corner = C contiguous floats
+        fm = _lib.dense(fmap.permute(0, 2, 3, 1))                    # channel-last rows: a corner = C contiguous floats, 16-byte loads
         if out is None:
             out = torch.empty((B, N, C), device=dev, dtype=torch.float32)
             col_off = 0
@@ -103,8 +103,8 @@ class _GatherFn(torch.autograd.Function):
         C, h, w = fmap.shape[1:]
         dev = pts.device
         need_p, _, need_f = ctx.needs_input_grad
-        g = d_feats.contiguous().float()
-        fm = fmap.detach().permute(0, 2, 3, 1).contiguous()
+        g = _lib.dense(d_feats.float())                              # (e3dge_local_query_bwd refuses a d_out that is not 16-byte aligned)
+        fm = _lib.dense(fmap.detach().permute(0, 2, 3, 1))
         d_fm = torch.zeros((B, h, w, C), device=dev, dtype=torch.float32) if need_f else None
         d_p = torch.empty((B, N, 3), device=dev, dtype=torch.float32) if need_p else None
         p = pts.detach().contiguous()
@@ -143,9 +143,7 @@ class _EncInFn(torch.autograd.Function):
     def backward(ctx, d_enc, _d_mask):
         pts, que_calibs, ref_calibs = ctx.saved_tensors
         B, N, _ = pts.shape
-        g = d_enc.float()
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g = _lib.dense(d_enc.float())
         ld = g.shape[-1]
         p = pts.detach().contiguous()
         out = []
@@ -367,9 +365,7 @@ class Fuse_sft_MLP(nn.Module):
         """`keep` (a dict): every intermediate gets a buffer of its own and is left there for _FuseFn.backward --
         net (fc_0's output), e (the block's output), s1 / t1 (the SFT branches' hidden activations), scale (the scale branch)."""
         lead = enc_in.shape[:-1]
-        x = enc_in.reshape(-1, enc_in.shape[-1])
-        if not x.is_contiguous():
-            x = x.contiguous()
+        x = _lib.dense(enc_in.reshape(-1, enc_in.shape[-1]))         # (e3dge_amax below requires a 16-byte pointer)
         N, ld = x.shape
         dev = x.device
         I = self._images(dev)
@@ -453,8 +449,9 @@ class _FuseFn(torch.autograd.Function):
         need = ctx.needs_input_grad[6:]
         need_x = ctx.needs_input_grad[1]
         g_rows = grad_out.reshape(-1, grad_out.shape[-1]).float()
-        if g_rows.stride(-1) != 1 or (g_rows.shape[0] > 1 and g_rows.stride(0) < g_rows.shape[1]) or g_rows.data_ptr() % 4:
-            g_rows = g_rows.contiguous()
+        rows_ok = g_rows.stride(-1) == 1 and (g_rows.shape[0] <= 1 or g_rows.stride(0) >= g_rows.shape[1]) and g_rows.data_ptr() % 16 == 0
+        if not rows_ok:                                       # (pitched, aligned rows are read in place; anything else is made dense)
+            g_rows = _lib.dense(g_rows)
         ld_g = g_rows.stride(0) if g_rows.shape[0] > 1 else g_rows.shape[1]
         g = g_rows[:, :256]                                   # (a view when the node also produced the positional-encoding columns)
         dec = x[:, b_off:]

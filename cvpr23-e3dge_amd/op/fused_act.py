@@ -112,10 +112,10 @@ class _NoiseBiasLrelu(Function):
     @staticmethod
     def forward(ctx, x, noise, noise_weight, bias, slope, scale):
         B, C = x.shape[0], x.shape[1]
-        xc = x.contiguous()
-        nz = None if noise is None else noise.contiguous()
+        xc = _lib.dense(x)                       # (e3dge_noise_bias_act requires 16-byte pointers: realigned here, not refused there)
+        nz = _lib.dense(noise)
         y = torch.empty_like(xc)
-        _lib.launch("e3dge_noise_bias_act", y, xc, nz, noise_weight, bias, float(slope), float(scale), B, C,
+        _lib.launch("e3dge_noise_bias_act", y, xc, nz, _lib.dense(noise_weight), _lib.dense(bias), float(slope), float(scale), B, C,
                     xc.numel() // max(B * C, 1), 0 if nz is None else nz.shape[0])
         ctx.save_for_backward(y, nz if nz is not None else y.new_empty(0))
         ctx.slope, ctx.scale = slope, scale

@@ -366,13 +366,13 @@ class ModulatedConv2d(nn.Module):
         in_amax / out_amax: amax buffers (_lib.AMAX_FLOATS floats, include/e3dge_hip.h): max|input| as tracked by the
         producer of `input` (computed here with e3dge_amax when not supplied) / zero-initialised buffer receiving max|output|."""
         B, Ci, H, W = input.shape
-        x = input.contiguous()
+        x = _lib.dense(input)
         img, wsq = self.device_image()
         dev = x.device
         if pre is not None:           # (s, demod, s_amax) from Decoder's e3dge_decoder_styles launch
             s, demod, s_amax = pre
         else:
-            s = self.modulation(style).contiguous()
+            s = self.modulation(style.contiguous()).contiguous()     # (the library GEMM rounds a transposed operand differently: one layout in)
             demod = torch.empty((B, self.out_channel), device=dev, dtype=torch.float32) if self.demodulate else None
             s_amax = torch.empty(B, device=dev, dtype=torch.float32)
         OH, OW = (2 * H + 1, 2 * W + 1) if self.upsample else (H, W)
@@ -400,7 +400,7 @@ class ModulatedConv2d(nn.Module):
         if self.fused_ok(input, style):
             out = self.forward_fused(input, style)
             return self.blur(out) if self.upsample else out
-        s = self.modulation(style)
+        s = self.modulation(style.contiguous())
         if self.upsample:
             w = self._weights(s, transpose=True)
             out = F.conv_transpose2d(input.reshape(1, B * Ci, H, W), w, padding=0, stride=2, groups=B)
@@ -540,8 +540,8 @@ class ToRGB(nn.Module):
         if self.fused_ok(input, skip, style):
             # 1x1 modulated conv (no demodulation) + bias + FIR-up-sampled skip: one HBM pass (e3dge_torgb)
             B, Ci, H, W = input.shape
-            x = input.contiguous()
-            s = pre[0] if pre is not None else self.conv.modulation(style).contiguous()
+            x = _lib.dense(input)                     # (e3dge_torgb requires 16-byte x / y)
+            s = pre[0] if pre is not None else self.conv.modulation(style.contiguous()).contiguous()
             w = self.conv.weight.detach().reshape(3, Ci).contiguous()
             y = torch.empty((B, 3, H, W), device=x.device, dtype=torch.float32)
             sk = None if skip is None else skip.contiguous()
@@ -824,7 +824,7 @@ class Decoder(nn.Module):
         dev = features.device
         st = self._dec2_state(B, res, dev)
         plan = st['plan']
-        x = features.contiguous()
+        x = _lib.dense(features)
         lat = latent.contiguous()
         convs3 = [self.conv1] + list(self.convs)
         hold = [x, lat]
@@ -835,7 +835,7 @@ class Decoder(nn.Module):
             nz = noise[i]
             if nz is None:                                   # NoiseInjection's own noise (reference :371-373)
                 nz = torch.empty((B, 1, r, r), device=dev, dtype=torch.float32).normal_()
-            nz = nz.contiguous()
+            nz = _lib.dense(nz)
             if nz.shape[0] not in (1, B) or nz.numel() != nz.shape[0] * r * r:
                 raise RuntimeError(f"noise[{i}] must be (1|B, 1, {r}, {r}); got {tuple(nz.shape)}")
             dst = plan.conv1 if i == 0 else (plan.up[(i - 1) // 2] if i % 2 == 1 else plan.conv[(i - 1) // 2])
@@ -915,7 +915,7 @@ class Decoder(nn.Module):
             raise RuntimeError("Decoder._backward_packed: the last packed forward of this workspace did not keep its activations")
         bw = self._dec2_bwd_state(st, B, res, dev)
         q = bw['plan']
-        g = d_img.contiguous()
+        g = _lib.dense(d_img)                             # (`img.sum().backward()` delivers a stride-0 gradient)
         if g.dtype != torch.float32 or g.shape != st['outs'][-1].shape:
             raise RuntimeError(f"d image must be float32 {tuple(st['outs'][-1].shape)}; got {g.dtype} {tuple(g.shape)}")
         d_feat = torch.empty((B, self.conv1.conv.in_channel, res, res), device=dev, dtype=torch.float32)

@@ -397,7 +397,7 @@ class SirenGenerator(nn.Module):
             styles = styles.unsqueeze(1).expand(-1, 9, -1)
         if styles.ndim != 3 or styles.shape[1] != 9 or styles.shape[2] != self.style_dim:
             raise RuntimeError(f"styles must be (B, 9, {self.style_dim}) or (B, {self.style_dim}); got {tuple(styles.shape)}")
-        styles = styles.contiguous()
+        styles = _lib.dense(styles)                 # (stride-0 `latent.unsqueeze(1).expand(...)` styles; e3dge_film_params requires 16-byte pointers)
         _, wg, bg, wb, bb = self.device_image()
         B = styles.shape[0]
         film = torch.empty((B, 9, 2, self.W), device=styles.device, dtype=torch.float32)
@@ -495,7 +495,8 @@ def siren_backward(siren, film, args, d_feat, d_rgb, d_sdf, tang=None, rsave=Non
     B, N = args.shape[0], args.shape[1]
     dev = args.device
     lib = _lib.load()
-    d_feat, d_rgb, d_sdf = [None if t is None else t.contiguous().float() for t in (d_feat, d_rgb, d_sdf)]
+    d_feat = None if d_feat is None else _lib.dense(d_feat.float())          # (16-byte loads: siren_bwd.hip:1142 guards it)
+    d_rgb, d_sdf = [None if t is None else t.contiguous().float() for t in (d_rgb, d_sdf)]
     n_part = lib.e3dge_siren_bwd_partial_floats(B, N)
     partials = torch.empty(max(n_part, 1), device=dev, dtype=torch.float32)
     dfilm = torch.empty((B, 9, 2, siren.W), device=dev, dtype=torch.float32)
@@ -740,7 +741,7 @@ class _RenderQuery(torch.autograd.Function):
             shared.siren, shared.film, shared.args, shared.box_scale = renderer.siren, film, args, renderer.box_scale
             shared.images = renderer.siren.device_image()
             shared.rsave = rsave if want_eik else None
-        ta = tex[0].contiguous() if tex is not None else torch.empty(0, device=c2w.device)
+        ta = _lib.dense(tex[0]) if tex is not None else torch.empty(0, device=c2w.device)
         extra = (styles.detach(), out['viewdirs']) if len(params) > 1 else ()
         ctx.save_for_backward(film, args, out['sdf'], out['dists'], out['points'], out['hit_prob'],
                               near.reshape(B).contiguous().float(), far.reshape(B).contiguous().float(), rsave, ta, *extra)
@@ -866,7 +867,7 @@ class _TexHead(torch.autograd.Function):
             return (dx if need[0] else None, None, dw0 if need[2] else None, db0 if need[3] else None,
                     dw1 if need[4] else None, db1 if need[5] else None, dws if need[6] else None)
         from .wgrad import amax_of, wgrad
-        d_alpha, d_beta = d_alpha.contiguous().float(), d_beta.contiguous().float()
+        d_alpha, d_beta = _lib.dense(d_alpha.float()), _lib.dense(d_beta.float())
         trainable = any(need[2:])
         r_ = ctx.block._launch_bwd(x, d_alpha, d_beta, want_net=need[4], want_amax=trainable)      # (n, 320) rows, columns >= cin zero
         dx, dnet_p, net_p = r_[:3]
@@ -1335,7 +1336,7 @@ class VolumeFeatureRenderer(nn.Module):
             _lib.require_gpu(ta, "tex alpha"); _lib.require_gpu(tb, "tex beta")
             if tuple(ta.shape) != (B, H, Wd, S, 256) or tuple(tb.shape) != (B, H, Wd, S, 256):
                 raise RuntimeError(f"tex conditions must be (B,H,W,S,256) = {(B, H, Wd, S, 256)}; got {tuple(ta.shape)}")
-            ta, tb = ta.contiguous(), tb.contiguous()
+            ta, tb = _lib.dense(ta), _lib.dense(tb)
         if use is not None:
             o1 = use['out']
             out = dict(o1, rgb=torch.empty((B, 3, H, Wd), **f32), features=torch.empty((B, 256, H, Wd), **f32))
