@@ -311,6 +311,22 @@ class AlignerArgs(_Args):
         ("out", _vp), ("taps", _vp * ALIGNER_TAPS), ("ws", _vp), ("ws_bytes", _i64)]
 
 
+class AlignerSaveArgs(_Args):
+    """Mirror of struct E3dgeAlignerSaveArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("packed_floats", _i64), ("src", _vp), ("n_src", _i32), ("train", _i32), ("res_gt", _vp), ("thumb", _vp)] + [
+        (n, _i32) for n in ("n", "size", "split", "thumb_up4")] + [("out", _vp), ("taps", _vp * ALIGNER_TAPS), ("saved", _vp), ("saved_bytes", _i64),
+                                                                   ("stats", _vp), ("stats_doubles", _i64)]
+
+
+class AlignerBwdArgs(_Args):
+    """Mirror of struct E3dgeAlignerBwdArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("packed_floats", _i64), ("packed_t", _vp), ("packed_t_floats", _i64), ("src", _vp), ("want", _vp), ("n_src", _i32),
+                ("train", _i32), ("res_gt", _vp), ("thumb", _vp), ("g_out", _vp)] + [
+        (n, _i32) for n in ("n", "size", "split", "thumb_up4", "want_input", "reserved")] + [
+        ("saved", _vp), ("saved_bytes", _i64), ("stats", _vp), ("d_res_gt", _vp), ("d_thumb", _vp), ("grads", _vp), ("grad_floats", _i64), ("ws", _vp),
+        ("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -484,6 +500,27 @@ SIGNATURES = {
     "e3dge_aligner_forward": (_i32, [ctypes.POINTER(AlignerArgs), _vp]),
     "e3dge_aln_conv": (_i32, [_vp] * 9 + [_i64] + [_i32] * 10 + [_vp]),
     "e3dge_aln_up2": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
+    "e3dge_aln_norm_ws_bytes": (_i64, [_i32] * 4),
+    "e3dge_aln_bn_stats": (_i32, [_vp] * 7 + [_i64] + [_i32] * 5 + [_vp]),
+    "e3dge_aln_bn_apply": (_i32, [_vp] * 6 + [_i32] * 8 + [_vp]),
+    "e3dge_aln_norm_bwd": (_i32, [_vp] * 12 + [_i64] + [_i32] * 6 + [_vp]),
+    "e3dge_aln_prelu_bwd": (_i32, [_vp] * 6 + [_i64] + [_i32] * 4 + [_vp]),
+    "e3dge_aln_up2_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
+    "e3dge_aln_pick_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "e3dge_aln_conv_dgrad": (_i32, [_vp] * 6 + [_i64] + [_i32] * 7 + [_vp]),
+    "e3dge_aln_wgrad_ws_floats": (_i64, [_i32] * 7),
+    "e3dge_aln_conv_wgrad": (_i32, [_vp] * 6 + [_i64] + [_i32] * 9 + [_vp]),
+    "e3dge_aligner_saved_bytes": (_i64, [_i32]),
+    "e3dge_aligner_bwd_workspace_bytes": (_i64, [_i32]),
+    "e3dge_aligner_grad_floats": (_i64, []),
+    "e3dge_aligner_grad_offset": (_i64, [_i32]),
+    "e3dge_aligner_stats_channels": (_i64, []),
+    "e3dge_aligner_packed_t_floats": (_i64, []),
+    "e3dge_aligner_branch_count": (_i64, [_i32]),
+    "e3dge_aligner_pack_t": (_i32, [_vp, _i64, _vp, _i32, _vp]),
+    "e3dge_aligner_forward_saving": (_i32, [ctypes.POINTER(AlignerSaveArgs), _vp]),
+    "e3dge_aligner_backward": (_i32, [ctypes.POINTER(AlignerBwdArgs), _vp]),
+    "e3dge_aligner_branch_bytes": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -9,7 +9,13 @@ float32 (B, 6, 256, 256) input runs the HIP kernels when the module is in eval m
 are aligner_norm_type 'batch' without demodulation and no gradient is wanted (grad mode off, or neither the input nor a parameter
 requires grad).  Everything else -- CPU tensors, other dtypes, train(), gradients, 'instance' / 'none' / demodulation, other sizes (which
 raise in torch.cat as the reference does), E3DGE_ALIGNER=torch -- runs the module's own torch layers in the reference's order; on the CPU
-they reproduce the reference bit for bit (tests/test_aligner_host.py against tools/gen_golden_aligner.py's recording)."""
+they reproduce the reference bit for bit (tests/test_aligner_host.py against tools/gen_golden_aligner.py's recording).
+
+Trainable form, opt-in: `ResidualAligner(opt_training, differentiable=True)` (also an attribute, or `differentiable_aligner` in the
+options; off by default, and with it off nothing above changes).  With it on, a call with grad mode on and a wanted gradient -- an input
+or a tensor of sources() requires grad -- is one autograd node (_AlignerNode) on csrc/aligner_train.h, in the form of `self.training`: the
+eval form, or the train form with BatchNorm on batch statistics and nn.BatchNorm2d's update of the running buffers.  Its backward returns
+the gradient to the input(s) and to every parameter that requires grad, once (a second differentiation raises).  DESIGN.md 4.17b."""
 import ctypes
 import functools
 import os
@@ -17,6 +23,7 @@ import os
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -112,8 +119,11 @@ class ResidualAligner(nn.Module):
     """`ResidualAligner(opt_training)(x)`: x (B, 6, 256, 256) = cat(res_gt, thumb at 256^2) -> (B, 3, 256, 256).  `opt_training` needs
     aligner_demodulate and aligner_norm_type (synthetic.aligner_opt has the scripts' values)."""
 
-    def __init__(self, opt_training=None):
+    def __init__(self, opt_training=None, differentiable=None):
         super().__init__()
+        if differentiable is None:                                   # from the options; off by default
+            differentiable = getattr(opt_training, 'differentiable_aligner', False)
+        self.differentiable = bool(differentiable)
         self.demodulate = bool(opt_training.aligner_demodulate)
         self.norm_type = 'none' if self.demodulate else opt_training.aligner_norm_type
         norm_layer = get_norm_layer(self.norm_type)
@@ -162,35 +172,96 @@ class ResidualAligner(nn.Module):
             return False
         return not (torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or any(p.requires_grad for p in _lib.params_of(self))))
 
+    def _covers(self, *inputs):
+        """The device, dtype, shape and batch checks of _runs_hip on the one-tensor or (res_gt, thumb) form."""
+        channels = 0
+        for i, t in enumerate(inputs):
+            if not (torch.is_tensor(t) and t.device.type == "cuda" and t.dtype == torch.float32 and t.ndim == 4):
+                return False
+            if t.device != inputs[0].device or t.shape[0] != inputs[0].shape[0] or t.shape[0] < 1 or t.shape[0] > 256:
+                return False
+            sizes = ((SIZE, SIZE), (SIZE // 4, SIZE // 4)) if i == 1 else ((SIZE, SIZE),)
+            if tuple(t.shape[-2:]) not in sizes:
+                return False
+            channels += t.shape[1]
+        return channels == IN_CHANNELS
+
+    def _runs_hip_grad(self, *inputs):
+        """Does this call run as one autograd node on the kernels (csrc/aligner_train.h)?  Opt-in (`differentiable`), grad mode on, the
+        kernels' options and inputs, a wanted gradient (an input or a source tensor requires grad) and, in train(), a numeric momentum on
+        every BatchNorm (momentum=None, the cumulative average, stays on the torch layers)."""
+        if not (self.differentiable and torch.is_grad_enabled() and self.native_options()) or os.environ.get("E3DGE_ALIGNER", "") == "torch":
+            return False
+        if not self._covers(*inputs):
+            return False
+        if not (any(t.requires_grad for t in inputs) or any(t.requires_grad for t in self.sources())):
+            return False
+        return not self.training or all(m.momentum is not None for m in self.batch_norms())
+
     # ---- launch plumbing --------------------------------------------------------------------------------------------------------------
     def sources(self):
-        """The source tensors in the order of e3dge_aligner_pack (include/e3dge_hip.h)."""
-        bn = lambda m: [m.weight, m.bias, m.running_mean, m.running_var]
-        out = [self.conv_layer1[0].weight] + bn(self.conv_layer1[1]) + [self.conv_layer1[2].weight]
-        for name in STAGES:
-            for u in getattr(self, name):
-                r = u.res_layer
-                out += bn(r[0]) + [r[1].weight, r[2].weight, r[3].weight] + bn(r[4])
-                if isinstance(u.shortcut_layer, nn.Sequential):
-                    out += [u.shortcut_layer[0].weight] + bn(u.shortcut_layer[1])
+        """The source tensors in the order of e3dge_aligner_pack (include/e3dge_hip.h).  The (dict, key) slots are listed once per module
+        and looked up per call, so a replaced Parameter is still seen; invalidate() drops the listing (after a sub-module was replaced)."""
+        slots = self.__dict__.get("_source_slots")
+        if slots is None:
+            slots = []
+            bn = lambda m: [(m._parameters, "weight"), (m._parameters, "bias"), (m._buffers, "running_mean"), (m._buffers, "running_var")]
+            w = lambda m: [(m._parameters, "weight")]
+            slots += w(self.conv_layer1[0]) + bn(self.conv_layer1[1]) + w(self.conv_layer1[2])
+            for name in STAGES:
+                for u in getattr(self, name):
+                    r = u.res_layer
+                    slots += bn(r[0]) + w(r[1]) + w(r[2]) + w(r[3]) + bn(r[4])
+                    if isinstance(u.shortcut_layer, nn.Sequential):
+                        slots += w(u.shortcut_layer[0]) + bn(u.shortcut_layer[1])
+            self.__dict__["_source_slots"] = slots
+        return [d[k] for d, k in slots]
+
+    def batch_norms(self):
+        """The BatchNorms in the order of sources() (the order of the statistics buffer of e3dge_aligner_forward_saving); listed once."""
+        out = self.__dict__.get("_batch_norms")
+        if out is None:
+            out = [self.conv_layer1[1]]
+            for name in STAGES:
+                for u in getattr(self, name):
+                    out += [u.res_layer[0], u.res_layer[4]] + ([u.shortcut_layer[1]] if isinstance(u.shortcut_layer, nn.Sequential) else [])
+            self.__dict__["_batch_norms"] = out
         return out
 
     def packed(self, device):
         """The packed weight image on `device`, from the shared weight-image cache."""
+        return self._image(device, "aligner_packed", "e3dge_aligner_packed_floats", "e3dge_aligner_pack", self.sources())
+
+    def packed_train(self, device):
+        """The same image for the train form, which reads no running statistics from it: keyed on the parameters alone, so that the
+        buffer update of every train-form forward does not rebuild it (an optimiser step does).  The buffers are still packed, so they
+        are checked like the parameters."""
+        return self._image(device, "aligner_packed_train", "e3dge_aligner_packed_floats", "e3dge_aligner_pack", list(_lib.params_of(self)))
+
+    def packed_t(self, device):
+        """The transposed, tap-flipped images of the convolutions beside it: the data gradients' operand."""
+        return self._image(device, "aligner_packed_t", "e3dge_aligner_packed_t_floats", "e3dge_aligner_pack_t", [t for t in self.sources() if t.ndim == 4])
+
+    def _image(self, device, slot, size_entry, pack_entry, keyed):
         src = self.sources()
 
         def build():
             with torch.no_grad():
                 keep = [t.detach().contiguous() for t in src]
                 ptrs = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-                image = torch.empty(_lib.query("e3dge_aligner_packed_floats"), device=device, dtype=torch.float32)
-                _lib.launch("e3dge_aligner_pack", image, image.numel(), ctypes.addressof(ptrs), len(keep))
+                image = torch.empty(_lib.query(size_entry), device=device, dtype=torch.float32)
+                _lib.launch(pack_entry, image, image.numel(), ctypes.addressof(ptrs), len(keep))
                 return image
 
-        return _lib.weight_image(self, "aligner_packed", src, device, "ResidualAligner", build)
+        for t in src:                                                # (weight_image checks what it is keyed on; the pack kernels read all of these)
+            if t.device != device or t.dtype != torch.float32:
+                raise RuntimeError(f"ResidualAligner weights must be float32 on the inputs' device {device} (got {t.dtype} on {t.device})")
+        return _lib.weight_image(self, slot, keyed, device, "ResidualAligner", build)
 
     def invalidate(self):
-        """Drop the packed weight image (needed only after writes through `.data`)."""
+        """Drop the packed weight images (needed only after writes through `.data`) and the listings of sources() and batch_norms()."""
+        self.__dict__.pop("_source_slots", None)
+        self.__dict__.pop("_batch_norms", None)
         _lib.invalidate(self)
 
     def forward_hip(self, res_gt, thumb=None, taps=None):
@@ -218,7 +289,17 @@ class ResidualAligner(nn.Module):
         _lib.launch("e3dge_aligner_forward", a)
         return out
 
+    def _node(self, res_gt, thumb):
+        """The call as one autograd node; in train() the running buffers are then updated, once, from the statistics it computed."""
+        train = bool(self.training)
+        out, stats = _AlignerNode.apply(self, train, res_gt, thumb, *self.sources())
+        if train:
+            _update_running_buffers(self.batch_norms(), stats, res_gt.shape[0])
+        return out
+
     def forward(self, x):
+        if self._runs_hip_grad(x):
+            return self._node(x, None)
         if not self._runs_hip(x):
             return self.forward_torch(x)
         return self.forward_hip(x)
@@ -226,6 +307,156 @@ class ResidualAligner(nn.Module):
     def align(self, res_gt, thumb):
         """The call site's composition forward(cat(res_gt, F.interpolate(thumb, (256, 256)))) (e3dge_full_runner.py:255-259, nearest), bit
         for bit.  On the native path with a 64^2 or 256^2 thumb neither the up-sampled thumb nor the 6-channel tensor is materialised."""
+        if self._runs_hip_grad(res_gt, thumb):
+            return self._node(res_gt, thumb)
         if self._runs_hip(res_gt, thumb):
             return self.forward_hip(res_gt, thumb)
         return self.forward(torch.cat((res_gt, F.interpolate(thumb, (SIZE, SIZE))), dim=1))
+
+
+class _AlignerNode(torch.autograd.Function):
+    """(output, batch statistics) of ResidualAligner on the kernels as one autograd node, from the 6-channel tensor (thumb None) or from
+    (res_gt, thumb).  params: ResidualAligner.sources(), so that autograd asks for their gradients (the running buffers among them get
+    None).  Forward: e3dge_aligner_forward_saving in the form `train` -- on running statistics the plain forward's output bit for bit, the
+    statistics empty; on batch statistics the (channels, 2) float64 (mean, biased variance) pairs, not differentiable, from which the
+    caller updates the running buffers (the node itself writes to none of its inputs).  Backward: e3dge_aligner_backward, once (a second
+    differentiation raises); each gradient only where autograd asks for it.  Every tensor the backward reads again -- the inputs, gamma,
+    the slopes and, in the eval form, the running statistics -- is saved with save_for_backward: an in-place change between forward and
+    backward raises, as under torch.  Inputs, upstream gradient and source tensors are handed over dense (_lib.dense)."""
+    branches = None                                                  # debug: a list that receives every forward's e3dge_aligner_branch_bytes buffer
+    taps = None                                                      # debug: a dict that receives the tensors of TAPS of every forward
+
+    @staticmethod
+    def forward(ctx, module, train, res_gt, thumb, *params):
+        n, dev = res_gt.shape[0], res_gt.device
+        image, image_t = (module.packed_train(dev) if train else module.packed(dev)), module.packed_t(dev)
+        res_gt = _lib.dense(res_gt.detach())
+        thumb = None if thumb is None else _lib.dense(thumb.detach())
+        up4 = int(thumb is not None and thumb.shape[-1] != SIZE)
+        saved = torch.empty(_lib.query("e3dge_aligner_saved_bytes", n), device=dev, dtype=torch.uint8)
+        out = torch.empty((n, 3, SIZE, SIZE), device=dev, dtype=torch.float32)
+        stats = torch.empty((_sizes(module)[0] if train else 0, 2), device=dev, dtype=torch.float64)
+        keep = [_lib.dense(p.detach(), align=4) for p in params]     # (the kernels read gamma, beta and the slopes one float at a time)
+        ptrs = (ctypes.c_void_p * len(keep))(*[p.data_ptr() for p in keep])
+        a = _lib.AlignerSaveArgs(packed=image, packed_floats=image.numel(), src=ctypes.addressof(ptrs), n_src=len(keep), train=int(train), res_gt=res_gt,
+                                 thumb=thumb, n=n, size=SIZE, split=res_gt.shape[1], thumb_up4=up4, out=out, saved=saved, saved_bytes=saved.numel(),
+                                 stats=stats if train else None, stats_doubles=stats.numel())
+        if _AlignerNode.taps is not None:
+            for i, (name, (c, s)) in enumerate(zip(TAPS, TAP_SHAPES)):
+                _AlignerNode.taps[name] = torch.empty((n, c, s, s), device=dev, dtype=torch.float32)
+                a.taps[i] = _AlignerNode.taps[name].data_ptr()
+        _lib.launch("e3dge_aligner_forward_saving", a)
+        if _AlignerNode.branches is not None:
+            branch = torch.empty(_lib.query("e3dge_aligner_branch_count", n), device=dev, dtype=torch.uint8)
+            _lib.launch("e3dge_aligner_branch_bytes", branch, branch.numel(), image, image.numel(), saved, saved.numel(), n, int(train))
+            _AlignerNode.branches.append(branch)
+        # what the backward reads again of the source tensors: everything but, in the train form, the running statistics (the caller
+        # updates those right after this forward; the train form's backward reads the batch statistics instead)
+        read_again = [i for i, p in enumerate(params) if not (train and _is_running_statistic(i))]
+        ctx.read_again, ctx.offsets = read_again, _sizes(module)[1]
+        ctx.save_for_backward(saved, image, image_t, stats, res_gt, *([] if thumb is None else [thumb]), *[params[i] for i in read_again])
+        ctx.form = (n, bool(train), thumb is not None, up4, len(params))
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, _g_stats):
+        n, train, two, up4, n_src = ctx.form
+        saved, image, image_t, stats, res_gt, *rest = ctx.saved_tensors
+        thumb = rest.pop(0) if two else None
+        dev = saved.device
+        params = [None] * n_src
+        for i, p in zip(ctx.read_again, rest):
+            params[i] = p
+        nothing = (None,) * (4 + n_src)
+        if g_out is None:
+            return nothing
+        g_out = _lib.dense(g_out.to(torch.float32))
+        want = [bool(w) for w in ctx.needs_input_grad[4:]]
+        want_input = bool(ctx.needs_input_grad[2] or (two and ctx.needs_input_grad[3]))
+        ws_bytes = _lib.query("e3dge_aligner_bwd_workspace_bytes", n)
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        offsets = ctx.offsets
+        grads = torch.empty(offsets[-1], device=dev, dtype=torch.float32) if any(want) else None
+        d_res_gt = torch.empty_like(res_gt) if want_input else None
+        d_thumb = torch.empty_like(thumb) if want_input and two else None
+        keep = [image if p is None else _lib.dense(p.detach(), align=4) for p in params]   # (a slot the train form never reads: any valid address)
+        ptrs = (ctypes.c_void_p * n_src)(*[p.data_ptr() for p in keep])
+        flags = (ctypes.c_uint8 * n_src)(*[int(w) for w in want])
+        a = _lib.AlignerBwdArgs(packed=image, packed_floats=image.numel(), packed_t=image_t, packed_t_floats=image_t.numel(), src=ctypes.addressof(ptrs),
+                                want=ctypes.addressof(flags), n_src=n_src, train=int(train), res_gt=res_gt, thumb=thumb, g_out=g_out, n=n, size=SIZE,
+                                split=res_gt.shape[1], thumb_up4=up4, want_input=int(want_input), saved=saved, saved_bytes=saved.numel(),
+                                stats=stats if train else None, d_res_gt=d_res_gt, d_thumb=d_thumb, grads=grads,
+                                grad_floats=0 if grads is None else grads.numel(), ws=ws, ws_bytes=ws_bytes)
+        _lib.launch("e3dge_aligner_backward", a)
+        out = [grads[offsets[i]:offsets[i + 1]].view(p.shape) if w else None for i, (p, w) in enumerate(zip(params, want))]
+        return (None, None, d_res_gt if ctx.needs_input_grad[2] else None, d_thumb if two and ctx.needs_input_grad[3] else None, *out)
+
+
+def _sizes(module):
+    """(BatchNorm channels in all, the slot of every source tensor in the gradient buffer with the buffer's size last): asked of the
+    library once per module, kept with its weight images."""
+    def build():
+        return (_lib.query("e3dge_aligner_stats_channels"), tuple(_lib.query("e3dge_aligner_grad_offset", i) for i in range(_lib.ALIGNER_SOURCES + 1)))
+    return _lib.cached(module, "aligner_sizes", (), build)
+
+
+@functools.lru_cache(maxsize=None)
+def _running_statistic_slots():
+    """The positions of running_mean / running_var in ResidualAligner.sources(): the third and fourth tensor of every BatchNorm."""
+    slots, at = set(), 1                                             # conv_layer1.0.weight, then its BatchNorm
+    slots.update((at + 2, at + 3))
+    at += 5                                                          # the BatchNorm's four and conv_layer1.2.weight
+    for units in STAGES.values():
+        for cin, depth, _ in units:
+            slots.update((at + 2, at + 3, at + 9, at + 10))          # res_layer.0; .1, .2, .3; res_layer.4
+            at += 11
+            if cin != depth:
+                slots.update((at + 3, at + 4))                       # shortcut_layer.0; shortcut_layer.1
+                at += 5
+    assert at == _lib.ALIGNER_SOURCES
+    return frozenset(slots)
+
+
+def _is_running_statistic(i):
+    return i in _running_statistic_slots()
+
+
+_TABLES = {}                                                         # (device, momenta, batch) -> the per-channel float64 factors of the buffer update
+
+
+def _update_running_buffers(bns, stats, n):
+    """nn.BatchNorm2d's buffer update of every BatchNorm from the (mean, biased variance) float64 pairs of one forward, in a handful of
+    launches whatever the number of BatchNorms: running <- (1 - m) running + m stat, the variance through M / (M - 1).  The per-channel
+    factors are built once per (device, momenta, batch)."""
+    with torch.no_grad():
+        sizes = [m.num_features for m in bns]
+        momenta = tuple(float(m.momentum) for m in bns)
+        key = (stats.device, momenta, n)
+        if key not in _TABLES:
+            momentum = torch.tensor([v for v, c in zip(momenta, sizes) for _ in range(c)], dtype=torch.float64)
+            count = torch.tensor([float(p * n) for p, c in zip(_bn_planes(len(bns)), sizes) for _ in range(c)], dtype=torch.float64)
+            _TABLES[key] = torch.stack((momentum, momentum * count / (count - 1)), 1).to(stats.device)
+        scaled = (stats * _TABLES[key]).float()
+        mean, var = scaled[:, 0].split(sizes), scaled[:, 1].split(sizes)
+        keep = [1.0 - v for v in momenta]
+        torch._foreach_mul_([m.running_mean for m in bns], keep)
+        torch._foreach_add_([m.running_mean for m in bns], list(mean))
+        torch._foreach_mul_([m.running_var for m in bns], keep)
+        torch._foreach_add_([m.running_var for m in bns], list(var))
+        torch._foreach_add_([m.num_batches_tracked for m in bns], 1)
+
+
+def _bn_planes(count):
+    """H W of every BatchNorm's input, in the order of ResidualAligner.batch_norms()."""
+    out = [SIZE * SIZE]                                              # conv_layer1.1
+    sizes = dict(conv_layer2=SIZE, conv_layer3=SIZE // 2, conv_layer4=SIZE // 4, dconv_layer1=SIZE // 4, dconv_layer2=SIZE // 2, dconv_layer3=SIZE)
+    for name, units in STAGES.items():
+        s = sizes[name]
+        for cin, depth, stride in units:
+            o = s // stride
+            out += [s * s, o * o] + ([o * o] if cin != depth else [])
+            s = o
+    assert len(out) == count
+    return out

@@ -220,6 +220,14 @@ static int aln_up2(float* out, const float* in, int64_t planes, int H, int W, hi
     return check_launch("aln(up2)");
 }
 
+}  // namespace e3dge
+
+// The trainable form (forward with saved state in the eval or the train form, backward with every parameter gradient): aligner_bwd.h (its
+// kernels) here, aligner_train.h (the network) after the packed layout; DESIGN.md 4.17b.
+#include "aligner_bwd.h"
+
+namespace e3dge {
+
 // ---- packed image ------------------------------------------------------------------------------------------------------------------
 // BatchNorm on its running statistics as the pair (a, b) = (gamma / sqrt(var + 1e-5), beta - mean a)
 __global__ void __launch_bounds__(256) aln_pack_bn_kernel(float* __restrict__ dst, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -304,6 +312,8 @@ static int aln_stage(float* out, const float* in0, const float* in1, int split, 
 }
 
 }  // namespace e3dge
+
+#include "aligner_train.h"                                          // the trainable form: forward with saved state, backward
 
 using namespace e3dge;
 
@@ -411,4 +421,390 @@ extern "C" int e3dge_aln_up2(float* out, const float* in, int64_t planes, int he
     E3DGE_REQUIRE(planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024,
                   "aln_up2: planes=%lld (1..2^20) height=%d width=%d (1..1024)", (long long)planes, height, width);
     return aln_up2(out, in, planes, height, width, as_stream(stream));
+}
+
+// ---- the trainable form's kernels around the convolutions (aligner_bwd.h), each at run-time shapes -------------------------------------------
+#define ALN_REQUIRE_PLANE(who)                                                                                                                  \
+    E3DGE_REQUIRE(n >= 1 && n <= 256 && channels >= 1 && channels <= 4096 && height >= 1 && width >= 1 && height <= 1024 && width <= 1024 &&    \
+                      (int64_t)n * channels * height * width <= ((int64_t)1 << 31),                                                              \
+                  who ": n=%d (1..256) channels=%d (1..4096) height=%d width=%d (1..1024), at most 2^31 elements", n, channels, height, width)
+
+extern "C" int64_t e3dge_aln_norm_ws_bytes(int n, int channels, int height, int width) {
+    if (n < 1 || n > 256 || channels < 1 || channels > 4096 || height < 1 || width < 1 || height > 1024 || width > 1024) {
+        fail(E3DGE_ERR_INVALID_ARG, "aln_norm_ws_bytes: n=%d (1..256) channels=%d (1..4096) height=%d width=%d (1..1024)", n, channels, height, width);
+        return -1;
+    }
+    return aln_norm_ws_bytes(n, channels, height * width);
+}
+
+extern "C" int e3dge_aln_bn_stats(float* ab, double* stats, const float* in0, const float* in1, const float* gamma, const float* beta, void* ws,
+                                  int64_t ws_bytes, int n, int channels, int split, int height, int width, e3dge_stream_t stream) {
+    E3DGE_REQUIRE((ab || stats) && ws && (!ab || (gamma && beta)), "aln_bn_stats: null pointer");
+    ALN_REQUIRE_PLANE("aln_bn_stats");
+    E3DGE_REQUIRE(split >= 0 && split <= channels, "aln_bn_stats: split=%d outside [0, channels=%d]", split, channels);
+    E3DGE_REQUIRE((split == 0 || in0) && (split == channels || in1), "aln_bn_stats: null pointer (a source with channels)");
+    const int hw = height * width, segs = aln_segments(hw);
+    E3DGE_REQUIRE((int64_t)n * hw >= 2, "aln_bn_stats: %lld values per channel (batch statistics need 2)", (long long)n * hw);
+    E3DGE_REQUIRE(ws_bytes >= aln_norm_ws_bytes(n, channels, hw), "aln_bn_stats: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                  (long long)aln_norm_ws_bytes(n, channels, hw));
+    hipStream_t st = as_stream(stream);
+    double* part = static_cast<double*>(ws);
+    aln_bn_stats_kernel<<<dim3(segs, n, channels), dim3(256), 0, st>>>(part, AlnSrc2{in0, in1, split, channels - split}, hw);
+    aln_bn_stats_fold_kernel<<<dim3((channels + 63) / 64), dim3(64), 0, st>>>(reinterpret_cast<float2*>(ab), stats, part, gamma, beta, channels, n * segs,
+                                                                              (double)n * hw);
+    return check_launch("aln_bn_stats");
+}
+
+extern "C" int e3dge_aln_bn_apply(float* out, const float* in, const float* ab, const float* slope, const float* shortcut, const float* shortcut_ab,
+                                  int n, int channels, int height, int width, int shortcut_height, int shortcut_width, int stride, int shortcut_mode,
+                                  e3dge_stream_t stream) {
+    E3DGE_REQUIRE(out && in && ab, "aln_bn_apply: null pointer");
+    ALN_REQUIRE_PLANE("aln_bn_apply");
+    E3DGE_REQUIRE(shortcut_mode >= kAlnScNone && shortcut_mode <= kAlnScAffine && (shortcut_mode == kAlnScNone || shortcut) &&
+                      (shortcut_mode != kAlnScAffine || shortcut_ab),
+                  "aln_bn_apply: shortcut_mode=%d (0 none, 1 strided pick, 2 read, 3 read under its own affine) needs its tensors", shortcut_mode);
+    if (shortcut_mode == kAlnScPick) {
+        E3DGE_REQUIRE(stride == 1 || stride == 2, "aln_bn_apply: stride=%d (1 or 2)", stride);
+        E3DGE_REQUIRE(shortcut_height >= 1 && shortcut_width >= 1 && shortcut_height <= 1024 && shortcut_width <= 1024 &&
+                          (shortcut_height - 1) / stride + 1 == height && (shortcut_width - 1) / stride + 1 == width,
+                      "aln_bn_apply: a %d x %d shortcut picked at stride %d is not %d x %d", shortcut_height, shortcut_width, stride, height, width);
+    }
+    AlnApplyArgs a;
+    a.out = out; a.in = in; a.ab = reinterpret_cast<const float2*>(ab); a.slope = slope; a.sc = shortcut;
+    a.sc_ab = reinterpret_cast<const float2*>(shortcut_ab);
+    a.C = channels; a.OH = height; a.OW = width; a.SH = shortcut_height; a.SW = shortcut_width; a.stride = stride; a.sc_mode = shortcut_mode;
+    a.total = (int64_t)n * channels * height * width;
+    aln_bn_apply_kernel<<<dim3(aln_blocks(a.total)), dim3(256), 0, as_stream(stream)>>>(a);
+    return check_launch("aln_bn_apply");
+}
+
+extern "C" int e3dge_aln_norm_bwd(float* gx, float* dgamma, float* dbeta, const float* gy, const float* in0, const float* in1, const float* gamma,
+                                  const double* stats, const float* running_mean, const float* running_var, const float* add, void* ws,
+                                  int64_t ws_bytes, int n, int channels, int split, int height, int width, int train, e3dge_stream_t stream) {
+    E3DGE_REQUIRE((gx || dgamma || dbeta) && gy && gamma && ws, "aln_norm_bwd: null pointer");
+    E3DGE_REQUIRE(train == 0 || train == 1, "aln_norm_bwd: train=%d (0 or 1)", train);
+    E3DGE_REQUIRE(train ? stats != nullptr : (running_mean && running_var), "aln_norm_bwd: null pointer (the statistics of this form)");
+    ALN_REQUIRE_PLANE("aln_norm_bwd");
+    E3DGE_REQUIRE(split >= 0 && split <= channels, "aln_norm_bwd: split=%d outside [0, channels=%d]", split, channels);
+    const bool sums = train || dgamma || dbeta;                       // on running statistics g_x = A g needs no sum
+    E3DGE_REQUIRE(!(sums || train) || ((split == 0 || in0) && (split == channels || in1)), "aln_norm_bwd: null pointer (a source with channels)");
+    const int hw = height * width, segs = aln_segments(hw);
+    E3DGE_REQUIRE(ws_bytes >= aln_norm_ws_bytes(n, channels, hw), "aln_norm_bwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                  (long long)aln_norm_ws_bytes(n, channels, hw));
+    hipStream_t st = as_stream(stream);
+    double* part = static_cast<double*>(ws);
+    double* coef = part + (int64_t)2 * channels * n * segs;
+    const AlnSrc2 src{in0, in1, split, channels - split};
+    const AlnNormStat ns{train ? stats : nullptr, running_mean, running_var};
+    if (sums) aln_norm_sums_kernel<<<dim3(segs, n, channels), dim3(256), 0, st>>>(part, gy, src, ns, channels, hw);
+    aln_norm_fold_kernel<<<dim3((channels + 63) / 64), dim3(64), 0, st>>>(coef, dgamma, dbeta, sums ? part : nullptr, gamma, ns, channels, n * segs,
+                                                                          (double)n * hw, train);
+    if (gx) {
+        const int64_t total = (int64_t)n * channels * hw;
+        aln_norm_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(AlnDst2{gx, nullptr, channels, 0}, gy, src, add, nullptr, coef, channels, hw, total,
+                                                                           train);
+    }
+    return check_launch("aln_norm_bwd");
+}
+
+extern "C" int e3dge_aln_prelu_bwd(float* gx, float* dslope, const float* gy, const float* pre, const float* slope, void* ws, int64_t ws_bytes, int n,
+                                   int channels, int height, int width, e3dge_stream_t stream) {
+    E3DGE_REQUIRE((gx || dslope) && gy && pre && slope && (!dslope || ws), "aln_prelu_bwd: null pointer");
+    ALN_REQUIRE_PLANE("aln_prelu_bwd");
+    const int hw = height * width, segs = aln_segments(hw);
+    E3DGE_REQUIRE(!dslope || ws_bytes >= aln_norm_ws_bytes(n, channels, hw), "aln_prelu_bwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                  (long long)aln_norm_ws_bytes(n, channels, hw));
+    hipStream_t st = as_stream(stream);
+    double* part = dslope ? static_cast<double*>(ws) : nullptr;
+    aln_prelu_bwd_kernel<<<dim3(segs, n, channels), dim3(256), 0, st>>>(gx, part, gy, pre, nullptr, slope, channels, hw);
+    if (dslope) aln_prelu_fold_kernel<<<dim3((channels + 63) / 64), dim3(64), 0, st>>>(dslope, part, channels, n * segs);
+    return check_launch("aln_prelu_bwd");
+}
+
+extern "C" int e3dge_aln_up2_bwd(float* gx, const float* gy, int64_t planes, int height, int width, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(gx && gy, "aln_up2_bwd: null pointer");
+    E3DGE_REQUIRE(planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024 &&
+                      planes * height * width <= ((int64_t)1 << 29),
+                  "aln_up2_bwd: planes=%lld (1..2^20) height=%d width=%d (1..1024), at most 2^29 elements", (long long)planes, height, width);
+    const int64_t total = planes * height * width;
+    aln_up2_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, as_stream(stream)>>>(gx, gy, height, width, total);
+    return check_launch("aln_up2_bwd");
+}
+
+extern "C" int e3dge_aln_pick_bwd(float* gx, const float* gy, const float* add, int64_t planes, int height, int width, int stride,
+                                  e3dge_stream_t stream) {
+    E3DGE_REQUIRE(gx && gy, "aln_pick_bwd: null pointer");
+    E3DGE_REQUIRE(planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024 &&
+                      planes * height * width <= ((int64_t)1 << 31),
+                  "aln_pick_bwd: planes=%lld (1..2^20) height=%d width=%d (1..1024), at most 2^31 elements", (long long)planes, height, width);
+    E3DGE_REQUIRE(stride == 1 || stride == 2, "aln_pick_bwd: stride=%d (1 or 2)", stride);
+    const int64_t total = planes * height * width;
+    aln_pick_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, as_stream(stream)>>>(gx, gy, add, height, width, (height - 1) / stride + 1,
+                                                                                      (width - 1) / stride + 1, stride, total);
+    return check_launch("aln_pick_bwd");
+}
+
+#define ALN_REQUIRE_CONV(who)                                                                                                                   \
+    E3DGE_REQUIRE(n >= 1 && n <= 256 && cin >= 1 && cin <= 4096, who ": n=%d (1..256) cin=%d (1..4096)", n, cin);                               \
+    E3DGE_REQUIRE(cout >= 1 && cout <= kAlnMaxCout, who ": cout=%d (1..64: the wide layers are the core's)", cout);                             \
+    E3DGE_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), who ": ksize=%d (1 or 3) stride=%d (1 or 2)", ksize, stride);     \
+    E3DGE_REQUIRE(height >= 1 && width >= 1 && height <= 1024 && width <= 1024, who ": height=%d width=%d (1..1024)", height, width)
+
+extern "C" int e3dge_aln_conv_dgrad(float* gx, const float* gy, const float* w, const float* add0, const float* add1, float* wfrag,
+                                    int64_t wfrag_floats, int n, int cin, int cout, int height, int width, int ksize, int stride, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(gx && gy && w && wfrag, "aln_conv_dgrad: null pointer");
+    ALN_REQUIRE_CONV("aln_conv_dgrad");
+    const int64_t floats = (int64_t)ig_mpad(cin) * ig_kpad(cout * ksize * ksize);
+    E3DGE_REQUIRE(wfrag_floats >= floats, "aln_conv_dgrad: wfrag of %lld floats, %lld needed", (long long)wfrag_floats, (long long)floats);
+    hipStream_t st = as_stream(stream);
+    ig_pack_t(wfrag, w, cin, cout, ksize, 1.0f, st);
+    int rc;
+    if ((rc = check_launch("aln_conv_dgrad(pack)"))) return rc;
+    return aln_dgrad({gx, gy, wfrag, add0, add1, n, cin, cout, height, width, ksize, stride}, st);
+}
+
+extern "C" int64_t e3dge_aln_wgrad_ws_floats(int n, int cin, int cout, int height, int width, int ksize, int stride) {
+    if (n < 1 || n > 256 || cin < 1 || cin > 4096 || cout < 1 || cout > kAlnMaxCout || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) ||
+        height < 1 || width < 1 || height > 1024 || width > 1024) {
+        fail(E3DGE_ERR_INVALID_ARG, "aln_wgrad_ws_floats: n=%d (1..256) cin=%d (1..4096) cout=%d (1..64) height=%d width=%d (1..1024) ksize=%d (1 or 3) "
+             "stride=%d (1 or 2)", n, cin, cout, height, width, ksize, stride);
+        return -1;
+    }
+    return aln_wgrad_ws_floats(n, cin, cout, height, width, ksize, stride);
+}
+
+extern "C" int e3dge_aln_conv_wgrad(float* dw, const float* gy, const float* in0, const float* in1, const float* in_ab, float* ws, int64_t ws_floats,
+                                    int n, int cin, int split, int up4, int cout, int height, int width, int ksize, int stride,
+                                    e3dge_stream_t stream) {
+    E3DGE_REQUIRE(dw && gy && ws, "aln_conv_wgrad: null pointer");
+    ALN_REQUIRE_CONV("aln_conv_wgrad");
+    E3DGE_REQUIRE(split >= 0 && split <= cin, "aln_conv_wgrad: split=%d outside [0, cin=%d]", split, cin);
+    E3DGE_REQUIRE((split == 0 || in0) && (split == cin || in1), "aln_conv_wgrad: null pointer (a source with channels)");
+    E3DGE_REQUIRE(up4 == 0 || (up4 == 1 && height % 4 == 0 && width % 4 == 0), "aln_conv_wgrad: up4=%d at %d x %d (0, or 1 at multiples of 4)", up4, height,
+                  width);
+    const int64_t floats = aln_wgrad_ws_floats(n, cin, cout, height, width, ksize, stride);
+    E3DGE_REQUIRE(ws_floats >= floats, "aln_conv_wgrad: workspace of %lld floats, %lld needed", (long long)ws_floats, (long long)floats);
+    return aln_wgrad({dw, gy, in0, in1, in_ab, ws, n, cin, split, up4, cout, height, width, ksize, stride}, as_stream(stream));
+}
+
+// ---- the trainable form of the network (aligner_train.h) ---------------------------------------------------------------------------------------
+extern "C" int64_t e3dge_aligner_saved_bytes(int n) {
+    AlnSaved d;
+    if (!aln_saved(n, &d)) {
+        fail(E3DGE_ERR_INVALID_ARG, "aligner_saved_bytes: n=%d (1..256)", n);
+        return -1;
+    }
+    return d.total_bytes;
+}
+
+extern "C" int64_t e3dge_aligner_bwd_workspace_bytes(int n) {
+    AlnBwdWs d;
+    if (!aln_bwd_ws(n, &d)) {
+        fail(E3DGE_ERR_INVALID_ARG, "aligner_bwd_workspace_bytes: n=%d (1..256)", n);
+        return -1;
+    }
+    return d.total_bytes;
+}
+
+extern "C" int64_t e3dge_aligner_grad_floats(void) { return aln_net().goff[kAlnSources]; }
+extern "C" int64_t e3dge_aligner_grad_offset(int source) {
+    if (source < 0 || source > kAlnSources) {
+        fail(E3DGE_ERR_INVALID_ARG, "aligner_grad_offset: source=%d (0..%d)", source, kAlnSources);
+        return -1;
+    }
+    return aln_net().goff[source];
+}
+extern "C" int64_t e3dge_aligner_stats_channels(void) { return aln_net().channels; }
+extern "C" int64_t e3dge_aligner_packed_t_floats(void) { return aln_net().t_total; }
+
+extern "C" int64_t e3dge_aligner_branch_count(int n) {
+    if (n < 1 || n > 256) {
+        fail(E3DGE_ERR_INVALID_ARG, "aligner_branch_count: n=%d (1..256)", n);
+        return -1;
+    }
+    int64_t per = (int64_t)kAlnStem * kAlnSize * kAlnSize;
+    for (int u = 0; u < kAlnUnits; ++u) {
+        int64_t S = kAlnStageSize[u / 3];
+        for (int v = u / 3 * 3; v < u; ++v) S /= kAlnUnit[v].stride;
+        per += kAlnUnit[u].depth * S * S;
+    }
+    return n * per;
+}
+
+extern "C" int e3dge_aligner_pack_t(float* packed_t, int64_t packed_t_floats, const float* const* src, int n_src, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(packed_t && src, "aligner_pack_t: null pointer");
+    const AlnNet& net = aln_net();
+    E3DGE_REQUIRE(packed_t_floats >= net.t_total, "aligner_pack_t: packed buffer of %lld floats, %lld needed", (long long)packed_t_floats,
+                  (long long)net.t_total);
+    E3DGE_REQUIRE(n_src == kAlnSources, "aligner_pack_t: n_src=%d, %d source tensors expected", n_src, kAlnSources);
+    for (int i = 0; i < n_src; ++i) E3DGE_REQUIRE(src[i], "aligner_pack_t: null pointer (source %d)", i);
+    hipStream_t st = as_stream(stream);
+    ig_pack_t(packed_t + net.t_stem, src[net.stem_w], kAlnIn, kAlnStem, 3, 1.0f, st);
+    for (int u = 0; u < kAlnUnits; ++u) {
+        const AlnUnit q = kAlnUnit[u];
+        ig_pack_t(packed_t + net.t_w1[u], src[net.u[u].w1], q.cin, q.depth, 3, 1.0f, st);
+        ig_pack_t(packed_t + net.t_w2[u], src[net.u[u].w2], q.depth, q.depth, 3, 1.0f, st);
+        if (q.cin != q.depth) ig_pack_t(packed_t + net.t_wsc[u], src[net.u[u].wsc], q.cin, q.depth, 1, 1.0f, st);
+    }
+    return check_launch("aligner_pack_t");
+}
+
+extern "C" int e3dge_aligner_forward_saving(const E3dgeAlignerSaveArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "aligner_forward_saving: null argument struct");
+    const E3dgeAlignerSaveArgs& a = *args;
+    E3DGE_REQUIRE(a.n >= 1 && a.n <= 256, "aligner_forward_saving: n=%d (1..256)", a.n);
+    E3DGE_REQUIRE(a.size == kAlnSize, "aligner_forward_saving: size=%d (the network's up-samplings are fixed: 256)", a.size);
+    E3DGE_REQUIRE(a.split >= 0 && a.split <= kAlnIn, "aligner_forward_saving: split=%d (0..6)", a.split);
+    E3DGE_REQUIRE(a.thumb_up4 == 0 || a.thumb_up4 == 1, "aligner_forward_saving: thumb_up4=%d (0 or 1)", a.thumb_up4);
+    E3DGE_REQUIRE(a.train == 0 || a.train == 1, "aligner_forward_saving: train=%d (0 or 1)", a.train);
+    E3DGE_REQUIRE(a.packed && a.out && a.saved && (a.split == 0 || a.res_gt) && (a.split == kAlnIn || a.thumb) && (!a.train || (a.stats && a.src)),
+                  "aligner_forward_saving: null pointer");
+    E3DGE_REQUIRE(!a.train || a.n_src == kAlnSources, "aligner_forward_saving: n_src=%d, %d source tensors expected", a.n_src, kAlnSources);
+    if (a.train)
+        for (int i = 0; i < a.n_src; ++i) E3DGE_REQUIRE(a.src[i], "aligner_forward_saving: null pointer (source %d)", i);
+    const AlnLayout& l = aln_layout();
+    const AlnNet& net = aln_net();
+    E3DGE_REQUIRE(a.packed_floats >= l.total, "aligner_forward_saving: packed buffer of %lld floats, %lld needed", (long long)a.packed_floats,
+                  (long long)l.total);
+    E3DGE_REQUIRE(!a.train || a.stats_doubles >= 2 * (int64_t)net.channels, "aligner_forward_saving: stats of %lld doubles, %lld needed",
+                  (long long)a.stats_doubles, (long long)(2 * net.channels));
+    AlnRun r;
+    E3DGE_REQUIRE(aln_saved(a.n, &r.lay), "aligner_forward_saving: n=%d", a.n);
+    E3DGE_REQUIRE(a.saved_bytes >= r.lay.total_bytes, "aligner_forward_saving: saved state of %lld bytes, %lld needed", (long long)a.saved_bytes,
+                  (long long)r.lay.total_bytes);
+    r.n = a.n; r.train = a.train; r.P = a.packed; r.src = a.src; r.S = static_cast<float*>(a.saved); r.stats = a.stats; r.st = as_stream(stream);
+    const int n = a.n, S = kAlnSize;
+    float* c0 = r.S + r.lay.c0;
+    float* feat1 = r.S + r.lay.feat1;
+    float* feat[4] = {feat1, r.S + r.lay.y[2], r.S + r.lay.y[5], r.S + r.lay.y[8]};
+    float* dfea[2] = {r.S + r.lay.y[11], r.S + r.lay.y[14]};
+    float* up[3] = {r.S + r.lay.up[0], r.S + r.lay.up[1], r.S + r.lay.up[2]};
+    int rc;
+    if ((rc = aln_conv({c0, a.res_gt, a.thumb, r.P + l.stem_w, nullptr, nullptr, nullptr, nullptr, n, kAlnIn, a.split, a.thumb_up4, kAlnStem, S, S, 3, 1, kAlnScNone},
+                       r.st)))
+        return rc;
+    if ((rc = r.batch_stats(net.stem_bn, c0, nullptr, kAlnStem, S * S))) return rc;
+    if ((rc = aln_apply(feat1, c0, r.ab(net.stem_bn, l.stem_bn), r.P + l.stem_prelu, nullptr, nullptr, n, kAlnStem, S, S, S, S, 1, kAlnScNone, r.st))) return rc;
+    if ((rc = aln_stage_saving(r, feat[1], feat[0], nullptr, 16, 0, S))) return rc;
+    if ((rc = aln_stage_saving(r, feat[2], feat[1], nullptr, 32, 3, S / 2))) return rc;
+    if ((rc = aln_stage_saving(r, feat[3], feat[2], nullptr, 48, 6, S / 4))) return rc;
+    if ((rc = aln_up2(up[0], feat[3], (int64_t)n * 64, S / 8, S / 8, r.st))) return rc;
+    if ((rc = aln_stage_saving(r, dfea[0], up[0], feat[2], 64, 9, S / 4))) return rc;
+    if ((rc = aln_up2(up[1], dfea[0], (int64_t)n * 32, S / 4, S / 4, r.st))) return rc;
+    if ((rc = aln_stage_saving(r, dfea[1], up[1], feat[1], 32, 12, S / 2))) return rc;
+    if ((rc = aln_up2(up[2], dfea[1], (int64_t)n * 16, S / 2, S / 2, r.st))) return rc;
+    if ((rc = aln_stage_saving(r, a.out, up[2], feat[0], 16, 15, S))) return rc;
+    const float* tap_src[kAlnTaps] = {feat[0], feat[1], feat[2], feat[3], dfea[0], dfea[1], a.out};
+    const int64_t tap_floats[kAlnTaps] = {16LL * S * S, 32LL * S * S / 4, 48LL * S * S / 16, 64LL * S * S / 64, 32LL * S * S / 16, 16LL * S * S / 4, 3LL * S * S};
+    bool copied = false;
+    for (int i = 0; i < kAlnTaps; ++i)
+        if (a.taps[i]) { ig_copy(a.taps[i], tap_src[i], n * tap_floats[i], 1.0f, 0, r.st); copied = true; }
+    return copied ? check_launch("aligner_forward_saving(tap)") : E3DGE_OK;
+}
+
+extern "C" int e3dge_aligner_backward(const E3dgeAlignerBwdArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "aligner_backward: null argument struct");
+    const E3dgeAlignerBwdArgs& a = *args;
+    E3DGE_REQUIRE(a.n >= 1 && a.n <= 256, "aligner_backward: n=%d (1..256)", a.n);
+    E3DGE_REQUIRE(a.size == kAlnSize, "aligner_backward: size=%d (the network's up-samplings are fixed: 256)", a.size);
+    E3DGE_REQUIRE(a.split >= 0 && a.split <= kAlnIn, "aligner_backward: split=%d (0..6)", a.split);
+    E3DGE_REQUIRE(a.thumb_up4 == 0 || a.thumb_up4 == 1, "aligner_backward: thumb_up4=%d (0 or 1)", a.thumb_up4);
+    E3DGE_REQUIRE(a.train == 0 || a.train == 1, "aligner_backward: train=%d (0 or 1)", a.train);
+    E3DGE_REQUIRE(a.want_input == 0 || a.want_input == 1, "aligner_backward: want_input=%d (0 or 1)", a.want_input);
+    E3DGE_REQUIRE(a.packed && a.packed_t && a.src && a.want && a.g_out && a.saved && a.ws && (a.split == 0 || a.res_gt) && (a.split == kAlnIn || a.thumb) &&
+                      (!a.train || a.stats),
+                  "aligner_backward: null pointer");
+    E3DGE_REQUIRE(!a.want_input || ((a.split == 0 || a.d_res_gt) && (a.split == kAlnIn || a.d_thumb)), "aligner_backward: null pointer (an input gradient)");
+    E3DGE_REQUIRE(a.n_src == kAlnSources, "aligner_backward: n_src=%d, %d source tensors expected", a.n_src, kAlnSources);
+    const AlnLayout& l = aln_layout();
+    const AlnNet& net = aln_net();
+    bool any = false;
+    for (int i = 0; i < a.n_src; ++i) {
+        E3DGE_REQUIRE(a.src[i], "aligner_backward: null pointer (source %d)", i);
+        any = any || a.want[i];
+    }
+    E3DGE_REQUIRE(!any || a.grads, "aligner_backward: null pointer (the gradient buffer)");
+    E3DGE_REQUIRE(!any || a.grad_floats >= net.goff[kAlnSources], "aligner_backward: gradient buffer of %lld floats, %lld needed", (long long)a.grad_floats,
+                  (long long)net.goff[kAlnSources]);
+    E3DGE_REQUIRE(a.packed_floats >= l.total && a.packed_t_floats >= net.t_total, "aligner_backward: packed buffers of %lld and %lld floats, %lld and %lld needed",
+                  (long long)a.packed_floats, (long long)a.packed_t_floats, (long long)l.total, (long long)net.t_total);
+    AlnBwdRun r;
+    E3DGE_REQUIRE(aln_saved(a.n, &r.lay) && aln_bwd_ws(a.n, &r.ws), "aligner_backward: n=%d", a.n);
+    E3DGE_REQUIRE(a.saved_bytes >= r.lay.total_bytes, "aligner_backward: saved state of %lld bytes, %lld needed", (long long)a.saved_bytes,
+                  (long long)r.lay.total_bytes);
+    E3DGE_REQUIRE(a.ws_bytes >= r.ws.total_bytes, "aligner_backward: workspace of %lld bytes, %lld needed", (long long)a.ws_bytes, (long long)r.ws.total_bytes);
+    r.n = a.n; r.train = a.train; r.want_input = a.want_input; r.P = a.packed; r.T = a.packed_t; r.src = a.src; r.want = a.want;
+    r.S = static_cast<const float*>(a.saved); r.stats = a.stats; r.W = static_cast<float*>(a.ws); r.grads = a.grads; r.st = as_stream(stream);
+    const int n = a.n, S = kAlnSize;
+    const float* feat[4] = {r.S + r.lay.feat1, r.S + r.lay.y[2], r.S + r.lay.y[5], r.S + r.lay.y[8]};
+    const float* up[3] = {r.S + r.lay.up[0], r.S + r.lay.up[1], r.S + r.lay.up[2]};
+    float* gstage = r.W + r.ws.gstage;
+    float* gup = r.W + r.ws.gup;
+    float* skip[3] = {r.W + r.ws.skip[0], r.W + r.ws.skip[1], r.W + r.ws.skip[2]};
+    int rc;
+    auto up_bwd = [&](int64_t planes, int h) {
+        const int64_t total = planes * h * h;
+        aln_up2_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, r.st>>>(gstage, gup, h, h, total);
+        return check_launch("aln(up2_bwd)");
+    };
+    if ((rc = aln_stage_bwd(r, gup, skip[0], a.g_out, up[2], feat[0], 16, 15, S, nullptr))) return rc;
+    if ((rc = up_bwd((int64_t)n * 16, S / 2))) return rc;
+    if ((rc = aln_stage_bwd(r, gup, skip[1], gstage, up[1], feat[1], 32, 12, S / 2, nullptr))) return rc;
+    if ((rc = up_bwd((int64_t)n * 32, S / 4))) return rc;
+    if ((rc = aln_stage_bwd(r, gup, skip[2], gstage, up[0], feat[2], 64, 9, S / 4, nullptr))) return rc;
+    if ((rc = up_bwd((int64_t)n * 64, S / 8))) return rc;
+    if ((rc = aln_stage_bwd(r, gstage, nullptr, gstage, feat[2], nullptr, 48, 6, S / 4, skip[2]))) return rc;
+    if ((rc = aln_stage_bwd(r, gstage, nullptr, gstage, feat[1], nullptr, 32, 3, S / 2, skip[1]))) return rc;
+    if ((rc = aln_stage_bwd(r, gstage, nullptr, gstage, feat[0], nullptr, 16, 0, S, skip[0]))) return rc;
+    // conv_layer1: PReLU (in place; its pre-activation is the BatchNorm's output), BatchNorm, convolution
+    const float* c0 = r.S + r.lay.c0;
+    float* gc0 = r.W + r.ws.gc2;
+    if ((rc = aln_prelu_bwd(gstage, r.grad(net.stem_prelu), gstage, c0, r.ab(net.stem_bn, l.stem_bn), a.src[net.stem_prelu], r.norm_ws(), n, kAlnStem, S * S,
+                            r.st)))
+        return rc;
+    if ((rc = r.norm_bwd(net.stem_bn, gc0, nullptr, 0, gstage, c0, nullptr, kAlnStem, nullptr, nullptr, S * S))) return rc;
+    if (a.want[net.stem_w] &&
+        (rc = aln_wgrad({r.grad(net.stem_w), gc0, a.res_gt, a.thumb, nullptr, r.W + r.ws.wg, n, kAlnIn, a.split, a.thumb_up4, kAlnStem, S, S, 3, 1}, r.st)))
+        return rc;
+    if (a.want_input) {
+        AlnDgrad d{a.d_res_gt, gc0, r.T + net.t_stem, nullptr, nullptr, n, kAlnIn, kAlnStem, S, S, 3, 1};
+        float* second = a.thumb_up4 ? r.W + r.ws.d256 : a.d_thumb;
+        if (a.split == 0) d.gx = second;
+        else if (a.split < kAlnIn) { d.gx1 = second; d.gsplit = a.split; }
+        if ((rc = aln_dgrad(d, r.st))) return rc;
+        if (a.thumb_up4 && a.split < kAlnIn) {
+            const int64_t total = (int64_t)n * (kAlnIn - a.split) * (S / 4) * (S / 4);
+            aln_down4_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, r.st>>>(a.d_thumb, second, S / 4, S / 4, total);
+            if ((rc = check_launch("aln(down4)"))) return rc;
+        }
+    }
+    return E3DGE_OK;
+}
+
+extern "C" int e3dge_aligner_branch_bytes(uint8_t* out, int64_t out_bytes, const float* packed, int64_t packed_floats, const void* saved,
+                                          int64_t saved_bytes, int n, int train, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(out && packed && saved, "aligner_branch_bytes: null pointer");
+    E3DGE_REQUIRE(n >= 1 && n <= 256 && (train == 0 || train == 1), "aligner_branch_bytes: n=%d (1..256) train=%d (0 or 1)", n, train);
+    const AlnLayout& l = aln_layout();
+    AlnSaved lay;
+    aln_saved(n, &lay);
+    E3DGE_REQUIRE(packed_floats >= l.total, "aligner_branch_bytes: packed buffer of %lld floats, %lld needed", (long long)packed_floats, (long long)l.total);
+    E3DGE_REQUIRE(saved_bytes >= lay.total_bytes, "aligner_branch_bytes: saved state of %lld bytes, %lld needed", (long long)saved_bytes,
+                  (long long)lay.total_bytes);
+    E3DGE_REQUIRE(out_bytes >= e3dge_aligner_branch_count(n), "aligner_branch_bytes: out of %lld bytes, %lld needed", (long long)out_bytes,
+                  (long long)e3dge_aligner_branch_count(n));
+    hipStream_t st = as_stream(stream);
+    const float* S = static_cast<const float*>(saved);
+    const int hw0 = kAlnSize * kAlnSize;
+    int64_t at = (int64_t)n * kAlnStem * hw0;
+    const float* stem_ab = train ? S + lay.ab + 2 * aln_net().stem_bn.chan : packed + l.stem_bn;
+    aln_branch_kernel<<<dim3(aln_blocks(at)), dim3(256), 0, st>>>(out, S + lay.c0, reinterpret_cast<const float2*>(stem_ab), kAlnStem, hw0, at);
+    for (int u = 0; u < kAlnUnits; ++u) {
+        int64_t sz = kAlnStageSize[u / 3];
+        for (int v = u / 3 * 3; v < u; ++v) sz /= kAlnUnit[v].stride;
+        const int64_t total = (int64_t)n * kAlnUnit[u].depth * sz * sz;
+        aln_branch_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(out + at, S + lay.c1[u], nullptr, kAlnUnit[u].depth, (int)(sz * sz), total);
+        at += total;
+    }
+    return check_launch("aligner_branch_bytes");
 }

@@ -1480,7 +1480,7 @@ int e3dge_enc_head_tail(float* out, const float* in, const float* conv_w, const 
  * atomics; bit-reproducible, and an image's results do not depend on its position in the batch or on the batch size.  Replaces
  * ResidualAligner.forward (project/models/helper_modules/alignment_old.py:316-398) with aligner_norm_type 'batch' (BatchNorm on its
  * running statistics, eps 1e-5) and no demodulation: conv_layer1, the 18 bottleneck_IR units of conv_layer2-4 and dconv_layer1-3 and
- * the three bilinear x2 up-samplings.  fp32.  No backward.  The network's up-sampling sizes are fixed: the input is 256 x 256.
+ * the three bilinear x2 up-samplings.  fp32.  The backward and the train form: the two blocks below.  The up-sampling sizes are fixed: 256 x 256.
  *
  * Source tensors, in this order (BN = weight, bias, running_mean, running_var): conv_layer1.0.weight, BN conv_layer1.1,
  * conv_layer1.2.weight; per unit of conv_layer2, 3, 4, dconv_layer1, 2, 3 (three each): BN res_layer.0, res_layer.1.weight,
@@ -1530,6 +1530,146 @@ int e3dge_aln_conv(float* out, const float* in0, const float* in1, const float* 
                    const float* shortcut, float* wfrag, int64_t wfrag_floats, int n, int cin, int split, int up4, int cout, int height,
                    int width, int ksize, int stride, int shortcut_mode, e3dge_stream_t stream);
 int e3dge_aln_up2(float* out, const float* in, int64_t planes, int height, int width, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The 2-D residual aligner, trainable form: its kernels (csrc/aligner_bwd.h), each through a debug entry at run-time shapes.
+ * Additions to ABI 17.  The network's forward with saved state and its backward (next block) are composed of them.  fp32 tensors; every per-channel sum in float64, partial sums
+ * per (image, segment of 4096 pixels) folded in ascending order: no atomics, bit-reproducible.  n 1..256, channels 1..4096, height and
+ * width 1..1024, at most 2^31 elements per tensor.  Every entry fails before any launch on a null pointer ("null"), a value out of
+ * range or a workspace that is too small ("workspace").
+ *
+ * e3dge_aln_norm_ws_bytes   workspace bytes of e3dge_aln_bn_stats, e3dge_aln_norm_bwd and e3dge_aln_prelu_bwd for (n, channels, height,
+ *                           width) tensors (-1: a value out of range).
+ * e3dge_aln_bn_stats        BatchNorm2d's batch statistics of the `channels` channels of which `split` come from in0 (n, split, height,
+ *                           width) and the rest from in1 (n, channels - split, height, width): stats (channels, 2) float64 = (mean,
+ *                           biased variance); ab (channels, 2) = (gamma rstd, beta - mean gamma rstd) with rstd = 1 / sqrt(var + 1e-5),
+ *                           computed in float64 and rounded once -- the in_ab / epi_ab pair of e3dge_aln_conv and the ab of
+ *                           e3dge_aln_bn_apply.  Either output may be NULL (ab needs gamma and beta).  n height width >= 2.  Two launches.
+ * e3dge_aln_bn_apply        out = ab[c].a in + ab[c].b, then PReLU (slope (channels), NULL: none), then the shortcut, added after that
+ *                           rounding: shortcut_mode 0 none, 1 + shortcut[:, :, ::stride, ::stride] of a (n, channels, shortcut_height,
+ *                           shortcut_width) tensor, 2 + a tensor of the output's shape, 3 + shortcut_ab[c].a shortcut + shortcut_ab[c].b
+ *                           (the raw 1x1 branch under its own BatchNorm).  The arithmetic of e3dge_aln_conv's epilogue.  One launch.
+ * e3dge_aln_norm_bwd        BatchNorm2d's backward at the input x (the two sources as above) and the incoming gy (n, channels, height,
+ *                           width): dbeta = P = sum gy, dgamma = Q = sum gy xhat with xhat = (x - mean) rstd, gx = A gy + B x + C + add
+ *                           in float64, rounded once (add: a tensor of gx's shape, NULL: none).  train 1: batch statistics from `stats`
+ *                           (e3dge_aln_bn_stats), A = gamma rstd, B = -A Q rstd / M, C = -A P / M - B mean, M = n height width.  train
+ *                           0: running_mean / running_var, B = C = 0.  gx, dgamma, dbeta: each may be NULL (not all); with train 0 and
+ *                           neither parameter gradient wanted the sums are not launched and x is not read.  At most three launches.
+ * e3dge_aln_prelu_bwd       gx = pre > 0 ? gy : slope[c] gy, dslope[c] = sum of gy pre over pre <= 0 (float64), from the saved
+ *                           pre-activation `pre`.  gx or dslope may be NULL; ws is needed for dslope.  One or two launches.
+ * e3dge_aln_up2_bwd         the adjoint of e3dge_aln_up2: gx (planes, height, width) from gy (planes, 2 height, 2 width), a gather with the
+ *                           forward's own weights, float64 sum, one rounding.
+ * e3dge_aln_pick_bwd        the adjoint of x[:, :, ::stride, ::stride]: gx (planes, height, width) = add + (gy at (y / stride, x / stride)
+ *                           where both are multiples of stride, else 0), gy (planes, (height - 1) / stride + 1, (width - 1) / stride + 1);
+ *                           add may be NULL.
+ * e3dge_aln_conv_dgrad      the data gradient of e3dge_aln_conv's convolution: gx (n, cin, height, width) from gy (n, cout, oh, ow) and
+ *                           w (cout, cin, ksize, ksize), cout 1..64; aln_conv_kernel's GEMM on the transposed, tap-flipped image with
+ *                           M = cin (four channel tiles per launch: cin 112 takes two), stride 2 as a parity predicate of the gather.
+ *                           gx = sum + add0 + add1, in that order: add0 / add1 fan-in addends of gx's shape; each may be NULL.  wfrag:
+ *                           scratch of roundup(cin, 16) * roundup(cout ksize^2, 32) floats.
+ * e3dge_aln_wgrad_ws_floats workspace floats of e3dge_aln_conv_wgrad: one (cout, cin ksize^2) partial per image and segment of 1024
+ *                           output pixels (-1: a value out of range).
+ * e3dge_aln_conv_wgrad      the weight gradient of that convolution: dw (cout, cin, ksize, ksize) = sum over images and output pixels
+ *                           of gy times the forward's own gather of (in0 | in1) (zero padding, in_ab on in-image elements only, the x4
+ *                           read with up4); fp32 MFMA partials per image and segment, folded in float64, images then segments ascending.
+ *                           Two launches.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int64_t e3dge_aln_norm_ws_bytes(int n, int channels, int height, int width);
+int e3dge_aln_bn_stats(float* ab, double* stats, const float* in0, const float* in1, const float* gamma, const float* beta, void* ws,
+                       int64_t ws_bytes, int n, int channels, int split, int height, int width, e3dge_stream_t stream);
+int e3dge_aln_bn_apply(float* out, const float* in, const float* ab, const float* slope, const float* shortcut, const float* shortcut_ab, int n,
+                       int channels, int height, int width, int shortcut_height, int shortcut_width, int stride, int shortcut_mode,
+                       e3dge_stream_t stream);
+int e3dge_aln_norm_bwd(float* gx, float* dgamma, float* dbeta, const float* gy, const float* in0, const float* in1, const float* gamma,
+                       const double* stats, const float* running_mean, const float* running_var, const float* add, void* ws, int64_t ws_bytes,
+                       int n, int channels, int split, int height, int width, int train, e3dge_stream_t stream);
+int e3dge_aln_prelu_bwd(float* gx, float* dslope, const float* gy, const float* pre, const float* slope, void* ws, int64_t ws_bytes, int n,
+                        int channels, int height, int width, e3dge_stream_t stream);
+int e3dge_aln_up2_bwd(float* gx, const float* gy, int64_t planes, int height, int width, e3dge_stream_t stream);
+int e3dge_aln_pick_bwd(float* gx, const float* gy, const float* add, int64_t planes, int height, int width, int stride, e3dge_stream_t stream);
+int e3dge_aln_conv_dgrad(float* gx, const float* gy, const float* w, const float* add0, const float* add1, float* wfrag,
+                         int64_t wfrag_floats, int n, int cin, int cout, int height, int width, int ksize, int stride, e3dge_stream_t stream);
+int64_t e3dge_aln_wgrad_ws_floats(int n, int cin, int cout, int height, int width, int ksize, int stride);
+int e3dge_aln_conv_wgrad(float* dw, const float* gy, const float* in0, const float* in1, const float* in_ab, float* ws, int64_t ws_floats, int n,
+                         int cin, int split, int up4, int cout, int height, int width, int ksize, int stride, e3dge_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The 2-D residual aligner, trainable form: the network (csrc/aligner_train.h).  Additions to ABI 17.  One forward that keeps what the
+ * backward needs, and the backward, on HIP launches only; the eval form (BatchNorm on its running statistics) and the train form (batch
+ * statistics).  No allocation, no synchronisation, no atomics; bit-reproducible.  Source tensors and their order: e3dge_aligner_pack.
+ *
+ * e3dge_aligner_saved_bytes          bytes of the saved state for n images (-1: bad n): every convolution's raw sums, the PReLU outputs, the
+ *                                    unit outputs and the three up-sampled maps, plus per call the (a, b) pairs of the batch statistics.
+ * e3dge_aligner_bwd_workspace_bytes  workspace bytes of e3dge_aligner_backward for n images (-1: bad n).
+ * e3dge_aligner_grad_floats          floats of the gradient buffer: one slot per source tensor in the source order, each of the tensor's
+ *                                    size and shape.  The slots of running_mean / running_var are never written.
+ * e3dge_aligner_grad_offset          offset of source tensor `source` (0..E3DGE_ALIGNER_SOURCES: the total) in that buffer (-1: out of range).
+ * e3dge_aligner_stats_channels       BatchNorm channels in all: the statistics buffer holds (mean, biased variance) float64 pairs per
+ *                                    channel, BatchNorms in source order.
+ * e3dge_aligner_packed_t_floats, e3dge_aligner_pack_t   the transposed, tap-flipped A-fragment images of every convolution (the data
+ *                                    gradients' operand); re-run after a weight update, like e3dge_aligner_pack.
+ * e3dge_aligner_branch_count         PReLU input elements of n images: the 19 PReLUs in launch order (-1: bad n).
+ * e3dge_aligner_forward_saving       e3dge_aligner_forward's arguments and results (out and taps bit for bit in the eval form) plus the saved
+ *                                    state.  Every convolution writes its raw sums and an apply launch does the epilogue's arithmetic; with
+ *                                    train 1 a statistics launch pair runs between them and `stats` (2 * stats_channels float64) receives
+ *                                    every BatchNorm's batch mean and biased variance (src is read for gamma and beta: needed with train 1).
+ *                                    Running buffers are not touched: the caller updates them from `stats`.
+ * e3dge_aligner_backward             from g_out (n, 3, 256, 256), the saved state, the inputs and (train 1) `stats` of that forward:
+ *                                    d_res_gt / d_thumb in the inputs' shapes with want_input (a 64^2 thumb read at nearest x4 gets the
+ *                                    float64 sum of its 4 x 4 block, rows then columns ascending), and the gradient of every source tensor i
+ *                                    with want[i] != 0 (HOST array of n_src bytes) at its slot of `grads`.  The weight gradient, slope and
+ *                                    (eval form) BatchNorm sum launches of unwanted tensors do not run, nor the stem's data gradient without
+ *                                    want_input; the data gradient chain above the stem always runs.
+ * e3dge_aligner_branch_bytes         debug: one byte per PReLU input element of the saved state (1: positive), the 19 PReLUs in launch order
+ *                                    (conv_layer1, then every unit's), each (n, channels, h, w).
+ * Each entry fails before any launch on a null pointer ("null"), n out of range, a size other than 256, a bad split or flag, and a packed
+ * ("packed"), saved ("saved"), statistics ("stats"), gradient ("gradient") or workspace ("workspace") buffer that is too small.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct E3dgeAlignerSaveArgs {
+    const float* packed;              /* e3dge_aligner_pack */
+    int64_t packed_floats;
+    const float* const* src;          /* HOST array of n_src device pointers (train 1) */
+    int32_t n_src, train;
+    const float* res_gt; const float* thumb;
+    int32_t n, size, split, thumb_up4;
+    float* out;
+    float* taps[E3DGE_ALIGNER_TAPS];
+    void* saved;
+    int64_t saved_bytes;
+    double* stats;
+    int64_t stats_doubles;
+} E3dgeAlignerSaveArgs;
+typedef struct E3dgeAlignerBwdArgs {
+    const float* packed;              /* e3dge_aligner_pack */
+    int64_t packed_floats;
+    const float* packed_t;            /* e3dge_aligner_pack_t */
+    int64_t packed_t_floats;
+    const float* const* src;          /* HOST array of n_src device pointers */
+    const uint8_t* want;              /* HOST array of n_src flags */
+    int32_t n_src, train;
+    const float* res_gt; const float* thumb; const float* g_out;
+    int32_t n, size, split, thumb_up4, want_input, reserved;
+    const void* saved;
+    int64_t saved_bytes;
+    const double* stats;
+    float* d_res_gt; float* d_thumb;
+    float* grads;
+    int64_t grad_floats;
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeAlignerBwdArgs;
+int64_t e3dge_aligner_saved_bytes(int n);
+int64_t e3dge_aligner_bwd_workspace_bytes(int n);
+int64_t e3dge_aligner_grad_floats(void);
+int64_t e3dge_aligner_grad_offset(int source);
+int64_t e3dge_aligner_stats_channels(void);
+int64_t e3dge_aligner_packed_t_floats(void);
+int64_t e3dge_aligner_branch_count(int n);
+int e3dge_aligner_pack_t(float* packed_t, int64_t packed_t_floats, const float* const* src, int n_src, e3dge_stream_t stream);
+int e3dge_aligner_forward_saving(const E3dgeAlignerSaveArgs* args, e3dge_stream_t stream);
+int e3dge_aligner_backward(const E3dgeAlignerBwdArgs* args, e3dge_stream_t stream);
+int e3dge_aligner_branch_bytes(uint8_t* out, int64_t out_bytes, const float* packed, int64_t packed_floats, const void* saved, int64_t saved_bytes,
+                               int n, int train, e3dge_stream_t stream);
 
 #ifdef __cplusplus
 }
