@@ -37,7 +37,27 @@ STAGES = {                                                         # (in, depth,
     "dconv_layer3": ((32, 16, 1), (16, 3, 1), (3, 3, 1)),
 }
 TAPS = ("feat1", "feat2", "feat3", "feat4", "dfea1", "dfea2", "dfea3")       # every stage's output, before its up-sampling
-TAP_SHAPES = ((16, 256), (32, 128), (48, 64), (64, 32), (32, 64), (16, 128), (3, 256))
+
+
+def _walk():
+    """One walk of STAGES with the sizes it implies (a dconv stage runs on the up-sampled map): the (channels, size) of every tap, and of
+    every BatchNorm in the order of ResidualAligner.sources() a getter from the module and the H W of its input."""
+    taps, size = [(16, SIZE)], SIZE
+    norms = [(lambda m: m.conv_layer1[1], size * size)]
+    for name, units in STAGES.items():
+        size *= 2 if name.startswith("dconv") else 1
+        for i, (cin, depth, stride) in enumerate(units):
+            out = size // stride
+            norms += [(lambda m, name=name, i=i: getattr(m, name)[i].res_layer[0], size * size),
+                      (lambda m, name=name, i=i: getattr(m, name)[i].res_layer[4], out * out)]
+            if cin != depth:
+                norms.append((lambda m, name=name, i=i: getattr(m, name)[i].shortcut_layer[1], out * out))
+            size = out
+        taps.append((units[-1][1], size))
+    return tuple(taps), tuple(norms)
+
+
+TAP_SHAPES, _NORMS = _walk()
 
 
 class DemodulatedConv2d(nn.Module):
@@ -156,24 +176,12 @@ class ResidualAligner(nn.Module):
 
     def _runs_hip(self, *inputs):
         """inputs: the 6-channel tensor, or (res_gt, thumb) with 3 channels each and a 64^2 or 256^2 thumb."""
-        if os.environ.get("E3DGE_ALIGNER", "") == "torch" or self.training or not self.native_options():
-            return False
-        channels = 0
-        for i, t in enumerate(inputs):
-            if not (torch.is_tensor(t) and t.device.type == "cuda" and t.dtype == torch.float32 and t.ndim == 4):
-                return False
-            if t.device != inputs[0].device or t.shape[0] != inputs[0].shape[0] or t.shape[0] < 1 or t.shape[0] > 256:
-                return False
-            sizes = ((SIZE, SIZE), (SIZE // 4, SIZE // 4)) if i == 1 else ((SIZE, SIZE),)
-            if tuple(t.shape[-2:]) not in sizes:
-                return False
-            channels += t.shape[1]
-        if channels != IN_CHANNELS:
+        if os.environ.get("E3DGE_ALIGNER", "") == "torch" or self.training or not self.native_options() or not self._covers(*inputs):
             return False
         return not (torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or any(p.requires_grad for p in _lib.params_of(self))))
 
     def _covers(self, *inputs):
-        """The device, dtype, shape and batch checks of _runs_hip on the one-tensor or (res_gt, thumb) form."""
+        """The device, dtype, shape and batch checks on the one-tensor or (res_gt, thumb) form."""
         channels = 0
         for i, t in enumerate(inputs):
             if not (torch.is_tensor(t) and t.device.type == "cuda" and t.dtype == torch.float32 and t.ndim == 4):
@@ -202,6 +210,9 @@ class ResidualAligner(nn.Module):
     def sources(self):
         """The source tensors in the order of e3dge_aligner_pack (include/e3dge_hip.h).  The (dict, key) slots are listed once per module
         and looked up per call, so a replaced Parameter is still seen; invalidate() drops the listing (after a sub-module was replaced)."""
+        return [d[k] for d, k in self._slots()]
+
+    def _slots(self):
         slots = self.__dict__.get("_source_slots")
         if slots is None:
             slots = []
@@ -215,17 +226,21 @@ class ResidualAligner(nn.Module):
                     if isinstance(u.shortcut_layer, nn.Sequential):
                         slots += w(u.shortcut_layer[0]) + bn(u.shortcut_layer[1])
             self.__dict__["_source_slots"] = slots
-        return [d[k] for d, k in slots]
+        return slots
+
+    def running_statistic_slots(self):
+        """The positions of the running buffers in sources(): the slots that point into a module's _buffers; listed once."""
+        out = self.__dict__.get("_statistic_slots")
+        if out is None:
+            buffers = {id(m._buffers) for m in self.modules()}
+            out = self.__dict__["_statistic_slots"] = frozenset(i for i, (d, _) in enumerate(self._slots()) if id(d) in buffers)
+        return out
 
     def batch_norms(self):
         """The BatchNorms in the order of sources() (the order of the statistics buffer of e3dge_aligner_forward_saving); listed once."""
         out = self.__dict__.get("_batch_norms")
         if out is None:
-            out = [self.conv_layer1[1]]
-            for name in STAGES:
-                for u in getattr(self, name):
-                    out += [u.res_layer[0], u.res_layer[4]] + ([u.shortcut_layer[1]] if isinstance(u.shortcut_layer, nn.Sequential) else [])
-            self.__dict__["_batch_norms"] = out
+            out = self.__dict__["_batch_norms"] = [get(self) for get, _ in _NORMS]
         return out
 
     def packed(self, device):
@@ -260,8 +275,8 @@ class ResidualAligner(nn.Module):
 
     def invalidate(self):
         """Drop the packed weight images (needed only after writes through `.data`) and the listings of sources() and batch_norms()."""
-        self.__dict__.pop("_source_slots", None)
-        self.__dict__.pop("_batch_norms", None)
+        for listing in ("_source_slots", "_statistic_slots", "_batch_norms"):
+            self.__dict__.pop(listing, None)
         _lib.invalidate(self)
 
     def forward_hip(self, res_gt, thumb=None, taps=None):
@@ -352,7 +367,7 @@ class _AlignerNode(torch.autograd.Function):
             _AlignerNode.branches.append(branch)
         # what the backward reads again of the source tensors: everything but, in the train form, the running statistics (the caller
         # updates those right after this forward; the train form's backward reads the batch statistics instead)
-        read_again = [i for i, p in enumerate(params) if not (train and _is_running_statistic(i))]
+        read_again = [i for i in range(len(params)) if not (train and i in module.running_statistic_slots())]
         ctx.read_again, ctx.offsets = read_again, _sizes(module)[1]
         ctx.save_for_backward(saved, image, image_t, stats, res_gt, *([] if thumb is None else [thumb]), *[params[i] for i in read_again])
         ctx.form = (n, bool(train), thumb is not None, up4, len(params))
@@ -402,27 +417,6 @@ def _sizes(module):
     return _lib.cached(module, "aligner_sizes", (), build)
 
 
-@functools.lru_cache(maxsize=None)
-def _running_statistic_slots():
-    """The positions of running_mean / running_var in ResidualAligner.sources(): the third and fourth tensor of every BatchNorm."""
-    slots, at = set(), 1                                             # conv_layer1.0.weight, then its BatchNorm
-    slots.update((at + 2, at + 3))
-    at += 5                                                          # the BatchNorm's four and conv_layer1.2.weight
-    for units in STAGES.values():
-        for cin, depth, _ in units:
-            slots.update((at + 2, at + 3, at + 9, at + 10))          # res_layer.0; .1, .2, .3; res_layer.4
-            at += 11
-            if cin != depth:
-                slots.update((at + 3, at + 4))                       # shortcut_layer.0; shortcut_layer.1
-                at += 5
-    assert at == _lib.ALIGNER_SOURCES
-    return frozenset(slots)
-
-
-def _is_running_statistic(i):
-    return i in _running_statistic_slots()
-
-
 _TABLES = {}                                                         # (device, momenta, batch) -> the per-channel float64 factors of the buffer update
 
 
@@ -450,13 +444,5 @@ def _update_running_buffers(bns, stats, n):
 
 def _bn_planes(count):
     """H W of every BatchNorm's input, in the order of ResidualAligner.batch_norms()."""
-    out = [SIZE * SIZE]                                              # conv_layer1.1
-    sizes = dict(conv_layer2=SIZE, conv_layer3=SIZE // 2, conv_layer4=SIZE // 4, dconv_layer1=SIZE // 4, dconv_layer2=SIZE // 2, dconv_layer3=SIZE)
-    for name, units in STAGES.items():
-        s = sizes[name]
-        for cin, depth, stride in units:
-            o = s // stride
-            out += [s * s, o * o] + ([o * o] if cin != depth else [])
-            s = o
-    assert len(out) == count
-    return out
+    assert len(_NORMS) == count
+    return [plane for _, plane in _NORMS]

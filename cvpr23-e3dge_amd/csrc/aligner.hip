@@ -36,7 +36,7 @@ namespace e3dge {
 constexpr int kAlnSize = 256, kAlnUnits = 18, kAlnTaps = E3DGE_ALIGNER_TAPS, kAlnSources = E3DGE_ALIGNER_SOURCES, kAlnIn = 6, kAlnStem = 16;
 constexpr int kAlnMaxCout = 64;
 
-struct AlnUnit { int cin, depth, stride; };
+struct AlnUnit { int cin, depth, stride; };                          // the only statement of the units on this side; aln_net() derives the rest
 constexpr AlnUnit kAlnUnit[kAlnUnits] = {{16, 32, 2}, {32, 32, 1}, {32, 32, 1}, {32, 48, 2}, {48, 48, 1}, {48, 48, 1}, {48, 64, 2}, {64, 64, 1}, {64, 64, 1},
                                          {112, 64, 1}, {64, 32, 1}, {32, 32, 1}, {64, 32, 1}, {32, 16, 1}, {16, 16, 1}, {32, 16, 1}, {16, 3, 1}, {3, 3, 1}};
 
@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(256) aln_conv_kernel(AlnConvArgs a) {
     }
 }
 
-static int aln_out_size(int in, int ks, int stride) { return (in + (ks == 3 ? 2 : 0) - ks) / stride + 1; }
+constexpr int aln_out_size(int in, int ks, int stride) { return (in + (ks == 3 ? 2 : 0) - ks) / stride + 1; }
 
 // Pixel tiles per wave: two where 128-pixel workgroups of two images (the evaluation shape) still give every CU one, from the layer alone.
 static int aln_tile_width(int64_t pixels) { return (pixels + 127) / 128 * 2 >= kIgCUs ? 2 : 1; }
@@ -222,13 +222,12 @@ static int aln_up2(float* out, const float* in, int64_t planes, int H, int W, hi
 
 }  // namespace e3dge
 
-// The trainable form (forward with saved state in the eval or the train form, backward with every parameter gradient): aligner_bwd.h (its
-// kernels) here, aligner_train.h (the network) after the packed layout; DESIGN.md 4.17b.
+// The kernels around the convolutions (BatchNorm on batch statistics, every backward) with their launch helpers: aligner_bwd.h.  The network
+// -- its table, its layouts, the forward walk in both forms and the backward walk: aligner_train.h.  DESIGN.md 4.17, 4.17b.
 #include "aligner_bwd.h"
 
 namespace e3dge {
 
-// ---- packed image ------------------------------------------------------------------------------------------------------------------
 // BatchNorm on its running statistics as the pair (a, b) = (gamma / sqrt(var + 1e-5), beta - mean a)
 __global__ void __launch_bounds__(256) aln_pack_bn_kernel(float* __restrict__ dst, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           const float* __restrict__ mean, const float* __restrict__ var, int C) {
@@ -239,176 +238,261 @@ __global__ void __launch_bounds__(256) aln_pack_bn_kernel(float* __restrict__ ds
     dst[2 * c + 1] = __fsub_rn(beta[c], __fmul_rn(mean[c], a));
 }
 
-struct AlnLayout {
-    int64_t stem_w, stem_bn, stem_prelu;
-    int64_t bn0[kAlnUnits], w1[kAlnUnits], prelu[kAlnUnits], w2[kAlnUnits], bn4[kAlnUnits], wsc[kAlnUnits], bnsc[kAlnUnits], total;
-};
-
-static int64_t aln_image_floats(int cin, int cout, int ks) { return (int64_t)ig_mpad(cout) * ig_kpad(cin * ks * ks); }
-
-static const AlnLayout& aln_layout() {
-    static const AlnLayout lay = [] {
-        AlnLayout l{};
-        int64_t off = 0;
-        auto take = [&](int64_t floats) { const int64_t at = off; off += (floats + 63) / 64 * 64; return at; };
-        l.stem_w = take(aln_image_floats(kAlnIn, kAlnStem, 3)); l.stem_bn = take(2 * kAlnStem); l.stem_prelu = take(kAlnStem);
-        for (int u = 0; u < kAlnUnits; ++u) {
-            const AlnUnit q = kAlnUnit[u];
-            l.bn0[u] = take(2 * q.cin); l.w1[u] = take(aln_image_floats(q.cin, q.depth, 3)); l.prelu[u] = take(q.depth);
-            l.w2[u] = take(aln_image_floats(q.depth, q.depth, 3)); l.bn4[u] = take(2 * q.depth);
-            if (q.cin != q.depth) { l.wsc[u] = take(aln_image_floats(q.cin, q.depth, 1)); l.bnsc[u] = take(2 * q.depth); }
-        }
-        l.total = off;
-        return l;
-    }();
-    return lay;
-}
-
-// ---- workspace (floats per image; every block starts on a multiple of 64 floats of the whole) -------------------------------------------
-struct AlnWs { int64_t feat[4], dfea[2], t1, sc, x[2], up, total_bytes; };
-
-static bool aln_ws(int64_t n, AlnWs* d) {
-    if (n < 1 || n > 256) return false;
-    int64_t off = 0;
-    auto take = [&](int64_t floats) { const int64_t at = off; off += (floats + 63) / 64 * 64; return at; };
-    const int64_t P = (int64_t)kAlnSize * kAlnSize;
-    d->feat[0] = take(n * 16 * P); d->feat[1] = take(n * 32 * (P / 4)); d->feat[2] = take(n * 48 * (P / 16)); d->feat[3] = take(n * 64 * (P / 64));
-    d->dfea[0] = take(n * 32 * (P / 16)); d->dfea[1] = take(n * 16 * (P / 4));
-    d->t1 = take(n * 32 * P);                                        // a unit's first convolution: depth channels at the input's size
-    d->sc = take(n * 16 * P);                                        // the 1x1 branch
-    d->x[0] = take(n * 16 * P); d->x[1] = take(n * 16 * P);         // unit outputs inside a stage
-    d->up = take(n * 16 * P);                                        // an up-sampled map
-    d->total_bytes = off * (int64_t)sizeof(float);
-    return true;
-}
-
-// one stage: three units from (in0 | in1 at channel `split`) at size S; the last one writes `out`
-static int aln_stage(float* out, const float* in0, const float* in1, int split, int u0, int S, const float* P, float* ws, const AlnWs& d, int n,
-                     hipStream_t st) {
-    const AlnLayout& l = aln_layout();
-    float* t1 = ws + d.t1;
-    float* sc = ws + d.sc;
-    int rc, size = S;
-    for (int i = 0; i < 3; ++i) {
-        const int u = u0 + i;
-        const AlnUnit q = kAlnUnit[u];
-        const int osize = aln_out_size(size, 3, q.stride);
-        float* y = i == 2 ? out : ws + d.x[i];
-        const bool conv_sc = q.cin != q.depth;
-        if (conv_sc &&
-            (rc = aln_conv({sc, in0, in1, P + l.wsc[u], nullptr, P + l.bnsc[u], nullptr, nullptr, n, q.cin, split, 0, q.depth, size, size, 1, q.stride,
-                            kAlnScNone}, st)))
-            return rc;
-        if ((rc = aln_conv({t1, in0, in1, P + l.w1[u], P + l.bn0[u], nullptr, P + l.prelu[u], nullptr, n, q.cin, split, 0, q.depth, size, size, 3, 1,
-                            kAlnScNone}, st)))
-            return rc;
-        if ((rc = aln_conv({y, t1, nullptr, P + l.w2[u], nullptr, P + l.bn4[u], nullptr, conv_sc ? sc : in0, n, q.depth, q.depth, 0, q.depth, size, size, 3,
-                            q.stride, conv_sc ? kAlnScRead : kAlnScPick}, st)))
-            return rc;
-        in0 = y; in1 = nullptr; split = q.depth;
-        size = osize;
-    }
-    return E3DGE_OK;
-}
-
 }  // namespace e3dge
 
-#include "aligner_train.h"                                          // the trainable form: forward with saved state, backward
+#include "aligner_train.h"
 
 using namespace e3dge;
 
-extern "C" int64_t e3dge_aligner_packed_floats(void) { return aln_layout().total; }
+// ---- argument ranges, each stated once --------------------------------------------------------------------------------------------------
+static bool aln_plane_ok(int n, int channels, int height, int width) {
+    return n >= 1 && n <= 256 && channels >= 1 && channels <= 4096 && height >= 1 && width >= 1 && height <= 1024 && width <= 1024;
+}
+#define ALN_REQUIRE_PLANE(who)                                                                                                                  \
+    E3DGE_REQUIRE(aln_plane_ok(n, channels, height, width) && (int64_t)n * channels * height * width <= ((int64_t)1 << 31),                     \
+                  who ": n=%d (1..256) channels=%d (1..4096) height=%d width=%d (1..1024), at most 2^31 elements", n, channels, height, width)
 
-extern "C" int e3dge_aligner_pack(float* packed, int64_t packed_floats, const float* const* src, int n_src, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(packed && src, "aligner_pack: null pointer");
-    const AlnLayout& l = aln_layout();
-    E3DGE_REQUIRE(packed_floats >= l.total, "aligner_pack: packed buffer of %lld floats, %lld needed", (long long)packed_floats, (long long)l.total);
-    E3DGE_REQUIRE(n_src == kAlnSources, "aligner_pack: n_src=%d, %d source tensors expected", n_src, kAlnSources);
-    for (int i = 0; i < n_src; ++i) E3DGE_REQUIRE(src[i], "aligner_pack: null pointer (source %d)", i);
-    hipStream_t st = as_stream(stream);
-    int at = 0;
-    auto next = [&]() { return src[at++]; };
-    auto conv = [&](int64_t off, int ci, int co, int ks) { ig_pack(packed + off, next(), ci, co, ks, 1.0f, st); };
-    auto copy = [&](int64_t off, int64_t cnt) { ig_copy(packed + off, next(), cnt, 1.0f, 0, st); };
-    auto bn = [&](int64_t off, int ch) {
-        const float* gamma = next(); const float* beta = next(); const float* mean = next(); const float* var = next();
-        aln_pack_bn_kernel<<<dim3((unsigned)((ch + 255) / 256)), dim3(256), 0, st>>>(packed + off, gamma, beta, mean, var, ch);
-    };
-    conv(l.stem_w, kAlnIn, kAlnStem, 3); bn(l.stem_bn, kAlnStem); copy(l.stem_prelu, kAlnStem);
-    for (int u = 0; u < kAlnUnits; ++u) {                             // res_layer.0 .. 4, then the shortcut
-        const AlnUnit q = kAlnUnit[u];
-        bn(l.bn0[u], q.cin); conv(l.w1[u], q.cin, q.depth, 3); copy(l.prelu[u], q.depth); conv(l.w2[u], q.depth, q.depth, 3); bn(l.bn4[u], q.depth);
-        if (q.cin != q.depth) { conv(l.wsc[u], q.cin, q.depth, 1); bn(l.bnsc[u], q.depth); }
-    }
-    return check_launch("aligner_pack");
+static bool aln_planes_ok(int64_t planes, int height, int width, int log2_elements) {
+    return planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024 &&
+           planes * height * width <= ((int64_t)1 << log2_elements);
 }
 
-extern "C" int64_t e3dge_aligner_workspace_bytes(int n) {
-    AlnWs d;
-    if (!aln_ws(n, &d)) {
-        fail(E3DGE_ERR_INVALID_ARG, "aligner_workspace_bytes: n=%d (1..256)", n);
+// 0, or the first clause of a convolution's shape that does not hold
+static int aln_conv_bad(int n, int cin, int cout, int height, int width, int ksize, int stride) {
+    if (!(n >= 1 && n <= 256 && cin >= 1 && cin <= 4096)) return 1;
+    if (!(cout >= 1 && cout <= kAlnMaxCout)) return 2;
+    if (!((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2))) return 3;
+    if (!(height >= 1 && width >= 1 && height <= 1024 && width <= 1024)) return 4;
+    return 0;
+}
+#define ALN_REQUIRE_CONV(who)                                                                                                                   \
+    switch (aln_conv_bad(n, cin, cout, height, width, ksize, stride)) {                                                                         \
+        case 1: return fail(E3DGE_ERR_INVALID_ARG, who ": n=%d (1..256) cin=%d (1..4096)", n, cin);                                             \
+        case 2: return fail(E3DGE_ERR_INVALID_ARG, who ": cout=%d (1..64: the wide layers are the core's)", cout);                              \
+        case 3: return fail(E3DGE_ERR_INVALID_ARG, who ": ksize=%d (1 or 3) stride=%d (1 or 2)", ksize, stride);                                \
+        case 4: return fail(E3DGE_ERR_INVALID_ARG, who ": height=%d width=%d (1..1024)", height, width);                                        \
+    }
+#define ALN_REQUIRE_SOURCES(who, channels)                                                                                                      \
+    E3DGE_REQUIRE(split >= 0 && split <= channels, who ": split=%d outside [0, " #channels "=%d]", split, channels);                            \
+    E3DGE_REQUIRE((split == 0 || in0) && (split == channels || in1), who ": null pointer (a source with channels)")
+
+// What the three network entries check alike, under the entry's name
+static int aln_check_call(const char* who, int n, int size, int split, int thumb_up4, const void* res_gt, const void* thumb, const void* packed) {
+    E3DGE_REQUIRE(n >= 1 && n <= 256, "%s: n=%d (1..256)", who, n);
+    E3DGE_REQUIRE(size == kAlnSize, "%s: size=%d (the network's up-samplings are fixed: 256)", who, size);
+    E3DGE_REQUIRE(split >= 0 && split <= kAlnIn, "%s: split=%d (0..6)", who, split);
+    E3DGE_REQUIRE(thumb_up4 == 0 || thumb_up4 == 1, "%s: thumb_up4=%d (0 or 1)", who, thumb_up4);
+    E3DGE_REQUIRE(packed && (split == 0 || res_gt) && (split == kAlnIn || thumb), "%s: null pointer", who);
+    return E3DGE_OK;
+}
+static int aln_check_sources(const char* who, const float* const* src, int n_src) {
+    E3DGE_REQUIRE(n_src == kAlnSources, "%s: n_src=%d, %d source tensors expected", who, n_src, kAlnSources);
+    for (int i = 0; i < n_src; ++i) E3DGE_REQUIRE(src[i], "%s: null pointer (source %d)", who, i);
+    return E3DGE_OK;
+}
+#define ALN_REQUIRE_FLOATS(who, what, have, need)                                                                                               \
+    E3DGE_REQUIRE((have) >= (need), who ": " what " of %lld floats, %lld needed", (long long)(have), (long long)(need))
+#define ALN_REQUIRE_BYTES(who, what, have, need)                                                                                                \
+    E3DGE_REQUIRE((have) >= (need), who ": " what " of %lld bytes, %lld needed", (long long)(have), (long long)(need))
+
+template <typename Layout>
+static int64_t aln_layout_bytes(const char* who, bool (*layout)(int64_t, Layout*), int n) {
+    Layout d;
+    if (!layout(n, &d)) {
+        fail(E3DGE_ERR_INVALID_ARG, "%s: n=%d (1..256)", who, n);
         return -1;
     }
     return d.total_bytes;
 }
 
+// ---- the network ------------------------------------------------------------------------------------------------------------------------------
+extern "C" int64_t e3dge_aligner_packed_floats(void) { return aln_net().packed_total; }
+extern "C" int64_t e3dge_aligner_packed_t_floats(void) { return aln_net().packed_t_total; }
+extern "C" int64_t e3dge_aligner_stats_channels(void) { return aln_net().channels; }
+extern "C" int64_t e3dge_aligner_grad_floats(void) { return aln_net().goff[kAlnSources]; }
+extern "C" int64_t e3dge_aligner_grad_offset(int source) {
+    if (source < 0 || source > kAlnSources) {
+        fail(E3DGE_ERR_INVALID_ARG, "aligner_grad_offset: source=%d (0..%d)", source, kAlnSources);
+        return -1;
+    }
+    return aln_net().goff[source];
+}
+extern "C" int64_t e3dge_aligner_workspace_bytes(int n) { return aln_layout_bytes("aligner_workspace_bytes", aln_ws, n); }
+extern "C" int64_t e3dge_aligner_saved_bytes(int n) { return aln_layout_bytes("aligner_saved_bytes", aln_saved, n); }
+extern "C" int64_t e3dge_aligner_bwd_workspace_bytes(int n) { return aln_layout_bytes("aligner_bwd_workspace_bytes", aln_bwd_ws, n); }
+
+extern "C" int e3dge_aligner_pack(float* packed, int64_t packed_floats, const float* const* src, int n_src, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(packed && src, "aligner_pack: null pointer");
+    const AlnNet& net = aln_net();
+    ALN_REQUIRE_FLOATS("aligner_pack", "packed buffer", packed_floats, net.packed_total);
+    int rc;
+    if ((rc = aln_check_sources("aligner_pack", src, n_src))) return rc;
+    hipStream_t st = as_stream(stream);
+    auto conv = [&](const AlnWeight& w, int ci, int co, int ks) { ig_pack(packed + w.packed, src[w.src], ci, co, ks, 1.0f, st); };
+    auto copy = [&](const AlnSlope& p, int ch) { ig_copy(packed + p.packed, src[p.src], ch, 1.0f, 0, st); };
+    auto bn = [&](const AlnBn& b) {
+        aln_pack_bn_kernel<<<dim3((unsigned)((b.ch + 255) / 256)), dim3(256), 0, st>>>(packed + b.packed, src[b.src], src[b.src + 1], src[b.src + 2],
+                                                                                        src[b.src + 3], b.ch);
+    };
+    conv(net.stem_w, kAlnIn, kAlnStem, 3); bn(net.stem_bn); copy(net.stem_prelu, kAlnStem);
+    for (const AlnUnitRow& q : net.u) {                               // res_layer.0 .. 4, then the shortcut
+        bn(q.bn0); conv(q.w1, q.cin, q.depth, 3); copy(q.prelu, q.depth); conv(q.w2, q.depth, q.depth, 3); bn(q.bn4);
+        if (q.conv_sc) { conv(q.wsc, q.cin, q.depth, 1); bn(q.bnsc); }
+    }
+    return check_launch("aligner_pack");
+}
+
+extern "C" int e3dge_aligner_pack_t(float* packed_t, int64_t packed_t_floats, const float* const* src, int n_src, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(packed_t && src, "aligner_pack_t: null pointer");
+    const AlnNet& net = aln_net();
+    ALN_REQUIRE_FLOATS("aligner_pack_t", "packed buffer", packed_t_floats, net.packed_t_total);
+    int rc;
+    if ((rc = aln_check_sources("aligner_pack_t", src, n_src))) return rc;
+    hipStream_t st = as_stream(stream);
+    auto conv = [&](const AlnWeight& w, int ci, int co, int ks) { ig_pack_t(packed_t + w.packed_t, src[w.src], ci, co, ks, 1.0f, st); };
+    conv(net.stem_w, kAlnIn, kAlnStem, 3);
+    for (const AlnUnitRow& q : net.u) {
+        conv(q.w1, q.cin, q.depth, 3); conv(q.w2, q.depth, q.depth, 3);
+        if (q.conv_sc) conv(q.wsc, q.cin, q.depth, 1);
+    }
+    return check_launch("aligner_pack_t");
+}
+
 extern "C" int e3dge_aligner_forward(const E3dgeAlignerArgs* args, e3dge_stream_t stream) {
     E3DGE_REQUIRE(args, "aligner_forward: null argument struct");
     const E3dgeAlignerArgs& a = *args;
-    E3DGE_REQUIRE(a.n >= 1 && a.n <= 256, "aligner_forward: n=%d (1..256)", a.n);
-    E3DGE_REQUIRE(a.size == kAlnSize, "aligner_forward: size=%d (the network's up-samplings are fixed: 256)", a.size);
-    E3DGE_REQUIRE(a.split >= 0 && a.split <= kAlnIn, "aligner_forward: split=%d (0..6)", a.split);
-    E3DGE_REQUIRE(a.thumb_up4 == 0 || a.thumb_up4 == 1, "aligner_forward: thumb_up4=%d (0 or 1)", a.thumb_up4);
-    E3DGE_REQUIRE(a.packed && a.out && a.ws && (a.split == 0 || a.res_gt) && (a.split == kAlnIn || a.thumb), "aligner_forward: null pointer");
-    const AlnLayout& l = aln_layout();
-    E3DGE_REQUIRE(a.packed_floats >= l.total, "aligner_forward: packed buffer of %lld floats, %lld needed", (long long)a.packed_floats, (long long)l.total);
-    AlnWs d;
-    E3DGE_REQUIRE(aln_ws(a.n, &d), "aligner_forward: n=%d", a.n);
-    E3DGE_REQUIRE(a.ws_bytes >= d.total_bytes, "aligner_forward: workspace of %lld bytes, %lld needed", (long long)a.ws_bytes, (long long)d.total_bytes);
-    hipStream_t st = as_stream(stream);
-    float* ws = static_cast<float*>(a.ws);
-    const float* P = a.packed;
-    const int n = a.n, S = kAlnSize;
-    float* feat[4];
-    for (int i = 0; i < 4; ++i) feat[i] = a.taps[i] ? a.taps[i] : ws + d.feat[i];
-    float* dfea[2];
-    for (int i = 0; i < 2; ++i) dfea[i] = a.taps[4 + i] ? a.taps[4 + i] : ws + d.dfea[i];
-    float* up = ws + d.up;
     int rc;
-    if ((rc = aln_conv({feat[0], a.res_gt, a.thumb, P + l.stem_w, nullptr, P + l.stem_bn, P + l.stem_prelu, nullptr, n, kAlnIn, a.split, a.thumb_up4,
-                        kAlnStem, S, S, 3, 1, kAlnScNone}, st)))
+    if ((rc = aln_check_call("aligner_forward", a.n, a.size, a.split, a.thumb_up4, a.res_gt, a.thumb, a.packed))) return rc;
+    E3DGE_REQUIRE(a.out && a.ws, "aligner_forward: null pointer");
+    ALN_REQUIRE_FLOATS("aligner_forward", "packed buffer", a.packed_floats, aln_net().packed_total);
+    AlnFwd r;
+    aln_ws(a.n, &r.ws);
+    ALN_REQUIRE_BYTES("aligner_forward", "workspace", a.ws_bytes, r.ws.total_bytes);
+    r.n = a.n; r.train = 0; r.P = a.packed; r.src = nullptr; r.stats = nullptr; r.st = as_stream(stream); r.S = nullptr; r.W = static_cast<float*>(a.ws);
+    for (int t = 0; t < kAlnTaps - 1; ++t) r.feature[t] = a.taps[t] ? a.taps[t] : r.W + r.ws.feature[t];   // a wanted tap is written in place
+    r.feature[kAlnTaps - 1] = a.out;
+    return aln_forward(r, a.res_gt, a.thumb, a.split, a.thumb_up4, a.taps, "aligner_forward(tap)");
+}
+
+extern "C" int e3dge_aligner_forward_saving(const E3dgeAlignerSaveArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "aligner_forward_saving: null argument struct");
+    const E3dgeAlignerSaveArgs& a = *args;
+    int rc;
+    if ((rc = aln_check_call("aligner_forward_saving", a.n, a.size, a.split, a.thumb_up4, a.res_gt, a.thumb, a.packed))) return rc;
+    E3DGE_REQUIRE(a.train == 0 || a.train == 1, "aligner_forward_saving: train=%d (0 or 1)", a.train);
+    E3DGE_REQUIRE(a.out && a.saved && (!a.train || (a.stats && a.src)), "aligner_forward_saving: null pointer");
+    if (a.train && (rc = aln_check_sources("aligner_forward_saving", a.src, a.n_src))) return rc;
+    const AlnNet& net = aln_net();
+    ALN_REQUIRE_FLOATS("aligner_forward_saving", "packed buffer", a.packed_floats, net.packed_total);
+    E3DGE_REQUIRE(!a.train || a.stats_doubles >= 2 * (int64_t)net.channels, "aligner_forward_saving: stats of %lld doubles, %lld needed",
+                  (long long)a.stats_doubles, (long long)(2 * net.channels));
+    AlnFwd r;
+    aln_saved(a.n, &r.lay);
+    ALN_REQUIRE_BYTES("aligner_forward_saving", "saved state", a.saved_bytes, r.lay.total_bytes);
+    r.n = a.n; r.train = a.train; r.P = a.packed; r.src = a.src; r.stats = a.stats; r.st = as_stream(stream); r.S = static_cast<float*>(a.saved); r.W = nullptr;
+    for (int t = 0; t < kAlnTaps - 1; ++t) r.feature[t] = r.S + r.lay.feature(t);
+    r.feature[kAlnTaps - 1] = a.out;
+    return aln_forward(r, a.res_gt, a.thumb, a.split, a.thumb_up4, a.taps, "aligner_forward_saving(tap)");
+}
+
+extern "C" int e3dge_aligner_backward(const E3dgeAlignerBwdArgs* args, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(args, "aligner_backward: null argument struct");
+    const E3dgeAlignerBwdArgs& a = *args;
+    int rc;
+    if ((rc = aln_check_call("aligner_backward", a.n, a.size, a.split, a.thumb_up4, a.res_gt, a.thumb, a.packed))) return rc;
+    E3DGE_REQUIRE(a.train == 0 || a.train == 1, "aligner_backward: train=%d (0 or 1)", a.train);
+    E3DGE_REQUIRE(a.want_input == 0 || a.want_input == 1, "aligner_backward: want_input=%d (0 or 1)", a.want_input);
+    E3DGE_REQUIRE(a.packed_t && a.src && a.want && a.g_out && a.saved && a.ws && (!a.train || a.stats), "aligner_backward: null pointer");
+    E3DGE_REQUIRE(!a.want_input || ((a.split == 0 || a.d_res_gt) && (a.split == kAlnIn || a.d_thumb)), "aligner_backward: null pointer (an input gradient)");
+    if ((rc = aln_check_sources("aligner_backward", a.src, a.n_src))) return rc;
+    const AlnNet& net = aln_net();
+    bool any = false;
+    for (int i = 0; i < a.n_src; ++i) any = any || a.want[i];
+    E3DGE_REQUIRE(!any || a.grads, "aligner_backward: null pointer (the gradient buffer)");
+    E3DGE_REQUIRE(!any || a.grad_floats >= net.goff[kAlnSources], "aligner_backward: gradient buffer of %lld floats, %lld needed", (long long)a.grad_floats,
+                  (long long)net.goff[kAlnSources]);
+    E3DGE_REQUIRE(a.packed_floats >= net.packed_total && a.packed_t_floats >= net.packed_t_total,
+                  "aligner_backward: packed buffers of %lld and %lld floats, %lld and %lld needed", (long long)a.packed_floats, (long long)a.packed_t_floats,
+                  (long long)net.packed_total, (long long)net.packed_t_total);
+    AlnBwdRun r;
+    aln_saved(a.n, &r.lay);
+    aln_bwd_ws(a.n, &r.ws);
+    ALN_REQUIRE_BYTES("aligner_backward", "saved state", a.saved_bytes, r.lay.total_bytes);
+    ALN_REQUIRE_BYTES("aligner_backward", "workspace", a.ws_bytes, r.ws.total_bytes);
+    r.n = a.n; r.train = a.train; r.want_input = a.want_input; r.P = a.packed; r.T = a.packed_t; r.src = a.src; r.want = a.want;
+    r.S = static_cast<const float*>(a.saved); r.stats = a.stats; r.W = static_cast<float*>(a.ws); r.grads = a.grads; r.st = as_stream(stream);
+    if ((rc = aln_stages_bwd(r, a.g_out))) return rc;
+    // conv_layer1: PReLU (in place; its pre-activation is the BatchNorm's output), BatchNorm, convolution
+    const int n = a.n, S = kAlnSize;
+    const float* c0 = r.S + r.lay.c0;
+    float* gstage = r.W + r.ws.gstage;
+    float* gc0 = r.W + r.ws.gc2;
+    if ((rc = aln_prelu_bwd(gstage, r.grad(net.stem_prelu.src), gstage, c0, r.ab(net.stem_bn), a.src[net.stem_prelu.src], r.norm_ws(), n, kAlnStem, S * S, r.st)))
         return rc;
-    if ((rc = aln_stage(feat[1], feat[0], nullptr, 16, 0, S, P, ws, d, n, st))) return rc;
-    if ((rc = aln_stage(feat[2], feat[1], nullptr, 32, 3, S / 2, P, ws, d, n, st))) return rc;
-    if ((rc = aln_stage(feat[3], feat[2], nullptr, 48, 6, S / 4, P, ws, d, n, st))) return rc;
-    if ((rc = aln_up2(up, feat[3], (int64_t)n * 64, S / 8, S / 8, st))) return rc;
-    if ((rc = aln_stage(dfea[0], up, feat[2], 64, 9, S / 4, P, ws, d, n, st))) return rc;
-    if ((rc = aln_up2(up, dfea[0], (int64_t)n * 32, S / 4, S / 4, st))) return rc;
-    if ((rc = aln_stage(dfea[1], up, feat[1], 32, 12, S / 2, P, ws, d, n, st))) return rc;
-    if ((rc = aln_up2(up, dfea[1], (int64_t)n * 16, S / 2, S / 2, st))) return rc;
-    if ((rc = aln_stage(a.out, up, feat[0], 16, 15, S, P, ws, d, n, st))) return rc;
-    if (a.taps[6]) {
-        ig_copy(a.taps[6], a.out, (int64_t)n * 3 * S * S, 1.0f, 0, st);
-        return check_launch("aligner_forward(tap)");
+    if ((rc = r.norm_bwd(net.stem_bn, gc0, nullptr, 0, gstage, c0, nullptr, kAlnStem, nullptr, nullptr, S * S))) return rc;
+    if (a.want[net.stem_w.src] &&
+        (rc = aln_wgrad({r.grad(net.stem_w.src), gc0, a.res_gt, a.thumb, nullptr, r.W + r.ws.wg, n, kAlnIn, a.split, a.thumb_up4, kAlnStem, S, S, 3, 1}, r.st)))
+        return rc;
+    if (a.want_input) {
+        AlnDgrad d{a.d_res_gt, gc0, r.T + net.stem_w.packed_t, nullptr, nullptr, n, kAlnIn, kAlnStem, S, S, 3, 1};
+        float* second = a.thumb_up4 ? r.W + r.ws.d256 : a.d_thumb;
+        if (a.split == 0) d.gx = second;
+        else if (a.split < kAlnIn) { d.gx1 = second; d.gsplit = a.split; }
+        if ((rc = aln_dgrad(d, r.st))) return rc;
+        if (a.thumb_up4 && a.split < kAlnIn) {
+            const int64_t total = (int64_t)n * (kAlnIn - a.split) * (S / 4) * (S / 4);
+            aln_down4_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, r.st>>>(a.d_thumb, second, S / 4, S / 4, total);
+            if ((rc = check_launch("aln(down4)"))) return rc;
+        }
     }
     return E3DGE_OK;
 }
 
+// The sign of every PReLU's input of one forward, from its saved state: the stem's, then every unit's
+extern "C" int64_t e3dge_aligner_branch_count(int n) {
+    if (n < 1 || n > 256) {
+        fail(E3DGE_ERR_INVALID_ARG, "aligner_branch_count: n=%d (1..256)", n);
+        return -1;
+    }
+    int64_t per = aln_feature_floats(0);
+    for (const AlnUnitRow& q : aln_net().u) per += (int64_t)q.depth * q.size * q.size;
+    return n * per;
+}
+
+extern "C" int e3dge_aligner_branch_bytes(uint8_t* out, int64_t out_bytes, const float* packed, int64_t packed_floats, const void* saved,
+                                          int64_t saved_bytes, int n, int train, e3dge_stream_t stream) {
+    E3DGE_REQUIRE(out && packed && saved, "aligner_branch_bytes: null pointer");
+    E3DGE_REQUIRE(n >= 1 && n <= 256 && (train == 0 || train == 1), "aligner_branch_bytes: n=%d (1..256) train=%d (0 or 1)", n, train);
+    const AlnNet& net = aln_net();
+    AlnSaved lay;
+    aln_saved(n, &lay);
+    ALN_REQUIRE_FLOATS("aligner_branch_bytes", "packed buffer", packed_floats, net.packed_total);
+    ALN_REQUIRE_BYTES("aligner_branch_bytes", "saved state", saved_bytes, lay.total_bytes);
+    ALN_REQUIRE_BYTES("aligner_branch_bytes", "out", out_bytes, e3dge_aligner_branch_count(n));
+    hipStream_t st = as_stream(stream);
+    const float* S = static_cast<const float*>(saved);
+    int64_t at = 0;
+    auto signs = [&](int64_t from, const float* ab, int ch, int size) {
+        const int64_t total = (int64_t)n * ch * size * size;
+        aln_branch_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(out + at, S + from, reinterpret_cast<const float2*>(ab), ch, size * size, total);
+        at += total;
+    };
+    signs(lay.c0, train ? S + lay.ab + 2 * net.stem_bn.chan : packed + net.stem_bn.packed, kAlnStem, kAlnSize);
+    for (int u = 0; u < kAlnUnits; ++u) signs(lay.c1[u], nullptr, net.u[u].depth, net.u[u].size);
+    return check_launch("aligner_branch_bytes");
+}
+
+// ---- every kernel at run-time shapes: the checks, then the helper the network calls -------------------------------------------------------
 extern "C" int e3dge_aln_conv(float* out, const float* in0, const float* in1, const float* w, const float* in_ab, const float* epi_ab,
                               const float* slope, const float* shortcut, float* wfrag, int64_t wfrag_floats, int n, int cin, int split, int up4,
                               int cout, int height, int width, int ksize, int stride, int shortcut_mode, e3dge_stream_t stream) {
     E3DGE_REQUIRE(out && w && wfrag, "aln_conv: null pointer");
-    E3DGE_REQUIRE(n >= 1 && n <= 256 && cin >= 1 && cin <= 4096, "aln_conv: n=%d (1..256) cin=%d (1..4096)", n, cin);
-    E3DGE_REQUIRE(cout >= 1 && cout <= kAlnMaxCout, "aln_conv: cout=%d (1..64: the wide layers are the core's)", cout);
-    E3DGE_REQUIRE(split >= 0 && split <= cin, "aln_conv: split=%d outside [0, cin=%d]", split, cin);
-    E3DGE_REQUIRE((split == 0 || in0) && (split == cin || in1), "aln_conv: null pointer (a source with channels)");
-    E3DGE_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "aln_conv: ksize=%d (1 or 3) stride=%d (1 or 2)", ksize, stride);
-    E3DGE_REQUIRE(height >= 1 && width >= 1 && height <= 1024 && width <= 1024, "aln_conv: height=%d width=%d (1..1024)", height, width);
+    ALN_REQUIRE_CONV("aln_conv");
+    ALN_REQUIRE_SOURCES("aln_conv", cin);
     E3DGE_REQUIRE(up4 == 0 || (up4 == 1 && height % 4 == 0 && width % 4 == 0), "aln_conv: up4=%d at %d x %d (0, or 1 at multiples of 4)", up4, height, width);
     E3DGE_REQUIRE(shortcut_mode >= kAlnScNone && shortcut_mode <= kAlnScRead && (shortcut_mode == kAlnScNone || shortcut),
                   "aln_conv: shortcut_mode=%d (0 none, 1 strided pick, 2 read) needs its tensor", shortcut_mode);
-    E3DGE_REQUIRE(wfrag_floats >= aln_image_floats(cin, cout, ksize), "aln_conv: wfrag of %lld floats, %lld needed", (long long)wfrag_floats,
-                  (long long)aln_image_floats(cin, cout, ksize));
+    ALN_REQUIRE_FLOATS("aln_conv", "wfrag", wfrag_floats, aln_image_floats(cin, cout, ksize));
     hipStream_t st = as_stream(stream);
     ig_pack(wfrag, w, cin, cout, ksize, 1.0f, st);
     int rc;
@@ -418,19 +502,12 @@ extern "C" int e3dge_aln_conv(float* out, const float* in0, const float* in1, co
 
 extern "C" int e3dge_aln_up2(float* out, const float* in, int64_t planes, int height, int width, e3dge_stream_t stream) {
     E3DGE_REQUIRE(out && in, "aln_up2: null pointer");
-    E3DGE_REQUIRE(planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024,
-                  "aln_up2: planes=%lld (1..2^20) height=%d width=%d (1..1024)", (long long)planes, height, width);
+    E3DGE_REQUIRE(aln_planes_ok(planes, height, width, 62 /* no bound on the elements */), "aln_up2: planes=%lld (1..2^20) height=%d width=%d (1..1024)", (long long)planes, height, width);
     return aln_up2(out, in, planes, height, width, as_stream(stream));
 }
 
-// ---- the trainable form's kernels around the convolutions (aligner_bwd.h), each at run-time shapes -------------------------------------------
-#define ALN_REQUIRE_PLANE(who)                                                                                                                  \
-    E3DGE_REQUIRE(n >= 1 && n <= 256 && channels >= 1 && channels <= 4096 && height >= 1 && width >= 1 && height <= 1024 && width <= 1024 &&    \
-                      (int64_t)n * channels * height * width <= ((int64_t)1 << 31),                                                              \
-                  who ": n=%d (1..256) channels=%d (1..4096) height=%d width=%d (1..1024), at most 2^31 elements", n, channels, height, width)
-
 extern "C" int64_t e3dge_aln_norm_ws_bytes(int n, int channels, int height, int width) {
-    if (n < 1 || n > 256 || channels < 1 || channels > 4096 || height < 1 || width < 1 || height > 1024 || width > 1024) {
+    if (!aln_plane_ok(n, channels, height, width)) {
         fail(E3DGE_ERR_INVALID_ARG, "aln_norm_ws_bytes: n=%d (1..256) channels=%d (1..4096) height=%d width=%d (1..1024)", n, channels, height, width);
         return -1;
     }
@@ -441,18 +518,11 @@ extern "C" int e3dge_aln_bn_stats(float* ab, double* stats, const float* in0, co
                                   int64_t ws_bytes, int n, int channels, int split, int height, int width, e3dge_stream_t stream) {
     E3DGE_REQUIRE((ab || stats) && ws && (!ab || (gamma && beta)), "aln_bn_stats: null pointer");
     ALN_REQUIRE_PLANE("aln_bn_stats");
-    E3DGE_REQUIRE(split >= 0 && split <= channels, "aln_bn_stats: split=%d outside [0, channels=%d]", split, channels);
-    E3DGE_REQUIRE((split == 0 || in0) && (split == channels || in1), "aln_bn_stats: null pointer (a source with channels)");
-    const int hw = height * width, segs = aln_segments(hw);
+    ALN_REQUIRE_SOURCES("aln_bn_stats", channels);
+    const int hw = height * width;
     E3DGE_REQUIRE((int64_t)n * hw >= 2, "aln_bn_stats: %lld values per channel (batch statistics need 2)", (long long)n * hw);
-    E3DGE_REQUIRE(ws_bytes >= aln_norm_ws_bytes(n, channels, hw), "aln_bn_stats: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-                  (long long)aln_norm_ws_bytes(n, channels, hw));
-    hipStream_t st = as_stream(stream);
-    double* part = static_cast<double*>(ws);
-    aln_bn_stats_kernel<<<dim3(segs, n, channels), dim3(256), 0, st>>>(part, AlnSrc2{in0, in1, split, channels - split}, hw);
-    aln_bn_stats_fold_kernel<<<dim3((channels + 63) / 64), dim3(64), 0, st>>>(reinterpret_cast<float2*>(ab), stats, part, gamma, beta, channels, n * segs,
-                                                                              (double)n * hw);
-    return check_launch("aln_bn_stats");
+    ALN_REQUIRE_BYTES("aln_bn_stats", "workspace", ws_bytes, aln_norm_ws_bytes(n, channels, hw));
+    return aln_stats(ab, stats, static_cast<double*>(ws), in0, in1, gamma, beta, n, channels, split, hw, as_stream(stream));
 }
 
 extern "C" int e3dge_aln_bn_apply(float* out, const float* in, const float* ab, const float* slope, const float* shortcut, const float* shortcut_ab,
@@ -469,13 +539,8 @@ extern "C" int e3dge_aln_bn_apply(float* out, const float* in, const float* ab, 
                           (shortcut_height - 1) / stride + 1 == height && (shortcut_width - 1) / stride + 1 == width,
                       "aln_bn_apply: a %d x %d shortcut picked at stride %d is not %d x %d", shortcut_height, shortcut_width, stride, height, width);
     }
-    AlnApplyArgs a;
-    a.out = out; a.in = in; a.ab = reinterpret_cast<const float2*>(ab); a.slope = slope; a.sc = shortcut;
-    a.sc_ab = reinterpret_cast<const float2*>(shortcut_ab);
-    a.C = channels; a.OH = height; a.OW = width; a.SH = shortcut_height; a.SW = shortcut_width; a.stride = stride; a.sc_mode = shortcut_mode;
-    a.total = (int64_t)n * channels * height * width;
-    aln_bn_apply_kernel<<<dim3(aln_blocks(a.total)), dim3(256), 0, as_stream(stream)>>>(a);
-    return check_launch("aln_bn_apply");
+    return aln_apply(out, in, ab, slope, shortcut, shortcut_ab, n, channels, height, width, shortcut_height, shortcut_width, stride, shortcut_mode,
+                     as_stream(stream));
 }
 
 extern "C" int e3dge_aln_norm_bwd(float* gx, float* dgamma, float* dbeta, const float* gy, const float* in0, const float* in1, const float* gamma,
@@ -486,76 +551,45 @@ extern "C" int e3dge_aln_norm_bwd(float* gx, float* dgamma, float* dbeta, const 
     E3DGE_REQUIRE(train ? stats != nullptr : (running_mean && running_var), "aln_norm_bwd: null pointer (the statistics of this form)");
     ALN_REQUIRE_PLANE("aln_norm_bwd");
     E3DGE_REQUIRE(split >= 0 && split <= channels, "aln_norm_bwd: split=%d outside [0, channels=%d]", split, channels);
-    const bool sums = train || dgamma || dbeta;                       // on running statistics g_x = A g needs no sum
-    E3DGE_REQUIRE(!(sums || train) || ((split == 0 || in0) && (split == channels || in1)), "aln_norm_bwd: null pointer (a source with channels)");
-    const int hw = height * width, segs = aln_segments(hw);
-    E3DGE_REQUIRE(ws_bytes >= aln_norm_ws_bytes(n, channels, hw), "aln_norm_bwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-                  (long long)aln_norm_ws_bytes(n, channels, hw));
-    hipStream_t st = as_stream(stream);
-    double* part = static_cast<double*>(ws);
-    double* coef = part + (int64_t)2 * channels * n * segs;
-    const AlnSrc2 src{in0, in1, split, channels - split};
-    const AlnNormStat ns{train ? stats : nullptr, running_mean, running_var};
-    if (sums) aln_norm_sums_kernel<<<dim3(segs, n, channels), dim3(256), 0, st>>>(part, gy, src, ns, channels, hw);
-    aln_norm_fold_kernel<<<dim3((channels + 63) / 64), dim3(64), 0, st>>>(coef, dgamma, dbeta, sums ? part : nullptr, gamma, ns, channels, n * segs,
-                                                                          (double)n * hw, train);
-    if (gx) {
-        const int64_t total = (int64_t)n * channels * hw;
-        aln_norm_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(AlnDst2{gx, nullptr, channels, 0}, gy, src, add, nullptr, coef, channels, hw, total,
-                                                                           train);
-    }
-    return check_launch("aln_norm_bwd");
+    const bool reads_x = train || dgamma || dbeta;                    // on running statistics g_x = A g reads no x
+    E3DGE_REQUIRE(!reads_x || ((split == 0 || in0) && (split == channels || in1)), "aln_norm_bwd: null pointer (a source with channels)");
+    const int hw = height * width;
+    ALN_REQUIRE_BYTES("aln_norm_bwd", "workspace", ws_bytes, aln_norm_ws_bytes(n, channels, hw));
+    return aln_norm_bwd(gx, nullptr, 0, dgamma, dbeta, gy, in0, in1, split, gamma, stats, running_mean, running_var, add, nullptr, static_cast<double*>(ws), n,
+                        channels, hw, train, as_stream(stream));
 }
 
 extern "C" int e3dge_aln_prelu_bwd(float* gx, float* dslope, const float* gy, const float* pre, const float* slope, void* ws, int64_t ws_bytes, int n,
                                    int channels, int height, int width, e3dge_stream_t stream) {
     E3DGE_REQUIRE((gx || dslope) && gy && pre && slope && (!dslope || ws), "aln_prelu_bwd: null pointer");
     ALN_REQUIRE_PLANE("aln_prelu_bwd");
-    const int hw = height * width, segs = aln_segments(hw);
+    const int hw = height * width;
     E3DGE_REQUIRE(!dslope || ws_bytes >= aln_norm_ws_bytes(n, channels, hw), "aln_prelu_bwd: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
                   (long long)aln_norm_ws_bytes(n, channels, hw));
-    hipStream_t st = as_stream(stream);
-    double* part = dslope ? static_cast<double*>(ws) : nullptr;
-    aln_prelu_bwd_kernel<<<dim3(segs, n, channels), dim3(256), 0, st>>>(gx, part, gy, pre, nullptr, slope, channels, hw);
-    if (dslope) aln_prelu_fold_kernel<<<dim3((channels + 63) / 64), dim3(64), 0, st>>>(dslope, part, channels, n * segs);
-    return check_launch("aln_prelu_bwd");
+    return aln_prelu_bwd(gx, dslope, gy, pre, nullptr, slope, static_cast<double*>(ws), n, channels, hw, as_stream(stream));
 }
 
 extern "C" int e3dge_aln_up2_bwd(float* gx, const float* gy, int64_t planes, int height, int width, e3dge_stream_t stream) {
     E3DGE_REQUIRE(gx && gy, "aln_up2_bwd: null pointer");
-    E3DGE_REQUIRE(planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024 &&
-                      planes * height * width <= ((int64_t)1 << 29),
-                  "aln_up2_bwd: planes=%lld (1..2^20) height=%d width=%d (1..1024), at most 2^29 elements", (long long)planes, height, width);
-    const int64_t total = planes * height * width;
-    aln_up2_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, as_stream(stream)>>>(gx, gy, height, width, total);
-    return check_launch("aln_up2_bwd");
+    E3DGE_REQUIRE(aln_planes_ok(planes, height, width, 29), "aln_up2_bwd: planes=%lld (1..2^20) height=%d width=%d (1..1024), at most 2^29 elements",
+                  (long long)planes, height, width);
+    return aln_up2_bwd(gx, gy, planes, height, width, as_stream(stream));
 }
 
 extern "C" int e3dge_aln_pick_bwd(float* gx, const float* gy, const float* add, int64_t planes, int height, int width, int stride,
                                   e3dge_stream_t stream) {
     E3DGE_REQUIRE(gx && gy, "aln_pick_bwd: null pointer");
-    E3DGE_REQUIRE(planes >= 1 && planes <= (1 << 20) && height >= 1 && width >= 1 && height <= 1024 && width <= 1024 &&
-                      planes * height * width <= ((int64_t)1 << 31),
-                  "aln_pick_bwd: planes=%lld (1..2^20) height=%d width=%d (1..1024), at most 2^31 elements", (long long)planes, height, width);
+    E3DGE_REQUIRE(aln_planes_ok(planes, height, width, 31), "aln_pick_bwd: planes=%lld (1..2^20) height=%d width=%d (1..1024), at most 2^31 elements",
+                  (long long)planes, height, width);
     E3DGE_REQUIRE(stride == 1 || stride == 2, "aln_pick_bwd: stride=%d (1 or 2)", stride);
-    const int64_t total = planes * height * width;
-    aln_pick_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, as_stream(stream)>>>(gx, gy, add, height, width, (height - 1) / stride + 1,
-                                                                                      (width - 1) / stride + 1, stride, total);
-    return check_launch("aln_pick_bwd");
+    return aln_pick_bwd(gx, gy, add, planes, height, width, stride, as_stream(stream));
 }
-
-#define ALN_REQUIRE_CONV(who)                                                                                                                   \
-    E3DGE_REQUIRE(n >= 1 && n <= 256 && cin >= 1 && cin <= 4096, who ": n=%d (1..256) cin=%d (1..4096)", n, cin);                               \
-    E3DGE_REQUIRE(cout >= 1 && cout <= kAlnMaxCout, who ": cout=%d (1..64: the wide layers are the core's)", cout);                             \
-    E3DGE_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), who ": ksize=%d (1 or 3) stride=%d (1 or 2)", ksize, stride);     \
-    E3DGE_REQUIRE(height >= 1 && width >= 1 && height <= 1024 && width <= 1024, who ": height=%d width=%d (1..1024)", height, width)
 
 extern "C" int e3dge_aln_conv_dgrad(float* gx, const float* gy, const float* w, const float* add0, const float* add1, float* wfrag,
                                     int64_t wfrag_floats, int n, int cin, int cout, int height, int width, int ksize, int stride, e3dge_stream_t stream) {
     E3DGE_REQUIRE(gx && gy && w && wfrag, "aln_conv_dgrad: null pointer");
     ALN_REQUIRE_CONV("aln_conv_dgrad");
-    const int64_t floats = (int64_t)ig_mpad(cin) * ig_kpad(cout * ksize * ksize);
-    E3DGE_REQUIRE(wfrag_floats >= floats, "aln_conv_dgrad: wfrag of %lld floats, %lld needed", (long long)wfrag_floats, (long long)floats);
+    ALN_REQUIRE_FLOATS("aln_conv_dgrad", "wfrag", wfrag_floats, aln_image_t_floats(cin, cout, ksize));
     hipStream_t st = as_stream(stream);
     ig_pack_t(wfrag, w, cin, cout, ksize, 1.0f, st);
     int rc;
@@ -564,8 +598,7 @@ extern "C" int e3dge_aln_conv_dgrad(float* gx, const float* gy, const float* w, 
 }
 
 extern "C" int64_t e3dge_aln_wgrad_ws_floats(int n, int cin, int cout, int height, int width, int ksize, int stride) {
-    if (n < 1 || n > 256 || cin < 1 || cin > 4096 || cout < 1 || cout > kAlnMaxCout || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) ||
-        height < 1 || width < 1 || height > 1024 || width > 1024) {
+    if (aln_conv_bad(n, cin, cout, height, width, ksize, stride)) {
         fail(E3DGE_ERR_INVALID_ARG, "aln_wgrad_ws_floats: n=%d (1..256) cin=%d (1..4096) cout=%d (1..64) height=%d width=%d (1..1024) ksize=%d (1 or 3) "
              "stride=%d (1 or 2)", n, cin, cout, height, width, ksize, stride);
         return -1;
@@ -578,233 +611,9 @@ extern "C" int e3dge_aln_conv_wgrad(float* dw, const float* gy, const float* in0
                                     e3dge_stream_t stream) {
     E3DGE_REQUIRE(dw && gy && ws, "aln_conv_wgrad: null pointer");
     ALN_REQUIRE_CONV("aln_conv_wgrad");
-    E3DGE_REQUIRE(split >= 0 && split <= cin, "aln_conv_wgrad: split=%d outside [0, cin=%d]", split, cin);
-    E3DGE_REQUIRE((split == 0 || in0) && (split == cin || in1), "aln_conv_wgrad: null pointer (a source with channels)");
+    ALN_REQUIRE_SOURCES("aln_conv_wgrad", cin);
     E3DGE_REQUIRE(up4 == 0 || (up4 == 1 && height % 4 == 0 && width % 4 == 0), "aln_conv_wgrad: up4=%d at %d x %d (0, or 1 at multiples of 4)", up4, height,
                   width);
-    const int64_t floats = aln_wgrad_ws_floats(n, cin, cout, height, width, ksize, stride);
-    E3DGE_REQUIRE(ws_floats >= floats, "aln_conv_wgrad: workspace of %lld floats, %lld needed", (long long)ws_floats, (long long)floats);
+    ALN_REQUIRE_FLOATS("aln_conv_wgrad", "workspace", ws_floats, aln_wgrad_ws_floats(n, cin, cout, height, width, ksize, stride));
     return aln_wgrad({dw, gy, in0, in1, in_ab, ws, n, cin, split, up4, cout, height, width, ksize, stride}, as_stream(stream));
-}
-
-// ---- the trainable form of the network (aligner_train.h) ---------------------------------------------------------------------------------------
-extern "C" int64_t e3dge_aligner_saved_bytes(int n) {
-    AlnSaved d;
-    if (!aln_saved(n, &d)) {
-        fail(E3DGE_ERR_INVALID_ARG, "aligner_saved_bytes: n=%d (1..256)", n);
-        return -1;
-    }
-    return d.total_bytes;
-}
-
-extern "C" int64_t e3dge_aligner_bwd_workspace_bytes(int n) {
-    AlnBwdWs d;
-    if (!aln_bwd_ws(n, &d)) {
-        fail(E3DGE_ERR_INVALID_ARG, "aligner_bwd_workspace_bytes: n=%d (1..256)", n);
-        return -1;
-    }
-    return d.total_bytes;
-}
-
-extern "C" int64_t e3dge_aligner_grad_floats(void) { return aln_net().goff[kAlnSources]; }
-extern "C" int64_t e3dge_aligner_grad_offset(int source) {
-    if (source < 0 || source > kAlnSources) {
-        fail(E3DGE_ERR_INVALID_ARG, "aligner_grad_offset: source=%d (0..%d)", source, kAlnSources);
-        return -1;
-    }
-    return aln_net().goff[source];
-}
-extern "C" int64_t e3dge_aligner_stats_channels(void) { return aln_net().channels; }
-extern "C" int64_t e3dge_aligner_packed_t_floats(void) { return aln_net().t_total; }
-
-extern "C" int64_t e3dge_aligner_branch_count(int n) {
-    if (n < 1 || n > 256) {
-        fail(E3DGE_ERR_INVALID_ARG, "aligner_branch_count: n=%d (1..256)", n);
-        return -1;
-    }
-    int64_t per = (int64_t)kAlnStem * kAlnSize * kAlnSize;
-    for (int u = 0; u < kAlnUnits; ++u) {
-        int64_t S = kAlnStageSize[u / 3];
-        for (int v = u / 3 * 3; v < u; ++v) S /= kAlnUnit[v].stride;
-        per += kAlnUnit[u].depth * S * S;
-    }
-    return n * per;
-}
-
-extern "C" int e3dge_aligner_pack_t(float* packed_t, int64_t packed_t_floats, const float* const* src, int n_src, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(packed_t && src, "aligner_pack_t: null pointer");
-    const AlnNet& net = aln_net();
-    E3DGE_REQUIRE(packed_t_floats >= net.t_total, "aligner_pack_t: packed buffer of %lld floats, %lld needed", (long long)packed_t_floats,
-                  (long long)net.t_total);
-    E3DGE_REQUIRE(n_src == kAlnSources, "aligner_pack_t: n_src=%d, %d source tensors expected", n_src, kAlnSources);
-    for (int i = 0; i < n_src; ++i) E3DGE_REQUIRE(src[i], "aligner_pack_t: null pointer (source %d)", i);
-    hipStream_t st = as_stream(stream);
-    ig_pack_t(packed_t + net.t_stem, src[net.stem_w], kAlnIn, kAlnStem, 3, 1.0f, st);
-    for (int u = 0; u < kAlnUnits; ++u) {
-        const AlnUnit q = kAlnUnit[u];
-        ig_pack_t(packed_t + net.t_w1[u], src[net.u[u].w1], q.cin, q.depth, 3, 1.0f, st);
-        ig_pack_t(packed_t + net.t_w2[u], src[net.u[u].w2], q.depth, q.depth, 3, 1.0f, st);
-        if (q.cin != q.depth) ig_pack_t(packed_t + net.t_wsc[u], src[net.u[u].wsc], q.cin, q.depth, 1, 1.0f, st);
-    }
-    return check_launch("aligner_pack_t");
-}
-
-extern "C" int e3dge_aligner_forward_saving(const E3dgeAlignerSaveArgs* args, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(args, "aligner_forward_saving: null argument struct");
-    const E3dgeAlignerSaveArgs& a = *args;
-    E3DGE_REQUIRE(a.n >= 1 && a.n <= 256, "aligner_forward_saving: n=%d (1..256)", a.n);
-    E3DGE_REQUIRE(a.size == kAlnSize, "aligner_forward_saving: size=%d (the network's up-samplings are fixed: 256)", a.size);
-    E3DGE_REQUIRE(a.split >= 0 && a.split <= kAlnIn, "aligner_forward_saving: split=%d (0..6)", a.split);
-    E3DGE_REQUIRE(a.thumb_up4 == 0 || a.thumb_up4 == 1, "aligner_forward_saving: thumb_up4=%d (0 or 1)", a.thumb_up4);
-    E3DGE_REQUIRE(a.train == 0 || a.train == 1, "aligner_forward_saving: train=%d (0 or 1)", a.train);
-    E3DGE_REQUIRE(a.packed && a.out && a.saved && (a.split == 0 || a.res_gt) && (a.split == kAlnIn || a.thumb) && (!a.train || (a.stats && a.src)),
-                  "aligner_forward_saving: null pointer");
-    E3DGE_REQUIRE(!a.train || a.n_src == kAlnSources, "aligner_forward_saving: n_src=%d, %d source tensors expected", a.n_src, kAlnSources);
-    if (a.train)
-        for (int i = 0; i < a.n_src; ++i) E3DGE_REQUIRE(a.src[i], "aligner_forward_saving: null pointer (source %d)", i);
-    const AlnLayout& l = aln_layout();
-    const AlnNet& net = aln_net();
-    E3DGE_REQUIRE(a.packed_floats >= l.total, "aligner_forward_saving: packed buffer of %lld floats, %lld needed", (long long)a.packed_floats,
-                  (long long)l.total);
-    E3DGE_REQUIRE(!a.train || a.stats_doubles >= 2 * (int64_t)net.channels, "aligner_forward_saving: stats of %lld doubles, %lld needed",
-                  (long long)a.stats_doubles, (long long)(2 * net.channels));
-    AlnRun r;
-    E3DGE_REQUIRE(aln_saved(a.n, &r.lay), "aligner_forward_saving: n=%d", a.n);
-    E3DGE_REQUIRE(a.saved_bytes >= r.lay.total_bytes, "aligner_forward_saving: saved state of %lld bytes, %lld needed", (long long)a.saved_bytes,
-                  (long long)r.lay.total_bytes);
-    r.n = a.n; r.train = a.train; r.P = a.packed; r.src = a.src; r.S = static_cast<float*>(a.saved); r.stats = a.stats; r.st = as_stream(stream);
-    const int n = a.n, S = kAlnSize;
-    float* c0 = r.S + r.lay.c0;
-    float* feat1 = r.S + r.lay.feat1;
-    float* feat[4] = {feat1, r.S + r.lay.y[2], r.S + r.lay.y[5], r.S + r.lay.y[8]};
-    float* dfea[2] = {r.S + r.lay.y[11], r.S + r.lay.y[14]};
-    float* up[3] = {r.S + r.lay.up[0], r.S + r.lay.up[1], r.S + r.lay.up[2]};
-    int rc;
-    if ((rc = aln_conv({c0, a.res_gt, a.thumb, r.P + l.stem_w, nullptr, nullptr, nullptr, nullptr, n, kAlnIn, a.split, a.thumb_up4, kAlnStem, S, S, 3, 1, kAlnScNone},
-                       r.st)))
-        return rc;
-    if ((rc = r.batch_stats(net.stem_bn, c0, nullptr, kAlnStem, S * S))) return rc;
-    if ((rc = aln_apply(feat1, c0, r.ab(net.stem_bn, l.stem_bn), r.P + l.stem_prelu, nullptr, nullptr, n, kAlnStem, S, S, S, S, 1, kAlnScNone, r.st))) return rc;
-    if ((rc = aln_stage_saving(r, feat[1], feat[0], nullptr, 16, 0, S))) return rc;
-    if ((rc = aln_stage_saving(r, feat[2], feat[1], nullptr, 32, 3, S / 2))) return rc;
-    if ((rc = aln_stage_saving(r, feat[3], feat[2], nullptr, 48, 6, S / 4))) return rc;
-    if ((rc = aln_up2(up[0], feat[3], (int64_t)n * 64, S / 8, S / 8, r.st))) return rc;
-    if ((rc = aln_stage_saving(r, dfea[0], up[0], feat[2], 64, 9, S / 4))) return rc;
-    if ((rc = aln_up2(up[1], dfea[0], (int64_t)n * 32, S / 4, S / 4, r.st))) return rc;
-    if ((rc = aln_stage_saving(r, dfea[1], up[1], feat[1], 32, 12, S / 2))) return rc;
-    if ((rc = aln_up2(up[2], dfea[1], (int64_t)n * 16, S / 2, S / 2, r.st))) return rc;
-    if ((rc = aln_stage_saving(r, a.out, up[2], feat[0], 16, 15, S))) return rc;
-    const float* tap_src[kAlnTaps] = {feat[0], feat[1], feat[2], feat[3], dfea[0], dfea[1], a.out};
-    const int64_t tap_floats[kAlnTaps] = {16LL * S * S, 32LL * S * S / 4, 48LL * S * S / 16, 64LL * S * S / 64, 32LL * S * S / 16, 16LL * S * S / 4, 3LL * S * S};
-    bool copied = false;
-    for (int i = 0; i < kAlnTaps; ++i)
-        if (a.taps[i]) { ig_copy(a.taps[i], tap_src[i], n * tap_floats[i], 1.0f, 0, r.st); copied = true; }
-    return copied ? check_launch("aligner_forward_saving(tap)") : E3DGE_OK;
-}
-
-extern "C" int e3dge_aligner_backward(const E3dgeAlignerBwdArgs* args, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(args, "aligner_backward: null argument struct");
-    const E3dgeAlignerBwdArgs& a = *args;
-    E3DGE_REQUIRE(a.n >= 1 && a.n <= 256, "aligner_backward: n=%d (1..256)", a.n);
-    E3DGE_REQUIRE(a.size == kAlnSize, "aligner_backward: size=%d (the network's up-samplings are fixed: 256)", a.size);
-    E3DGE_REQUIRE(a.split >= 0 && a.split <= kAlnIn, "aligner_backward: split=%d (0..6)", a.split);
-    E3DGE_REQUIRE(a.thumb_up4 == 0 || a.thumb_up4 == 1, "aligner_backward: thumb_up4=%d (0 or 1)", a.thumb_up4);
-    E3DGE_REQUIRE(a.train == 0 || a.train == 1, "aligner_backward: train=%d (0 or 1)", a.train);
-    E3DGE_REQUIRE(a.want_input == 0 || a.want_input == 1, "aligner_backward: want_input=%d (0 or 1)", a.want_input);
-    E3DGE_REQUIRE(a.packed && a.packed_t && a.src && a.want && a.g_out && a.saved && a.ws && (a.split == 0 || a.res_gt) && (a.split == kAlnIn || a.thumb) &&
-                      (!a.train || a.stats),
-                  "aligner_backward: null pointer");
-    E3DGE_REQUIRE(!a.want_input || ((a.split == 0 || a.d_res_gt) && (a.split == kAlnIn || a.d_thumb)), "aligner_backward: null pointer (an input gradient)");
-    E3DGE_REQUIRE(a.n_src == kAlnSources, "aligner_backward: n_src=%d, %d source tensors expected", a.n_src, kAlnSources);
-    const AlnLayout& l = aln_layout();
-    const AlnNet& net = aln_net();
-    bool any = false;
-    for (int i = 0; i < a.n_src; ++i) {
-        E3DGE_REQUIRE(a.src[i], "aligner_backward: null pointer (source %d)", i);
-        any = any || a.want[i];
-    }
-    E3DGE_REQUIRE(!any || a.grads, "aligner_backward: null pointer (the gradient buffer)");
-    E3DGE_REQUIRE(!any || a.grad_floats >= net.goff[kAlnSources], "aligner_backward: gradient buffer of %lld floats, %lld needed", (long long)a.grad_floats,
-                  (long long)net.goff[kAlnSources]);
-    E3DGE_REQUIRE(a.packed_floats >= l.total && a.packed_t_floats >= net.t_total, "aligner_backward: packed buffers of %lld and %lld floats, %lld and %lld needed",
-                  (long long)a.packed_floats, (long long)a.packed_t_floats, (long long)l.total, (long long)net.t_total);
-    AlnBwdRun r;
-    E3DGE_REQUIRE(aln_saved(a.n, &r.lay) && aln_bwd_ws(a.n, &r.ws), "aligner_backward: n=%d", a.n);
-    E3DGE_REQUIRE(a.saved_bytes >= r.lay.total_bytes, "aligner_backward: saved state of %lld bytes, %lld needed", (long long)a.saved_bytes,
-                  (long long)r.lay.total_bytes);
-    E3DGE_REQUIRE(a.ws_bytes >= r.ws.total_bytes, "aligner_backward: workspace of %lld bytes, %lld needed", (long long)a.ws_bytes, (long long)r.ws.total_bytes);
-    r.n = a.n; r.train = a.train; r.want_input = a.want_input; r.P = a.packed; r.T = a.packed_t; r.src = a.src; r.want = a.want;
-    r.S = static_cast<const float*>(a.saved); r.stats = a.stats; r.W = static_cast<float*>(a.ws); r.grads = a.grads; r.st = as_stream(stream);
-    const int n = a.n, S = kAlnSize;
-    const float* feat[4] = {r.S + r.lay.feat1, r.S + r.lay.y[2], r.S + r.lay.y[5], r.S + r.lay.y[8]};
-    const float* up[3] = {r.S + r.lay.up[0], r.S + r.lay.up[1], r.S + r.lay.up[2]};
-    float* gstage = r.W + r.ws.gstage;
-    float* gup = r.W + r.ws.gup;
-    float* skip[3] = {r.W + r.ws.skip[0], r.W + r.ws.skip[1], r.W + r.ws.skip[2]};
-    int rc;
-    auto up_bwd = [&](int64_t planes, int h) {
-        const int64_t total = planes * h * h;
-        aln_up2_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, r.st>>>(gstage, gup, h, h, total);
-        return check_launch("aln(up2_bwd)");
-    };
-    if ((rc = aln_stage_bwd(r, gup, skip[0], a.g_out, up[2], feat[0], 16, 15, S, nullptr))) return rc;
-    if ((rc = up_bwd((int64_t)n * 16, S / 2))) return rc;
-    if ((rc = aln_stage_bwd(r, gup, skip[1], gstage, up[1], feat[1], 32, 12, S / 2, nullptr))) return rc;
-    if ((rc = up_bwd((int64_t)n * 32, S / 4))) return rc;
-    if ((rc = aln_stage_bwd(r, gup, skip[2], gstage, up[0], feat[2], 64, 9, S / 4, nullptr))) return rc;
-    if ((rc = up_bwd((int64_t)n * 64, S / 8))) return rc;
-    if ((rc = aln_stage_bwd(r, gstage, nullptr, gstage, feat[2], nullptr, 48, 6, S / 4, skip[2]))) return rc;
-    if ((rc = aln_stage_bwd(r, gstage, nullptr, gstage, feat[1], nullptr, 32, 3, S / 2, skip[1]))) return rc;
-    if ((rc = aln_stage_bwd(r, gstage, nullptr, gstage, feat[0], nullptr, 16, 0, S, skip[0]))) return rc;
-    // conv_layer1: PReLU (in place; its pre-activation is the BatchNorm's output), BatchNorm, convolution
-    const float* c0 = r.S + r.lay.c0;
-    float* gc0 = r.W + r.ws.gc2;
-    if ((rc = aln_prelu_bwd(gstage, r.grad(net.stem_prelu), gstage, c0, r.ab(net.stem_bn, l.stem_bn), a.src[net.stem_prelu], r.norm_ws(), n, kAlnStem, S * S,
-                            r.st)))
-        return rc;
-    if ((rc = r.norm_bwd(net.stem_bn, gc0, nullptr, 0, gstage, c0, nullptr, kAlnStem, nullptr, nullptr, S * S))) return rc;
-    if (a.want[net.stem_w] &&
-        (rc = aln_wgrad({r.grad(net.stem_w), gc0, a.res_gt, a.thumb, nullptr, r.W + r.ws.wg, n, kAlnIn, a.split, a.thumb_up4, kAlnStem, S, S, 3, 1}, r.st)))
-        return rc;
-    if (a.want_input) {
-        AlnDgrad d{a.d_res_gt, gc0, r.T + net.t_stem, nullptr, nullptr, n, kAlnIn, kAlnStem, S, S, 3, 1};
-        float* second = a.thumb_up4 ? r.W + r.ws.d256 : a.d_thumb;
-        if (a.split == 0) d.gx = second;
-        else if (a.split < kAlnIn) { d.gx1 = second; d.gsplit = a.split; }
-        if ((rc = aln_dgrad(d, r.st))) return rc;
-        if (a.thumb_up4 && a.split < kAlnIn) {
-            const int64_t total = (int64_t)n * (kAlnIn - a.split) * (S / 4) * (S / 4);
-            aln_down4_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, r.st>>>(a.d_thumb, second, S / 4, S / 4, total);
-            if ((rc = check_launch("aln(down4)"))) return rc;
-        }
-    }
-    return E3DGE_OK;
-}
-
-extern "C" int e3dge_aligner_branch_bytes(uint8_t* out, int64_t out_bytes, const float* packed, int64_t packed_floats, const void* saved,
-                                          int64_t saved_bytes, int n, int train, e3dge_stream_t stream) {
-    E3DGE_REQUIRE(out && packed && saved, "aligner_branch_bytes: null pointer");
-    E3DGE_REQUIRE(n >= 1 && n <= 256 && (train == 0 || train == 1), "aligner_branch_bytes: n=%d (1..256) train=%d (0 or 1)", n, train);
-    const AlnLayout& l = aln_layout();
-    AlnSaved lay;
-    aln_saved(n, &lay);
-    E3DGE_REQUIRE(packed_floats >= l.total, "aligner_branch_bytes: packed buffer of %lld floats, %lld needed", (long long)packed_floats, (long long)l.total);
-    E3DGE_REQUIRE(saved_bytes >= lay.total_bytes, "aligner_branch_bytes: saved state of %lld bytes, %lld needed", (long long)saved_bytes,
-                  (long long)lay.total_bytes);
-    E3DGE_REQUIRE(out_bytes >= e3dge_aligner_branch_count(n), "aligner_branch_bytes: out of %lld bytes, %lld needed", (long long)out_bytes,
-                  (long long)e3dge_aligner_branch_count(n));
-    hipStream_t st = as_stream(stream);
-    const float* S = static_cast<const float*>(saved);
-    const int hw0 = kAlnSize * kAlnSize;
-    int64_t at = (int64_t)n * kAlnStem * hw0;
-    const float* stem_ab = train ? S + lay.ab + 2 * aln_net().stem_bn.chan : packed + l.stem_bn;
-    aln_branch_kernel<<<dim3(aln_blocks(at)), dim3(256), 0, st>>>(out, S + lay.c0, reinterpret_cast<const float2*>(stem_ab), kAlnStem, hw0, at);
-    for (int u = 0; u < kAlnUnits; ++u) {
-        int64_t sz = kAlnStageSize[u / 3];
-        for (int v = u / 3 * 3; v < u; ++v) sz /= kAlnUnit[v].stride;
-        const int64_t total = (int64_t)n * kAlnUnit[u].depth * sz * sz;
-        aln_branch_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(out + at, S + lay.c1[u], nullptr, kAlnUnit[u].depth, (int)(sz * sz), total);
-        at += total;
-    }
-    return check_launch("aligner_branch_bytes");
 }

@@ -1,7 +1,7 @@
 // The 2-D residual aligner (ADA), trainable form: the kernels around the convolutions -- BatchNorm on batch statistics (forward and
 // backward), the PReLU backward with its slope gradient, and the adjoints of aln_up2_kernel and of MaxPool2d(1, stride).  Included by
-// aligner.hip (after aln_up2_tap and the kAlnSc* modes); below them the data and the weight gradient of a convolution.  The network's
-// forward with saved state and its backward are composed of these in aligner_train.h.  Measured errors and times: DESIGN.md 4.17b.
+// aligner.hip (after aln_up2_tap and the kAlnSc* modes); below them the data and the weight gradient of a convolution.  Every kernel is
+// followed by its launch helper, which the network (aligner_train.h) and the run-time-shape entry of aligner.hip both call.  Measured errors and times: DESIGN.md 4.17b.
 //
 // Every per-channel sum runs in float64 in a fixed order: a workgroup sums one (channel, image, pixel segment) -- 256 strided partial
 // sums, then a fixed tree through LDS -- and one thread per channel folds the partials, images then segments ascending.  The segment
@@ -30,6 +30,9 @@ constexpr double kAlnEps = 1e-5;                                     // nn.Batch
 enum { kAlnScAffine = 3 };                                           // aln_bn_apply: + sc_ab.x sc + sc_ab.y (beside kAlnScNone / Pick / Read)
 
 static int aln_segments(int hw) { return (hw + kAlnSeg - 1) / kAlnSeg; }
+static unsigned aln_blocks(int64_t total) { return (unsigned)((total + 255) / 256); }
+// workspace of the per-channel sums: the partials (two float64 per channel, image and segment), then three float64 per channel
+static int64_t aln_norm_ws_bytes(int64_t n, int64_t c, int hw) { return (2 * c * n * aln_segments(hw) + 3 * c) * (int64_t)sizeof(double); }
 
 struct AlnSrc2 { const float* p0; const float* p1; int c0, c1; };   // channels [0, c0) of p0 (n, c0, h, w), then c1 of p1 (n, c1, h, w)
 
@@ -90,6 +93,14 @@ __global__ void __launch_bounds__(64) aln_bn_stats_fold_kernel(float2* __restric
     }
 }
 
+static int aln_stats(float* ab, double* stats, double* part, const float* in0, const float* in1, const float* gamma, const float* beta, int n, int c,
+                     int split, int hw, hipStream_t st) {
+    const int segs = aln_segments(hw);
+    aln_bn_stats_kernel<<<dim3(segs, n, c), dim3(256), 0, st>>>(part, AlnSrc2{in0, in1, split, c - split}, hw);
+    aln_bn_stats_fold_kernel<<<dim3((c + 63) / 64), dim3(64), 0, st>>>(reinterpret_cast<float2*>(ab), stats, part, gamma, beta, c, n * segs, (double)n * hw);
+    return check_launch("aln(stats)");
+}
+
 // ---- a v + b, PReLU, shortcut -----------------------------------------------------------------------------------------------------------
 struct AlnApplyArgs {
     float* out; const float* in; const float2* ab; const float* slope; const float* sc; const float2* sc_ab;
@@ -115,6 +126,15 @@ __global__ void __launch_bounds__(256) aln_bn_apply_kernel(AlnApplyArgs a) {
         v = __fadd_rn(v, __fmaf_rn(s.x, a.sc[i], s.y));
     }
     a.out[i] = v;
+}
+
+static int aln_apply(float* out, const float* in, const float* ab, const float* slope, const float* sc, const float* sc_ab, int n, int c, int oh, int ow,
+                     int sh, int sw, int stride, int mode, hipStream_t st) {
+    AlnApplyArgs a;
+    a.out = out; a.in = in; a.ab = reinterpret_cast<const float2*>(ab); a.slope = slope; a.sc = sc; a.sc_ab = reinterpret_cast<const float2*>(sc_ab);
+    a.C = c; a.OH = oh; a.OW = ow; a.SH = sh; a.SW = sw; a.stride = stride; a.sc_mode = mode; a.total = (int64_t)n * c * oh * ow;
+    aln_bn_apply_kernel<<<dim3(aln_blocks(a.total)), dim3(256), 0, st>>>(a);
+    return check_launch("aln(apply)");
 }
 
 // ---- BatchNorm backward -----------------------------------------------------------------------------------------------------------------
@@ -179,6 +199,25 @@ __global__ void __launch_bounds__(256) aln_norm_bwd_kernel(AlnDst2 gx, const flo
     aln_plane(gx, img, c, hw)[pix] = (float)v;
 }
 
+// gx split at gsplit (gx1 NULL: one tensor; gx0 NULL: the parameter gradients alone); dgamma / dbeta NULL: not wanted; ws: aln_norm_ws_bytes
+static int aln_norm_bwd(float* gx0, float* gx1, int gsplit, float* dgamma, float* dbeta, const float* gy, const float* in0, const float* in1, int split,
+                        const float* gamma, const double* stats, const float* rmean, const float* rvar, const float* add0, const float* add1, double* ws,
+                        int n, int c, int hw, int train, hipStream_t st) {
+    const int segs = aln_segments(hw);
+    double* coef = ws + (int64_t)2 * c * n * segs;
+    const AlnSrc2 src{in0, in1, split, c - split};
+    const AlnNormStat ns{train ? stats : nullptr, rmean, rvar};
+    const bool sums = train || dgamma || dbeta;                       // on running statistics g_x = A g needs no sum
+    if (sums) aln_norm_sums_kernel<<<dim3(segs, n, c), dim3(256), 0, st>>>(ws, gy, src, ns, c, hw);
+    aln_norm_fold_kernel<<<dim3((c + 63) / 64), dim3(64), 0, st>>>(coef, dgamma, dbeta, sums ? ws : nullptr, gamma, ns, c, n * segs, (double)n * hw, train);
+    if (gx0) {
+        const int64_t total = (int64_t)n * c * hw;
+        aln_norm_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(AlnDst2{gx0, gx1, gx1 ? gsplit : c, gx1 ? c - gsplit : 0}, gy, src, add0, add1, coef,
+                                                                           c, hw, total, train);
+    }
+    return check_launch("aln(norm_bwd)");
+}
+
 // ---- PReLU backward -----------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) aln_prelu_bwd_kernel(float* __restrict__ gx, double* __restrict__ part, const float* __restrict__ gy,
                                                             const float* __restrict__ pre, const float2* __restrict__ pre_ab, const float* __restrict__ slope, int C,
@@ -203,6 +242,15 @@ __global__ void __launch_bounds__(64) aln_prelu_fold_kernel(float* __restrict__ 
     double s, unused;
     aln_fold(part, c, count, s, unused);
     dslope[c] = (float)s;
+}
+
+// pre_ab: the affine under which `pre` was the PReLU's input (NULL: pre itself); ws (aln_norm_ws_bytes) is read only with dslope
+static int aln_prelu_bwd(float* gx, float* dslope, const float* gy, const float* pre, const float* pre_ab, const float* slope, double* ws, int n, int c,
+                         int hw, hipStream_t st) {
+    const int segs = aln_segments(hw);
+    aln_prelu_bwd_kernel<<<dim3(segs, n, c), dim3(256), 0, st>>>(gx, dslope ? ws : nullptr, gy, pre, reinterpret_cast<const float2*>(pre_ab), slope, c, hw);
+    if (dslope) aln_prelu_fold_kernel<<<dim3((c + 63) / 64), dim3(64), 0, st>>>(dslope, ws, c, n * segs);
+    return check_launch("aln(prelu_bwd)");
 }
 
 // ---- adjoint of aln_up2_kernel --------------------------------------------------------------------------------------------------------------
@@ -233,6 +281,12 @@ __global__ void __launch_bounds__(256) aln_up2_bwd_kernel(float* __restrict__ gx
     gx[i] = (float)sum;
 }
 
+static int aln_up2_bwd(float* gx, const float* gy, int64_t planes, int h, int w, hipStream_t st) {   // h, w: gx's plane
+    const int64_t total = planes * h * w;
+    aln_up2_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(gx, gy, h, w, total);
+    return check_launch("aln(up2_bwd)");
+}
+
 // ---- adjoint of the strided pick ------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) aln_pick_bwd_kernel(float* __restrict__ gx, const float* __restrict__ gy, const float* __restrict__ add,
                                                            int H, int W, int OH, int OW, int stride, int64_t total) {
@@ -244,6 +298,12 @@ __global__ void __launch_bounds__(256) aln_pick_bwd_kernel(float* __restrict__ g
     float v = 0.0f;
     if (y % stride == 0 && x % stride == 0) v = gy[(plane * OH + y / stride) * OW + x / stride];
     gx[i] = add ? __fadd_rn(add[i], v) : v;
+}
+
+static int aln_pick_bwd(float* gx, const float* gy, const float* add, int64_t planes, int h, int w, int stride, hipStream_t st) {   // h, w: gx's plane
+    const int64_t total = planes * h * w;
+    aln_pick_bwd_kernel<<<dim3(aln_blocks(total)), dim3(256), 0, st>>>(gx, gy, add, h, w, (h - 1) / stride + 1, (w - 1) / stride + 1, stride, total);
+    return check_launch("aln(pick_bwd)");
 }
 
 // ---- data gradient of a convolution -----------------------------------------------------------------------------------------------------------
@@ -468,11 +528,5 @@ static int aln_wgrad(const AlnWgrad& c, hipStream_t st) {
     aln_wgrad_fold_kernel<<<dim3((total + 255) / 256), dim3(256), 0, st>>>(c.dw, c.ws, c.n * segs, total);
     return check_launch("aln(wgrad)");
 }
-
-// ---- host side ------------------------------------------------------------------------------------------------------------------------------
-// workspace: the partial sums (two float64 per channel, image and segment), then three float64 per channel
-static int64_t aln_norm_ws_bytes(int64_t n, int64_t c, int hw) { return (2 * c * n * aln_segments(hw) + 3 * c) * (int64_t)sizeof(double); }
-
-static unsigned aln_blocks(int64_t total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace e3dge

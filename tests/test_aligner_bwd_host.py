@@ -407,3 +407,31 @@ def test_cpu_autograd_in_train_mode_reproduces_the_recording_bit_for_bit():
         assert np.array_equal(state[k].numpy(), gold[f"buffer_{i}_f32"]), k
         assert float(np.abs(gold[f"buffer_{i}_f32"] - gold[f"buffer_{i}_f64"]).max()) < 1e-5
     assert float(gold["max_f64"][0]) > 10 and len(gold["buffer_names"]) == 6
+
+
+# ---- the listings alignment.py derives ------------------------------------------------------------------------------------------------------
+def test_running_statistic_slots_are_the_running_buffers_of_sources():
+    """The derived slots against the state dict: the positions in sources() of the tensors whose keys end in running_mean / running_var."""
+    m = ResidualAligner(syn.aligner_opt())
+    src = m.sources()
+    running = [t for k, t in m.state_dict(keep_vars=True).items() if k.endswith(("running_mean", "running_var"))]
+    want = {i for i, t in enumerate(src) if any(t is r for r in running)}
+    assert len(running) == 2 * len(m.batch_norms()) == 92 and len(want) == 92
+    assert m.running_statistic_slots() == want
+    assert all(src[i].requires_grad for i in range(len(src)) if i not in want)      # (everything else is a Parameter)
+
+
+def test_bn_planes_are_what_every_batch_norm_sees():
+    """_bn_planes against a forward hook on every BatchNorm of one B = 1 forward_torch, in batch_norms() order."""
+    m = syn.load_synthetic_aligner(ResidualAligner(syn.aligner_opt())).eval()
+    seen = {}
+
+    def hook(mod, inp, out):
+        seen[id(mod)] = inp[0].shape[-2] * inp[0].shape[-1]
+    hooks = [bn.register_forward_hook(hook) for bn in m.batch_norms()]
+    with torch.no_grad():
+        m.forward_torch(host.aligner_input(1, 0))
+    for h in hooks:
+        h.remove()
+    assert len(m.batch_norms()) == 46 == len({id(bn) for bn in m.batch_norms()})
+    assert alignment._bn_planes(46) == [seen[id(bn)] for bn in m.batch_norms()]
