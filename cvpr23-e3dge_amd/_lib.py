@@ -327,6 +327,17 @@ class AlignerBwdArgs(_Args):
         ("ws_bytes", _i64)]
 
 
+VDISC_MAX_BLOCKS, VDISC_TAPS = 6, 7                                # E3DGE_VDISC_* (include/e3dge_hip.h)
+VDISC_FORM_STEM, VDISC_FORM_CONV, VDISC_FORM_CONV_POOL, VDISC_FORM_SKIP, VDISC_FORM_FINAL = 0, 1, 2, 3, 4
+VDISC_SKIP_READ, VDISC_SKIP_POOL = 1, 2
+
+
+class VdiscArgs(_Args):
+    """Mirror of struct E3dgeVdiscArgs (include/e3dge_hip.h)."""
+    _fields_ = [("packed", _vp), ("images", _vp), ("n", _i32), ("size", _i32), ("logits", _vp), ("viewpoints", _vp), ("taps", _vp * VDISC_TAPS),
+                ("ws", _vp), ("ws_bytes", _i64)]
+
+
 def has_experimental():
     """Was the loaded library built with -DE3DGE_EXPERIMENTAL (include/e3dge_hip_experimental.h, tools/build_variant.sh: one more
     precision mode, f16x3_v1, and no extra symbols; f16x3_g2 is in every build)?"""
@@ -521,6 +532,11 @@ SIGNATURES = {
     "e3dge_aligner_forward_saving": (_i32, [ctypes.POINTER(AlignerSaveArgs), _vp]),
     "e3dge_aligner_backward": (_i32, [ctypes.POINTER(AlignerBwdArgs), _vp]),
     "e3dge_aligner_branch_bytes": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
+    "e3dge_vdisc_packed_floats": (_i64, [_i32]),
+    "e3dge_vdisc_pack_weights": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "e3dge_vdisc_ws_bytes": (_i64, [_i32, _i32]),
+    "e3dge_vdisc_forward": (_i32, [ctypes.POINTER(VdiscArgs), _vp]),
+    "e3dge_vdisc_conv": (_i32, [_vp] * 6 + [_i64] + [_i32] * 7 + [_vp]),
 }
 
 _lib = None

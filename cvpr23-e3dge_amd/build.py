@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "libe3dge_hip.so"
 SOURCES = ["stream_ops.hip", "upfirdn2d.hip", "siren.hip", "siren_bwd.hip", "resblock.hip", "modconv.hip", "decoder2.hip", "local_query.hip", "metrics.hip", "align_volume.hip", "hitprob.hip", "siren_ws.hip", "wgrad.hip",
-           "marching_cubes.hip", "mesh_render.hip", "lpips.hip", "idnet.hip", "losses.hip", "disc.hip", "hgfilter.hip", "aligner.hip"]
+           "marching_cubes.hip", "mesh_render.hip", "lpips.hip", "idnet.hip", "losses.hip", "disc.hip", "hgfilter.hip", "aligner.hip", "volume_disc.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=on", "-fno-slp-vectorize",
          "-Wno-unused-result"]  # no SLP: packed-f32 VALU next to MFMAs is slower and un-does the epilogue interleave

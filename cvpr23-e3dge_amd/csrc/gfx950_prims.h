@@ -128,7 +128,7 @@ __device__ __forceinline__ float wave_max(const float& v) {
     return m;
 }
 
-// DPP moves (gfx9 controls: row_shr:n = 0x110 + n, row_ror:n = 0x120 + n, wave_shl:1 = 0x130, wave_shr:1 = 0x138, row_bcast:15 = 0x142,
+// DPP moves (gfx9 controls: quad_perm:[a,b,c,d] = a | b << 2 | c << 4 | d << 6, row_shr:n = 0x110 + n, row_ror:n = 0x120 + n, wave_shl:1 = 0x130, wave_shr:1 = 0x138, row_bcast:15 = 0x142,
 // row_bcast:31 = 0x143).  dpp_f32: lanes the control does not reach read 0.  dpp_or: those lanes, and the rows outside ROW_MASK, get `ident`.
 template <int CTRL> __device__ __forceinline__ float dpp_f32(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
@@ -139,6 +139,12 @@ template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_or(float 
 // value of the lane one below / one above in the wavefront (the end lanes read 0)
 __device__ __forceinline__ float dpp_wave_shr1(float v) { return dpp_f32<0x138>(v); }
 __device__ __forceinline__ float dpp_wave_shl1(float v) { return dpp_f32<0x130>(v); }
+// value of lane 4 q + I of the lane's quad (quad_perm:[I,I,I,I]), and ((v0 + v1) + v2) + v3 over the quad's lanes in that order, in every
+// lane of the quad.  Whole quads must be active.
+template <int I> __device__ __forceinline__ float dpp_quad_bcast(float v) { return dpp_f32<I * 0x55>(v); }
+__device__ __forceinline__ float quad_sum(float v) {
+    return __fadd_rn(__fadd_rn(__fadd_rn(dpp_quad_bcast<0>(v), dpp_quad_bcast<1>(v)), dpp_quad_bcast<2>(v)), dpp_quad_bcast<3>(v));
+}
 
 // XCD-aware tile order (block b runs on XCD b % 8, each XCD has its own L2): workgroup-tile t -> logical tile id such that every
 // XCD walks one CONTIGUOUS range of logical ids, so tiles with neighbouring ids (they share operands) share an L2.

@@ -20,7 +20,8 @@ Two paths compute `forward(input)` -> (B, 1) logits:
          image only; it is once-differentiable: a double backward raises, as in IDLoss.
 
 Weight images go through _lib.cached (drop them with `invalidate()` after writes through `.data`).  Out of scope, as before:
-StyleGANEncoder, DEncoder and the VolumeRenderDiscriminator* family (stylesdf_model.py:1193-1510, :1620-1765)."""
+StyleGANEncoder, DEncoder and the VolumeRenderDiscriminator* family (stylesdf_model.py:1193-1510, :1620-1765); of that family
+`VolumeRenderDiscriminator` itself now lives in e3dge_amd.volume_discriminator."""
 import math
 import os
 

@@ -11,8 +11,9 @@ activations stay in the split-f16 packed layout of the matrix pipe between the k
 the blur, ToRGB and the modulation GEMVs are hand-written HIP kernels.  `E3DGE_DECODER=planar` keeps the round-2 path
 (fp32 planes between fused kernels, e3dge_modconv3x3 etc.); anything that needs an autograd graph through the decoder
 uses weight modulation as a HIP launch (e3dge_modconv_weights) + library convolutions (MIOpen through torch).
-The StyleGAN2 `Discriminator` (:1514-1617) lives in e3dge_amd.discriminator; the VolumeRenderDiscriminator* family and the legacy
-encoders (:1192-1510, :1620-1765) are out of scope.
+The StyleGAN2 `Discriminator` (:1514-1617) lives in e3dge_amd.discriminator and the camera-pose predictor `VolumeRenderDiscriminator` with
+its building blocks (:1193-1419) in e3dge_amd.volume_discriminator; its encoder variants `VolumeRenderDiscriminatorEncoder` and
+`VolumeStyleEncoder` (:1422-1510) and the legacy encoders (:1620-1765) are out of scope.
 """
 import ctypes
 import math

@@ -304,6 +304,48 @@ def load_synthetic_discriminator(module, seed=0, variant=None):
     return module
 
 
+VDISC_CONV2_GAIN, VDISC_SKIP_GAIN = 1.5, 1.0
+
+
+def load_synthetic_volume_discriminator(module, seed=0, variant=None):
+    """Deterministic weights for an `e3dge_amd.volume_discriminator.VolumeRenderDiscriminator` (or the reference's: the keys are the same).
+    variant=None: the constructor's ranges -- nn.Conv2d's U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)) for weights and convolution biases, the
+    activation biases U(-c, c) with c = sqrt(1 / (in_channels k k)), in_channels without the two coordinate channels
+    (stylesdf_model.py:1215-1219, :1326-1329).  Every layer then shrinks its input, so the angles of two images lie about 1e-3 apart.
+    variant='wide': weights N(0, 2 / (1.04 fan_in)) (He for leaky_relu 0.2) times a per-role gain chosen so that every block output keeps a
+    standard deviation of order 1 (a block's second 3x3 makes up for the average over four pixels: VDISC_CONV2_GAIN; the 1x1 skip reads
+    an averaged map: VDISC_SKIP_GAIN), final_conv N(0, 1 / fan_in), biases 0.1 N(0, 1)."""
+    if variant not in (None, 'wide'):
+        raise ValueError(f"variant={variant!r}: None or 'wide'")
+    sd, shapes = {}, {k: tuple(v.shape) for k, v in module.state_dict().items()}
+    for k, v in module.state_dict().items():
+        rs = _rs('volume_discriminator.' + k, seed)
+        leaf = k.rsplit('.', 1)[1]
+        if leaf == 'weight':
+            fan_in = v.shape[1] * v.shape[2] * v.shape[3]
+            if variant is None:
+                t = rs.uniform(-1.0, 1.0, size=tuple(v.shape)) / math.sqrt(fan_in)
+            elif k.startswith('final_conv.'):
+                t = rs.standard_normal(tuple(v.shape)) / math.sqrt(fan_in)
+            else:
+                gain = VDISC_CONV2_GAIN if '.conv2.' in k else VDISC_SKIP_GAIN if '.skip.' in k else 1.0
+                t = rs.standard_normal(tuple(v.shape)) * (gain * _kaiming_std(fan_in))
+        elif variant is None:
+            if leaf == 'bias' and k.endswith('activation.bias'):      # FusedLeakyReLU's, behind a plain (the stem) or a coordinate convolution
+                plain = k.startswith('convs.0.')
+                w = shapes[k.replace('activation.bias', 'conv.weight' if plain else 'conv.conv.weight')]
+                fan_in = (w[1] - (0 if plain else 2)) * w[2] * w[3]
+            else:                                                     # nn.Conv2d's own
+                w = shapes[k.replace('.bias', '.weight')]
+                fan_in = w[1] * w[2] * w[3]
+            t = rs.uniform(-1.0, 1.0, size=tuple(v.shape)) / math.sqrt(fan_in)
+        else:
+            t = 0.1 * rs.standard_normal(tuple(v.shape))
+        sd[k] = torch.from_numpy(np.asarray(t, dtype=np.float32))
+    module.load_state_dict(sd, strict=True)
+    return module
+
+
 def pifu_opt(**over):
     """The PIFu-style `local_options` that `e3dge_amd.hg_filter.HGFilter` / `ResidualImageFilter` read, at the reference's defaults
     (vendor/pifu/lib/options.py with the stage-2 scripts' --norm group --hg_input_channel 64)."""

@@ -1671,6 +1671,64 @@ int e3dge_aligner_backward(const E3dgeAlignerBwdArgs* args, e3dge_stream_t strea
 int e3dge_aligner_branch_bytes(uint8_t* out, int64_t out_bytes, const float* packed, int64_t packed_floats, const void* saved, int64_t saved_bytes,
                                int n, int train, e3dge_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The camera-pose predictor, forward, eval form (csrc/volume_disc.hip).  Additions to ABI 17.  No allocation, no synchronisation, no
+ * atomics; bit-reproducible, and an image's results do not depend on its position in the batch or on the batch size.  Replaces
+ * VolumeRenderDiscriminator.forward (project/models/stylesdf_model.py:1369-1419): the 1x1 stem, log2(size) - 1 VolumeRenderResBlocks
+ * of two 3x3 CoordConv layers with AvgPool2d(2) and the (out + skip) / sqrt(2) merge, and the 2x2 final layer.  fp32.  `size` is
+ * renderer_spatial_output_dim: 16, 32, 64 or 128.
+ *
+ * Source tensors, in state-dict order: convs.0.conv.weight, convs.0.activation.bias; per block i = 1 ..: convs.i.conv1.conv.conv.weight,
+ * convs.i.conv1.activation.bias, convs.i.conv2.conv.conv.weight, convs.i.conv2.activation.bias and, where the block changes the channel
+ * count, convs.i.skip.conv.weight, convs.i.skip.conv.bias; final_conv.conv.weight, final_conv.conv.bias.
+ *
+ * e3dge_vdisc_packed_floats   floats of the packed image at `size`: per layer its A-fragment image, roundup(cout, 16) * roundup(K, 32)
+ *                             floats with K = cin (stem, skip) or 9 (cin + 2) (CoordConv, the reference's channel order), then its cout
+ *                             bias floats; the final layer's weight as it is, 3 * 4 cin floats, and its 3 bias floats (-1: unsupported
+ *                             size).
+ * e3dge_vdisc_pack_weights    ptrs: HOST array of n device pointers, n as the list above gives it at `size`.  Re-run after a weight update.
+ * e3dge_vdisc_ws_bytes        workspace bytes of e3dge_vdisc_forward for n images (1..256): two block inputs / outputs, one conv1 output
+ *                             and one skip output of the largest layer each; neither a concatenated nor a pre-pool tensor (-1: bad n or size).
+ * e3dge_vdisc_forward         images (n, 3, size, size) -> logits (n, 1), viewpoints (n, 2).  taps[0]: the stem's output (n, c0, size,
+ *                             size); taps[1 + b]: block b's output (n, cout, size >> (b + 1), size >> (b + 1)); any may be NULL.  Fails
+ *                             before any launch on a null pointer, an unsupported size, n outside 1..256 or a workspace that is too
+ *                             small.  8 / 11 / 14 / 17 launches at size 16 / 32 / 64 / 128.
+ * e3dge_vdisc_conv            debug entry: one launch of vdisc_conv_kernel (_FINAL: of vdisc_final_kernel) after packing w into wfrag, on in
+ *                             (n, cin, height, width).
+ *                             form E3DGE_VDISC_FORM_STEM: out (n, cout, height, width) = lrelu(conv1x1 + bias), w (cout, cin, 1, 1);
+ *                             _CONV: lrelu(conv3x3 pad 1 of cat(in, yy, xx) + bias), w (cout, cin + 2, 3, 3), height, width >= 2;
+ *                             _CONV_POOL: out (n, cout, height / 2, width / 2) = (avgpool2(that) + s) / sqrt(2) with s = skip
+ *                             (n, cout, height / 2, width / 2) (skip_mode E3DGE_VDISC_SKIP_READ) or avgpool2(skip (n, cout, height,
+ *                             width)) (_SKIP_POOL); _SKIP: out (n, cout, height / 2, width / 2) = conv1x1(avgpool2(in)) + bias;
+ *                             _FINAL: out (n, cout, 1, 1) = conv2x2 + bias of the 2 x 2 map (height = width = 2, cout 1..64), w
+ *                             (cout, cin, 2, 2), summed in float64.  lrelu: slope 0.2, scale 1.  The pooled forms refuse odd planes.
+ *                             wfrag: scratch of roundup(cout, 16) * roundup(K, 32) floats (_FINAL: cout * 4 cin).  Two launches.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define E3DGE_VDISC_MAX_BLOCKS 6
+#define E3DGE_VDISC_TAPS 7
+#define E3DGE_VDISC_FORM_STEM 0
+#define E3DGE_VDISC_FORM_CONV 1
+#define E3DGE_VDISC_FORM_CONV_POOL 2
+#define E3DGE_VDISC_FORM_SKIP 3
+#define E3DGE_VDISC_FORM_FINAL 4
+#define E3DGE_VDISC_SKIP_READ 1
+#define E3DGE_VDISC_SKIP_POOL 2
+typedef struct E3dgeVdiscArgs {
+    const float* packed;              /* e3dge_vdisc_pack_weights */
+    const float* images;
+    int32_t n, size;
+    float* logits; float* viewpoints;
+    float* taps[E3DGE_VDISC_TAPS];
+    void* ws;
+    int64_t ws_bytes;
+} E3dgeVdiscArgs;
+int64_t e3dge_vdisc_packed_floats(int size);
+int e3dge_vdisc_pack_weights(float* image, const float* const* ptrs, int n, int size, e3dge_stream_t stream);
+int64_t e3dge_vdisc_ws_bytes(int n, int size);
+int e3dge_vdisc_forward(const E3dgeVdiscArgs* args, e3dge_stream_t stream);
+int e3dge_vdisc_conv(float* out, const float* in, const float* w, const float* bias, const float* skip, float* wfrag, int64_t wfrag_floats,
+                     int n, int cin, int cout, int height, int width, int form, int skip_mode, e3dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
